@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- pressure-solves/sec of the surrogate hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run measures the headline only: set-up, an untimed settling pass (>= 200 solves), W warm-up steps, the K timed
+steps, the fields of the last timed step written to DIR/fields.npy when ``--dump-outputs`` is given, and the result line
+(contract keys and the workload's config).  ``--full`` adds everything described below the workload paragraph: the
+roofline and per-kernel passes, the per-solve quantiles, the end-to-end / solver-boundary / case-stream rates, the case
+batch, the other legs, the CPU baselines and the oracle and golden comparisons.
 
 ``--gpus N`` with no torchrun environment starts the N ranks itself (fresh child processes, one per GPU, before this
 process touches the GPU; every child is supervised: the first rank that fails ends the job within seconds, each rank's
@@ -13,7 +19,7 @@ Workload of ``value`` at every N (weak scaling: the per-GPU work is fixed): BASE
 channel-with-obstacle U_to_gradP inference, batch 1, fp32, P_i = P_o = 128, MLP 3x512 (SURVEY.md §8 d config 1;
 synthetic seeded input, seeded random-init weights of that architecture).  One step = one solve
 (grid[256,256,3] -> fields[256,256,2]) through the C-ABI with the input already resident in HBM (the bench contract:
-the PCIe-inclusive rate is never ``value``; it is ``value_end_to_end`` on the same line); steps are issued back to back
+the PCIe-inclusive rate is never ``value``; it is ``value_end_to_end`` on the --full line); steps are issued back to back
 on one stream, K steps are timed between barrier + synchronize on both sides, MAX over ranks.  Each rank drives its own
 GPU with its own independent case stream (no data-path collective); RCCL carries the model broadcast (outside the timed
 region), the barrier and the max-reduction of the time.
@@ -22,7 +28,7 @@ The ONE line on stdout is a summary shorter than 4096 characters (compact_line: 
 of the headline, a few numbers per extra leg); the full record described below -- per-kernel tables, per-launch stamps,
 planner dumps -- is written to bench_detail.json (PSM_BENCH_LOGDIR, default: next to this script).
 
-Objects of the full record (the line carries their summary):
+Objects of the full record of a --full run (the line carries their summary):
   value_end_to_end / end_to_end   SURVEY §8(d)'s solve INCLUDING the H2D copy of the grid and the D2H copy of the field
                (host buffers in, host buffers out), measured by a C++ loop inside the library through the public C-ABI
                (psm_bench_host): the pinned ring on caller-registered memory, next to the synchronous psm_solve_grid,
@@ -587,6 +593,22 @@ def emit_result(detail):
 
 
 
+DUMP_LIMIT = 64 << 20        # bytes of --dump-outputs in all
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs: {name: host array} -> dirpath/<name>.npy in float32 (float64 kept).  The inputs are seeded, so two builds
+    run with the same arguments can be compared array for array."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT})")
+    os.makedirs(dirpath, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirpath, k + ".npy"), a)
+
+
 def finish(pdist_mod=None):
     try:
         import torch.distributed as dist
@@ -889,8 +911,10 @@ def pca_roofline(sur, model, ny, nx, n_cases, precision, d_grid, d_fields, steps
     return roof
 
 
-def unet_leg(name, args, torch, pdist, rank, world, local_rank, backend, steps, warmup, with_cpu, cpu_budget_s=4.0):
-    """The convolutional path with the bench protocol: K forward passes back to back, input resident in HBM."""
+def unet_leg(name, args, torch, pdist, rank, world, local_rank, backend, steps, warmup, with_cpu, cpu_budget_s=4.0, full=True, dump_dir=None):
+    """The convolutional path with the bench protocol: K forward passes back to back, input resident in HBM.  ``full``: the
+    per-launch roofline pass and (``with_cpu``) the NumPy U-Net as cpu_baseline after the timed region; ``dump_dir``: the
+    fields of the last timed pass are written there (dump_outputs)."""
     import numpy as np
     from psm_amd import UNetSurrogate, synthetic
     NY, NX, NC, desc = UNET_WORKLOADS[name]
@@ -910,6 +934,15 @@ def unet_leg(name, args, torch, pdist, rank, world, local_rank, backend, steps, 
         net.forward_device(d_in[k].data_ptr(), NC, d_out[k].data_ptr(), stream)
     dt_max = pdist.timed_region(step, steps, warmup, torch.cuda.synchronize, "cuda" if backend == "nccl" else "cpu")
     torch.cuda.synchronize()
+    if dump_dir:
+        dump_outputs(dump_dir, {"fields": to_host(torch, d_out[(steps - 1) % len(d_in)])})       # [NC, NY, NX, 1]
+    leg = {"workload": desc, "value": pdist.aggregate_throughput(NC, steps, world, dt_max), "unit": "solves/s", "steps": steps, "warmup": warmup,
+           "ms_per_step": dt_max / steps * 1e3, "dtype": prec, "cases_per_step_per_gpu": NC, "grid": [NY, NX],
+           "parity": "unpinned (no reference network): l2_vs_oracle is against the build-defined NumPy U-Net with the same rounding points",
+           "planner": {"autotuned_split_k": net.autotuned}}
+    if not full:
+        net.close()
+        return leg
     got = to_host(torch, d_out[0][0])
     flops = net.flops * NC
     achieved = flops * steps / dt_max / 1e12
@@ -948,11 +981,7 @@ def unet_leg(name, args, torch, pdist, rank, world, local_rank, backend, steps, 
                             "frac_mfma_priced_against": "time-weighted ceiling of the launches (x6 launches: bf16 peak / 6 = 419.4; f32 MFMA 157.3; bf16 2516.6 TFLOP/s)",
                             "sum_of_launches_us": sum(l["avg_us"] for l in launches), "n_launches": len(launches)},
                 launches=launches)
-    leg = {"workload": desc, "value": pdist.aggregate_throughput(NC, steps, world, dt_max), "unit": "solves/s", "steps": steps, "warmup": warmup,
-           "ms_per_step": dt_max / steps * 1e3, "dtype": prec, "cases_per_step_per_gpu": NC, "grid": [NY, NX],
-           "parity": "unpinned (no reference network): l2_vs_oracle is against the build-defined NumPy U-Net with the same rounding points",
-           "planner": {"autotuned_split_k": net.autotuned},
-           "roofline": roof}
+    leg["roofline"] = roof
     if with_cpu:
         from oracle import unet_oracle as uo           # checker + cpu_baseline leg only
         from psm_amd import hostinfo
@@ -980,16 +1009,16 @@ def main_unet(args):
     torch.cuda.set_device(local_rank)
     pdist.init(backend, torch.device("cuda", local_rank))
     leg = unet_leg(args.workload, args, torch, pdist, rank, world, local_rank, backend, args.steps, args.warmup,
-                   rank == 0 and world == 1 and not args.no_cpu_baseline, cpu_budget_s=12.0)
+                   args.full and rank == 0 and world == 1 and not args.no_cpu_baseline, cpu_budget_s=12.0, full=args.full,
+                   dump_dir=args.dump_outputs if rank == 0 else None)
     out = {"metric": "pressure-solves/sec (256x256 U->p inference)", "value": leg["value"], "unit": "solves/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": leg["ms_per_step"], "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": leg["dtype"], "data": "synthetic",
            "config": {"workload": leg["workload"], "grid": leg["grid"], "cases_per_step_per_gpu": leg["cases_per_step_per_gpu"],
                       "parallelism": f"case-sharded x{world} (no data-path collective)", "parity": leg["parity"], "planner": leg["planner"],
                       "arithmetic": ("bf16 operands / f32 accumulate (bf16 MFMA)" if leg["dtype"] == "bf16" else
-                                     "f32 MFMA; layers with c_in >= 64 on 8-row tiles as x6 split-bf16 (6 bf16 MFMA terms, f32-grade error)")},
-           "roofline": leg["roofline"]}
-    for k in ("cpu_baseline", "l2_vs_oracle"):
+                                     "f32 MFMA; layers with c_in >= 64 on 8-row tiles as x6 split-bf16 (6 bf16 MFMA terms, f32-grade error)")}}
+    for k in ("roofline", "cpu_baseline", "l2_vs_oracle"):
         if k in leg:
             out[k] = leg[k]
     if rank == 0:
@@ -1057,6 +1086,11 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="launcher / process-group plumbing only (no GPU work)")
     ap.add_argument("--workload", default="config1", choices=sorted(WORKLOADS) + sorted(UNET_WORKLOADS),
                     help="BASELINE.json config to run as the headline (default: configs[1], the one the metric is quoted on)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: roofline and per-kernel passes, per-solve quantiles, end-to-end and solver-boundary "
+                         "rates, case batch, the other legs, CPU baselines and oracle / golden comparisons (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the arrays the last timed step returned (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -1134,19 +1168,53 @@ def main():
         k = i % len(d_in)
         sur.solve_device(d_in[k].data_ptr(), NC, d_out[k].data_ptr(), stream)
 
-    # The instrumented pass of the roofline (every dispatch stamped, at least 200 solves) runs BEFORE the contract's W warm-up
-    # steps and K timed steps: it is not part of either, and it leaves clocks, caches and the runtime's kernel objects warm, so
-    # that a short driver run (K = 20) measures the same steady state as the default K = 2000.
-    kt_steps = max(args.steps, 200)
-    kt_head = time_kernels(sur, d_in[0].data_ptr(), NC, d_out[0].data_ptr(), kt_steps, quantiles=True)
-    kt_head = [(nm, us, n * args.steps // kt_steps, q) for nm, us, n, q in kt_head]    # launches per `steps` solves, as pca_roofline counts them
+    # Before the contract's W warm-up steps and K timed steps, at least 200 untimed solves leave clocks, caches and the runtime's
+    # kernel objects warm, so that a short driver run (K = 20) measures the same steady state as the default K = 2000.  With --full
+    # that pass is the roofline's instrumented one (every dispatch stamped); a plain run issues up to 2000 of the same solves unstamped.
+    if args.full:
+        kt_steps = max(args.steps, 200)
+        kt_head = time_kernels(sur, d_in[0].data_ptr(), NC, d_out[0].data_ptr(), kt_steps, quantiles=True)
+        kt_head = [(nm, us, n * args.steps // kt_steps, q) for nm, us, n, q in kt_head]    # launches per `steps` solves, as pca_roofline counts them
+    else:
+        for i in range(max(200, min(args.steps, 2000))):
+            step(i)
     torch.cuda.synchronize()
 
     dt_max = pdist.timed_region(step, args.steps, args.warmup, torch.cuda.synchronize, red_dev)
     torch.cuda.synchronize()
     trips = guard_trips_after(sur, args.workload)
-    got_dev = to_host(torch, d_out[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"fields": to_host(torch, d_out[(args.steps - 1) % len(d_in)])})    # [NC, NY, NX, c_out]
     value = pdist.aggregate_throughput(NC, args.steps, world, dt_max)
+    out = {
+        "metric": "pressure-solves/sec (256x256 U->p inference)",
+        "value": value, "value_device_resident": value,
+        "unit": "solves/s", "n_gpus": world, "world_size_reported": world_reported, "devices": devices,
+        "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": precision, "data": "synthetic",
+        "config": {"workload": wl_desc,
+                   "grid": [NY, NX], "blocks": sur.B, "p_in": P, "p_out": P, "cases_per_step_per_gpu": NC,
+                   "parallelism": f"case-sharded x{world} (no data-path collective; model broadcast from rank 0 over "
+                                  f"{'RCCL' if backend == 'nccl' else backend} before the timed region: {broadcast_s * 1e3:.0f} ms)",
+                   "value_is": "device-resident rate: the input grid is already in HBM when the timed region starts and the "
+                               "field stays in HBM (the bench contract: the PCIe-inclusive rate is never `value`); the solve of "
+                               "SURVEY section 8(d) / BASELINE.md:4 -- host grid in, host field out, H2D and D2H included -- is "
+                               "value_end_to_end on the --full line",
+                   "degenerate": degenerate_note(variant, NY, NX),
+                   "geometry": ("bound once per case stream (psm_bind_geometry = the reference's computeOnlyOnce / init_func split): "
+                                "6 launches per solve, 7 for case batches; the contract is checked on the device at every solve") if bound
+                               else "general path (any geometry per call): 8 launches per solve (9 for case batches)",
+                   "guard_trips": trips},
+    }
+    if not args.full:
+        if rank == 0:
+            emit_result(out)
+        sur.close()
+        finish()
+        return
+
+    got_dev = to_host(torch, d_out[0])
     roofline = pca_roofline(sur, model, NY, NX, NC, precision, d_in[0].data_ptr(), d_out[0].data_ptr(), args.steps, dt_max / args.steps,
                             args.workload, bound, kt=kt_head)
     # BASELINE.md section 2's protocol beside the contract's K-step mean: >= 200 timed samples, median and 10th / 90th percentile.
@@ -1174,9 +1242,7 @@ def main():
     per_ms.sort()
     q_ms = {"p50": per_ms[n_q // 2], "p10": per_ms[n_q // 10], "p90": per_ms[(n_q * 9) // 10]}
 
-    out = {
-        "metric": "pressure-solves/sec (256x256 U->p inference)",
-        "value": value, "value_device_resident": value,
+    out.update({
         # rates at the median / 90th / 10th percentile of the per-solve time of n_q event-separated samples on this rank (x world: case-
         # sharded, no collective): value_p10 is computed from ms_p90, the SLOW decile of the times (the low rate), value_p90 from ms_p10
         "value_p50": NC * world / (q_ms["p50"] * 1e-3), "value_p10": NC * world / (q_ms["p90"] * 1e-3), "value_p90": NC * world / (q_ms["p10"] * 1e-3),
@@ -1188,26 +1254,9 @@ def main():
         # (~25 us of pipeline fill).  At K = 2000 that is 0.04 % of the region, at the driver's K = 20 it is 3-4 %: the round-4 driver line
         # (27.8 k) against the builder's K = 2000 lines (29.2 k) on equal boxes; value_p50 (chunks of 50) sits between the two.
         "pipeline_fill_note": f"K={args.steps}: one fill of ~25 us = {25.0 / (dt_max / args.steps * 1e6 * args.steps) * 100:.1f} % of the timed region",
-        "unit": "solves/s", "n_gpus": world, "world_size_reported": world_reported, "devices": devices,
-        "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": precision, "data": "synthetic",
-        "config": {"workload": wl_desc,
-                   "grid": [NY, NX], "blocks": sur.B, "p_in": P, "p_out": P, "cases_per_step_per_gpu": NC,
-                   "parallelism": f"case-sharded x{world} (no data-path collective; model broadcast from rank 0 over "
-                                  f"{'RCCL' if backend == 'nccl' else backend} before the timed region: {broadcast_s * 1e3:.0f} ms)",
-                   "value_is": "device-resident rate: the input grid is already in HBM when the timed region starts and the "
-                               "field stays in HBM (the bench contract: the PCIe-inclusive rate is never `value`); the solve of "
-                               "SURVEY section 8(d) / BASELINE.md:4 -- host grid in, host field out, H2D and D2H included -- is "
-                               "value_end_to_end on this line",
-                   "degenerate": degenerate_note(variant, NY, NX),
-                   "geometry": ("bound once per case stream (psm_bind_geometry = the reference's computeOnlyOnce / init_func split): "
-                                "6 launches per solve, 7 for case batches; the contract is checked on the device at every solve") if bound
-                               else "general path (any geometry per call): 8 launches per solve (9 for case batches)",
-                   "arithmetic": arithmetic_note(precision, roofline["kernels"]),
-                   "guard_trips": trips},
         "roofline": roofline,
-    }
+    })
+    out["config"]["arithmetic"] = arithmetic_note(precision, roofline["kernels"])
 
     # ---- one solve = host grid in, host field out (H2D + D2H included)
     if not args.no_extras:

@@ -54,6 +54,35 @@ BLOCK_ERROR_CASES = ["deltas_256x256", "deltas_300x420", "deltas_nan_256x256"]
 DENSE_GOLDEN_CASES = [k for k, v in GOLDEN_CASES.items() if not v.get("conv1d") and not v.get("attention")]     # Dense-stack networks (C port, bound path)
 
 
+REFERENCE_FILES = os.path.join(GOLDEN_DIR, "reference_files")
+
+
+def rebuild_reference_h5(dst: str):
+    """The reference's Keras HDF5 files whose weights are already kept in chapter4/5_weights.npz, rebuilt byte for byte
+    under ``dst`` (same relative paths): REFERENCE_FILES/h5_skeletons.json names, per file, its skeleton (the file with
+    every weight and bias array zeroed, xz-compressed), the npz array that fills each zeroed range, and the sha256 of the
+    original file, which the rebuilt file must match (tests/golden/make_golden.py writes both).  -> rebuilt paths."""
+    import hashlib
+    import json
+    import lzma
+    man = json.load(open(os.path.join(REFERENCE_FILES, "h5_skeletons.json")))
+    out = []
+    for rel, e in sorted(man.items()):
+        raw = bytearray(lzma.decompress(open(os.path.join(REFERENCE_FILES, e["skeleton"]), "rb").read()))
+        arrays = np.load(os.path.join(GOLDEN_DIR, e["npz"]))
+        for key, off in e["arrays"]:
+            b = np.ascontiguousarray(arrays[key], "<f4").tobytes()
+            raw[off:off + len(b)] = b
+        if hashlib.sha256(raw).hexdigest() != e["sha256"]:
+            raise ValueError(f"{rel}: rebuilt file differs from the reference's (sha256)")
+        path = os.path.join(dst, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(raw)
+        out.append(path)
+    return out
+
+
 def real_chapter5_weights():
     d = np.load(os.path.join(GOLDEN_DIR, "chapter5_weights.npz"))
     n = len([k for k in d.files if k.startswith("W")])

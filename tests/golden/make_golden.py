@@ -432,6 +432,50 @@ C4_MODELS = {"M_u": f"{REF}/Thesis_Work/Chapter4/MLP/M_u/trained_models/cil.h5",
              "M_fU": f"{REF}/Thesis_Work/Chapter4/MLP/M_fU/Evaluation/model_first_.h5"}
 
 
+# Reference files kept under tests/golden/reference_files (same relative paths) for the HDF5 / maxs reader tests: the maxs
+# files and one PINN of each Chapter-3 layout as they are; the two 4-layer surrogates as skeletons, since their weights are
+# already in chapter5_weights.npz / chapter4_weights.npz (cases.rebuild_reference_h5 puts them back, checked by sha256).
+REF_COPIED = ["Thesis_Work/Chapter3/Physics-informed/PINN1/beta1/my_model_ref.h5",
+              "Thesis_Work/Chapter3/Physics-informed/PINN2/beta1/my_model_ref.h5",
+              "Thesis_Work/Chapter3/Physics-informed/PINN3/beta1/my_model_ref_afterLFGS.h5",
+              "Thesis_Work/Chapter3/Physics-informed/PINN4/beta10/my_model_ref.h5",
+              "Thesis_Work/Chapter4/MLP/M_fU/Evaluation/maxs", "Thesis_Work/Chapter4/MLP/M_fU/Evaluation/maxs_PCA",
+              "Thesis_Work/Chapter5/parallelized/test_case/maxs", "Thesis_Work/Chapter5/parallelized/test_case/maxs_PCA",
+              "Thesis_Work/Chapter5/singleCore/test_Case/maxs", "Thesis_Work/Chapter5/singleCore/test_Case/maxs_PCA"]
+REF_SKELETONS = {"Thesis_Work/Chapter5/parallelized/test_case/weights.h5": ("chapter5_weights.npz", ""),
+                 "Thesis_Work/Chapter4/MLP/M_fU/Evaluation/model_first_.h5": ("chapter4_weights.npz", "M_fU_")}
+
+
+def write_reference_files():
+    import hashlib
+    import json
+    import lzma
+    import shutil
+    dst = os.path.join(HERE, "reference_files")
+    for rel in REF_COPIED:
+        os.makedirs(os.path.dirname(os.path.join(dst, rel)), exist_ok=True)
+        shutil.copyfile(os.path.join(REF, rel), os.path.join(dst, rel))
+    man = {}
+    for rel, (npz, prefix) in REF_SKELETONS.items():
+        raw = open(os.path.join(REF, rel), "rb").read()
+        skel = bytearray(raw)
+        arrays = np.load(os.path.join(HERE, npz))
+        ranges = []
+        for key in sorted(k for k in arrays.files if k.startswith(prefix) and k[len(prefix):][:1] in ("W", "b")):
+            b = np.ascontiguousarray(arrays[key], "<f4").tobytes()
+            off = raw.find(b)
+            assert off >= 0 and raw.find(b, off + 1) < 0, (rel, key)        # stored contiguously, exactly once
+            skel[off:off + len(b)] = bytes(len(b))
+            ranges.append([key, off])
+        name = rel.replace("/", "__") + ".skel.xz"
+        with open(os.path.join(dst, name), "wb") as f:
+            f.write(lzma.compress(bytes(skel)))
+        man[rel] = {"skeleton": name, "npz": npz, "arrays": ranges, "sha256": hashlib.sha256(raw).hexdigest()}
+    with open(os.path.join(dst, "h5_skeletons.json"), "w") as f:
+        json.dump(man, f, indent=1)
+    print("reference_files:", len(REF_COPIED), "copied,", len(man), "skeletons")
+
+
 def run_chapter4(grid, model, which):
     """Thesis_Work/Chapter4 evaluators (M_u/Evaluation/Eval_dual_Dense_onlycil.py:236-414, M_fU/Evaluation/Eval.py:
     227-411): `timeStep` from the block extraction to the final shift, avance = int(0.75 * shape)."""
@@ -609,6 +653,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "chapter4_weights.npz"), MfU_maxs=formats.read_maxs(f"{c4dir}/maxs"),
                         MfU_maxs_PCA=formats.read_maxs(f"{c4dir}/maxs_PCA"), **flat)
     print("chapter4_weights.npz", sorted(k for k in flat if k.endswith("W0")), [flat[k].shape for k in sorted(flat) if "_W" in k])
+    write_reference_files()
 
     # ---- domain_dist (a3) and the IDW fallback of the Improved_SM interp_weights (a2)
     dd = {}

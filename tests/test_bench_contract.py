@@ -207,7 +207,7 @@ def test_world_size_must_match_gpus():
 
 @pytest.mark.gpu
 def test_default_bench_line():
-    d, full = run_bench()
+    d, full = run_bench("--full")
     # ---- the line the driver parses
     assert KEYS <= set(d) and ROOF <= set(d["roofline"])
     assert d["metric"].startswith("pressure-solves/sec") and d["unit"] == "solves/s" and d["n_gpus"] == 1
@@ -270,8 +270,39 @@ def test_default_bench_line():
 
 @pytest.mark.gpu
 def test_general_path_and_conv_bench_lines():
-    d, _ = run_bench("--no-bind", "--no-cpu-baseline")
+    d, _ = run_bench("--full", "--no-bind", "--no-cpu-baseline")
     assert d["config"]["geometry"].startswith("general path") and "cpu_baseline" not in d
-    u, full = run_bench("--workload", "unet", "--no-cpu-baseline")
+    u, full = run_bench("--full", "--workload", "unet", "--no-cpu-baseline")
     assert KEYS <= set(u) and u["roofline"]["bound"] in ("mfma", "hbm") and u["value"] > 100 and "arithmetic" in u["config"]
     assert full["roofline"]["whole_pass"]["achieved_TFLOPs"] > 1
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: float32 (float64 kept) .npy files, one per name; more than DUMP_LIMIT bytes in all is an error."""
+    import numpy as np
+    b = _bench_module()
+    b.dump_outputs(str(tmp_path / "d"), {"fields": np.arange(6, dtype=np.float16).reshape(2, 3), "p": np.ones(4)})
+    f, p = np.load(tmp_path / "d" / "fields.npy"), np.load(tmp_path / "d" / "p.npy")
+    assert f.dtype == np.float32 and f.shape == (2, 3) and (f.ravel() == np.arange(6)).all() and p.dtype == np.float64
+    with pytest.raises(SystemExit):
+        b.dump_outputs(str(tmp_path / "e"), {"big": np.zeros(b.DUMP_LIMIT // 4 + 1, np.float32)})
+    assert not (tmp_path / "e").exists()
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_fields(tmp_path):
+    """A plain run times the headline only: exactly --steps timed steps, ms_per_step on the line, none of the --full parts; with
+    --dump-outputs the fields of the last timed step, identical between two runs with the same arguments (seeded inputs)."""
+    import numpy as np
+    got = []
+    for r in range(2):
+        d, full = run_bench("--dump-outputs", str(tmp_path / f"out{r}"), logdir=tmp_path / f"log{r}")
+        assert {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"} <= set(d)
+        assert d["steps"] == 60 and d["warmup"] == 10 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["value"] > 1000 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        assert "configs[1]" in d["config"]["workload"] and d["config"]["guard_trips"] == 0
+        assert not {"roofline", "cpu_baseline", "l2_vs_oracle", "legs", "case_batch", "value_end_to_end"} & set(full)
+        f = np.load(tmp_path / f"out{r}" / "fields.npy")
+        assert f.dtype == np.float32 and f.shape == (1, 256, 256, 2) and np.isfinite(f).all() and np.abs(f).max() > 0
+        got.append(f)
+    np.testing.assert_array_equal(got[0], got[1])

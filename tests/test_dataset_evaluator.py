@@ -314,18 +314,20 @@ def test_poisson_main_and_metrics(tmp_path):
     assert out["sims"][0]["sim"] == 0 and out["sims"][0]["phi"] == 0.16
 
 
-_REF = "/root/reference"
+# Data files of the reference kept as fixtures, under their paths in the reference (tests/golden/make_golden.py): the six
+# `maxs` / `maxs_PCA` files it ships and one Keras HDF5 file of every layout the reader test names -- the four Chapter-3
+# PINNs as they are, the Chapter-4 M_fU evaluator's network and the Chapter-5 solver case's weights.h5 rebuilt byte for byte
+# from their skeletons and the weights in chapter4/5_weights.npz (cases.rebuild_reference_h5).
+_REF = cases.REFERENCE_FILES
 
 
-@pytest.mark.skipif(not os.path.isdir(_REF), reason="the reference checkout is only present in the build container")
-def test_keras_reader_reads_every_h5_file_of_the_reference():
-    """Every Keras HDF5 file the reference ships (56: the Chapter-4 / Chapter-5 surrogates, full-model files with optimizer
-    state, the Chapter-3 PINNs) goes through formats.read_keras_dense_weights: a chain of Dense layers whose shapes fit each
-    other, finite float32 values.  Reads the files as DATA where they lie (nothing is copied); skipped where the checkout is
-    absent (the GPU box)."""
+def test_keras_reader_reads_the_stored_reference_h5_files(tmp_path):
+    """Keras HDF5 files the reference ships (the Chapter-4 / Chapter-5 surrogates, a full-model file after the L-BFGS stage,
+    the Chapter-3 PINNs of all four layouts) go through formats.read_keras_dense_weights: a chain of Dense layers whose
+    shapes fit each other, finite float32 values."""
     import glob
-    files = sorted(glob.glob(os.path.join(_REF, "**", "*.h5"), recursive=True))
-    assert len(files) >= 40
+    files = sorted(glob.glob(os.path.join(_REF, "**", "*.h5"), recursive=True)) + cases.rebuild_reference_h5(str(tmp_path))
+    assert len(files) >= 6
     shapes = set()
     for f in files:
         layers = formats.read_keras_dense_weights(f)
@@ -335,9 +337,9 @@ def test_keras_reader_reads_every_h5_file_of_the_reference():
         assert all(W.dtype == np.float32 and np.isfinite(W).all() and np.isfinite(b).all() for W, b in layers), f
         shapes.add((layers[0][0].shape[0], layers[-1][0].shape[1], len(layers)))
     assert (45, 48, 4) in shapes and (116, 39, 4) in shapes and (2, 5, 8) in shapes     # test_case/weights.h5, M_fU/model_first_.h5, a PINN
+    assert {(2, 2, 8), (2, 3, 8), (2, 6, 8)} <= shapes                                   # the other three PINN layouts
 
 
-@pytest.mark.skipif(not os.path.isdir(_REF), reason="the reference checkout is only present in the build container")
 def test_maxs_reader_reads_every_maxs_file_of_the_reference():
     """The reference's normalisation constants (`maxs`: one value per line; `maxs_PCA`: two) -- the values SURVEY.md section 8(c)
     quotes for the shipped solver case and the Chapter-4 evaluator."""

@@ -5,8 +5,8 @@
 TAG=$1; WL=${2:-unet8_bf16}
 export TMPDIR=/tmp; R=$PWD; O=$R/gpurun_out/uh_$TAG; mkdir -p $O
 cd /tmp
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 $R/bench.py --workload $WL --steps 30 --warmup 5 --no-cpu-baseline > $O/fetch.log 2>&1; echo "fetch rc=$?"
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -- python3 $R/bench.py --workload $WL --steps 30 --warmup 5 --no-cpu-baseline > $O/write.log 2>&1; echo "write rc=$?"
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 $R/bench.py --workload $WL --steps 30 --warmup 5 --no-cpu-baseline > $O/trace.log 2>&1; echo "trace rc=$?"
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/fetch -- python3 $R/bench.py --full --workload $WL --steps 30 --warmup 5 --no-cpu-baseline > $O/fetch.log 2>&1; echo "fetch rc=$?"
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/write -- python3 $R/bench.py --full --workload $WL --steps 30 --warmup 5 --no-cpu-baseline > $O/write.log 2>&1; echo "write rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python3 $R/bench.py --full --workload $WL --steps 30 --warmup 5 --no-cpu-baseline > $O/trace.log 2>&1; echo "trace rc=$?"
 cd $R
 python3 tools/unet_hbm_summary.py $TAG $WL
