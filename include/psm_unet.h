@@ -89,6 +89,15 @@ int psm_unet_get_choices(const psm_unet* u, int32_t* choices, int32_t n);
 int psm_unet_set_choices(psm_unet* u, const int32_t* choices, int32_t n);
 int psm_unet_ksplit(const psm_unet* u, int32_t idx);
 int psm_unet_plan_info(const psm_unet* u, int32_t idx, int32_t* info);
+/* Everything the launchers dispatch on for convolution idx in the current plan (introspection for the kernel tests): fills
+ * info[0 .. min(n, 16) - 1] and returns the number of fields the library knows (16):
+ *   0 arrangement 0..4, 1 channel tiles per workgroup (nct), 2 split over workgroups (ksplit), 3 in-workgroup K split (kw, 1 or 2),
+ *   4 x6, 5 pair role (0 none, 1 leader, 2 computed by the leader's launch), 6 pair kind (0 stem, 1 upsample ++ skip, 2 pool),
+ *   7 source (0 image, 1 previous activation, 2 its 2x2 max-pool, 3 upsample ++ skip, 4 upsample ++ skip with the seam inside a
+ *   chunk), 8 stem form (0 none, 1 flat-K stem kernel, 2 generic kernel with unaligned channels), 9 in_bf, 10 out_bf,
+ *   11 fuse_head, 12 deepest split of the layer's producers (km: 1 = finished inputs), 13 one chunk per workgroup,
+ *   14 keep_activations, 15 bf16 mode. */
+int psm_unet_plan_detail(const psm_unet* u, int32_t idx, int32_t* info, int32_t n);
 /* Dispatch-level time of every launch of the forward pass: `steps` passes on the handle's stream, each dispatch stamped with
  * its own begin / end by hipExtLaunchKernelGGL (the timestamps rocprofv3 --kernel-trace reads; no marker packets between
  * the layers).  us [num_convs]: average duration in microseconds of the launch that STARTS at convolution i -- a fused pair

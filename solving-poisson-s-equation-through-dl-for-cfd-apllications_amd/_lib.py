@@ -142,6 +142,7 @@ SIGNATURES_UNET = {
     "psm_unet_set_choices": (C.c_int, [_up, _i32ptr, C.c_int32]),
     "psm_unet_ksplit": (C.c_int, [_up, C.c_int32]),
     "psm_unet_plan_info": (C.c_int, [_up, C.c_int32, _i32ptr]),
+    "psm_unet_plan_detail": (C.c_int, [_up, C.c_int32, _i32ptr, C.c_int32]),
     "psm_unet_time_kernels": (C.c_int, [_up, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_double), _i32ptr, C.c_char_p]),
     "psm_unet_time_kernels_q": (C.c_int, [_up, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double), _i32ptr, C.c_char_p]),

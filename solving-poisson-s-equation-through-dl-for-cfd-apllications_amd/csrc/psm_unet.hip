@@ -162,7 +162,7 @@ __device__ __forceinline__ f32x4 fetch4_stem(const PsmConvArgs& a, const float* 
 // Loop-invariant part of one 4-channel fetch (pixel position -> element offsets, padding predicate), computed once
 // per workgroup: inside the chunk loop a fetch is then one add and one (slab-summed) 16-byte load.  The address
 // arithmetic would otherwise run again for every chunk, in front of the MFMAs (~600 VALU instructions per chunk).
-struct PsmFetchPos {
+struct PsmFetchPos {   // 32-bit offsets: a case's tensor holds < 2^31 elements (psm_unet_plan checks it)
   int off0;      // element offset of channel 0 of the source pixel in in0 (for max-pool: its top-left pixel)
   int off1;      // same in the skip input
   bool ok;       // inside the image (else the zero padding)
@@ -370,8 +370,9 @@ __global__ __launch_bounds__(256 * KW) void psm_conv3x3_kernel(PsmConvArgs a, in
       if constexpr (ABF) {                  // 8 bf16 channels per 16-byte load, element offsets in halves
         const unsigned short* h0 = reinterpret_cast<const unsigned short*>(a.in0) + (int64_t)cs * a.in0_case;
         const unsigned short* h1 = reinterpret_cast<const unsigned short*>(a.in1) + (int64_t)cs * a.in1_case;
-        // a wave-uniform base pointer + an unsigned 32-bit element offset per lane (offsets into a case's tensor are non-negative and
-        // below 2^31: act_layout): the scalar-base form of global_load, one or two vector instructions per request instead of a 64-bit chain
+        // a wave-uniform base pointer + an unsigned 32-bit element offset per lane (offsets into a case's tensor are non-negative,
+        // PsmFetchPos holds them as int, and psm_unet_plan refuses any shape whose per-case tensors reach 2^31 elements): the
+        // scalar-base form of global_load, one or two vector instructions per request instead of a 64-bit chain
         if constexpr (SRCP == PSM_SRC_MAXPOOL) {
           const unsigned e = (unsigned)(fp[u].off0 + chc);
           xr[u][0] = *reinterpret_cast<const f32x4*>(h0 + e);

@@ -82,6 +82,7 @@ void free_dev(void* p) { if (p) (void)psm_dev_free(p); }
 // and 4 when it is read through a 2x2 max-pool; right / bottom the last 30 x 14 tile's overhang + halo (32 / 16), doubled
 // through a max-pool (64 / 32).  288 GB of HBM: the 20-45 % of extra footprint are never traffic.
 constexpr int ACT_PADL = 4, ACT_PADT = 4, ACT_PADR = 64, ACT_PADB = 32;
+constexpr int64_t PSM_UNET_MAX_CASE_ELEMS = (int64_t)1 << 31;   // per-case tensor elements the 32-bit loader offsets reach (psm_unet_plan)
 void act_layout(Conv& c, int H, int W, bool padded) {
   c.padded = padded;
   if (padded) {
@@ -517,6 +518,23 @@ int psm_unet_plan(psm_unet* u, int32_t ny, int32_t nx, int32_t max_cases) {
   const int m = 1 << (u->L - 1);
   if (ny < m || nx < m || ny % m || nx % m) return fail(u, PSM_ERR_ARG, "ny and nx must be multiples of 2^(n_levels-1)");
   if (max_cases < 1 || (int64_t)ny * nx * max_cases > ((int64_t)1 << 28)) return fail(u, PSM_ERR_ARG, "bad case batch");
+  {
+    // The 3x3 loaders address a case's input tensor with 32-bit element offsets (psm_unet.hip: PsmFetchPos::off0 / off1 are int,
+    // the bf16 loaders add channel and row offsets to them as unsigned): every tensor a loader reads -- the image, and each
+    // activation at its own resolution, which covers the max-pool source's doubled extent and the upsample / skip sources -- must
+    // hold fewer than 2^31 elements per case.  Counted on the zero-haloed layout in bf16 mode (act_layout: whether a tensor is
+    // stored haloed depends on choices a re-plan may change) and on the dense float32 layout otherwise; split-K slabs are
+    // addressed per slab with 64-bit strides.
+    int64_t worst = (int64_t)ny * nx * u->c_in;
+    for (size_t i = 0; i + 1 < u->convs.size(); ++i) {
+      const Conv& c = u->convs[i];
+      const int64_t H = ny >> c.level, W = nx >> c.level;
+      worst = std::max(worst, u->bf16 ? (ACT_PADT + H + ACT_PADB) * (ACT_PADL + W + ACT_PADR) * c.cout : H * W * c.cout);
+    }
+    if (worst >= PSM_UNET_MAX_CASE_ELEMS)
+      return fail(u, PSM_ERR_ARG, "image too large: a case's activation tensor would hold " + std::to_string(worst) +
+                                  " elements, the convolution loaders' 32-bit offsets allow fewer than 2^31 per case");
+  }
   UCHK(u, hipSetDevice(u->device));
   UCHK(u, hipStreamSynchronize(u->stream));
   u->ny = ny; u->nx = nx; u->max_cases = max_cases;
@@ -990,6 +1008,24 @@ int psm_unet_plan_info(const psm_unet* u, int32_t idx, int32_t* info) {
   const Conv& c = u->convs[idx];
   info[0] = psm_conv_tile_rows(c.arrangement); info[1] = c.nct; info[2] = c.ksplit; info[3] = c.pair | (c.x6 ? 4 : 0) | (c.kw == 2 ? 8 : 0);
   return PSM_OK;
+}
+
+int psm_unet_plan_detail(const psm_unet* u, int32_t idx, int32_t* info, int32_t n) {
+  if (!u || !info || n < 0 || !u->planned || idx < 0 || idx >= (int)u->convs.size()) return PSM_ERR_ARG;
+  const Conv& c = u->convs[idx];
+  int src = c.src == 0 ? 0 : c.src == 1 ? 1 : c.src == 2 ? 2 : 3;
+  int km = 1;
+  if (c.src != 0) km = std::max(km, u->convs[idx - 1].ksplit);
+  if (c.src == 3) {
+    km = std::max(km, u->convs[c.skip].ksplit);
+    if (u->convs[idx - 1].cout % ((u->bf16 || c.x6) ? 32 : 16) != 0) src = 4;       // the launchers' seam_inside
+  }
+  const int stem = c.stem ? 1 : (c.k == 3 && c.src == 0 && c.cin % 4 != 0) ? 2 : 0;
+  const int v[16] = {c.arrangement, c.nct, c.ksplit, c.kw, c.x6 ? 1 : 0, c.pair, c.pair ? c.pair_kind : 0, src, stem,
+                     c.in_bf ? 1 : 0, c.out_bf ? 1 : 0, c.fuse_head ? 1 : 0, km,
+                     (c.n_chunks + c.ksplit - 1) / c.ksplit <= 1 ? 1 : 0, u->keep_act ? 1 : 0, u->bf16};
+  for (int k = 0; k < 16 && k < n; ++k) info[k] = v[k];
+  return 16;
 }
 
 int psm_unet_debug_run_layer(psm_unet* u, int32_t idx, float* stamps_us) {

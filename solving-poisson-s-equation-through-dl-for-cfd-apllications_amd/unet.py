@@ -163,6 +163,21 @@ class UNetSurrogate:
         self._chk(self.lib.psm_unet_plan_info(self.h, idx, info))
         return [int(v) for v in info]
 
+    PLAN_DETAIL_FIELDS = ("arrangement", "nct", "ksplit", "kw", "x6", "pair", "pair_kind", "src", "stem", "in_bf", "out_bf",
+                          "fuse_head", "km", "one", "keep", "bf16")
+
+    def plan_detail(self, idx: int) -> dict:
+        """Everything the launchers dispatch on for convolution idx (psm_unet_plan_detail): a dict keyed by PLAN_DETAIL_FIELDS --
+        src 0 image / 1 previous / 2 max-pool / 3 upsample ++ skip / 4 the same with the seam inside a chunk; stem 0 none / 1 flat-K
+        stem kernel / 2 generic kernel on unaligned channels; km the deepest split of the layer's producers; one = one chunk per
+        workgroup."""
+        n = len(self.PLAN_DETAIL_FIELDS)
+        info = (C.c_int32 * n)()
+        rc = self.lib.psm_unet_plan_detail(self.h, idx, info, n)
+        if rc < n:
+            self._chk(rc if rc < 0 else -1)
+        return dict(zip(self.PLAN_DETAIL_FIELDS, (int(v) for v in info)))
+
     def time_kernels(self, d_grid: int, n_cases: int, d_field: int, steps: int = 20, quantiles: bool = False):
         """Dispatch-level timing -> per launch (first conv index, convs covered, kernel name, MEDIAN us) -- psm_unet_time_kernels_q;
         with ``quantiles`` a fifth element (p10 us, p90 us).  (The mean of psm_unet_time_kernels let one slow dispatch pick the
