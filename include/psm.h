@@ -61,6 +61,10 @@ extern "C" {
 #define PSM_STAGE_BLOCK_PRED 2 /* [rows, S*S*c_out] decoded blocks (PM:365-366)      */
 #define PSM_STAGE_OFFSETS    3 /* [cases, c_out, B] per-block corrections (BC_coor)  */
 #define PSM_STAGE_SHIFT      4 /* [cases, c_out] global shift (PM:472)               */
+/* [rows, n_out(l)] output of hidden Dense layer l as the next launch read it (after a standalone LayerNormalization; before
+ * one the next launch applies itself), rows in row-major order: stage PSM_STAGE_HIDDEN + l, 0 <= l < layers - 1.  Needs
+ * keep mode (PSM_KEEP_HIDDEN=1 at psm_create: every hidden layer writes a buffer of its own; off by default). */
+#define PSM_STAGE_HIDDEN    16
 
 /* kernels of one solve, in launch order (psm_profile_solve) */
 #define PSM_K_ENCODE   0
@@ -375,7 +379,9 @@ int psm_integrate_gradp(psm_handle* h, const float* gradp, float* p_out);
 int psm_synchronize(psm_handle* h);
 
 /* ---- introspection ------------------------------------------------------- */
-/* Copy an intermediate of the LAST solve to host memory (float32). */
+/* Copy an intermediate of the LAST solve to host memory (float32).  PSM_ERR_STATE when that solve did not leave it: it ran
+ * on a ring slot's workspace (psm_submit_grid*, psm_ring_submit), or, for PSM_STAGE_BLOCK_PRED, on the geometry-bound path,
+ * which never stores the decoded blocks. */
 int psm_read_stage(psm_handle* h, int32_t stage, float* dst, size_t dst_floats);
 /* Run one solve with a HIP event pair around every kernel group on the
  * launch stream; ms[PSM_K_COUNT] receives the durations in milliseconds. */

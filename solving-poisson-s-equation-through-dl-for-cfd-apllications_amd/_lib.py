@@ -20,6 +20,7 @@ VARIANTS = {"chapter5": 0, "deltas": 1, "gradp": 2}
 SCALERS = {"max_abs": 0, "std": 1, "min_max": 2}
 PRECISIONS = {"f32": 0, "bf16": 1}
 STAGES = {"x_input": 0, "res": 1, "block_pred": 2, "offsets": 3, "shift": 4}
+STAGE_HIDDEN = 16        # psm.h PSM_STAGE_HIDDEN: hidden Dense layer l is stage STAGE_HIDDEN + l (keep mode)
 KERNELS = ("encode", "reduce", "mlp", "decode", "strips", "chain", "paste")
 ERRORS = {0: "PSM_OK", -1: "PSM_ERR_ARG", -2: "PSM_ERR_STATE", -3: "PSM_ERR_HIP", -4: "PSM_ERR_NO_DEVICE",
           -5: "PSM_ERR_UNSUPPORTED", -6: "PSM_ERR_NOMEM", -7: "PSM_ERR_GEOMETRY"}

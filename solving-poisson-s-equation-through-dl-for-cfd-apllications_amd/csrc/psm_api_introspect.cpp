@@ -66,6 +66,13 @@ int psm_read_stage(psm_handle* h, int32_t stage, float* dst, size_t dst_floats) 
   HIPCHK(h, hipSetDevice(h->cfg.device));
   HIPCHK(h, hipDeviceSynchronize());
   const int M = h->last_cases * h->B;
+  const bool hidden = stage >= PSM_STAGE_HIDDEN && stage - PSM_STAGE_HIDDEN < (int)h->dense.size() - 1;
+  const bool data_stage = (stage >= PSM_STAGE_X_INPUT && stage <= PSM_STAGE_SHIFT) || hidden;
+  if (!data_stage && stage != 5 && stage != 6) return fail(h, PSM_ERR_ARG, "unknown stage");
+  if (data_stage && !h->last_on_ws0)
+    return fail(h, PSM_ERR_STATE, "the last solve ran on a ring slot's workspace: its intermediates are not readable");
+  if (stage == PSM_STAGE_BLOCK_PRED && !h->last_pred_stored)
+    return fail(h, PSM_ERR_STATE, "the last solve did not store the decoded blocks (the geometry-bound path pastes them directly)");
   auto rows = [&](const float* src, int ld, int width) -> int {
     if (dst_floats < (size_t)M * width) return fail(h, PSM_ERR_ARG, "destination too small");
     HIPCHK(h, psm_copy_d2h_2d(dst, (size_t)width * sizeof(float), src, (size_t)ld * sizeof(float), (size_t)width * sizeof(float), M));
@@ -81,7 +88,8 @@ int psm_read_stage(psm_handle* h, int32_t stage, float* dst, size_t dst_floats) 
         // the last solve took the closed form: run the chain itself once, from the strip means of the same activations
         const int nl = (int)h->dense.size();
         const bool bf = h->cfg.precision == PSM_PRECISION_BF16;
-        const float* act = bf ? h->ws0.d_res : (h->last_act_packed ? h->ws0.d_act_rows : h->ws0.d_act[(nl - 2) & 1]);
+        const float* act = bf ? h->ws0.d_res : !h->d_keep.empty() ? h->d_keep[nl - 2]
+                                                  : (h->last_act_packed ? h->ws0.d_act_rows : h->ws0.d_act[(nl - 2) & 1]);
         const int ld_act = bf ? h->ld_out : h->dense[nl - 2].ldw;
         PsmDotsArgs dd{h->d_g2, h->d_c2, h->d_cnt, h->d_row_of, h->last_row_scale ? h->last_row_scale : h->d_ones, h->ws0.d_dots,
                        h->bound_rows * h->last_cases, bf ? h->ld_out : h->dense[nl - 1].Kpad, PsmGuardArgs{}};
@@ -125,6 +133,11 @@ int psm_read_stage(psm_handle* h, int32_t stage, float* dst, size_t dst_floats) 
       dst[63] = 0.f;
       return PSM_OK;
     }
+  }
+  if (hidden) {
+    if (h->d_keep.empty()) return fail(h, PSM_ERR_STATE, "hidden activations are kept only in keep mode (PSM_KEEP_HIDDEN=1 at psm_create)");
+    const DenseLayer& d = h->dense[stage - PSM_STAGE_HIDDEN];
+    return rows(h->d_keep[stage - PSM_STAGE_HIDDEN], d.ldw, d.n_out);
   }
   return fail(h, PSM_ERR_ARG, "unknown stage");
 }

@@ -282,6 +282,9 @@ int psm_solve_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank,
         e = hipGraphInstantiate(&h->mesh_graph, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) { h->mesh_graph = nullptr; return fail(h, PSM_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
+        h->mesh_graph_state = ws0_state(h);
+      } else {
+        set_ws0_state(h, h->mesh_graph_state);
       }
       HIPCHK(h, hipGraphLaunch(h->mesh_graph, st));
     }

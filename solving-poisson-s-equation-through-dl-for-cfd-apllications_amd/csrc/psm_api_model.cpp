@@ -68,6 +68,7 @@ int scratch_reserve(psm_handle* h, size_t dev_bytes, size_t pin_bytes) {
 void destroy_graphs(psm_handle* h) {
   for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
   h->graphs.clear();
+  h->graph_state.clear();
   if (h->mesh_graph) { (void)hipGraphExecDestroy(h->mesh_graph); h->mesh_graph = nullptr; }
   ring_drop_graphs(h);
 }
@@ -108,6 +109,8 @@ void free_plan(psm_handle* h) {
   h->ring_ready = false;
   destroy_graphs(h);
   ws_free(h->ws0);
+  for (auto& p : h->d_keep) dev_free(p);
+  h->d_keep.clear();
   dev_free(h->d_row_base); dev_free(h->d_ones); dev_free(h->d_strips);
   dev_free(h->d_blk); dev_free(h->d_owner); dev_free(h->d_shiftA); dev_free(h->d_shiftB); dev_free(h->d_shiftOwnA); dev_free(h->d_shiftOwnB); dev_free(h->d_shiftW); dev_free(h->d_blocks);
   dev_free(h->d_stamps); dev_free(h->d_grid_stage); dev_free(h->d_fields_stage);
@@ -296,6 +299,7 @@ int psm_create(const psm_config* cfg, psm_handle** out) {
     const char* ng = getenv("PSM_NO_GUARD");
     h->guard_on = !(ng && ng[0] == '1');
     h->x6_mode = getenv("PSM_X6") ? atoi(getenv("PSM_X6")) : -1;
+    h->keep_hidden = getenv("PSM_KEEP_HIDDEN") && atoi(getenv("PSM_KEEP_HIDDEN")) != 0;
     if (hipHostMalloc((void**)&h->h_guard, 64 * sizeof(int), hipHostMallocMapped) == hipSuccess) {
       memset(h->h_guard, 0, 64 * sizeof(int));
       if (hipHostGetDevicePointer((void**)&h->m_guard, h->h_guard, 0) != hipSuccess) { (void)hipGetLastError(); h->m_guard = nullptr; }

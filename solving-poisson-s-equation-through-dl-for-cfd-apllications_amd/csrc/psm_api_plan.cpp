@@ -261,6 +261,12 @@ int psm_plan_grid(psm_handle* h, int32_t ny, int32_t nx) {
   const size_t npix = (size_t)ny * nx;
   h->n_bands = h->S / PSM_STRIP_BAND;
   if ((rc = ws_alloc(h, h->ws0))) return rc;
+  for (auto& p : h->d_keep) dev_free(p);
+  h->d_keep.assign(h->keep_hidden ? h->dense.size() - 1 : 0, nullptr);
+  for (auto& p : h->d_keep) {                              // padding columns are read by the next layer: zero like d_act
+    if ((rc = dev_alloc(h, &p, (size_t)h->Mpad_cap * h->max_width))) return rc;
+    HIPCHK(h, hipMemset(p, 0, (size_t)h->Mpad_cap * h->max_width * sizeof(float)));
+  }
   if ((rc = dev_alloc(h, &h->d_stamps, (size_t)16))) return rc;
   HIPCHK(h, hipMemset(h->d_stamps, 0, 16 * sizeof(unsigned long long)));
   if ((rc = dev_alloc(h, &h->d_grid_stage, (size_t)h->cfg.max_cases * npix * h->cfg.c_in))) return rc;

@@ -56,6 +56,18 @@ int ensure_encode_aux(psm_handle* h, int n_cases) {
 }
 
 
+Ws0Solve ws0_state(const psm_handle* h) {
+  Ws0Solve s;
+  s.pred_stored = h->last_pred_stored; s.used_cf = h->last_used_cf; s.act_packed = h->last_act_packed; s.row_scale = h->last_row_scale;
+  return s;
+}
+
+void set_ws0_state(psm_handle* h, const Ws0Solve& s) {
+  h->last_on_ws0 = true;
+  h->last_pred_stored = s.pred_stored; h->last_used_cf = s.used_cf; h->last_act_packed = s.act_packed; h->last_row_scale = s.row_scale;
+}
+
+
 int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, float* d_fields, const float* d_row_scale,
                hipStream_t st, hipEvent_t* prof) {
   const int M = n_cases * h->B, Mpad = round_up(M, 32);
@@ -116,7 +128,10 @@ int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, fl
   // case batches (and single cases of more than 64 blocks) on a bound geometry: closed form of the chain where it was built
   const bool use_cf = use_bound && h->bound_cf && w.d_dots2;
   const int CB = h->cfg.c_out * h->B;
-  if (&w == &h->ws0) { h->last_row_scale = d_row_scale; h->last_used_cf = use_cf; }
+  if (&w == &h->ws0) {
+    h->last_row_scale = d_row_scale; h->last_used_cf = use_cf;
+    h->last_pred_stored = !use_bound && !((h->debug_skip >> PSM_K_DECODE) & 1);
+  }
   PsmReduceArgs ra{w.d_part, w.d_xin, h->d_ia, h->d_ib, n_slabs, Mpad, h->ld_in};
   const int nl = (int)h->dense.size();
   // Large case batches (more than 128 block rows): the activation between two plain float32 Dense launches in MFMA operand order
@@ -146,6 +161,11 @@ int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, fl
     // the head's strip-dot riders (and psm_read_stage) read whole rows: the last hidden layer also leaves a row-major copy
     if (da.out_packed && l == nl - 2) da.out_rows = w.d_act_rows;
     if (da.in_packed && head) da.in_rows = w.d_act_rows;
+    // keep mode: output pointers only -- a hidden layer stores into its own buffer (packed chains: its row-major copy there)
+    if (&w == &h->ws0 && !h->d_keep.empty()) {
+      if (!head) { if (da.out_packed) da.out_rows = h->d_keep[l]; else da.out = h->d_keep[l]; }
+      if (head && da.in_packed) da.in_rows = h->d_keep[nl - 2];
+    }
     return da;
   };
   // few block rows: slab reduce + first dense layer in one launch (one workgroup per row)
@@ -396,6 +416,9 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
     (void)hipGraphDestroy(graph);
     if (e != hipSuccess) return fail(h, PSM_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
     it = h->graphs.emplace(key, exec).first;
+    h->graph_state[key] = ws0_state(h);            // launch_all ran for the capture
+  } else {
+    set_ws0_state(h, h->graph_state[key]);        // a replay runs no host code of launch_all
   }
   HIPCHK(h, hipGraphLaunch(it->second, st));
   return PSM_OK;
@@ -530,6 +553,7 @@ int ring_capture(psm_handle* h, psm_handle::Slot& s, int n_cases, bool scale, co
 // registered caller memory).
 int ring_launch(psm_handle* h, psm_handle::Slot& s, int n_cases, const float* out_scale, const float* src, float* dst) {
   { int rc0 = ensure_encode_aux(h, n_cases); if (rc0) return rc0; }
+  h->last_on_ws0 = false;                               // captured or replayed, the ticket runs on the slot's workspace
   const size_t npix = (size_t)h->Ny * h->Nx;
   const size_t gin = (size_t)n_cases * npix * h->cfg.c_in * sizeof(float), gout = (size_t)n_cases * npix * h->cfg.c_out * sizeof(float);
   const bool scale = out_scale != nullptr;

@@ -59,6 +59,10 @@ struct Conv1dLayer {            // conv1D_PCA head (NNs.py:75-124)
   bool set = false;
 };
 
+// What a solve on ws0 left there, set by launch_all when the launches are enqueued or captured.  A graph replay does not run
+// launch_all: the state its capture recorded is put back on every replay (psm_read_stage and psm_block_error read it).
+struct Ws0Solve { bool pred_stored = false, used_cf = false, act_packed = false; const float* row_scale = nullptr; };
+
 struct GraphKey {
   int n; const void* g; void* f;
   bool operator<(const GraphKey& o) const { return std::tie(n, g, f) < std::tie(o.n, o.g, o.f); }
@@ -123,6 +127,7 @@ struct psm_handle {
   double* pinned_p_dev = nullptr;       // device-side address of the registered output (the last kernel writes p straight into it)
   const double* pinned_cells_dev = nullptr;   // device-side address of the registered input (psm_stage_cells_kernel reads it over PCIe)
   hipGraphExec_t mesh_graph = nullptr;  // psm_solve on registered buffers: stage + to_grid + the solve + to_mesh as ONE graph replay
+  Ws0Solve mesh_graph_state;            // what mesh_graph leaves on ws0
   double maxs[4] = {1, 1, 1, 1};
   int normalise_sdf = 0, fill_input = 0;
   double case_maxs[4] = {1, 1, 1, 1}, case_delta = 5e-3, case_wall = 0.05;   // psm_set_case (PM:106-109, 195, 494)
@@ -166,6 +171,7 @@ struct psm_handle {
   int scale_pos = 0;
   hipStream_t stream = nullptr;
   std::map<GraphKey, hipGraphExec_t> graphs;
+  std::map<GraphKey, Ws0Solve> graph_state;   // what each captured graph leaves on ws0
   bool use_graph = true;
   bool fused_assemble = false;
   // scratch of the helper entries (gaussian filter, mesh -> grid, Poisson features, gradp integration): one device and one
@@ -196,6 +202,11 @@ struct psm_handle {
   const float* last_row_scale = nullptr;   // row scale of the last solve on ws0 (introspection)
   bool last_act_packed = false;         // the last solve on ws0 left its last hidden activation in MFMA operand order (PsmDenseArgs::out_packed)
   bool last_used_cf = false;            // the last solve on ws0 took the closed form: offsets / shift are computed on demand
+  bool last_pred_stored = false;        // the last solve on ws0 stored the decoded blocks (general path; the bound path pastes them)
+  // keep mode (PSM_KEEP_HIDDEN=1 at psm_create): hidden Dense layer l of a ws0 solve writes d_keep[l] ([Mpad_cap][max_width],
+  // row-major; where the chain is packed, its row-major copy) instead of a ping-pong buffer, for psm_read_stage(PSM_STAGE_HIDDEN + l)
+  bool keep_hidden = false;
+  std::vector<float*> d_keep;
   // guard of the bound-geometry contract (psm_kernels.h PsmGuardArgs)
   unsigned long long* d_maskbits = nullptr;   // bound flow-cell pattern, one 64-pixel ballot per word
   int guard_ballots = 0, guard_waves = 0;
@@ -259,6 +270,8 @@ int ring_capture(psm_handle* h, psm_handle::Slot& s, int n_cases, bool scale, co
                         bool with_copies, hipGraphExec_t* out);
 int ring_launch(psm_handle* h, psm_handle::Slot& s, int n_cases, const float* out_scale, const float* src, float* dst);
 int ring_check(psm_handle* h, int32_t n_cases);
+Ws0Solve ws0_state(const psm_handle* h);
+void set_ws0_state(psm_handle* h, const Ws0Solve& s);
 int ring_guard_rerun(psm_handle* h, psm_handle::Slot& s, const char* where);
 int slot_of(psm_handle* h, int64_t ticket, int state, psm_handle::Slot** out);
 int collect_kernel_samples(psm_handle* h, const float* d_grid, int32_t n_cases, float* d_fields, int32_t steps,

@@ -359,9 +359,17 @@ class GridSurrogate:
         return out
 
     # -- introspection
-    def stage(self, name: str, n_cases: int = 1) -> np.ndarray:
+    def stage(self, name: str, n_cases: int = 1, layer: int = 0) -> np.ndarray:
+        """An intermediate of the last solve; ``name='hidden'``: the output of hidden Dense layer ``layer`` (the handle must have
+        been created with PSM_KEEP_HIDDEN=1 in the environment)."""
         m = self.model
         rows = n_cases * self.B
+        if name == "hidden":
+            if not 0 <= layer < len(m.weights) - 1:
+                raise ValueError("layer must name a hidden Dense layer")
+            out = np.empty((rows, np.shape(m.weights[layer][0])[1]), np.float32)
+            self._chk(self.lib.psm_read_stage(self.h, _lib.STAGE_HIDDEN + layer, _p(out, C.c_float), out.size))
+            return out
         shape = {"x_input": (rows, m.p_in), "res": (rows, m.p_out), "block_pred": (rows, m.S, m.S, m.c_out),
                  "offsets": (n_cases, m.c_out, self.B), "shift": (n_cases, m.c_out)}[name]
         out = np.empty(shape, np.float32)
