@@ -1,6 +1,8 @@
 // psm_api_introspect.cpp -- C-ABI of libpsm_hip.so (include/psm.h): stage read-back, profiling, kernel timing, host-side reference.  See psm_handle.h for the map of the five files.
 #include "psm_handle.h"
 
+thread_local PsmLaunchProbe* psm_launch_probe = nullptr;   // psm_launch.h: installed by collect_kernel_samples below and by psm_unet_time_kernels
+
 namespace psm_impl {
 
 

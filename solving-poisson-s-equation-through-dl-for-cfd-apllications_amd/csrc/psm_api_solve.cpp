@@ -35,7 +35,7 @@ int encode_groups(const psm_handle* h, int Mpad) {
   if (kg_env > 0) groups = kg_env;
   return (groups > 1 && groups <= h->n_slices && (h->n_slices + groups - 1) / groups <= 8) ? groups : 1;
 }
-// Slabs the float32 / x6 encode launch (psm_launch_encode, psm_kernels.hip) writes for these arguments = what the reduce behind it must sum.
+// Slabs the float32 / x6 encode launch (psm_launch_encode, psm_encode.hip) writes for these arguments = what the reduce behind it must sum.
 // ONE place mirrors the launcher's three branches (the count used to be rebuilt step by step inside launch_all).
 static int encode_slabs(const PsmEncodeArgs& a) {
   const int n_slices = a.S * a.S / PSM_PIX_PER_SLICE;

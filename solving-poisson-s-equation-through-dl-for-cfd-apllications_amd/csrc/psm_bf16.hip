@@ -3,24 +3,11 @@
 // even, v_cvt_pk_bf16_f32), products are exact and accumulated in f32 by
 // v_mfma_f32_32x32x16_bf16.  Halves the streamed basis bytes and cuts the MFMA time 16x, so
 // both kernels become pure HBM/MALL streams.  Same launch geometry, slab layout and epilogues
-// as the f32 kernels (psm_kernels.hip); reference lines: PM:341-352 (encode), PM:365-366 /
-// SMD:541-551 (decode).
-//
-// MFMA operand maps (wave64, 32x32x16): lane l (r = l&31, h = l>>5) holds A[r][8h+j] and
-// B[8h+j][r], j = 0..7 (one 16-byte register group each); D as for the f32 32x32 form.
+// as the f32 kernels (psm_encode_kernel in psm_encode.hip, psm_decode_kernel in psm_decode.hip); reference lines:
+// PM:341-352 (encode), PM:365-366 / SMD:541-551 (decode).  MFMA operand maps (wave64, 32x32x16): psm_mfma.h.
 #include "psm_kernels.h"
 #include "psm_devutil.h"
-
-#include <hip/hip_ext.h>
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
-#define MFMA_BF16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ int acc_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
+#include "psm_mfma.h"
 
 // ---------------------------------------------------------------------------
 // encode
@@ -44,18 +31,18 @@ __global__ __launch_bounds__(256) void psm_encode_bf16_kernel(PsmEncodeArgs a) {
   const float4 mu = *reinterpret_cast<const float4*>(a.mean + (int64_t)s * KS + 4 * ql);
   const bf16x8* bpack = reinterpret_cast<const bf16x8*>(a.bpack);
 
-  auto load_rows = [&](v4f (&x)[8], int m0, int row0) {
+  auto load_rows = [&](f32x4 (&x)[8], int m0, int row0) {
     int64_t rb[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) rb[u] = psm_row_base(a.row_base, min(m0 + row0 + wave + 4 * u, a.M - 1));
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const float* src = a.grid + rb[u] + src_off + 4 * ql;
-      if (ALIGNED) x[u] = *reinterpret_cast<const v4f*>(src);
-      else x[u] = (v4f){src[0], src[1], src[2], src[3]};
+      if (ALIGNED) x[u] = *reinterpret_cast<const f32x4*>(src);
+      else x[u] = (f32x4){src[0], src[1], src[2], src[3]};
     }
   };
-  auto write_rows = [&](const v4f (&x)[8], int m0, int row0) {
+  auto write_rows = [&](const f32x4 (&x)[8], int m0, int row0) {
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
       const int row = row0 + wave + 4 * u;
@@ -85,7 +72,7 @@ __global__ __launch_bounds__(256) void psm_encode_bf16_kernel(PsmEncodeArgs a) {
   int cur_t = -1;
   for (int m0 = 0; m0 < a.Mpad; m0 += 32 * PSM_MT_CHUNK) {
     const int rows = min(32 * PSM_MT_CHUNK, a.Mpad - m0);
-    v4f x0[8];
+    f32x4 x0[8];
     load_rows(x0, m0, 0);                       // activation rows first, then the weight stream
     __builtin_amdgcn_sched_barrier(0);
     if (m0 == 0 && wave < NT) {
@@ -97,7 +84,7 @@ __global__ __launch_bounds__(256) void psm_encode_bf16_kernel(PsmEncodeArgs a) {
     __builtin_amdgcn_sched_barrier(0);
     write_rows(x0, m0, 0);
     for (int row0 = 32; row0 < rows; row0 += 32) {
-      v4f x[8];
+      f32x4 x[8];
       load_rows(x, m0, row0);
       write_rows(x, m0, row0);
     }
@@ -119,16 +106,7 @@ hipError_t psm_launch_encode_bf16(const PsmEncodeArgs& a, hipStream_t st, hipEve
   const int n_slices = a.S * a.S / PSM_PIX_PER_SLICE;
   const int rows = a.Mpad < 32 * PSM_MT_CHUNK ? a.Mpad : 32 * PSM_MT_CHUNK;
   const size_t lds = (size_t)rows * (PSM_PIX_PER_SLICE * a.c_in + 8) * 2;
-#define ENC2(C, AL)                                                                                          \
-  if (ev_start) hipExtLaunchKernelGGL((psm_encode_bf16_kernel<C, AL>), dim3(n_slices), dim3(256), (std::uint32_t)lds, st, ev_start, ev_stop, 0, a); \
-  else PSM_LAUNCH((psm_encode_bf16_kernel<C, AL>), dim3(n_slices), dim3(256), lds, st, a)
-#define ENC(C) case C: if (a.aligned) { ENC2(C, true); } else { ENC2(C, false); } break;
-  switch (a.c_in) {
-    ENC(1) ENC(2) ENC(3) ENC(4)
-    default: return hipErrorInvalidValue;
-  }
-#undef ENC
-#undef ENC2
+  PSM_LAUNCH_ENCODE_FAMILY(psm_encode_bf16_kernel, dim3(n_slices), lds, st, ev_start, ev_stop, a);
   return hipGetLastError();
 }
 
@@ -148,7 +126,7 @@ __global__ __launch_bounds__(256) void psm_decode_bf16_kernel(PsmDecodeArgs a, i
   for (int idx = tid; idx < MTC * 32 * Q; idx += 256) {
     const int row = idx / Q, q = idx - row * Q;
     const int m = min(m_base + row, a.Mpad - 1);
-    const v4f x = *reinterpret_cast<const v4f*>(a.res + (int64_t)m * a.ld_res + 4 * q);
+    const f32x4 x = *reinterpret_cast<const f32x4*>(a.res + (int64_t)m * a.ld_res + 4 * q);
     bf16x4 v;
     v[0] = (__bf16)x.x; v[1] = (__bf16)x.y; v[2] = (__bf16)x.z; v[3] = (__bf16)x.w;
     *reinterpret_cast<bf16x4*>(&ldsb[row * LDA + 4 * q]) = v;

@@ -28,3 +28,25 @@ extern thread_local PsmLaunchProbe* psm_launch_probe;
     }                                                                                                                 \
   } while (0)
 
+
+// The encode kernel families are templates on <c_in, aligned>: the one ladder over both for all of them (psm_launch_encode,
+// psm_launch_encode_bf16).  With events, hipExtLaunchKernelGGL stamps them with the dispatch's own begin / end times (the
+// source rocprofv3 reads), not with separate marker packets around the launch; without, PSM_LAUNCH.  A macro, not a function
+// template: PSM_LAUNCH records the kernel's name by stringising `(family<C, AL>)` after C and AL were substituted, and tools key
+// on those names.  Returns hipErrorInvalidValue from the calling function for a c_in outside 1..4.
+#define PSM_ENCODE_LAUNCH_(family, C, AL, grid, lds, st, ev0, ev1, a)                                                              \
+  if (ev0) hipExtLaunchKernelGGL((family<C, AL>), grid, dim3(256), (std::uint32_t)(lds), st, ev0, ev1, 0, a);                      \
+  else PSM_LAUNCH((family<C, AL>), grid, dim3(256), lds, st, a)
+#define PSM_ENCODE_CASE_(family, C, grid, lds, st, ev0, ev1, a)                                                                    \
+  case C:                                                                                                                         \
+    if ((a).aligned) { PSM_ENCODE_LAUNCH_(family, C, true, grid, lds, st, ev0, ev1, a); }                                         \
+    else { PSM_ENCODE_LAUNCH_(family, C, false, grid, lds, st, ev0, ev1, a); }                                                    \
+    break;
+#define PSM_LAUNCH_ENCODE_FAMILY(family, grid, lds, st, ev0, ev1, a)                                                               \
+  switch ((a).c_in) {                                                                                                             \
+    PSM_ENCODE_CASE_(family, 1, grid, lds, st, ev0, ev1, a)                                                                       \
+    PSM_ENCODE_CASE_(family, 2, grid, lds, st, ev0, ev1, a)                                                                       \
+    PSM_ENCODE_CASE_(family, 3, grid, lds, st, ev0, ev1, a)                                                                       \
+    PSM_ENCODE_CASE_(family, 4, grid, lds, st, ev0, ev1, a)                                                                       \
+    default: return hipErrorInvalidValue;                                                                                         \
+  }

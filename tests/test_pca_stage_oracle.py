@@ -375,7 +375,7 @@ def _b(v):
 
 
 def solve_path_table():
-    """Every solve-path instantiation the launchers compile (psm_kernels.hip, psm_bf16.hip), as demangled without spaces."""
+    """Every solve-path instantiation the launchers compile (the stage files psm_encode / psm_dense / psm_decode / psm_assemble / psm_bound .hip, and psm_bf16.hip), as demangled without spaces."""
     t = set()
     for kern in _ENC_FORMS:
         t |= {f"{kern}<{c},{_b(al)}>" for c in (1, 2, 3, 4) for al in (False, True)}

@@ -38,9 +38,12 @@ def _short(k):
         elif ch == "(" and depth == 0: return k[:i]
     return k
 json.dump({"workload": "config1", "kernel_source_hash": _bench.kernel_source_hash(), "profile_tag": tag,
-           "unit": "HBM-side bytes per launch = (2*FETCH_SIZE + WRITE_SIZE) * 1024; separate --pmc passes with --kernel-trace only",
+           "unit": "HBM-side bytes per launch = (2*FETCH_SIZE + WRITE_SIZE) * 1024; separate --pmc passes, one counter each",
            "kernels": {_short(r[0]): r[3] for r in rows}}, open(_bench.PMC_FILE, "w"), indent=1)
-st = sorted(glob.glob(f"{O}/stats/*/*kernel_stats.csv"))[-1]
+st = sorted(glob.glob(f"{O}/stats/*/*kernel_stats.csv"))
+if not st:                       # counter passes only (the kernel sources moved, the timings did not): the two files above are all
+    sys.exit(0)
+st = st[-1]
 shutil.copy(st, f"profiles/{tag}_kernel_stats.csv")
 # per-kernel median / p10 / p90 from the same trace (bench.py's roofline uses medians; --stats reports means)
 import subprocess
