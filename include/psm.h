@@ -375,6 +375,31 @@ int psm_set_integration(psm_handle* h, int32_t ny, int32_t nx, const double* sdf
                         int32_t center_x, double dx, double dy);
 int psm_integrate_gradp(psm_handle* h, const float* gradp, float* p_out);
 
+/* The same integration on the device, in stream order and for a case batch: the step that turns the gradP variant's
+ * solve (psm_solve_grid_device leaves (dp/dx, dp/dy) in device memory) into a pressure without leaving the device.
+ * Two launches for the whole batch (row scans of every case, then column scans + stitching means + the add).
+ * psm_bind_integration: one integration geometry per case slot of the PLANNED grid (c_out == 2): sdfunct
+ * [n_cases][ny*nx] float64, center_y / center_x [n_cases], spacings as psm_set_integration.  All-or-nothing:
+ * PSM_ERR_UNSUPPORTED (the message names the case and the reason) where the reference itself raises for ANY case, and
+ * then nothing is bound.  A psm_plan_grid or a model change drops the binding like it drops the geometry binding.
+ * It is independent of psm_set_integration, whose single geometry of any size stays with the host entry above.
+ * State errors (PSM_ERR_STATE): nothing bound, n_cases != the bound count, c_out != 2, plan dropped after the bind.
+ * A NaN in the gradient reaches every p that is integrated through it; after a trip of the bound-geometry guard the
+ * gradient is NaN everywhere and so is p (no special case; psm_synchronize reports the trip as for the solve). */
+int psm_bind_integration(psm_handle* h, const double* sdfunct, int32_t n_cases,
+                         const int32_t* center_y, const int32_t* center_x, double dx, double dy);
+int psm_unbind_integration(psm_handle* h);
+/* d_gradp [n_cases,ny,nx,2] (8-byte aligned) -> d_p [n_cases,ny,nx], device pointers, asynchronous on `stream`
+ * (NULL: the handle's) */
+int psm_integrate_gradp_device(psm_handle* h, const float* d_gradp, int32_t n_cases, float* d_p, void* stream);
+/* psm_solve_grid_device + the integration in the same stream.  d_gradp may be NULL (the gradient then lives in a
+ * buffer of the handle) or receive the assembled gradient as psm_solve_grid_device would have written it. */
+int psm_solve_pressure_device(psm_handle* h, const float* d_grid, int32_t n_cases, const float* out_scale,
+                              float* d_gradp, float* d_p, void* stream);
+/* host buffers, synchronous: grid [n_cases,ny,nx,c_in] -> p [n_cases,ny,nx] (one H2D, one D2H of half the size).
+ * Like psm_solve_grid it solves again on the general path when the bound-geometry guard trips. */
+int psm_solve_pressure(psm_handle* h, const float* grid, int32_t n_cases, const float* out_scale, float* p);
+
 /* Wait for everything submitted through this handle. */
 int psm_synchronize(psm_handle* h);
 
@@ -399,7 +424,8 @@ int psm_get_kernel_timing(psm_handle* h, int32_t kernel, double* total_ms, int64
  * psm_solve_grid_device on the handle's stream, each dispatch stamped with its own begin / end by
  * hipExtLaunchKernelGGL (the timestamps rocprofv3 --kernel-trace reads).  names [cap][64] receives the kernel
  * names in first-launch order, total_ms / launches [cap] their accumulated duration and dispatch count,
- * *n_kernels the number of distinct kernels (may exceed cap). */
+ * *n_kernels the number of distinct kernels (may exceed cap).  While an integration is bound for n_cases cases
+ * (psm_bind_integration) the timed step is that of psm_solve_pressure_device: its two launches are stamped too. */
 int psm_time_kernels(psm_handle* h, const float* d_grid, int32_t n_cases, float* d_fields, int32_t steps, char* names,
                      double* total_ms, int64_t* launches, int32_t cap, int32_t* n_kernels);
 /* The same pass, reported per kernel as the MEDIAN and the 10th / 90th percentile of its dispatch durations in microseconds

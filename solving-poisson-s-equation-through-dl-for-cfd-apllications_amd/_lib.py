@@ -97,6 +97,11 @@ SIGNATURES = {
     "psm_gaussian_filter": (C.c_int, [_hp, _f32p, C.c_int32, C.c_int32, C.c_double, C.c_double, _f32p]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
+    "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),
+    "psm_unbind_integration": (C.c_int, [_hp]),
+    "psm_integrate_gradp_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "psm_solve_pressure_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, _f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_solve_pressure": (C.c_int, [_hp, _f32p, C.c_int32, _f32p, _f32p]),
     "psm_synchronize": (C.c_int, [_hp]),
     "psm_read_stage": (C.c_int, [_hp, C.c_int32, _f32p, C.c_size_t]),
     "psm_profile_solve": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_void_p, _f32p]),

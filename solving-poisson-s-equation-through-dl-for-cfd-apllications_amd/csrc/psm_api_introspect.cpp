@@ -45,7 +45,9 @@ int collect_kernel_samples(psm_handle* h, const float* d_grid, int32_t n_cases, 
   int rc = PSM_OK;
   psm_launch_probe = &probe;
   for (int i = 0; i < steps && rc == PSM_OK; ++i) {
-    rc = solve_device(h, d_grid, n_cases, nullptr, d_fields, h->stream, nullptr);
+    // with an integration bound for this case count (psm_bind_integration) the step is U -> p: its two launches are stamped too
+    const bool integ = h->integ_dev.ready && h->integ_dev.n_cases == n_cases && h->cfg.c_out == 2 && (reinterpret_cast<uintptr_t>(d_fields) & 7) == 0;
+    rc = solve_device(h, d_grid, n_cases, nullptr, d_fields, h->stream, nullptr, integ ? h->integ_dev.d_p : nullptr);
     if (rc == PSM_OK && (i % 64) == 63) rc = drain();
   }
   psm_launch_probe = nullptr;

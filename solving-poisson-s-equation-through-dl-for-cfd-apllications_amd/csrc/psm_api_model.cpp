@@ -122,6 +122,7 @@ void free_plan(psm_handle* h) {
   // (The registered host arrays stay registered; the graph that holds their addresses goes with the plan.)
   h->have_geometry = false;
   if (h->mesh_graph) { (void)hipGraphExecDestroy(h->mesh_graph); h->mesh_graph = nullptr; }
+  integ_free(h->integ_dev);             // psm_bind_integration is sized by this plan's grid
 }
 
 
@@ -179,8 +180,7 @@ void free_geometry(psm_handle* h) {
   dev_free(h->d_vtx_m2g); dev_free(h->d_src_of_cell); dev_free(h->d_vtx_g2m); dev_free(h->d_cell_of_point);
   dev_free(h->d_wts_m2g); dev_free(h->d_sdf); dev_free(h->d_wts_g2m); dev_free(h->d_cells); dev_free(h->d_p);
   dev_free(h->d_umax); dev_free(h->d_umax_part); dev_free(h->d_near_wall);
-  dev_free(h->d_fixups); dev_free(h->d_pairs); dev_free(h->d_integ_buf); dev_free(h->d_gradp);
-  h->have_integ = false;
+  integ_free(h->integ_host); integ_free(h->integ_dev);
   if (h->h_cells) { (void)hipHostFree(h->h_cells); h->h_cells = nullptr; }
   if (h->h_p) { (void)hipHostFree(h->h_p); h->h_p = nullptr; }
   h->have_geometry = false;
@@ -351,6 +351,7 @@ int psm_set_pca(psm_handle* h, const double* comp_in, const double* mean_in, con
   HIPCHK(h, hipSetDevice(h->cfg.device));
   destroy_graphs(h);
   h->bound = false;
+  h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   std::vector<float> mi(h->K_in), mo(h->K_out);
   for (int k = 0; k < h->K_in; ++k) mi[k] = (float)mean_in[k];
   for (int k = 0; k < h->K_out; ++k) mo[k] = (float)mean_out[k];
@@ -405,6 +406,7 @@ int psm_set_dense(psm_handle* h, int32_t layer, int32_t n_in, int32_t n_out, con
   HIPCHK(h, hipSetDevice(h->cfg.device));
   destroy_graphs(h);
   h->bound = false;
+  h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   DenseLayer& d = h->dense[layer];
   d.linear = false;                                     // psm_set_attention sets it again after this call
   if (d.ln && (d.n_out != n_out || (d.ln_residual && n_in != n_out))) {      // a LayerNormalization of another width, or its residual x + input on a
@@ -491,6 +493,7 @@ int psm_set_layernorm(psm_handle* h, int32_t layer, int32_t n, const float* gamm
   HIPCHK(h, hipStreamSynchronize(h->stream));
   destroy_graphs(h);
   h->bound = false;
+  h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   // zero-padded to whole 16-byte pieces past the consumer's leading dimension: a Dense launch that applies this normalisation to
   // its input (launch_all) reads gamma / beta with the clamped column index of its operand loads
   std::vector<float> g(round_up(n, 32) + 32, 0.f), b(round_up(n, 32) + 32, 0.f);
@@ -518,6 +521,7 @@ int psm_set_conv1d(psm_handle* h, int32_t layer, int32_t n_layers, int32_t kerne
   HIPCHK(h, hipStreamSynchronize(h->stream));
   destroy_graphs(h);
   h->bound = false;
+  h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   if (!same_stack) {
     for (auto& c : h->conv1d) { dev_free(c.W); dev_free(c.b); }
     h->conv1d.assign(n_layers, Conv1dLayer{});
@@ -543,6 +547,7 @@ int psm_set_scaler(psm_handle* h, const double* in_a, const double* in_b, const 
   HIPCHK(h, hipStreamSynchronize(h->stream));
   destroy_graphs(h);                          // captured launches hold the addresses of the arrays re-uploaded below
   h->bound = false;
+  h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   std::vector<float> ia(h->ld_in, 0.f), ib(h->ld_in, 0.f), sa(h->ld_out, 0.f), sb(h->ld_out, 0.f);
   // x_in = coeff*ia + ib ; res' = res*sa + sb  (affine forms of SMD:505-539, evaluated in f64 here)
   for (int p = 0; p < h->cfg.p_in; ++p) {

@@ -3,7 +3,7 @@
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       the launch sequence of one solve (launch_all), psm_solve_grid*, the pinned submission ring
-//   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*), evaluator helpers (labels, block error, filters, integration)
+//   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*), evaluator helpers (labels, block error, filters), the gradP integration (host entry and device-resident U -> p)
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -65,7 +65,8 @@ struct Ws0Solve { bool pred_stored = false, used_cf = false, act_packed = false;
 
 struct GraphKey {
   int n; const void* g; void* f;
-  bool operator<(const GraphKey& o) const { return std::tie(n, g, f) < std::tie(o.n, o.g, o.f); }
+  void* p = nullptr;                    // psm_solve_pressure*: where the integration behind the solve writes p (null: the solve alone)
+  bool operator<(const GraphKey& o) const { return std::tie(n, g, f, p) < std::tie(o.n, o.g, o.f, o.p); }
 };
 
 // Everything ONE in-flight solve writes.  The handle owns one for the synchronous / device entries (ws0) and one per
@@ -82,6 +83,17 @@ struct Workspace {
   float* d_c1[2] = {nullptr, nullptr}; // Conv1D activations of the conv1D_PCA head (ping-pong), [Mpad][c1_stride]
   float* d_gflags = nullptr;          // guard flags of the bound-geometry contract (psm_kernels.h PsmGuardArgs; allocated by the bind)
   int gidx = 0;                       // this workspace's word in the handle's mapped guard page (0 = ws0, 1 + i = ring slot i)
+};
+
+// Device tables of one integration binding (PsmIntegArgs, psm_mesh.h) and the handle's own gradient / pressure buffers.
+struct IntegSet {
+  bool ready = false;
+  int n_cases = 0;
+  int2 *d_fix = nullptr, *d_cuts = nullptr, *d_npair = nullptr;
+  uint8_t* d_mask = nullptr;
+  float4* d_aux = nullptr;
+  float *d_gradp = nullptr, *d_p = nullptr;
+  PsmIntegArgs args{};
 };
 }  // namespace psm_impl
 using namespace psm_impl;
@@ -116,11 +128,9 @@ struct psm_handle {
   int32_t *d_vtx_m2g = nullptr, *d_src_of_cell = nullptr, *d_vtx_g2m = nullptr, *d_cell_of_point = nullptr;
   double *d_wts_m2g = nullptr, *d_sdf = nullptr, *d_wts_g2m = nullptr, *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;
   uint8_t* d_near_wall = nullptr;
-  // U_to_gradP integration (psm_set_integration)
-  bool have_integ = false;
-  PsmIntegArgs integ{};
-  int2 *d_fixups = nullptr, *d_pairs = nullptr;
-  float *d_integ_buf = nullptr, *d_gradp = nullptr;
+  // U_to_gradP integration: the evaluator's single geometry of any size (psm_set_integration, host buffers) and the case
+  // batch on the planned grid (psm_bind_integration, device buffers)
+  IntegSet integ_host, integ_dev;
   double *h_cells = nullptr, *h_p = nullptr;
   const double* pinned_cells = nullptr;   // caller buffers registered with psm_pin_buffers (DMA without staging copies)
   double* pinned_p = nullptr;
@@ -245,6 +255,8 @@ std::vector<float4> pack_comp_in(const double* comp, int P, int K, int c_in, int
 std::vector<float4> pack_comp_out(const double* comp, int P, int K_out, int Gd);
 void unpin_buffers(psm_handle* h);
 void free_geometry(psm_handle* h);
+void integ_free(IntegSet& s);
+int integrate_device(psm_handle* h, const float* d_gradp, int n_cases, float* d_p, hipStream_t st);
 std::vector<uint16_t> pack_comp_in_bf16(const double* comp, int P, int K, int c_in, int S, int NT);
 std::vector<uint16_t> pack_comp_out_bf16(const double* comp, int P, int K_out, int G);
 bool model_complete(const psm_handle* h);
@@ -253,8 +265,9 @@ int ensure_encode_aux(psm_handle* h, int n_cases);
 int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, float* d_fields, const float* d_row_scale,
                hipStream_t st, hipEvent_t* prof);
 int prepare_scale(psm_handle* h, Workspace& w, const float* out_scale, int n_cases, hipStream_t st, const float** d_scale);
+// d_p != nullptr: the bound integration (psm_bind_integration) of d_fields into d_p follows in the same stream / the same graph
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
-                 hipStream_t st, hipEvent_t* prof);
+                 hipStream_t st, hipEvent_t* prof, float* d_p = nullptr);
 int mesh_sequence(psm_handle* h, int64_t n, hipStream_t st);
 bool guard_take(psm_handle* h, Workspace& w);
 int guard_drop(psm_handle* h, const char* where);

@@ -358,6 +358,57 @@ class GridSurrogate:
         self._chk(self.lib.psm_integrate_gradp(self.h, _p(g, C.c_float), _p(out, C.c_float)))
         return out
 
+    # -- U -> p on the device (gradP variant): psm_bind_integration once, then one call per step
+    def bind_integration(self, sdfunct, center_y, center_x, dx: float, dy: float) -> bool:
+        """One integration geometry per case slot of the planned grid: ``sdfunct`` [Ny,Nx] with scalar cuts, or [n,Ny,Nx]
+        with length-n ``center_y`` / ``center_x``.  Returns False -- nothing bound -- where the reference itself raises for
+        any case (unequal flow-cell counts on the cut columns, ``int(sdfunct)`` outside a quadrant row)."""
+        sd = _f64(np.asarray(sdfunct))
+        if sd.ndim == 2:
+            sd = sd[None]
+        if sd.ndim != 3 or sd.shape[1:] != (self.ny, self.nx):
+            raise ValueError(f"sdfunct must be [{self.ny},{self.nx}] or [n,{self.ny},{self.nx}]")
+        n = sd.shape[0]
+        cy = np.ascontiguousarray(np.broadcast_to(np.asarray(center_y, np.int32).reshape(-1), (n,)))
+        cx = np.ascontiguousarray(np.broadcast_to(np.asarray(center_x, np.int32).reshape(-1), (n,)))
+        rc = self.lib.psm_bind_integration(self.h, _p(sd, C.c_double), n, _p(cy, C.c_int32), _p(cx, C.c_int32), float(dx), float(dy))
+        if rc == -5:                    # PSM_ERR_UNSUPPORTED
+            return False
+        self._chk(rc)
+        return True
+
+    def unbind_integration(self):
+        self._chk(self.lib.psm_unbind_integration(self.h))
+
+    def integrate_device(self, d_gradp: int, n_cases: int, d_p: int, stream: int = 0):
+        """(dp/dx, dp/dy) [n,Ny,Nx,2] -> p [n,Ny,Nx] on raw device pointers, asynchronous on ``stream``."""
+        self._chk(self.lib.psm_integrate_gradp_device(self.h, C.c_void_p(d_gradp), n_cases, C.c_void_p(d_p), C.c_void_p(stream)))
+
+    def solve_pressure_device(self, d_grid: int, n_cases: int, d_p: int, d_gradp: int = 0, stream: int = 0,
+                              out_scale: Optional[Sequence[float]] = None):
+        """Solve + integration in one stream on raw device pointers: grid [n,Ny,Nx,c_in] -> p [n,Ny,Nx]; ``d_gradp``
+        (optional) receives the assembled gradient [n,Ny,Nx,2]."""
+        sc = _f32(np.broadcast_to(out_scale, (n_cases,))) if out_scale is not None else None
+        self._chk(self.lib.psm_solve_pressure_device(self.h, C.c_void_p(d_grid), n_cases,
+                                                     _p(sc, C.c_float) if sc is not None else None,
+                                                     C.c_void_p(d_gradp or None), C.c_void_p(d_p), C.c_void_p(stream)))
+
+    def solve_pressure(self, grid: np.ndarray, out_scale: Optional[Sequence[float]] = None) -> np.ndarray:
+        """grid [Ny,Nx,>=c_in] or [n,Ny,Nx,>=c_in] -> p [n,Ny,Nx] f32 (host buffers, synchronous)."""
+        g = np.asarray(grid)
+        if g.ndim == 3:
+            g = g[None]
+        if g.ndim != 4 or g.shape[1:3] != (self.ny, self.nx) or g.shape[3] < self.model.c_in:
+            raise ValueError(f"grid must be [n,{self.ny},{self.nx},>={self.model.c_in}]")
+        g = _f32(g[..., :self.model.c_in])
+        n = g.shape[0]
+        self._check_bound(g)
+        out = np.empty((n, self.ny, self.nx), np.float32)
+        sc = _f32(np.broadcast_to(out_scale, (n,))) if out_scale is not None else None
+        self._chk(self.lib.psm_solve_pressure(self.h, _p(g, C.c_float), n, _p(sc, C.c_float) if sc is not None else None,
+                                              _p(out, C.c_float)))
+        return out
+
     # -- introspection
     def stage(self, name: str, n_cases: int = 1, layer: int = 0) -> np.ndarray:
         """An intermediate of the last solve; ``name='hidden'``: the output of hidden Dense layer ``layer`` (the handle must have
