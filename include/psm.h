@@ -364,6 +364,36 @@ int psm_poisson_features(psm_handle* h, const double* ux, const double* uy, cons
 int psm_gaussian_filter(psm_handle* h, const float* in, int32_t ny, int32_t nx, double sigma_y,
                         double sigma_x, float* out);
 
+/* The same filter, and the whole tail of assemble_prediction (SM_call.py:352-363), on the device: in stream order, for a
+ * case batch on the PLANNED grid, float32.
+ *     result = gaussian_filter(field, sigma_field)                       if apply_filter
+ *     w      = gaussian_filter(dU, sigma_weight)
+ *     change = gaussian_filter((result - prev) * w, sigma_field);   next = prev + change   (pressureSM_Poisson, :843-848)
+ * One launch per separable pass for the whole batch (csrc/psm_filter.hip): at most 4 launches with the weighting, 2 for a
+ * filter alone.  Every output is the plain sum over its taps in a fixed order: case i of a batch is bit-identical to the same
+ * field alone, and an output is NaN exactly where SciPy's is.
+ * psm_bind_poststeps: sigma_field[2] / sigma_weight[2] = (sigma_y, sigma_x) of the two filters ((10,10) and (50,50) in the
+ * reference).  Uploads the tap tables and reserves per-case scratch for max_cases cases: after it a step allocates nothing
+ * and copies nothing.  PSM_ERR_ARG for a sigma that is not in (0, 1e4].  A psm_plan_grid or a model change drops the binding.
+ * State errors (PSM_ERR_STATE) of the entries below: nothing bound, plan dropped after the bind, c_out != 1 with d_dU. */
+int psm_bind_poststeps(psm_handle* h, const double* sigma_field, const double* sigma_weight);
+int psm_unbind_poststeps(psm_handle* h);
+/* d_in [n_cases,ny,nx,c_out] -> d_out, sigma_field on every channel; device pointers, asynchronous on `stream` (NULL: the
+ * handle's); d_out may be d_in. */
+int psm_filter_fields_device(psm_handle* h, const float* d_in, int32_t n_cases, float* d_out, void* stream);
+/* The tail above on d_fields [n_cases,ny,nx] (c_out == 1): d_dU, d_prev [n_cases,ny,nx]; d_result receives the (filtered)
+ * field and may be d_fields; d_change and d_next may each be NULL.  d_dU == NULL: filter only (apply_filter == 0: a copy),
+ * any c_out. */
+int psm_poststeps_device(psm_handle* h, const float* d_fields, int32_t n_cases, int32_t apply_filter, const float* d_dU,
+                         const float* d_prev, float* d_result, float* d_change, float* d_next, void* stream);
+/* psm_solve_grid_device + the tail in the same stream, as one graph replay; the solved field lives in a buffer of the handle. */
+int psm_solve_poststeps_device(psm_handle* h, const float* d_grid, int32_t n_cases, const float* out_scale, int32_t apply_filter,
+                               const float* d_dU, const float* d_prev, float* d_result, float* d_change, float* d_next, void* stream);
+/* host buffers, synchronous; dU == NULL: filter only.  Like psm_solve_grid it solves again on the general path when the
+ * bound-geometry guard trips. */
+int psm_solve_poststeps(psm_handle* h, const float* grid, int32_t n_cases, const float* out_scale, int32_t apply_filter,
+                        const float* dU, const float* prev, float* result, float* change, float* next);
+
 /* U_to_gradP: integrate the assembled (dp/dx, dp/dy) into p (integrate_field,
  * Eval_dual_Dense_onlycil.py:371-416, and the four-quadrant stitching :597-628).
  * psm_set_integration fixes the geometry: sdfunct [ny*nx] (self.sdfunct[:,:,0], also used by the
@@ -425,7 +455,9 @@ int psm_get_kernel_timing(psm_handle* h, int32_t kernel, double* total_ms, int64
  * hipExtLaunchKernelGGL (the timestamps rocprofv3 --kernel-trace reads).  names [cap][64] receives the kernel
  * names in first-launch order, total_ms / launches [cap] their accumulated duration and dispatch count,
  * *n_kernels the number of distinct kernels (may exceed cap).  While an integration is bound for n_cases cases
- * (psm_bind_integration) the timed step is that of psm_solve_pressure_device: its two launches are stamped too. */
+ * (psm_bind_integration) the timed step is that of psm_solve_pressure_device: its two launches are stamped too; while
+ * post-steps are bound on a c_out == 1 handle (psm_bind_poststeps), that of psm_solve_poststeps_device with the weighting
+ * and apply_filter (dU and prev: the handle's scratch). */
 int psm_time_kernels(psm_handle* h, const float* d_grid, int32_t n_cases, float* d_fields, int32_t steps, char* names,
                      double* total_ms, int64_t* launches, int32_t cap, int32_t* n_kernels);
 /* The same pass, reported per kernel as the MEDIAN and the 10th / 90th percentile of its dispatch durations in microseconds

@@ -95,6 +95,12 @@ SIGNATURES = {
     "psm_unpin_buffers": (C.c_int, [_hp]),
     "psm_mesh_to_grid": (C.c_int, [_hp, _f64p, C.c_int64, C.c_int32, C.c_int32, _f64p]),
     "psm_gaussian_filter": (C.c_int, [_hp, _f32p, C.c_int32, C.c_int32, C.c_double, C.c_double, _f32p]),
+    "psm_bind_poststeps": (C.c_int, [_hp, _f64p, _f64p]),
+    "psm_unbind_poststeps": (C.c_int, [_hp]),
+    "psm_filter_fields_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "psm_poststeps_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_solve_poststeps_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_solve_poststeps": (C.c_int, [_hp, _f32p, C.c_int32, _f32p, C.c_int32, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
     "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),

@@ -47,7 +47,12 @@ int collect_kernel_samples(psm_handle* h, const float* d_grid, int32_t n_cases, 
   for (int i = 0; i < steps && rc == PSM_OK; ++i) {
     // with an integration bound for this case count (psm_bind_integration) the step is U -> p: its two launches are stamped too
     const bool integ = h->integ_dev.ready && h->integ_dev.n_cases == n_cases && h->cfg.c_out == 2 && (reinterpret_cast<uintptr_t>(d_fields) & 7) == 0;
-    rc = solve_device(h, d_grid, n_cases, nullptr, d_fields, h->stream, nullptr, integ ? h->integ_dev.d_p : nullptr);
+    // with post-steps bound on a c_out == 1 handle (psm_bind_poststeps) it is the step of psm_solve_poststeps_device with the
+    // weighting; dU and prev are the handle's scratch, whatever it holds
+    PostCall pc;
+    const bool post = h->post.ready && h->cfg.c_out == 1;
+    if (post) { pc.apply_filter = 1; pc.dU = h->post.d_dU; pc.prev = h->post.d_prev; pc.result = h->post.d_out; pc.change = h->post.d_out + (size_t)h->cfg.max_cases * h->Ny * h->Nx; pc.next = pc.change + (size_t)h->cfg.max_cases * h->Ny * h->Nx; }
+    rc = solve_device(h, d_grid, n_cases, nullptr, d_fields, h->stream, nullptr, integ ? h->integ_dev.d_p : nullptr, post ? &pc : nullptr);
     if (rc == PSM_OK && (i % 64) == 63) rc = drain();
   }
   psm_launch_probe = nullptr;

@@ -505,46 +505,6 @@ int psm_unpin_buffers(psm_handle* h) {
 }
 
 
-int psm_gaussian_filter(psm_handle* h, const float* in, int32_t ny, int32_t nx, double sigma_y, double sigma_x, float* out) {
-  if (!h) return PSM_ERR_ARG;
-  if (!in || !out || ny < 1 || nx < 1 || (int64_t)ny * nx > ((int64_t)1 << 28)) return fail(h, PSM_ERR_ARG, "bad field");
-  if (!(sigma_y > 0.0) || !(sigma_x > 0.0) || sigma_y > 1e4 || sigma_x > 1e4) return fail(h, PSM_ERR_ARG, "sigma must be positive");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  hipStream_t st = h->stream;
-  const size_t n = (size_t)ny * nx;
-  float *d_a = nullptr, *d_b = nullptr, *d_w = nullptr;
-  int rc = PSM_OK;
-  auto weights = [](double sigma, std::vector<float>& w) {      // scipy.ndimage._gaussian_kernel1d, order 0
-    const int r = (int)(4.0 * sigma + 0.5);
-    std::vector<double> p(2 * r + 1);
-    double sum = 0.0;
-    for (int x = -r; x <= r; ++x) { p[x + r] = std::exp(-0.5 / (sigma * sigma) * (double)x * (double)x); sum += p[x + r]; }
-    w.resize(2 * r + 1);
-    for (int k = 0; k < 2 * r + 1; ++k) w[k] = (float)(p[k] / sum);
-    return r;
-  };
-  std::vector<float> wy, wx;
-  const int ry = weights(sigma_y, wy), rx = weights(sigma_x, wx);
-  std::vector<float> wall(wy);
-  wall.insert(wall.end(), wx.begin(), wx.end());
-  const size_t nb = n * sizeof(float), wb = wall.size() * sizeof(float);
-  if ((rc = scratch_reserve(h, carve_size({nb, nb, wb}), carve_size({nb, wb})))) return rc;
-  Carver cd{(char*)h->scr_dev}, cp{(char*)h->scr_pin};
-  d_a = cd.take<float>(n); d_b = cd.take<float>(n); d_w = cd.take<float>(wall.size());
-  float* p_io = cp.take<float>(n); float* p_w = cp.take<float>(wall.size());
-  memcpy(p_io, in, nb); memcpy(p_w, wall.data(), wb);
-  hipError_t e = hipMemcpyAsync(d_a, p_io, nb, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_w, p_w, wb, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = psm_launch_gauss1d(d_a, d_b, ny, nx, 0, ry, d_w, st);
-  if (e == hipSuccess) e = psm_launch_gauss1d(d_b, d_a, ny, nx, 1, rx, d_w + wy.size(), st);
-  if (e == hipSuccess) e = hipMemcpyAsync(p_io, d_a, nb, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = wait_stream(st);
-  if (e == hipSuccess) memcpy(out, p_io, nb);
-  if (e != hipSuccess) return fail(h, PSM_ERR_HIP, std::string("gaussian filter: ") + hipGetErrorString(e));
-  return PSM_OK;
-}
-
-
 int psm_mesh_to_grid(psm_handle* h, const double* values, int64_t n, int32_t k, int32_t fill, double* grid_out) {
   if (!h) return PSM_ERR_ARG;
   if (!h->have_geometry) return fail(h, PSM_ERR_STATE, "psm_set_geometry has not been called");

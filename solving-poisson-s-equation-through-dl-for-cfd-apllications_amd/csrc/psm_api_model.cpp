@@ -123,6 +123,7 @@ void free_plan(psm_handle* h) {
   h->have_geometry = false;
   if (h->mesh_graph) { (void)hipGraphExecDestroy(h->mesh_graph); h->mesh_graph = nullptr; }
   integ_free(h->integ_dev);             // psm_bind_integration is sized by this plan's grid
+  post_free(h->post);                   // and so is psm_bind_poststeps
 }
 
 
@@ -352,6 +353,7 @@ int psm_set_pca(psm_handle* h, const double* comp_in, const double* mean_in, con
   destroy_graphs(h);
   h->bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
+  h->post.ready = false;                 // and so does psm_bind_poststeps
   std::vector<float> mi(h->K_in), mo(h->K_out);
   for (int k = 0; k < h->K_in; ++k) mi[k] = (float)mean_in[k];
   for (int k = 0; k < h->K_out; ++k) mo[k] = (float)mean_out[k];
@@ -407,6 +409,7 @@ int psm_set_dense(psm_handle* h, int32_t layer, int32_t n_in, int32_t n_out, con
   destroy_graphs(h);
   h->bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
+  h->post.ready = false;                 // and so does psm_bind_poststeps
   DenseLayer& d = h->dense[layer];
   d.linear = false;                                     // psm_set_attention sets it again after this call
   if (d.ln && (d.n_out != n_out || (d.ln_residual && n_in != n_out))) {      // a LayerNormalization of another width, or its residual x + input on a
@@ -494,6 +497,7 @@ int psm_set_layernorm(psm_handle* h, int32_t layer, int32_t n, const float* gamm
   destroy_graphs(h);
   h->bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
+  h->post.ready = false;                 // and so does psm_bind_poststeps
   // zero-padded to whole 16-byte pieces past the consumer's leading dimension: a Dense launch that applies this normalisation to
   // its input (launch_all) reads gamma / beta with the clamped column index of its operand loads
   std::vector<float> g(round_up(n, 32) + 32, 0.f), b(round_up(n, 32) + 32, 0.f);
@@ -522,6 +526,7 @@ int psm_set_conv1d(psm_handle* h, int32_t layer, int32_t n_layers, int32_t kerne
   destroy_graphs(h);
   h->bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
+  h->post.ready = false;                 // and so does psm_bind_poststeps
   if (!same_stack) {
     for (auto& c : h->conv1d) { dev_free(c.W); dev_free(c.b); }
     h->conv1d.assign(n_layers, Conv1dLayer{});
@@ -548,6 +553,7 @@ int psm_set_scaler(psm_handle* h, const double* in_a, const double* in_b, const 
   destroy_graphs(h);                          // captured launches hold the addresses of the arrays re-uploaded below
   h->bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
+  h->post.ready = false;                 // and so does psm_bind_poststeps
   std::vector<float> ia(h->ld_in, 0.f), ib(h->ld_in, 0.f), sa(h->ld_out, 0.f), sb(h->ld_out, 0.f);
   // x_in = coeff*ia + ib ; res' = res*sa + sb  (affine forms of SMD:505-539, evaluated in f64 here)
   for (int p = 0; p < h->cfg.p_in; ++p) {

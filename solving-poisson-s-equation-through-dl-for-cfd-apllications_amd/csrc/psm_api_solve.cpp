@@ -386,7 +386,7 @@ int prepare_scale(psm_handle* h, Workspace& w, const float* out_scale, int n_cas
 
 
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
-                 hipStream_t st, hipEvent_t* prof, float* d_p) {
+                 hipStream_t st, hipEvent_t* prof, float* d_p, const PostCall* post) {
   if (!h) return PSM_ERR_ARG;
   if (!h->planned) return fail(h, PSM_ERR_STATE, "psm_plan_grid has not been called");
   if (!d_grid || !d_fields) return fail(h, PSM_ERR_ARG, "null buffer");
@@ -402,9 +402,12 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
   const bool eager = prof || h->timed_kernel >= 0 || !h->use_graph;
   if (eager) {
     rc = launch_all(h, h->ws0, d_grid, n_cases, d_fields, d_scale, st, prof);
-    return (rc || !d_p) ? rc : integrate_device(h, d_fields, n_cases, d_p, st);
+    if (!rc && d_p) rc = integrate_device(h, d_fields, n_cases, d_p, st);
+    if (!rc && post) rc = poststeps_device(h, d_fields, n_cases, *post, st);
+    return rc;
   }
-  GraphKey key{(n_cases * 2 + (out_scale ? 1 : 0)) * 2 + ((h->bound && (h->bound_scope == 2 || h->in_mesh_solve)) ? 1 : 0), d_grid, d_fields, d_p};
+  GraphKey key{(n_cases * 2 + (out_scale ? 1 : 0)) * 2 + ((h->bound && (h->bound_scope == 2 || h->in_mesh_solve)) ? 1 : 0), d_grid, d_fields, d_p,
+               post ? *post : PostCall{}};
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     if (h->graphs.size() > 64) destroy_graphs(h);
@@ -412,6 +415,7 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
     HIPCHK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeRelaxed));
     rc = launch_all(h, h->ws0, d_grid, n_cases, d_fields, d_scale, h->stream, nullptr);
     if (!rc && d_p) rc = integrate_device(h, d_fields, n_cases, d_p, h->stream);     // the two integration launches end the graph
+    if (!rc && post) rc = poststeps_device(h, d_fields, n_cases, *post, h->stream);   // or the post-steps' (at most four): still one linear chain
     hipError_t e = hipStreamEndCapture(h->stream, &graph);
     if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
     if (e != hipSuccess) return fail(h, PSM_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));

@@ -4,6 +4,7 @@
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       the launch sequence of one solve (launch_all), psm_solve_grid*, the pinned submission ring
 //   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*), evaluator helpers (labels, block error, filters), the gradP integration (host entry and device-resident U -> p)
+//   psm_api_filter.cpp      the Gaussian post-steps: psm_gaussian_filter (host entry), psm_bind_poststeps and the device-resident / case-batched entries
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -63,10 +64,19 @@ struct Conv1dLayer {            // conv1D_PCA head (NNs.py:75-124)
 // launch_all: the state its capture recorded is put back on every replay (psm_read_stage and psm_block_error read it).
 struct Ws0Solve { bool pred_stored = false, used_cf = false, act_packed = false; const float* row_scale = nullptr; };
 
+// What the Gaussian post-steps behind a solve read and write (psm_solve_poststeps*): every pointer is part of the captured launches.
+struct PostCall {
+  int apply_filter = -1;                // -1: no post-steps
+  const float *dU = nullptr, *prev = nullptr;        // dU == nullptr: filter only
+  float *result = nullptr, *change = nullptr, *next = nullptr;
+  auto tie() const { return std::tie(apply_filter, dU, prev, result, change, next); }
+};
+
 struct GraphKey {
   int n; const void* g; void* f;
   void* p = nullptr;                    // psm_solve_pressure*: where the integration behind the solve writes p (null: the solve alone)
-  bool operator<(const GraphKey& o) const { return std::tie(n, g, f, p) < std::tie(o.n, o.g, o.f, o.p); }
+  PostCall post{};                      // psm_solve_poststeps*: the post-steps behind the solve (apply_filter == -1: none)
+  bool operator<(const GraphKey& o) const { return std::tie(n, g, f, p) < std::tie(o.n, o.g, o.f, o.p) || (std::tie(n, g, f, p) == std::tie(o.n, o.g, o.f, o.p) && post.tie() < o.post.tie()); }
 };
 
 // Everything ONE in-flight solve writes.  The handle owns one for the synchronous / device entries (ws0) and one per
@@ -94,6 +104,18 @@ struct IntegSet {
   float4* d_aux = nullptr;
   float *d_gradp = nullptr, *d_p = nullptr;
   PsmIntegArgs args{};
+};
+
+// Binding of the Gaussian post-steps to the planned grid (psm_bind_poststeps): the four tap tables and per-case scratch for
+// max_cases cases, so that a step allocates nothing and copies nothing.
+struct PostSet {
+  bool ready = false;
+  int r_field[2] = {0, 0}, r_weight[2] = {0, 0};         // radii per axis (y, x)
+  float* d_taps = nullptr;                               // the four tables, 16-byte aligned pieces
+  const float *w_field[2] = {nullptr, nullptr}, *w_weight[2] = {nullptr, nullptr};
+  float *d_tmp_a = nullptr, *d_tmp_b = nullptr, *d_t = nullptr;     // axis-0 outputs of field / weighting input [max_cases][npix][c_out], t [max_cases][npix]
+  float* d_fields = nullptr;                             // the solve's field in front of the post-steps [max_cases][npix][c_out]
+  float *d_dU = nullptr, *d_prev = nullptr, *d_out = nullptr;       // staging of the host entry (and of psm_time_kernels): [max_cases][npix], d_out x 3
 };
 }  // namespace psm_impl
 using namespace psm_impl;
@@ -131,6 +153,7 @@ struct psm_handle {
   // U_to_gradP integration: the evaluator's single geometry of any size (psm_set_integration, host buffers) and the case
   // batch on the planned grid (psm_bind_integration, device buffers)
   IntegSet integ_host, integ_dev;
+  PostSet post;                         // Gaussian post-steps on the planned grid (psm_bind_poststeps)
   double *h_cells = nullptr, *h_p = nullptr;
   const double* pinned_cells = nullptr;   // caller buffers registered with psm_pin_buffers (DMA without staging copies)
   double* pinned_p = nullptr;
@@ -257,6 +280,8 @@ void unpin_buffers(psm_handle* h);
 void free_geometry(psm_handle* h);
 void integ_free(IntegSet& s);
 int integrate_device(psm_handle* h, const float* d_gradp, int n_cases, float* d_p, hipStream_t st);
+void post_free(PostSet& s);
+int poststeps_device(psm_handle* h, const float* d_fields, int n_cases, const PostCall& pc, hipStream_t st);
 std::vector<uint16_t> pack_comp_in_bf16(const double* comp, int P, int K, int c_in, int S, int NT);
 std::vector<uint16_t> pack_comp_out_bf16(const double* comp, int P, int K_out, int G);
 bool model_complete(const psm_handle* h);
@@ -265,9 +290,10 @@ int ensure_encode_aux(psm_handle* h, int n_cases);
 int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, float* d_fields, const float* d_row_scale,
                hipStream_t st, hipEvent_t* prof);
 int prepare_scale(psm_handle* h, Workspace& w, const float* out_scale, int n_cases, hipStream_t st, const float** d_scale);
-// d_p != nullptr: the bound integration (psm_bind_integration) of d_fields into d_p follows in the same stream / the same graph
+// d_p != nullptr: the bound integration (psm_bind_integration) of d_fields into d_p follows in the same stream / the same graph;
+// post (apply_filter >= 0): the bound post-steps (psm_bind_poststeps) of d_fields follow likewise
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
-                 hipStream_t st, hipEvent_t* prof, float* d_p = nullptr);
+                 hipStream_t st, hipEvent_t* prof, float* d_p = nullptr, const PostCall* post = nullptr);
 int mesh_sequence(psm_handle* h, int64_t n, hipStream_t st);
 bool guard_take(psm_handle* h, Workspace& w);
 int guard_drop(psm_handle* h, const char* where);

@@ -45,8 +45,28 @@ hipError_t psm_launch_to_grid(const PsmToGridArgs& a, hipStream_t st);
 hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st);
 hipError_t psm_launch_interp_to_grid(const double* values, int k, const int32_t* vtx, const double* wts, const int32_t* src_of_cell,
                                      int fill, double* out, int64_t n_grid, hipStream_t st);
-// one pass of the separable Gaussian filter (axis 0 = rows direction, 1 = columns)
-hipError_t psm_launch_gauss1d(const float* in, float* out, int ny, int nx, int axis, int radius, const float* wts, hipStream_t st);
+
+// ---- Gaussian post-steps (SMD:353-363, UGP:366-367), case-batched: one launch per separable pass, see psm_filter.hip
+struct PsmGaussJob {
+  const float* in;           // [n_cases][ny][nx][c]
+  const float* w;            // [2 * radius + 1] normalised taps
+  int radius;
+};
+struct PsmGaussArgs {
+  PsmGaussJob job[2];        // axis 0: n_jobs independent inputs (blockIdx.z); axis 1 with epilogue 1: field (in == nullptr: not filtered) and weighting input
+  float* out[2];             // axis 0: one per job; axis 1 without an epilogue: out[0]
+  const float* prev;         // epilogues 1 and 2: [n_cases][ny][nx]
+  const float* fields;       // epilogue 1 without job 0: the unfiltered field
+  float* result; float* t;   // epilogue 1: result (may be nullptr), t = (result - prev) * w
+  float* change; float* next;   // epilogue 2: either may be nullptr
+  int ny, nx, c, n_cases, n_jobs;
+  int tap_chunk;             // taps staged at a time (psm_gauss_tap_chunk of the widest table of the launch)
+  int tiles_x;               // set by the launcher
+};
+void psm_gauss_init();
+int psm_gauss_tap_chunk(int max_radius);
+// axis 0: along y, no epilogue.  axis 1: along x, epilogue 0 (none), 1 or 2 (c == 1 only)
+hipError_t psm_launch_gauss(PsmGaussArgs a, int axis, int epi, hipStream_t st);
 
 // label blocks [B][S*S*c_out] with the per-block flow-cell mean removed (SM_call.py:487-488, UGP:509-511)
 hipError_t psm_launch_label_blocks(const float* grid, const float* labels, const int32_t* blk_y0x0, float* out, int B, int S,

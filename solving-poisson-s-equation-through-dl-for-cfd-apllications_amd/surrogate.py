@@ -409,6 +409,71 @@ class GridSurrogate:
                                               _p(out, C.c_float)))
         return out
 
+    # -- Gaussian post-steps on the device (SM_call.py:352-363): psm_bind_poststeps once, then one call per step
+    _post_bound = False
+
+    def bind_poststeps(self, sigma_field=(10.0, 10.0), sigma_weight=(50.0, 50.0)):
+        """Tap tables of the field filter and of the deltaU-change weight filter ((sigma_y, sigma_x) each; the reference's
+        (10,10) and (50,50)) and per-case scratch on the planned grid: after it a step allocates and copies nothing."""
+        sf, sw = _f64(np.asarray(sigma_field, np.float64).reshape(2)), _f64(np.asarray(sigma_weight, np.float64).reshape(2))
+        self._post_bound = False
+        self._chk(self.lib.psm_bind_poststeps(self.h, _p(sf, C.c_double), _p(sw, C.c_double)))
+        self._post_bound = True
+
+    def unbind_poststeps(self):
+        self._post_bound = False
+        self._chk(self.lib.psm_unbind_poststeps(self.h))
+
+    def filter_device(self, d_in: int, n_cases: int, d_out: int, stream: int = 0):
+        """gaussian_filter(sigma_field) of every channel of [n,Ny,Nx,c_out] on raw device pointers (``d_out`` may be
+        ``d_in``), asynchronous on ``stream``: two launches for the batch."""
+        self._chk(self.lib.psm_filter_fields_device(self.h, C.c_void_p(d_in), n_cases, C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def poststeps_device(self, d_fields: int, n_cases: int, d_result: int, apply_filter: bool = True, d_dU: int = 0,
+                         d_prev: int = 0, d_change: int = 0, d_next: int = 0, stream: int = 0):
+        """Tail of ``assemble_prediction`` on raw device pointers [n,Ny,Nx]: result = filter(fields) if ``apply_filter``;
+        with ``d_dU`` / ``d_prev`` also change = filter((result - prev) * filter(dU, sigma_weight)) and next = prev + change
+        (either may be 0).  At most four launches for the batch; ``d_result`` may be ``d_fields``."""
+        self._chk(self.lib.psm_poststeps_device(self.h, C.c_void_p(d_fields), n_cases, int(bool(apply_filter)),
+                                                C.c_void_p(d_dU or None), C.c_void_p(d_prev or None), C.c_void_p(d_result),
+                                                C.c_void_p(d_change or None), C.c_void_p(d_next or None), C.c_void_p(stream)))
+
+    def solve_poststeps_device(self, d_grid: int, n_cases: int, d_result: int, apply_filter: bool = True, d_dU: int = 0,
+                               d_prev: int = 0, d_change: int = 0, d_next: int = 0, stream: int = 0,
+                               out_scale: Optional[Sequence[float]] = None):
+        """Solve + post-steps in one stream (one graph replay) on raw device pointers: grid [n,Ny,Nx,c_in] -> result (and
+        change / next) [n,Ny,Nx]."""
+        sc = _f32(np.broadcast_to(out_scale, (n_cases,))) if out_scale is not None else None
+        self._chk(self.lib.psm_solve_poststeps_device(self.h, C.c_void_p(d_grid), n_cases,
+                                                      _p(sc, C.c_float) if sc is not None else None, int(bool(apply_filter)),
+                                                      C.c_void_p(d_dU or None), C.c_void_p(d_prev or None), C.c_void_p(d_result),
+                                                      C.c_void_p(d_change or None), C.c_void_p(d_next or None), C.c_void_p(stream)))
+
+    def solve_poststeps(self, grid: np.ndarray, apply_filter: bool = False, dU=None, prev=None,
+                        out_scale: Optional[Sequence[float]] = None):
+        """Host buffers, synchronous: grid [Ny,Nx,>=c_in] or [n,Ny,Nx,>=c_in] -> (result [n,Ny,Nx,c_out], change, next); change
+        and next [n,Ny,Nx] are None without ``dU`` / ``prev`` [n,Ny,Nx] (filter only)."""
+        g = np.asarray(grid)
+        if g.ndim == 3:
+            g = g[None]
+        if g.ndim != 4 or g.shape[1:3] != (self.ny, self.nx) or g.shape[3] < self.model.c_in:
+            raise ValueError(f"grid must be [n,{self.ny},{self.nx},>={self.model.c_in}]")
+        g = _f32(g[..., :self.model.c_in])
+        n = g.shape[0]
+        self._check_bound(g)
+        if (dU is None) != (prev is None):
+            raise ValueError("dU and prev go together")
+        result = np.empty((n, self.ny, self.nx, self.model.c_out), np.float32)
+        change = nxt = None
+        if dU is not None:
+            dU, prev = (_f32(np.asarray(a, np.float32).reshape(n, self.ny, self.nx)) for a in (dU, prev))
+            change, nxt = np.empty((n, self.ny, self.nx), np.float32), np.empty((n, self.ny, self.nx), np.float32)
+        sc = _f32(np.broadcast_to(out_scale, (n,))) if out_scale is not None else None
+        opt = lambda a: _p(a, C.c_float) if a is not None else None
+        self._chk(self.lib.psm_solve_poststeps(self.h, _p(g, C.c_float), n, opt(sc), int(bool(apply_filter)), opt(dU), opt(prev),
+                                               _p(result, C.c_float), opt(change), opt(nxt)))
+        return result, change, nxt
+
     # -- introspection
     def stage(self, name: str, n_cases: int = 1, layer: int = 0) -> np.ndarray:
         """An intermediate of the last solve; ``name='hidden'``: the output of hidden Dense layer ``layer`` (the handle must have
@@ -932,11 +997,18 @@ class EvaluationPoisson(Evaluation):
         -> field_deltap [Ny,Nx] (``deltaP_prev_grid + change_in_deltap`` with the weighting, :843-848)."""
         grid = self.build_features(ux_grid, uy_grid, delta_ux_grid, delta_uy_grid, sdfunct, phi, U_max_norm)
         sur = self._surrogate(grid.shape[0], grid.shape[1])
-        res = sur.solve(grid, out_scale=[self.max_abs_delta_p * U_max_norm ** 2])[0, :, :, 0]     # :816
         wgt = apply_deltaU_change_wgt and deltaU_change_grid is not None and deltaP_prev_grid is not None
-        res, change = self._post_steps(sur, res, apply_filter, deltaU_change_grid, deltaP_prev_grid, wgt)
-        self.deltap_res = res                                    # the assembled delta-p before the weighting (:833)
-        return np.asarray(deltaP_prev_grid, np.float32) + change if wgt else res
+        scale = [self.max_abs_delta_p * U_max_norm ** 2]                                          # :816
+        if not (wgt or apply_filter):
+            self.deltap_res = sur.solve(grid, out_scale=scale)[0, :, :, 0]
+            return self.deltap_res
+        # solve and post-steps (:352-363, :843-848) as one call: the field stays on the device between the stages
+        if not sur._post_bound:
+            sur.bind_poststeps((10, 10), (50, 50))                # SM_call.py:353, :360
+        res, _, nxt = sur.solve_poststeps(grid, apply_filter, deltaU_change_grid if wgt else None,
+                                          deltaP_prev_grid if wgt else None, out_scale=scale)
+        self.deltap_res = res[0, :, :, 0]                        # the assembled delta-p before the weighting (:833)
+        return nxt[0] if wgt else self.deltap_res
 
 
 class EvaluationGradP(Evaluation):
@@ -1004,9 +1076,12 @@ class EvaluationGradP(Evaluation):
         self.grid = grid
         self.U_max_norm = float(U_max_norm)
         sur = self._surrogate(*grid.shape[:2])
-        gradP = sur.solve(grid[..., :3])[0]                                               # :470-544
-        if apply_filter:                                                                 # :366-367, per field
-            gradP = np.stack([sur.gaussian_filter(gradP[..., c], (10, 10)) for c in range(2)], axis=-1)
+        if apply_filter:                                                                 # :470-544 and :366-367 (per field) in one call
+            if not sur._post_bound:
+                sur.bind_poststeps((10, 10), (50, 50))
+            gradP = sur.solve_poststeps(grid[..., :3], apply_filter=True)[0][0]
+        else:
+            gradP = sur.solve(grid[..., :3])[0]                                           # :470-544
         self.gradP = gradP
         xl = np.linspace(self.min_x, self.max_x, grid.shape[1])                            # :591-592
         yl = np.linspace(self.min_y, self.max_y, grid.shape[0])
