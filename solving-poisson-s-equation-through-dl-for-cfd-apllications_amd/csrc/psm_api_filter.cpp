@@ -24,14 +24,7 @@ void post_free(PostSet& s) {
 }
 
 // captured solve + post-step graphs (GraphKey::post) hold the addresses of the binding's tables and scratch
-static void drop_post_graphs(psm_handle* h) {
-  for (auto it = h->graphs.begin(); it != h->graphs.end();) {
-    if (it->first.post.apply_filter < 0) { ++it; continue; }
-    (void)hipGraphExecDestroy(it->second);
-    h->graph_state.erase(it->first);
-    it = h->graphs.erase(it);
-  }
-}
+static void drop_post_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.post.apply_filter >= 0; }); }
 
 // axis 0 then axis 1 of ONE filter over [n][ny][nx][c]: in -> tmp -> out (in and out may alias)
 static int filter_pair(psm_handle* h, const float* in, int n, int ny, int nx, int c, float* tmp, float* out, const float* wy, int ry,

@@ -1,4 +1,4 @@
-// psm_api_introspect.cpp -- C-ABI of libpsm_hip.so (include/psm.h): stage read-back, profiling, kernel timing, host-side reference.  See psm_handle.h for the map of the five files.
+// psm_api_introspect.cpp -- C-ABI of libpsm_hip.so (include/psm.h): stage read-back, profiling, kernel timing, host-side reference.  See psm_handle.h for the map of the files.
 #include "psm_handle.h"
 
 thread_local PsmLaunchProbe* psm_launch_probe = nullptr;   // psm_launch.h: installed by collect_kernel_samples below and by psm_unet_time_kernels
@@ -9,7 +9,7 @@ namespace psm_impl {
 // Dispatch-level time of EVERY kernel of the solve path: `steps` solves through the same launch sequence as
 // psm_solve_grid_device, each dispatch stamped by hipExtLaunchKernelGGL (its own begin / end, what rocprofv3 reads).
 // every dispatch of `steps` solves with its own begin / end stamps: per kernel (launch order of first appearance) the samples in ms
-int collect_kernel_samples(psm_handle* h, const float* d_grid, int32_t n_cases, float* d_fields, int32_t steps,
+static int collect_kernel_samples(psm_handle* h, const float* d_grid, int32_t n_cases, float* d_fields, int32_t steps,
                                   std::vector<std::string>& seen, std::vector<std::vector<float>>& samp) {
   if (!h->planned) return fail(h, PSM_ERR_STATE, "psm_plan_grid has not been called");
   if (h->timed_kernel >= 0) return fail(h, PSM_ERR_STATE, "psm_enable_kernel_timing is active");
@@ -78,9 +78,9 @@ int psm_read_stage(psm_handle* h, int32_t stage, float* dst, size_t dst_floats) 
   const bool hidden = stage >= PSM_STAGE_HIDDEN && stage - PSM_STAGE_HIDDEN < (int)h->dense.size() - 1;
   const bool data_stage = (stage >= PSM_STAGE_X_INPUT && stage <= PSM_STAGE_SHIFT) || hidden;
   if (!data_stage && stage != 5 && stage != 6) return fail(h, PSM_ERR_ARG, "unknown stage");
-  if (data_stage && !h->last_on_ws0)
+  if (data_stage && !h->last.on_ws0)
     return fail(h, PSM_ERR_STATE, "the last solve ran on a ring slot's workspace: its intermediates are not readable");
-  if (stage == PSM_STAGE_BLOCK_PRED && !h->last_pred_stored)
+  if (stage == PSM_STAGE_BLOCK_PRED && !h->last.pred_stored)
     return fail(h, PSM_ERR_STATE, "the last solve did not store the decoded blocks (the geometry-bound path pastes them directly)");
   auto rows = [&](const float* src, int ld, int width) -> int {
     if (dst_floats < (size_t)M * width) return fail(h, PSM_ERR_ARG, "destination too small");
@@ -93,23 +93,18 @@ int psm_read_stage(psm_handle* h, int32_t stage, float* dst, size_t dst_floats) 
     case PSM_STAGE_BLOCK_PRED: return rows(h->ws0.d_pred, h->K_out, h->K_out);
     case PSM_STAGE_OFFSETS:
     case PSM_STAGE_SHIFT:
-      if (h->bound && h->bound_cf && h->last_used_cf && h->last_cases == h->bound_cases) {
+      if (h->bound && h->bound_cf && h->last.used_cf && h->last_cases == h->bound_cases) {
         // the last solve took the closed form: run the chain itself once, from the strip means of the same activations
         const int nl = (int)h->dense.size();
         const bool bf = h->cfg.precision == PSM_PRECISION_BF16;
         const float* act = bf ? h->ws0.d_res : !h->d_keep.empty() ? h->d_keep[nl - 2]
-                                                  : (h->last_act_packed ? h->ws0.d_act_rows : h->ws0.d_act[(nl - 2) & 1]);
+                                                  : (h->last.act_packed ? h->ws0.d_act_rows : h->ws0.d_act[(nl - 2) & 1]);
         const int ld_act = bf ? h->ld_out : h->dense[nl - 2].ldw;
-        PsmDotsArgs dd{h->d_g2, h->d_c2, h->d_cnt, h->d_row_of, h->last_row_scale ? h->last_row_scale : h->d_ones, h->ws0.d_dots,
-                       h->bound_rows * h->last_cases, bf ? h->ld_out : h->dense[nl - 1].Kpad, PsmGuardArgs{}};
+        const PsmDotsArgs dd = dots_args(h, h->ws0, false, h->last_cases, h->last.row_scale ? h->last.row_scale : h->d_ones, PsmGuardArgs{});   // strip rows
         HIPCHK(h, psm_launch_act_dots(dd, act, ld_act, bf ? 1 : 0, h->stream));
         PsmBoundBatchArgs bb{};
-        bb.cp = h->plan.cp; bb.blocks = h->d_blocks; bb.dots = h->ws0.d_dots; bb.scnt = h->d_cnt; bb.ownbits = h->d_ownbits;
-        bb.blk_y0x0 = h->d_blk; bb.shiftW = h->d_shiftW;
-        for (int f = 0; f < 2; ++f) bb.shiftL[f] = (int)h->plan.shiftA[f].size();
-        bb.offs = h->ws0.d_offs; bb.shift = h->ws0.d_shift; bb.Nx = h->Nx; bb.npix = h->Ny * h->Nx;
-        bb.n_strips = h->n_strips; bb.B = h->B; bb.rows_pc = h->bound_rows; bb.n_cases = h->last_cases;
-        bb.gflags = h->d_gzero; bb.n_gwaves = 1;
+        bound_common(bb, h, h->ws0, SolveRoute{}, nullptr);      // the chain form, no guard, no field
+        bb.npix = h->Ny * h->Nx; bb.rows_pc = h->bound_rows; bb.n_cases = h->last_cases;
         HIPCHK(h, psm_launch_chain_dots(bb, h->cfg.c_out, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
       }

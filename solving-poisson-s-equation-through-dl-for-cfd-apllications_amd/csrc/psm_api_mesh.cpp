@@ -1,10 +1,10 @@
-// psm_api_mesh.cpp -- C-ABI of libpsm_hip.so (include/psm.h): solver boundary (mesh <-> grid) and evaluator helpers.  See psm_handle.h for the map of the five files.
+// psm_api_mesh.cpp -- C-ABI of libpsm_hip.so (include/psm.h): solver boundary (mesh <-> grid) and evaluator helpers.  See psm_handle.h for the map of the files.
 #include "psm_handle.h"
 
 namespace psm_impl {
 
 // psm_solve on registered, mapped caller buffers: every device-side step of the call, in stream order (captured once)
-int mesh_sequence(psm_handle* h, int64_t n, hipStream_t st) {
+static int mesh_sequence(psm_handle* h, int64_t n, hipStream_t st) {
   int n_partials = 0;
   HIPCHK(h, psm_launch_stage_cells(h->pinned_cells_dev, h->d_cells, n, h->d_umax_part, &n_partials, st));
   PsmToGridArgs ga{};
@@ -99,14 +99,7 @@ static int integ_bind(psm_handle* h, IntegSet& s, int ny, int nx, const double* 
 }
 
 // captured solve + integration graphs (GraphKey::p) hold the addresses of the binding's tables
-static void drop_pressure_graphs(psm_handle* h) {
-  for (auto it = h->graphs.begin(); it != h->graphs.end();) {
-    if (!it->first.p) { ++it; continue; }
-    (void)hipGraphExecDestroy(it->second);
-    h->graph_state.erase(it->first);
-    it = h->graphs.erase(it);
-  }
-}
+static void drop_pressure_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.p != nullptr; }); }
 
 // state checks shared by the device-resident entries
 static int integ_check(psm_handle* h, int n_cases) {
@@ -143,19 +136,9 @@ int psm_reassemble(psm_handle* h, const float* grid, const float* block_pred, fl
   HIPCHK(h, hipStreamSynchronize(st));                    // the staging buffers are free; caller memory goes through the bounce buffer
   HIPCHK(h, psm_copy_h2d(h->d_grid_stage, grid, npix * h->cfg.c_in * sizeof(float)));
   HIPCHK(h, psm_copy_h2d(h->ws0.d_pred, block_pred, (size_t)h->B * h->K_out * sizeof(float)));
-  PsmStripArgs sa{};
-  sa.pred = h->ws0.d_pred; sa.grid = h->d_grid_stage; sa.strips = h->d_strips; sa.blk_y0x0 = h->d_blk; sa.spart = h->ws0.d_spart; sa.colpart = h->ws0.d_colpart; sa.NS = h->plan.cp.NS; sa.n_bands = h->n_bands;
-  sa.B = h->B; sa.S = h->S; sa.c_in = h->cfg.c_in; sa.c_out = h->cfg.c_out;
-  sa.sdf_ch = h->cfg.sdf_channel; sa.Ny = h->Ny; sa.Nx = h->Nx;
-  HIPCHK(h, psm_launch_strips(sa, 1, st));
-  PsmChainArgs ca{};
-  ca.cp = h->plan.cp; ca.blocks = h->d_blocks; ca.spart = h->ws0.d_spart; ca.colpart = h->ws0.d_colpart; ca.n_bands = h->n_bands; ca.pred = h->ws0.d_pred; ca.owner = h->d_owner;
-  ca.shiftA = h->d_shiftA; ca.shiftB = h->d_shiftB; ca.shiftOwnA = h->d_shiftOwnA; ca.shiftOwnB = h->d_shiftOwnB; ca.shiftW = h->d_shiftW;
-  for (int f = 0; f < 2; ++f) ca.shiftL[f] = (int)h->plan.shiftA[f].size();
-  ca.Lmax = h->Lmax; ca.offs = h->ws0.d_offs; ca.shift = h->ws0.d_shift; ca.n_strips = h->n_strips; ca.c_out = h->cfg.c_out; ca.stamps = h->d_stamps;
-  HIPCHK(h, psm_launch_chain(ca, 1, st));
-  PsmPasteArgs pa{h->ws0.d_pred, h->d_owner, h->ws0.d_offs, h->ws0.d_shift, h->d_fields_stage, h->B, h->S, h->cfg.c_out, h->Ny * h->Nx};
-  HIPCHK(h, psm_launch_paste(pa, 1, st));
+  HIPCHK(h, psm_launch_strips(strip_args(h, h->ws0, h->d_grid_stage), 1, st));
+  HIPCHK(h, psm_launch_chain(chain_args(h, h->ws0), 1, st));
+  HIPCHK(h, psm_launch_paste(paste_args(h, h->ws0, h->d_fields_stage), 1, st));
   HIPCHK(h, wait_stream(st));
   HIPCHK(h, psm_copy_d2h(fields, h->d_fields_stage, npix * h->cfg.c_out * sizeof(float)));
   h->last_cases = 1;
@@ -193,7 +176,7 @@ int psm_block_error(psm_handle* h, const float* grid, const float* labels, doubl
   if (!h->planned || h->last_cases < 1) return fail(h, PSM_ERR_STATE, "no solve has run yet");
   // The network output it decodes lives in the handle's own workspace.  A solve through the asynchronous ring
   // (psm_submit_grid*, psm_ring_*, psm_bench_host) ran on a ring slot's workspace and left an OLDER solve here.
-  if (!h->last_on_ws0)
+  if (!h->last.on_ws0)
     return fail(h, PSM_ERR_STATE, "psm_block_error follows a synchronous solve (psm_solve_grid / psm_solve_grid_device / psm_solve); the last solve ran on the ring");
   if (!grid || !labels || !out) return fail(h, PSM_ERR_ARG, "null buffer");
   HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -210,11 +193,8 @@ int psm_block_error(psm_handle* h, const float* grid, const float* labels, doubl
   float* p_g = cp.take<float>(npix * h->cfg.c_in); float* p_l = cp.take<float>(npix * h->cfg.c_out); double* p_p = cp.take<double>((size_t)h->B * 8);
   memcpy(p_g, grid, gb); memcpy(p_l, labels, lb);
   // the decoded blocks of the last solve (case 0): on the geometry-bound path they were never stored -- decode its network output again
-  const int M = h->B, Mpad = round_up(M, 32);
-  const float* scale = h->last_row_scale ? h->last_row_scale : h->d_ones;
-  PsmDecodeArgs de{};
-  de.res = h->ws0.d_res; de.ld_res = h->ld_out; de.bpack = h->d_bpack_out; de.mean = h->d_mean_out;
-  de.row_scale = scale; de.pred = h->ws0.d_pred; de.M = M; de.Mpad = Mpad; de.Gd = h->Gd; de.n_coltiles = h->n_coltiles; de.K_out = h->K_out;
+  const float* scale = h->last.row_scale ? h->last.row_scale : h->d_ones;
+  const PsmDecodeArgs de = decode_args(h, h->ws0, 1, scale, h->ws0.d_pred);
   const bool bf16 = h->cfg.precision == PSM_PRECISION_BF16;
   hipError_t e = bf16 ? psm_launch_decode_bf16(de, st) : psm_launch_decode(de, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_g, p_g, gb, hipMemcpyHostToDevice, st);
@@ -373,18 +353,11 @@ int psm_solve_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank,
       if (rc) return rc;
     } else {
       if (!h->mesh_graph) {
-        hipGraph_t graph = nullptr;
-        HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-        int rc = mesh_sequence(h, n, st);
-        hipError_t e = hipStreamEndCapture(st, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess) { if (graph) (void)hipGraphDestroy(graph); return fail(h, PSM_ERR_HIP, std::string("psm_solve capture: ") + hipGetErrorString(e)); }
-        e = hipGraphInstantiate(&h->mesh_graph, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { h->mesh_graph = nullptr; return fail(h, PSM_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e)); }
-        h->mesh_graph_state = ws0_state(h);
+        int rc = capture_graph(h, st, "psm_solve", [&] { return mesh_sequence(h, n, st); }, &h->mesh_graph);
+        if (rc) return rc;
+        h->mesh_graph_left = h->last;
       } else {
-        set_ws0_state(h, h->mesh_graph_state);
+        h->last = h->mesh_graph_left;
       }
       HIPCHK(h, hipGraphLaunch(h->mesh_graph, st));
     }

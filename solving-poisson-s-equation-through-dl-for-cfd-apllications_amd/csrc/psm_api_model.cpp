@@ -1,4 +1,4 @@
-// psm_api_model.cpp -- C-ABI of libpsm_hip.so (include/psm.h): handle lifetime and model artefacts.  See psm_handle.h for the map of the five files.
+// psm_api_model.cpp -- C-ABI of libpsm_hip.so (include/psm.h): handle lifetime and model artefacts.  See psm_handle.h for the map of the files.
 #include "psm_handle.h"
 
 namespace psm_impl { thread_local std::string g_create_error; }
@@ -11,7 +11,7 @@ namespace psm_impl {
 // 300 us), after which the thread blocks, and never when this process shares its cores with more MPI / torchrun
 // ranks than it has cores (a spinning rank would then steal the time of another rank's solver thread).
 // PSM_SYNC_BLOCK=1 forces blocking waits, PSM_SYNC_BLOCK=0 forces the bounded spin.
-int local_ranks_from_env() {
+static int local_ranks_from_env() {
   for (const char* k : {"OMPI_COMM_WORLD_LOCAL_SIZE", "MPI_LOCALNRANKS", "PMI_LOCAL_SIZE", "SLURM_NTASKS_PER_NODE", "LOCAL_WORLD_SIZE"}) {
     const char* v = getenv(k);
     if (v && atoi(v) > 0) return atoi(v);
@@ -66,9 +66,7 @@ int scratch_reserve(psm_handle* h, size_t dev_bytes, size_t pin_bytes) {
 }
 
 void destroy_graphs(psm_handle* h) {
-  for (auto& kv : h->graphs) (void)hipGraphExecDestroy(kv.second);
-  h->graphs.clear();
-  h->graph_state.clear();
+  drop_graphs_if(h, [](const GraphKey&) { return true; });
   if (h->mesh_graph) { (void)hipGraphExecDestroy(h->mesh_graph); h->mesh_graph = nullptr; }
   ring_drop_graphs(h);
 }

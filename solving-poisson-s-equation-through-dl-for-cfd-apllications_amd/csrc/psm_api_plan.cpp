@@ -1,4 +1,4 @@
-// psm_api_plan.cpp -- C-ABI of libpsm_hip.so (include/psm.h): grid plan and bound geometries.  See psm_handle.h for the map of the five files.
+// psm_api_plan.cpp -- C-ABI of libpsm_hip.so (include/psm.h): grid plan and bound geometries.  See psm_handle.h for the map of the files.
 #include "psm_handle.h"
 
 namespace psm_impl {
@@ -51,7 +51,7 @@ int ws_alloc(psm_handle* h, Workspace& w) {
 // probing it with unit vectors, checked against a random probe, and folded into one table row per (field, block, source
 // block) -- a linear combination of the strip / shift rows the bind kernels have just built.  Leaves bound_cf false (the
 // chain launch stays) if the probe disagrees.
-int build_closed_form(psm_handle* h, int n_cases, int rows, int Kh) {
+static int build_closed_form(psm_handle* h, int n_cases, int rows, int Kh) {
   const int C = h->cfg.c_out, B = h->B, nst = h->n_strips, NS = h->plan.cp.NS;
   std::vector<float> hcnt((size_t)rows * n_cases);
   HIPCHK(h, psm_copy_d2h(hcnt.data(), h->d_cnt, hcnt.size() * sizeof(float)));
@@ -249,6 +249,8 @@ int psm_plan_grid(psm_handle* h, int32_t ny, int32_t nx) {
   h->Mcap = h->cfg.max_cases * h->B;
   h->Mpad_cap = round_up(h->Mcap, 32);
   h->n_strips = (int)h->plan.strips.size();
+  h->plan_aligned = (nx * h->cfg.c_in) % 4 == 0 && (ny * (int64_t)nx * h->cfg.c_in) % 4 == 0;
+  for (auto& b : h->plan.blocks) if ((b.x0 * h->cfg.c_in) % 4 != 0) h->plan_aligned = false;
   h->max_width = h->ld_in;
   for (auto& d : h->dense) h->max_width = std::max(h->max_width, d.ldw);
   h->c1_stride = 0;

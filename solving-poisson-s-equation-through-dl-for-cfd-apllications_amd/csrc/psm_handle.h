@@ -1,8 +1,9 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in five files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in seven files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
-//   psm_api_solve.cpp       the launch sequence of one solve (launch_all), psm_solve_grid*, the pinned submission ring
+//   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, graph capture and key, psm_solve_grid*
+//   psm_api_ring.cpp        the pinned submission ring (psm_ring_*, psm_submit_grid*, psm_wait_grid) and registered host memory (psm_host_*)
 //   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*), evaluator helpers (labels, block error, filters), the gradP integration (host entry and device-resident U -> p)
 //   psm_api_filter.cpp      the Gaussian post-steps: psm_gaussian_filter (host entry), psm_bind_poststeps and the device-resident / case-batched entries
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
@@ -20,6 +21,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <string>
 #include <tuple>
@@ -60,9 +62,38 @@ struct Conv1dLayer {            // conv1D_PCA head (NNs.py:75-124)
   bool set = false;
 };
 
-// What a solve on ws0 left there, set by launch_all when the launches are enqueued or captured.  A graph replay does not run
-// launch_all: the state its capture recorded is put back on every replay (psm_read_stage and psm_block_error read it).
-struct Ws0Solve { bool pred_stored = false, used_cf = false, act_packed = false; const float* row_scale = nullptr; };
+// What the most recent solve left on ws0 (psm_read_stage and psm_block_error read it), derived from the route by launch_all when the
+// launches are enqueued or captured.  A graph replay does not run launch_all: the record stored at capture is put back.
+struct Ws0Solve {
+  bool on_ws0 = false;                  // the solve ran on the handle's own workspace, not a ring slot's (then the rest is stale)
+  // it stored the decoded blocks (general path; the bound path pastes them) / took the closed form (offsets and shift are computed on
+  // demand) / left its last hidden activation in MFMA operand order (PsmDenseArgs::out_packed: readers take d_act_rows)
+  bool pred_stored = false, used_cf = false, act_packed = false;
+  const float* row_scale = nullptr;     // its row scale
+};
+
+// Every decision of one solve's launch sequence, made once by choose_route (psm_api_solve.cpp) from the handle, the workspace, the grid
+// pointer and the case count; the stage functions and the argument builders branch on nothing else.
+struct SolveRoute {
+  int n_cases = 0, M = 0, Mpad = 0;     // block rows, padded to the 32-row MFMA tile
+  bool bf16 = false;
+  bool bound = false;                   // geometry-bound path (6 / 7 launches), else the general path
+  bool cf = false;                      // bound: closed form of the offset chain (pair dots, no chain launch)
+  bool guard = false;                   // bound: guard riders check the grid's flow-cell pattern
+  int guard_wgs = 0;                    // guard workgroups of the solve (one flag each)
+  bool spread = false;                  // they are dealt over the `rider_carriers` hidden Dense launches, `rider_share` each; the head launch
+  int rider_share = 0, rider_carriers = 0;   // (bf16 handles: their dots launch) carries the rest.  Not spread: all of them ride there
+  bool stamp_encode = false;            // encode timed by dispatch stamps (no event pair around the launch)
+  int aligned = 0, whole = 1, x6 = 0, kgroup = 1, n_slabs = 0;   // encode: PsmEncodeArgs fields of the same name; slabs the reduce sums
+  bool fuse1 = false;                   // slab reduce + Dense 0 in one launch
+  std::vector<char> packed;             // [layers] the output of Dense layer l is written in MFMA operand order
+  bool ln_fuse = true;                  // LayerNormalization deferred into the next hidden launch where there is one
+  int decode_x6 = 0;                    // bound: x6 arithmetic of decode + paste
+  bool one_launch_tail = false;         // bound: decode + chain + paste in one launch (single case of <= 64 blocks), else chain launch + batch paste
+  uint32_t field_bytes = 0;             // bound: the paste stores through a buffer descriptor of this size (PsmBoundArgs::field_bytes)
+  bool fused_assemble = false;          // general: chain + paste in one launch
+  bool pred_stored = false;             // the decode stores the blocks
+};
 
 // What the Gaussian post-steps behind a solve read and write (psm_solve_poststeps*): every pointer is part of the captured launches.
 struct PostCall {
@@ -73,7 +104,7 @@ struct PostCall {
 };
 
 struct GraphKey {
-  int n; const void* g; void* f;
+  int n; const void* g; void* f;        // n: sequence_key()
   void* p = nullptr;                    // psm_solve_pressure*: where the integration behind the solve writes p (null: the solve alone)
   PostCall post{};                      // psm_solve_poststeps*: the post-steps behind the solve (apply_filter == -1: none)
   bool operator<(const GraphKey& o) const { return std::tie(n, g, f, p) < std::tie(o.n, o.g, o.f, o.p) || (std::tie(n, g, f, p) == std::tie(o.n, o.g, o.f, o.p) && post.tie() < o.post.tie()); }
@@ -136,6 +167,7 @@ struct psm_handle {
   bool planned = false;
   PsmPlan plan;
   int Ny = 0, Nx = 0, B = 0, Mcap = 0, Mpad_cap = 0, n_strips = 0, Lmax = 0, max_width = 0;
+  bool plan_aligned = false;            // every block origin and the case stride are multiples of four floats: the encode's 16-byte loads
   Workspace ws0;
   int64_t* d_row_base = nullptr;
   float* d_ones = nullptr;
@@ -160,7 +192,7 @@ struct psm_handle {
   double* pinned_p_dev = nullptr;       // device-side address of the registered output (the last kernel writes p straight into it)
   const double* pinned_cells_dev = nullptr;   // device-side address of the registered input (psm_stage_cells_kernel reads it over PCIe)
   hipGraphExec_t mesh_graph = nullptr;  // psm_solve on registered buffers: stage + to_grid + the solve + to_mesh as ONE graph replay
-  Ws0Solve mesh_graph_state;            // what mesh_graph leaves on ws0
+  Ws0Solve mesh_graph_left;             // what mesh_graph leaves on ws0
   double maxs[4] = {1, 1, 1, 1};
   int normalise_sdf = 0, fill_input = 0;
   double case_maxs[4] = {1, 1, 1, 1}, case_delta = 5e-3, case_wall = 0.05;   // psm_set_case (PM:106-109, 195, 494)
@@ -203,8 +235,8 @@ struct psm_handle {
   hipEvent_t scale_ev[RING] = {};
   int scale_pos = 0;
   hipStream_t stream = nullptr;
-  std::map<GraphKey, hipGraphExec_t> graphs;
-  std::map<GraphKey, Ws0Solve> graph_state;   // what each captured graph leaves on ws0
+  struct SolveGraph { hipGraphExec_t exec; Ws0Solve left; };   // left: what the captured solve leaves on ws0
+  std::map<GraphKey, SolveGraph> graphs;
   bool use_graph = true;
   bool fused_assemble = false;
   // scratch of the helper entries (gaussian filter, mesh -> grid, Poisson features, gradp integration): one device and one
@@ -232,10 +264,7 @@ struct psm_handle {
   float *d_g2p = nullptr, *d_c2p = nullptr, *d_cntp = nullptr, *d_cfa0 = nullptr;
   int32_t* d_row_of_p = nullptr;
   std::vector<float> h_shiftW;          // host copy of d_shiftW [c_out][B]
-  const float* last_row_scale = nullptr;   // row scale of the last solve on ws0 (introspection)
-  bool last_act_packed = false;         // the last solve on ws0 left its last hidden activation in MFMA operand order (PsmDenseArgs::out_packed)
-  bool last_used_cf = false;            // the last solve on ws0 took the closed form: offsets / shift are computed on demand
-  bool last_pred_stored = false;        // the last solve on ws0 stored the decoded blocks (general path; the bound path pastes them)
+  Ws0Solve last;
   // keep mode (PSM_KEEP_HIDDEN=1 at psm_create): hidden Dense layer l of a ws0 solve writes d_keep[l] ([Mpad_cap][max_width],
   // row-major; where the chain is packed, its row-major copy) instead of a ping-pong buffer, for psm_read_stage(PSM_STAGE_HIDDEN + l)
   bool keep_hidden = false;
@@ -250,7 +279,6 @@ struct psm_handle {
   int debug_skip = 0;                   // PSM_DEBUG_SKIP bit mask of kernel groups NOT launched (timing experiments only)
   bool fuse_reduce_dense1 = true;       // PSM_NO_FUSED_REDUCE=1 disables
   int last_cases = 0;
-  bool last_on_ws0 = false;             // the most recent solve ran on the handle's own workspace (not a ring slot's): what psm_block_error decodes
   // event timing of one kernel group
   int timed_kernel = -1;
   int timed_repeat = 1;
@@ -262,13 +290,18 @@ struct psm_handle {
 namespace psm_impl __attribute__((visibility("hidden"))) {
 
 // ---- helpers shared by the translation units (defined in the file named in the list above) ----
-int local_ranks_from_env();
 bool sync_blocks();
 hipError_t wait_stream(hipStream_t st);
 hipError_t wait_event(hipEvent_t ev);
 int fail(psm_handle* h, int code, const std::string& msg);
 int scratch_reserve(psm_handle* h, size_t dev_bytes, size_t pin_bytes);
 void destroy_graphs(psm_handle* h);
+// drops the captured solve graphs whose key `gone` names (graphs that hold the addresses of a binding's tables, when the binding goes)
+template <typename P>
+void drop_graphs_if(psm_handle* h, P gone) {
+  for (auto it = h->graphs.begin(); it != h->graphs.end();)
+    if (gone(it->first)) { (void)hipGraphExecDestroy(it->second.exec); it = h->graphs.erase(it); } else ++it;
+}
 void ws_free(Workspace& w);
 int ws_alloc_guard(psm_handle* h, Workspace& w);
 int ws_alloc(psm_handle* h, Workspace& w);
@@ -285,36 +318,26 @@ int poststeps_device(psm_handle* h, const float* d_fields, int n_cases, const Po
 std::vector<uint16_t> pack_comp_in_bf16(const double* comp, int P, int K, int c_in, int S, int NT);
 std::vector<uint16_t> pack_comp_out_bf16(const double* comp, int P, int K_out, int G);
 bool model_complete(const psm_handle* h);
-int encode_groups(const psm_handle* h, int Mpad);
 int ensure_encode_aux(psm_handle* h, int n_cases);
+SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_grid, int n_cases, bool profiled);
 int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, float* d_fields, const float* d_row_scale,
                hipStream_t st, hipEvent_t* prof);
-int prepare_scale(psm_handle* h, Workspace& w, const float* out_scale, int n_cases, hipStream_t st, const float** d_scale);
+int sequence_key(const psm_handle* h, int n_cases, bool scale, bool ring = false);
+int capture_graph(psm_handle* h, hipStream_t st, const char* label, const std::function<int()>& enqueue, hipGraphExec_t* exec);
+// one builder per kernel-argument block (psm_api_solve.cpp): the stages of launch_all, psm_read_stage, psm_block_error and psm_reassemble
+PsmDecodeArgs decode_args(const psm_handle* h, const Workspace& w, int n_cases, const float* row_scale, float* pred, int x6 = 0);
+PsmDotsArgs dots_args(const psm_handle* h, const Workspace& w, bool cf, int n_cases, const float* row_scale, const PsmGuardArgs& guard);
+PsmStripArgs strip_args(const psm_handle* h, const Workspace& w, const float* d_grid);
+PsmChainArgs chain_args(const psm_handle* h, const Workspace& w);
+PsmPasteArgs paste_args(const psm_handle* h, const Workspace& w, float* d_fields);
 // d_p != nullptr: the bound integration (psm_bind_integration) of d_fields into d_p follows in the same stream / the same graph;
 // post (apply_filter >= 0): the bound post-steps (psm_bind_poststeps) of d_fields follow likewise
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
                  hipStream_t st, hipEvent_t* prof, float* d_p = nullptr, const PostCall* post = nullptr);
-int mesh_sequence(psm_handle* h, int64_t n, hipStream_t st);
 bool guard_take(psm_handle* h, Workspace& w);
 int guard_drop(psm_handle* h, const char* where);
-int build_closed_form(psm_handle* h, int n_cases, int rows, int Kh);
 int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases = 1);
 bool host_registered(const psm_handle* h, const void* p, size_t bytes);
-float* host_mapped(const psm_handle* h, const void* p, size_t bytes);
-int ring_init(psm_handle* h);
-int ring_key(const psm_handle* h, int n_cases, bool scale);
-int ring_sequence(psm_handle* h, psm_handle::Slot& s, int n_cases, bool scale, const float* src_dev, float* dst_dev,
-                         const float* src, float* dst, bool with_copies);
-int ring_capture(psm_handle* h, psm_handle::Slot& s, int n_cases, bool scale, const float* src_dev, float* dst_dev,
-                        bool with_copies, hipGraphExec_t* out);
-int ring_launch(psm_handle* h, psm_handle::Slot& s, int n_cases, const float* out_scale, const float* src, float* dst);
-int ring_check(psm_handle* h, int32_t n_cases);
-Ws0Solve ws0_state(const psm_handle* h);
-void set_ws0_state(psm_handle* h, const Ws0Solve& s);
-int ring_guard_rerun(psm_handle* h, psm_handle::Slot& s, const char* where);
-int slot_of(psm_handle* h, int64_t ticket, int state, psm_handle::Slot** out);
-int collect_kernel_samples(psm_handle* h, const float* d_grid, int32_t n_cases, float* d_fields, int32_t steps,
-                                  std::vector<std::string>& seen, std::vector<std::vector<float>>& samp);
 
 inline double spin_budget_us() { static const double v = [] { const char* e = getenv("PSM_SPIN_US"); return e ? atof(e) : 300.0; }(); return v; }
 
@@ -380,6 +403,19 @@ inline uint16_t f2bf(double v) {             // round-to-nearest-even float -> b
 }
 
 
+// the fields PsmBoundArgs and PsmBoundBatchArgs share (two kernel-argument structs, one set of assignments)
+template <typename A>
+void bound_common(A& a, const psm_handle* h, const Workspace& w, const SolveRoute& r, float* d_fields) {
+  a.cp = h->plan.cp; a.blocks = h->d_blocks; a.dots = w.d_dots; a.scnt = h->d_cnt; a.ownbits = h->d_ownbits;
+  a.blk_y0x0 = h->d_blk; a.shiftW = h->d_shiftW;
+  for (int f = 0; f < 2; ++f) a.shiftL[f] = (int)h->plan.shiftA[f].size();
+  a.fields = d_fields; a.offs = w.d_offs; a.shift = w.d_shift; a.Nx = h->Nx; a.n_strips = h->n_strips; a.B = h->B;
+  a.field_bytes = r.field_bytes;
+  a.gflags = r.guard ? w.d_gflags : h->d_gzero; a.n_gwaves = r.guard ? r.guard_wgs : 1;   // flags the launch sums: one per guard workgroup
+  a.cf = r.cf ? 1 : 0; a.cf_dots = w.d_dots2; a.cf_a0 = h->d_cfa0;
+}
+
+
 // ---- the launch sequence -------------------------------------------------------
 // launches of a kernel group: once, or `timed_repeat` times back to back between the two timing
 // events when that group is being timed (the group is idempotent; amortises the ~2.7 us an event
@@ -402,6 +438,7 @@ struct Timer {                      // optional event pair around one kernel gro
     if (ev) (void)hipEventRecord(ev[kernel + 1], st);
     if (h->timed_kernel == kernel && !(kernel == PSM_K_ENCODE && !ev)) (void)hipEventRecord(h->timed_events.back().second, st);
   }
+  void skip(int kernel) { before(kernel); after(kernel); }   // a group this route does not launch: its (empty) event pair, in order
 };
 
 
