@@ -173,8 +173,14 @@ int psm_grid_shape(const psm_handle* h, int32_t* shape);
  * CONTRACT: until psm_unbind_geometry / a new bind / a model or plan change, the SDF channel of every solved grid
  * must have the flow-cell pattern of the bound one; the other channels are free.  Case counts other than the bound
  * one keep the general path.
+ * SDF FOLD (float32 handles, one bound case of at most 32 blocks, cfg.sdf_channel == c_in - 1; PSM_SDF_FOLD=0 in the
+ * environment switches it off): the SDF channel's share of the PCA coefficients is computed once at the bind and the
+ * encode of a bound solve contracts the other channels only.  The contract is then the SDF channel's VALUES: every
+ * pixel of the solved grid's SDF channel must compare equal (float ==; a NaN on either side is a mismatch) to the
+ * bound one.  The device check below compares the values in that case, with the same consequences.
  * The contract is CHECKED ON THE DEVICE at every bound solve: spare waves of the launch that computes the strip dots
- * compare the pattern of the grid being solved (one ballot per 64 pixels) with the bound one.  On a mismatch the
+ * compare the pattern of the grid being solved (one ballot per 64 pixels) with the bound one (with the SDF fold: also
+ * its values with the bound SDF image).  On a mismatch the
  * solve's field is NaN everywhere -- never a plausible field of the wrong geometry -- and a flag in mapped pinned
  * memory is raised.  The host-buffer entries (psm_solve_grid, psm_wait_grid, psm_ring_wait) see the flag when the
  * solve has finished, drop the binding, solve the same grid again on the general path and return the correct

@@ -287,6 +287,7 @@ int psm_set_geometry(psm_handle* h, int64_t n_cells, int32_t ny, int32_t nx, con
       g[(size_t)t * 3 + 2] = (sdv != sdv) ? 0.f : (float)sdv;
     }
     HIPCHK(h, psm_copy_h2d(h->d_grid_stage, g.data(), g.size() * sizeof(float)));
+    h->bound_scope = 1;                                      // before the bind: this scope builds no SDF-fold tables
     rc = bind_geometry_device(h, h->d_grid_stage);
     if (rc == PSM_OK) h->bound_scope = 1;
     else if (rc == PSM_ERR_UNSUPPORTED) h->err.clear();      // configuration outside the fused path: general path

@@ -329,6 +329,7 @@ void psm_destroy(psm_handle* h) {
   dev_free(h->d_comp_nat); dev_free(h->d_g2); dev_free(h->d_c2); dev_free(h->d_cnt); dev_free(h->d_row_of); dev_free(h->d_ownbits);
   dev_free(h->d_ia); dev_free(h->d_ib); dev_free(h->d_sa); dev_free(h->d_sb);
   dev_free(h->d_maskbits); dev_free(h->d_gzero);
+  dev_free(h->d_bpack_fold); dev_free(h->d_ib_fold); dev_free(h->d_sdf_bound);
   dev_free(h->d_g2p); dev_free(h->d_c2p); dev_free(h->d_cntp); dev_free(h->d_cfa0); dev_free(h->d_row_of_p);
   for (auto& c : h->conv1d) { dev_free(c.W); dev_free(c.b); }
   for (auto& d : h->dense) { dev_free(d.ln_gamma); dev_free(d.ln_beta); }
@@ -350,6 +351,7 @@ int psm_set_pca(psm_handle* h, const double* comp_in, const double* mean_in, con
   HIPCHK(h, hipSetDevice(h->cfg.device));
   destroy_graphs(h);
   h->bound = false;
+  h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
   std::vector<float> mi(h->K_in), mo(h->K_out);
@@ -380,6 +382,16 @@ int psm_set_pca(psm_handle* h, const double* comp_in, const double* mean_in, con
   } else {
   if ((rc = dev_upload(h, &h->d_bpack_in, pack_comp_in(comp_in, h->cfg.p_in, h->K_in, h->cfg.c_in, h->S, h->NT)))) return rc;
   dev_free(h->d_bpack_x6);                                  // the pre-split copy of the large-batch encode is rebuilt on first use
+  // SDF fold (psm_handle.h): the basis as the device sees it (float32), kept on the host until the first bind that folds
+  static_assert(psm_fold::PIX_PER_SLICE == PSM_PIX_PER_SLICE, "psm_fold.h packs the encode's slices");
+  dev_free(h->d_bpack_fold); h->fold_bound = false;
+  h->h_comp_sdf.clear(); h->h_mean_sdf.clear(); h->h_comp_in.clear();
+  if (h->cfg.c_in >= 2 && h->cfg.sdf_channel == h->cfg.c_in - 1 && h->NT <= 4) {
+    h->h_comp_in.resize((size_t)h->cfg.p_in * h->K_in);
+    for (size_t q = 0; q < h->h_comp_in.size(); ++q) h->h_comp_in[q] = (float)comp_in[q];
+    h->h_mean_sdf.resize((size_t)h->S * h->S);
+    for (size_t q = 0; q < h->h_mean_sdf.size(); ++q) h->h_mean_sdf[q] = mi[q * h->cfg.c_in + h->cfg.c_in - 1];
+  }
   if ((rc = dev_upload(h, &h->d_bpack_out, pack_comp_out(comp_out, h->cfg.p_out, h->K_out, h->Gd)))) return rc;
   {
     std::vector<float> nat((size_t)h->ld_out * h->K_out, 0.f);
@@ -406,6 +418,7 @@ int psm_set_dense(psm_handle* h, int32_t layer, int32_t n_in, int32_t n_out, con
   HIPCHK(h, hipSetDevice(h->cfg.device));
   destroy_graphs(h);
   h->bound = false;
+  h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
   DenseLayer& d = h->dense[layer];
@@ -494,6 +507,7 @@ int psm_set_layernorm(psm_handle* h, int32_t layer, int32_t n, const float* gamm
   HIPCHK(h, hipStreamSynchronize(h->stream));
   destroy_graphs(h);
   h->bound = false;
+  h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
   // zero-padded to whole 16-byte pieces past the consumer's leading dimension: a Dense launch that applies this normalisation to
@@ -523,6 +537,7 @@ int psm_set_conv1d(psm_handle* h, int32_t layer, int32_t n_layers, int32_t kerne
   HIPCHK(h, hipStreamSynchronize(h->stream));
   destroy_graphs(h);
   h->bound = false;
+  h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
   if (!same_stack) {
@@ -550,6 +565,7 @@ int psm_set_scaler(psm_handle* h, const double* in_a, const double* in_b, const 
   HIPCHK(h, hipStreamSynchronize(h->stream));
   destroy_graphs(h);                          // captured launches hold the addresses of the arrays re-uploaded below
   h->bound = false;
+  h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
   std::vector<float> ia(h->ld_in, 0.f), ib(h->ld_in, 0.f), sa(h->ld_out, 0.f), sb(h->ld_out, 0.f);
@@ -573,6 +589,7 @@ int psm_set_scaler(psm_handle* h, const double* in_a, const double* in_b, const 
   if ((rc = dev_upload(h, &h->d_ib, ib))) return rc;
   if ((rc = dev_upload(h, &h->d_sa, sa))) return rc;
   if ((rc = dev_upload(h, &h->d_sb, sb))) return rc;
+  h->h_ia = ia; h->h_ib = ib;
   h->have_scaler = true;
   return PSM_OK;
 }

@@ -140,10 +140,47 @@ static int build_closed_form(psm_handle* h, int n_cases, int rows, int Kh) {
 }
 
 
+// SDF fold of the bound single-case encode (psm_handle.h, psm_fold.h): `g` is the host copy of the bound grid [Ny][Nx][c_in].
+// Once per handle: the basis packed over the leading channels and the SDF channel's rows.  Per bind: c_sdf[b][p] (host, double
+// accumulation, the components dealt over a few threads: 19 M multiply-adds for nine blocks of 128 x 128 and 128 components), folded
+// into a per-row copy of the input scaler's offset, and the bound SDF image for the guard riders.  The tables are shared by ws0 and
+// the ring slots; h->fold_bound goes down with h->bound wherever the binding is dropped (choose_route asks for both).
+static int bind_sdf_fold(psm_handle* h, const std::vector<float>& g) {
+  h->fold_bound = false;
+  const int cin = h->cfg.c_in, P = h->cfg.p_in, S = h->S;
+  if (h->bound_scope != 2 || h->cfg.precision != PSM_PRECISION_F32 || h->h_mean_sdf.empty() || h->h_ia.empty() || round_up(h->B, 32) != 32) return PSM_OK;
+  int rc;
+  if (!h->d_bpack_fold) {
+    if (h->h_comp_in.empty()) return PSM_OK;
+    const std::vector<float> pk = psm_fold::pack_comp_in_fold(h->h_comp_in.data(), P, cin, S, h->NT);
+    float* d = nullptr;
+    if ((rc = dev_upload(h, &d, pk))) return rc;
+    h->d_bpack_fold = reinterpret_cast<float4*>(d);
+    h->h_comp_sdf = psm_fold::last_channel_rows(h->h_comp_in.data(), P, cin, S);
+    std::vector<float>().swap(h->h_comp_in);
+  }
+  const size_t npix = (size_t)h->Ny * h->Nx;
+  std::vector<float> sdf(npix);
+  for (size_t q = 0; q < npix; ++q) sdf[q] = g[q * cin + cin - 1];
+  std::vector<int32_t> yx((size_t)h->B * 2);
+  for (int b = 0; b < h->B; ++b) { yx[2 * b] = h->plan.blocks[b].y0; yx[2 * b + 1] = h->plan.blocks[b].x0; }
+  std::vector<double> c((size_t)h->B * P);
+  const int threads = (int)std::min<unsigned>(8u, std::max(1u, std::thread::hardware_concurrency()));
+  psm_fold::sdf_coeffs(sdf.data(), h->Nx, yx.data(), h->B, S, h->h_comp_sdf.data(), h->h_mean_sdf.data(), P, c.data(), threads);
+  std::vector<float> ibf((size_t)32 * h->ld_in);
+  for (int m = 0; m < 32; ++m)
+    for (int p = 0; p < h->ld_in; ++p)
+      ibf[(size_t)m * h->ld_in + p] = (m < h->B && p < P) ? (float)((double)h->h_ib[p] + (double)h->h_ia[p] * c[(size_t)m * P + p]) : h->h_ib[p];
+  if ((rc = dev_upload(h, &h->d_ib_fold, ibf)) || (rc = dev_upload(h, &h->d_sdf_bound, sdf))) return rc;
+  h->fold_bound = true;
+  return PSM_OK;
+}
+
 // Bind the geometry (the flow-cell masks) of the planned grid: builds the tables of the 6-launch solve.
 int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases) {
   const int nl = (int)h->dense.size();
   h->bound = false;
+  h->fold_bound = false;
   const bool bf16 = h->cfg.precision == PSM_PRECISION_BF16;
   // the chain runs row-parallel in one wave (lane = block column); more than 64 blocks take the two-launch form of the
   // case batches (chain launch + chunked decode + paste), f32 only
@@ -202,6 +239,8 @@ int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases) {
         if (h->bound_mask[std::min(w * 64 + l, T - 1)]) bits[w] |= 1ull << l;
     if ((rc = dev_upload(h, &h->d_maskbits, bits))) return rc;
     if ((rc = ws_alloc_guard(h, h->ws0))) return rc;
+    h->fold_bound = false;
+    if (n_cases == 1 && (rc = bind_sdf_fold(h, g))) return rc;
   }
   h->bound_rows = rows;
   h->bound_cases = n_cases;
@@ -241,6 +280,7 @@ int psm_plan_grid(psm_handle* h, int32_t ny, int32_t nx) {
   HIPCHK(h, hipSetDevice(h->cfg.device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   h->bound = false;
+  h->fold_bound = false;
   free_plan(h);
   std::string err;
   int rc = psm_build_plan(h->cfg.variant, ny, nx, h->S, h->ov, h->cfg.strict_degenerate != 0, h->plan, err);
@@ -367,6 +407,7 @@ int psm_unbind_geometry(psm_handle* h) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   destroy_graphs(h);
   h->bound = false;
+  h->fold_bound = false;
   return PSM_OK;
 }
 

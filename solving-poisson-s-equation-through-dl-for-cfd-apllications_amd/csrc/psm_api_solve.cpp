@@ -62,9 +62,20 @@ static bool bound_applies(const psm_handle* h, int n_cases) {
   return h->bound && (h->bound_scope == 2 || h->in_mesh_solve) && n_cases == h->bound_cases;
 }
 
+// The SDF fold applies to a solve of this many cases (psm_handle.h): a float32 single case of one row tile on a geometry bound with
+// psm_bind_geometry (whose guard riders then check the SDF channel's values; not psm_solve's own binding, whose grids nobody checks),
+// float32 MFMA arithmetic.  PSM_SDF_FOLD=0 switches it off; read per solve, and part of sequence_key.
+static bool fold_applies(const psm_handle* h, int n_cases) {
+  if (!(bound_applies(h, n_cases) && n_cases == 1 && h->bound_scope == 2 && h->fold_bound && h->d_bpack_fold && h->d_ib_fold && h->d_sdf_bound)) return false;
+  if (h->cfg.precision != PSM_PRECISION_F32 || h->NT > 4 || round_up(h->B, 32) != 32 || (h->x6_mode >= 0 && (h->x6_mode & 1))) return false;
+  const char* e = getenv("PSM_SDF_FOLD");
+  return !(e && atoi(e) == 0);
+}
+
 static PsmEncodeArgs encode_args(const psm_handle* h, const Workspace& w, const SolveRoute& r, const float* d_grid) {
   PsmEncodeArgs ea{};
-  ea.grid = d_grid; ea.mean = h->d_mean_in; ea.bpack = h->d_bpack_in; ea.part = w.d_part;
+  ea.grid = d_grid; ea.mean = h->d_mean_in; ea.bpack = r.fold ? h->d_bpack_fold : h->d_bpack_in; ea.part = w.d_part;
+  ea.fold = r.fold ? 1 : 0;
   ea.row_base = h->d_row_base; ea.row_stride = (int64_t)h->Nx * h->cfg.c_in;
   ea.M = r.M; ea.Mpad = r.Mpad; ea.NT = h->NT; ea.ldp = h->ld_in; ea.S = h->S; ea.c_in = h->cfg.c_in;
   ea.aligned = r.aligned; ea.whole = r.whole; ea.x6 = r.x6; ea.kgroup = r.kgroup;
@@ -96,6 +107,7 @@ SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_
   // psm_encode_x6_kernel) from two row tiles up, where the matrix phase is the longest serial phase of the launch
   // (8 cases: 17.6 -> 15.5 us, 64 cases: 75 -> 60 us).  PSM_X6=0 / 1 forces float32 / x6 everywhere.
   r.x6 = h->x6_mode < 0 ? (r.Mpad > 32 ? 1 : 0) : ((h->x6_mode & 1) ? 1 : 0);
+  r.fold = r.bound && !r.bf16 && !r.x6 && r.Mpad == 32 && fold_applies(h, n_cases);
   // Large case batches (>= 32 cases of 9 blocks): the M-tiled, wave-specialised x6 form (encode_groups / ensure_encode_aux)
   const int groups = (r.x6 && !r.bf16) ? encode_groups(h, r.Mpad) : 1;
   r.kgroup = (groups > 1 && h->d_bpack_x6) ? groups : 1;
@@ -200,6 +212,7 @@ static PsmGuardArgs guard_args(const Solve& s, int carrier) {
   ga.npix = (long long)s.r.n_cases * h->Ny * h->Nx; ga.c_in = h->cfg.c_in; ga.n_ballots = h->guard_ballots; ga.n_waves = h->guard_waves;
   ga.wg_first = carrier * s.r.rider_share;
   ga.wg_count = carrier < s.r.rider_carriers ? s.r.rider_share : s.r.guard_wgs - ga.wg_first;
+  ga.sdf_ref = s.r.fold ? h->d_sdf_bound : nullptr;       // folded encode: the contract is the SDF channel's values
   return ga;
 }
 
@@ -267,7 +280,8 @@ static int stage_mlp(Solve& s) {
   psm_handle* h = s.h;
   const SolveRoute& r = s.r;
   const int nl = (int)h->dense.size();
-  const PsmReduceArgs ra{s.w.d_part, s.w.d_xin, h->d_ia, h->d_ib, r.n_slabs, r.Mpad, h->ld_in};
+  // folded encode: the SDF channel's share of the coefficients is in the binding's per-row copy of the scaler offset
+  const PsmReduceArgs ra{s.w.d_part, s.w.d_xin, h->d_ia, r.fold ? h->d_ib_fold : h->d_ib, r.n_slabs, r.Mpad, h->ld_in, r.fold ? h->ld_in : 0};
   s.tm.before(PSM_K_REDUCE);
   if (!r.fuse1) PSM_REPEAT(h, PSM_K_REDUCE) HIPCHK(h, psm_launch_reduce(ra, s.st));      // fused: Dense 0's launch sums the slabs
   s.tm.after(PSM_K_REDUCE);
@@ -404,9 +418,11 @@ static int prepare_scale(psm_handle* h, Workspace& w, const float* out_scale, in
 // else the route depends on is fixed while cached graphs live, because what changes it drops them: psm_plan_grid (free_plan), the
 // model setters, psm_bind_geometry* / psm_unbind_geometry and a guard trip (destroy_graphs, which calls ring_drop_graphs), the
 // integration and post-step bind / unbind entries (the graphs that hold their tables); timed and profiled solves are never captured.
+// PSM_SDF_FOLD, which the route also reads per solve, IS part of the key (fold_applies): a sequence captured with the folded encode is
+// never replayed under PSM_SDF_FOLD=0, nor the other way round.
 // NOT covered: PSM_LN_FUSE, which the route reads per solve -- a graph captured under one value is replayed under the other.
 int sequence_key(const psm_handle* h, int n_cases, bool scale, bool ring) {
-  const int k = (n_cases * 2 + (scale ? 1 : 0)) * 2 + (bound_applies(h, n_cases) ? 1 : 0);
+  const int k = ((n_cases * 2 + (scale ? 1 : 0)) * 2 + (bound_applies(h, n_cases) ? 1 : 0)) * 2 + (fold_applies(h, n_cases) ? 1 : 0);
   return ring ? k * 2 + (h->ring_dma ? 1 : 0) : k;
 }
 
@@ -480,7 +496,8 @@ int guard_drop(psm_handle* h, const char* where) {
   HIPCHK(h, hipStreamSynchronize(h->stream));
   destroy_graphs(h);
   h->bound = false;
-  h->err = std::string(where) + ": the grid's flow-cell pattern (SDF channel != 0) is not the one bound with psm_bind_geometry; the binding was dropped";
+  h->fold_bound = false;
+  h->err = std::string(where) + ": the grid's flow-cell pattern (SDF channel != 0; with the SDF fold, the SDF channel's values) is not the one bound with psm_bind_geometry; the binding was dropped";
   return PSM_OK;
 }
 

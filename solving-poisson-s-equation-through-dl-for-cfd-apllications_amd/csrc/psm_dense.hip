@@ -48,7 +48,7 @@ __global__ __launch_bounds__(1024) void psm_reduce_kernel(PsmReduceArgs a) {
 #pragma unroll
     for (int w = 0; w < 16; ++w) v += red[w][lane];
     const int col = (int)(o % a.ldp);
-    a.xin[o] = v * a.ia[col] + a.ib[col];
+    a.xin[o] = v * a.ia[col] + a.ib[(o / a.ldp) * a.ib_stride + col];
   }
 }
 
@@ -93,7 +93,7 @@ __global__ __launch_bounds__(1024) void psm_reduce_dense1_kernel(PsmReduceArgs r
   }
   // input-scaler operands of the coefficient this thread finishes below
   const int pfin = min(tid, r.ldp - 1);
-  const float ia_v = r.ia[pfin], ib_v = r.ib[pfin];
+  const float ia_v = r.ia[pfin], ib_v = r.ib[(int64_t)m * r.ib_stride + pfin];
   const float bias0 = d.bias[n0 + min(tid, ncols - 1)];
   __builtin_amdgcn_sched_barrier(0);
   // slab sums: wave w adds slabs [16w, 16w+16) for two 64-column groups per pass, all 32 loads

@@ -107,6 +107,13 @@ __device__ __forceinline__ bool psm_guard_wave(const PsmGuardArgs& g, int gw, in
     const unsigned long long got = __ballot(v[u] != 0.f);           // NaN != 0 is true, like NumPy's `!= 0`
     bad |= (gw * NB + u < g.n_ballots) && got != want[u];
   }
+  if (g.sdf_ref) {                                     // uniform.  SDF fold: the bound VALUES (the pixels of the clamped tail compare a pixel with itself)
+    float ref[NB];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) ref[u] = g.sdf_ref[min((long long)(gw * NB + u) * 64 + lane, g.npix - 1)];
+#pragma unroll
+    for (int u = 0; u < NB; ++u) bad |= __ballot(!(v[u] == ref[u])) != 0ull;      // NaN == x is false: a mismatch
+  }
   return bad;                                          // wave-uniform
 }
 // One guard workgroup (index gwg of this launch's range, uniform): PSM_GUARD_WG_WAVES guard waves' worth of pixels by the WAVES

@@ -16,6 +16,91 @@
 #include <cstdlib>
 
 // ---------------------------------------------------------------------------
+// SDF fold (PsmEncodeArgs::fold; bound geometry, SDF channel last): the contraction runs over the CH = C_IN - 1 leading channels
+// only.  A row is still loaded as the 16-byte pieces of its C_IN interleaved channels (same addresses, same aligned loads); on
+// the way into LDS the piece's elements of the leading channels are centred and written COMPACTED -- element e = 4 lane + j of
+// the slice (pixel e / C_IN, channel e % C_IN) goes to float (e / C_IN) CH + e % C_IN of the row, LDS row stride 64 CH + 4 --
+// and its SDF elements go to the row's four padding floats, which no MFMA operand read touches (no predicated store).
+// ---------------------------------------------------------------------------
+template <int C_IN, int CH>
+__device__ __forceinline__ void psm_fold_slots(int lane, int (&dst)[4]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int e = 4 * lane + j, pix = e / C_IN, ch = e - pix * C_IN;
+    dst[j] = ch < CH ? pix * CH + ch : PSM_PIX_PER_SLICE * CH + j;
+  }
+}
+
+// One row tile (<= 32 block rows), one slab per slice, SDF channel folded: the straight-line form of psm_encode_kernel's common
+// case (rows requested before the basis slice, counted waits) over CH channels.
+template <int C_IN, bool ALIGNED>
+__device__ __forceinline__ void psm_encode_tile_fold(const PsmEncodeArgs& a, float* lds) {
+  constexpr int CH = C_IN > 1 ? C_IN - 1 : 1;
+  constexpr int KS = PSM_PIX_PER_SLICE * C_IN;  // K elements of a slice in the grid
+  constexpr int KC = PSM_PIX_PER_SLICE * CH;    // ... contracted
+  constexpr int G = KC / 8, LDA = KC + 4, Q = KS / 4;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int s = blockIdx.x;
+  const int runs = a.S / PSM_PIX_PER_SLICE;
+  const int r = s / runs, c0 = (s - r * runs) * PSM_PIX_PER_SLICE;
+  const int64_t src_off = (int64_t)r * a.row_stride + (int64_t)c0 * C_IN;
+  const int NT = a.NT;
+  const int i = lane & 31, h = lane >> 5;
+  const int ql = lane < Q ? lane : Q - 1;
+  const float4 mu = *reinterpret_cast<const float4*>(a.mean + (int64_t)s * KS + 4 * ql);
+  int dst[4];
+  psm_fold_slots<C_IN, CH>(ql, dst);
+  const int t = min(wave, NT - 1);
+  int64_t rb[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) rb[u] = psm_row_base(a.row_base, min(wave + 4 * u, a.M - 1));   // wave-uniform: scalar loads
+  float4 x[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    const float* src = a.grid + rb[u] + src_off + 4 * ql;
+    if (ALIGNED) x[u] = *reinterpret_cast<const float4*>(src);
+    else x[u] = make_float4(src[0], src[1], src[2], src[3]);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  float4 b[G];
+  {
+    const float4* p = a.bpack + (((int64_t)s * NT + t) * G) * 64 + lane;
+#pragma unroll
+    for (int g = 0; g < G; ++g) b[g] = stream_load(p + g * 64);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {                 // waits for the activation rows only (counted vmcnt)
+    const int row = wave + 4 * u;
+    const float keep = row < a.M ? 1.f : 0.f;   // padding rows -> 0 (no branch)
+    if (lane < Q) {
+      float* o = &lds[row * LDA];
+      o[dst[0]] = (x[u].x - mu.x) * keep; o[dst[1]] = (x[u].y - mu.y) * keep;
+      o[dst[2]] = (x[u].z - mu.z) * keep; o[dst[3]] = (x[u].w - mu.w) * keep;
+    }
+  }
+  __syncthreads();
+  f32x16 acc = {0};
+  const float* arow = &lds[i * LDA + 4 * h];
+  float4 av = *reinterpret_cast<const float4*>(arow);
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    const float4 an = *reinterpret_cast<const float4*>(arow + 8 * (g + 1 < G ? g + 1 : g));   // next group in flight
+    acc = MFMA32(av.x, b[g].x, acc);
+    acc = MFMA32(av.y, b[g].y, acc);
+    acc = MFMA32(av.z, b[g].z, acc);
+    acc = MFMA32(av.w, b[g].w, acc);
+    av = an;
+  }
+  if (wave < NT) {
+    float* out = a.part + ((int64_t)s * a.Mpad) * a.ldp + t * 32 + i;
+#pragma unroll
+    for (int rg = 0; rg < 16; ++rg) out[(int64_t)acc_row(rg, h) * a.ldp] = acc[rg];
+  }
+}
+
+// ---------------------------------------------------------------------------
 // encode
 // ---------------------------------------------------------------------------
 template <int C_IN, bool ALIGNED>
@@ -26,6 +111,7 @@ __global__ __launch_bounds__(256) void psm_encode_kernel(PsmEncodeArgs a) {
   constexpr int LDA = KS + 4;                   // LDS row stride (floats): 16-B slots rotate by one per row
   constexpr int Q = KS / 4;                     // 16-byte pieces per activation row (<= 64)
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  if (C_IN > 1 && a.fold) { psm_encode_tile_fold<C_IN, ALIGNED>(a, lds); return; }   // uniform; the launcher sets it for one row tile, NT <= 4 only
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int s = blockIdx.x;
@@ -251,14 +337,17 @@ __global__ __launch_bounds__(256) void psm_encode_kernel(PsmEncodeArgs a) {
 // form above; what halves is the slab traffic (4.2 -> 2.1 MB written) and, above all, what the ONE workgroup per block row
 // of psm_reduce_dense1_kernel has to pull in front of the first Dense layer (128 -> 64 KB: that launch's longest phase).
 // ---------------------------------------------------------------------------
-template <int C_IN, bool ALIGNED>
-__global__ __launch_bounds__(256) void psm_encode_pair_kernel(PsmEncodeArgs a) {
-  psm_warm_kernargs<sizeof(PsmEncodeArgs)>();
-  constexpr int KS = PSM_PIX_PER_SLICE * C_IN;  // K elements per slice
-  constexpr int G = KS / 8;                     // groups of 8 k
-  constexpr int LDA = KS + 4;                   // LDS row stride (floats): 16-B slots rotate by one per row
+// The body is a template over the CONTRACTED channel count CH: C_IN (every channel), or C_IN - 1 with the SDF channel folded
+// (PsmEncodeArgs::fold, see psm_fold_slots): fewer basis groups in registers, fewer MFMAs, a narrower LDS row; the row loads, the
+// request order and the pair sum are the same.
+template <int C_IN, int CH, bool ALIGNED>
+__device__ __forceinline__ void psm_encode_pair_body(const PsmEncodeArgs& a, float* lds) {
+  constexpr int KS = PSM_PIX_PER_SLICE * C_IN;  // K elements per slice in the grid
+  constexpr int KC = PSM_PIX_PER_SLICE * CH;    // ... contracted
+  constexpr int G = KC / 8;                     // groups of 8 k
+  constexpr int LDA = KC + 4;                   // LDS row stride (floats): 16-B slots rotate by one per row
   constexpr int Q = KS / 4;                     // 16-byte pieces per activation row (<= 64)
-  extern __shared__ __attribute__((aligned(16))) float lds[];                  // [2 slices][32 rows][LDA], then [2 tiles][64 lanes][16]
+  constexpr bool FOLD = CH != C_IN;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int sl = wave >> 1, j = wave & 1;       // this wave's slice of the pair; its row parity in the staging and its component tile of the half
@@ -271,6 +360,8 @@ __global__ __launch_bounds__(256) void psm_encode_pair_kernel(PsmEncodeArgs a) {
   const int i = lane & 31, h = lane >> 5;
   const int ql = lane < Q ? lane : Q - 1;       // lanes >= Q idle in the staging (C_IN < 4)
   const float4 mu = *reinterpret_cast<const float4*>(a.mean + (int64_t)s * KS + 4 * ql);
+  int dst[4];
+  if (FOLD) psm_fold_slots<C_IN, CH>(ql, dst);
   // Request order (round 6): the block-row offsets are a dependent table lookup in front of the activation rows.  They are
   // wave-uniform, so they come through the scalar cache (address space 4: s_load_dwordx2, its own counter) instead of sixteen
   // wave-wide vector loads, and the FIRST HALF of the basis stream is requested before anything waits for them: the lookup's round
@@ -305,7 +396,10 @@ __global__ __launch_bounds__(256) void psm_encode_pair_kernel(PsmEncodeArgs a) {
     const int row = j + 2 * u;
     const float keep = row < a.M ? 1.f : 0.f;   // padding rows -> 0 (no branch)
     const float4 v = make_float4((x[u].x - mu.x) * keep, (x[u].y - mu.y) * keep, (x[u].z - mu.z) * keep, (x[u].w - mu.w) * keep);
-    if (lane < Q) *reinterpret_cast<float4*>(&tile[row * LDA + 4 * lane]) = v;
+    if (FOLD) {
+      float* o = &tile[row * LDA];
+      if (lane < Q) { o[dst[0]] = v.x; o[dst[1]] = v.y; o[dst[2]] = v.z; o[dst[3]] = v.w; }
+    } else if (lane < Q) *reinterpret_cast<float4*>(&tile[row * LDA + 4 * lane]) = v;
   }
   __syncthreads();
   f32x16 acc = {0};
@@ -334,6 +428,14 @@ __global__ __launch_bounds__(256) void psm_encode_pair_kernel(PsmEncodeArgs a) {
 #pragma unroll
     for (int rg = 0; rg < 16; ++rg) out[(int64_t)acc_row(rg, h) * a.ldp] = acc[rg] + red[rg * 64 + lane];
   }
+}
+
+template <int C_IN, bool ALIGNED>
+__global__ __launch_bounds__(256) void psm_encode_pair_kernel(PsmEncodeArgs a) {
+  psm_warm_kernargs<sizeof(PsmEncodeArgs)>();
+  extern __shared__ __attribute__((aligned(16))) float lds[];                  // [2 slices][32 rows][LDA], then [2 tiles][64 lanes][16]
+  if (C_IN > 1 && a.fold) psm_encode_pair_body<C_IN, (C_IN > 1 ? C_IN - 1 : 1), ALIGNED>(a, lds);   // uniform
+  else psm_encode_pair_body<C_IN, C_IN, ALIGNED>(a, lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -753,6 +855,8 @@ hipError_t psm_launch_encode(const PsmEncodeArgs& a, hipStream_t st, hipEvent_t 
   size_t lds = (size_t)rows * (PSM_PIX_PER_SLICE * a.c_in + 4) * sizeof(float);
   size_t lds_x6 = 0;
   int row_wgs = 1;
+  // SDF fold: only the float32 forms of one row tile have the arm (choose_route, psm_api_solve.cpp, asks for nothing else)
+  if (a.fold && (a.x6 || a.kgroup > 1 || a.Mpad != 32 || a.NT > 4 || a.c_in < 2)) return hipErrorInvalidValue;
   if (a.x6 && a.kgroup > 1) {
     // kgroup = number of K GROUPS here (the slab count); a group holds n_slices / kgroup slices, rounded either way, at most 8
     if (a.NT > 4 || a.Mpad % 32 != 0 || a.kgroup > n_slices || (n_slices + a.kgroup - 1) / a.kgroup > 8 || !a.bpack_x6) return hipErrorInvalidValue;

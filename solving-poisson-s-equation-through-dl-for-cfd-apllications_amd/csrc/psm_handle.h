@@ -31,6 +31,7 @@
 #include "psm_kernels.h"
 #include "psm_mesh.h"
 #include "psm_plan.h"
+#include "psm_fold.h"
 
 namespace psm_impl __attribute__((visibility("hidden"))) {
 extern thread_local std::string g_create_error;   // message of the last failed psm_create (psm_api_model.cpp)
@@ -79,7 +80,9 @@ struct SolveRoute {
   bool bf16 = false;
   bool bound = false;                   // geometry-bound path (6 / 7 launches), else the general path
   bool cf = false;                      // bound: closed form of the offset chain (pair dots, no chain launch)
-  bool guard = false;                   // bound: guard riders check the grid's flow-cell pattern
+  bool guard = false;                   // bound: guard riders check the grid's flow-cell pattern (fold: the SDF channel's values)
+  bool fold = false;                    // bound single case: the encode contracts the c_in - 1 leading channels, the SDF channel's share of the
+                                        // coefficients comes from the binding (PsmEncodeArgs::fold, PsmReduceArgs::ib_stride); PSM_SDF_FOLD=0: off
   int guard_wgs = 0;                    // guard workgroups of the solve (one flag each)
   bool spread = false;                  // they are dealt over the `rider_carriers` hidden Dense launches, `rider_share` each; the head launch
   int rider_share = 0, rider_carriers = 0;   // (bf16 handles: their dots launch) carries the rest.  Not spread: all of them ride there
@@ -276,6 +279,17 @@ struct psm_handle {
   int *h_guard = nullptr, *m_guard = nullptr;   // mapped pinned page: one word per workspace, raised by a guard wave on mismatch
   float* d_gzero = nullptr;             // one zero: the flags of solves without a guard
   int64_t guard_trips = 0;
+  // SDF fold of the bound single-case encode (PsmEncodeArgs::fold, psm_fold.h): float32 handles whose SDF channel
+  // is the last one.  psm_set_pca keeps a float32 host copy of comp_in until the first bind that can use it (bind_sdf_fold, psm_api_plan.cpp),
+  // which turns it into the basis packed over the leading channels (d_bpack_fold: as many bytes as (c_in - 1) / c_in of d_bpack_in) and
+  // the SDF channel's rows; every bind builds the per-row input-scaler offset and keeps the bound SDF image for the guard riders.
+  std::vector<float> h_comp_in;         // [p_in][K_in], released by the first fold bind
+  std::vector<float> h_comp_sdf, h_mean_sdf;   // [p_in][S*S], [S*S]
+  std::vector<float> h_ia, h_ib;        // host copies of d_ia / d_ib
+  float4* d_bpack_fold = nullptr;
+  float* d_ib_fold = nullptr;           // [32][ld_in]: ib[p] + ia[p] * c_sdf[m][p] (rows beyond B: ib)
+  float* d_sdf_bound = nullptr;         // [Ny*Nx] SDF channel of the bound grid
+  bool fold_bound = false;              // the three tables above belong to the current binding
   int debug_skip = 0;                   // PSM_DEBUG_SKIP bit mask of kernel groups NOT launched (timing experiments only)
   bool fuse_reduce_dense1 = true;       // PSM_NO_FUSED_REDUCE=1 disables
   int last_cases = 0;

@@ -24,6 +24,10 @@ struct PsmEncodeArgs {
   int M, Mpad, NT, ldp, S, c_in, aligned;
   int whole;               // 33..128 rows: stage all rows at once (PSM_ENCODE_CHUNKED=1 keeps the double-buffered chunks)
   int x6;                  // float32 contraction as six bf16 MFMA terms of exactly split operands (psm_encode_x6_kernel)
+  int fold;                // bound geometry, SDF channel last (psm_api_plan.cpp, bind_sdf_fold): contract the c_in - 1 leading channels only.  The launched
+                           // instantiation and the row loads stay those of c_in; `bpack` is then the basis packed over c_in - 1 channels (pack_comp_in_fold,
+                           // KS = 64 (c_in - 1)) and the SDF channel's share of the coefficients arrives through the reduce's per-row `ib` (PsmReduceArgs::ib_stride).
+                           // One row tile only: psm_encode_pair_kernel and the <= 32-row arm of psm_encode_kernel.  (Sits in what was padding: no other field moved.)
   const uint4* bpack_x6;   // the basis pre-split into three bf16 planes, MFMA fragment order (pack_comp_in_x6); psm_encode_x6_mt_kernel only
   int kgroup;              // > 1: the M-tiled, wave-specialised form for large case batches (psm_encode_x6_mt_kernel) with `kgroup` K GROUPS: a
                            // workgroup owns one group of consecutive K slices x PSM_ENC_MT_ROWS (64) block rows and writes ONE slab -- part [kgroup][Mpad][ldp];
@@ -37,6 +41,7 @@ struct PsmReduceArgs {
   const float* part; float* xin;       // xin [Mpad][ldp]
   const float* ia; const float* ib;    // affine input scaler per column (0 on padding)
   int n_slices, Mpad, ldp;
+  int ib_stride;                       // floats between the `ib` rows of two block rows; 0: one row for all (no SDF fold)
 };
 
 struct PsmDenseArgs {
@@ -176,6 +181,8 @@ struct PsmGuardArgs {
   long long npix;                      // cases * Ny * Nx
   int c_in, n_ballots, n_waves;
   int wg_first, wg_count;              // the guard workgroups THIS launch carries
+  const float* sdf_ref;                // [npix] SDF image of the binding when the encode folds the SDF channel (PsmEncodeArgs::fold): the contract is then the
+                                       // channel's VALUES -- float ==, a NaN on either side is a mismatch; null: the pattern alone
 };
 constexpr int PSM_GUARD_WG_WAVES = 8;  // guard waves per flag
 constexpr int PSM_GUARD_BALLOTS = 8;   // per guard wave: 512 pixels

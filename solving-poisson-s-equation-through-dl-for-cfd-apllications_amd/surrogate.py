@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Optional, Sequence
 
 import numpy as np
@@ -40,6 +41,15 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _fold_switch_on() -> bool:
+    """PSM_SDF_FOLD as the library reads it (``atoi(value) == 0`` switches the fold off; unset: on)."""
+    e = os.environ.get("PSM_SDF_FOLD")
+    if e is None:
+        return True
+    m = re.match(r"\s*[+-]?\d+", e)
+    return (int(m.group(0)) if m else 0) != 0
+
+
 class GridSurrogate:
     """One surrogate model bound to one uniform grid shape on one GPU."""
 
@@ -51,6 +61,7 @@ class GridSurrogate:
             raise ValueError("Standardization method not valid")
         self.lib = _lib.load()
         self.model, self.ny, self.nx, self.max_cases = model, int(ny), int(nx), int(max_cases)
+        self.precision = precision
         cfg = _lib.psm_config(
             abi_version=_lib.PSM_ABI_VERSION, variant=_lib.VARIANTS[model.variant], block=model.S,
             overlap=0 if model.ov is None else int(model.ov), c_in=model.c_in, c_out=model.c_out,
@@ -233,6 +244,7 @@ class GridSurrogate:
                 raise ValueError(f"grid must be [{self.ny},{self.nx},{self.model.c_in}] or [n,{self.ny},{self.nx},{self.model.c_in}]")
             rc = self.lib.psm_bind_geometry_cases(self.h, g.ctypes.data_as(C.c_void_p), g.shape[0], 0)
         self._bound_mask = None
+        self._bound_sdf = None
         if rc == -5:                    # PSM_ERR_UNSUPPORTED: configuration outside the fused path
             return False
         self._chk(rc)
@@ -240,10 +252,17 @@ class GridSurrogate:
         m = np.empty((n, self.ny, self.nx), np.uint8)          # the pattern the library bound (also for device grids)
         self._chk(self.lib.psm_bound_mask(self.h, m.ctypes.data_as(C.POINTER(C.c_uint8)), m.size))
         self._bound_mask = m.astype(bool)
+        # SDF fold of the bound single-case encode: the contract is then the SDF channel's VALUES.  The
+        # conditions mirror fold_applies (psm_api_solve.cpp); a grid bound from a device pointer leaves the host check at the pattern
+        # (the guard riders on the device compare the values in every case).
+        if (not on_device and n == 1 and self.precision == "f32" and self.model.c_in >= 2
+                and self.model.sdf_ch == self.model.c_in - 1):
+            self._bound_sdf = g[..., self.model.sdf_ch].copy()
         return True
 
     def unbind_geometry(self):
         self._bound_mask = None
+        self._bound_sdf = None
         self._chk(self.lib.psm_unbind_geometry(self.h))
 
     # Host-grid entries can verify the contract of psm_bind_geometry: with ``check_bound = True`` a grid whose flow-cell
@@ -256,6 +275,10 @@ class GridSurrogate:
             return
         m = getattr(self, "_bound_mask", None)
         if m is not None and g.shape[0] == m.shape[0] and not np.array_equal(g[..., self.model.sdf_ch] != 0, m):
+            self.unbind_geometry()
+            return
+        v = getattr(self, "_bound_sdf", None)           # folded encode: values (a NaN on either side is a mismatch, as on the device)
+        if v is not None and g.shape[0] == v.shape[0] and _fold_switch_on() and not bool(np.all(g[..., self.model.sdf_ch] == v)):
             self.unbind_geometry()
 
     @property
