@@ -400,6 +400,35 @@ int psm_solve_poststeps_device(psm_handle* h, const float* d_grid, int32_t n_cas
 int psm_solve_poststeps(psm_handle* h, const float* grid, int32_t n_cases, const float* out_scale, int32_t apply_filter,
                         const float* dU, const float* prev, float* result, float* change, float* next);
 
+/* The pressureSM_Poisson input features on the device, for a case batch on the PLANNED grid, and the whole time step behind
+ * them: d_vel (Ux, Uy, dUx, dUy) -> features -> 4-channel deltas solve -> post-steps -> result / change / next, in device
+ * memory from end to end.  Two launches for the whole batch (csrc/psm_features.hip): the arithmetic, its order and the
+ * reduction partition are those of psm_poisson_features, so image i of a batch is bit-identical to that entry's on case i;
+ * mean and standard deviation of the arcsinh transform are per case.
+ * psm_bind_features: once per simulation, on the PLANNED grid; c_in == 4 and sdf_channel == 3, else PSM_ERR_STATE.
+ * sdfunct [n_cases][ny*nx] float64 (raw SDF image, 0 in solids), k, max_abs[4] as in psm_poisson_features.
+ * Uploads the SDF planes; reserves term / partial / image / staging buffers for n_cases cases and the pinned
+ * slots for the per-step scalars: after it a step allocates nothing.  PSM_ERR_ARG: n_cases outside
+ * [1, max_cases], a zero max_abs, non-finite k.  psm_plan_grid or a model change drops the binding.
+ * The entries below take any n_cases in [1, bound count] (PSM_ERR_ARG otherwise); case i uses SDF slot i. */
+int psm_bind_features(psm_handle* h, const double* sdfunct, int32_t n_cases, double k, const double* max_abs);
+int psm_unbind_features(psm_handle* h);
+/* d_vel [n_cases][4][ny*nx] float64 planes (ux, uy, dux, duy; dimensional, zero outside the flow, NaN allowed)
+ * -> d_grid [n_cases,ny,nx,4] float32 (16-byte aligned).  LU: HOST array [n_cases][2] = (L, U) per case, copied
+ * before the call returns (as out_scale is); PSM_ERR_ARG and nothing enqueued if any U == 0 or is not finite.
+ * Device pointers, asynchronous on `stream` (NULL: the handle's). */
+int psm_features_device(psm_handle* h, const double* d_vel, int32_t n_cases, const double* LU, float* d_grid, void* stream);
+/* features + psm_solve_poststeps_device as ONE graph replay; the image lives in a buffer of the handle.  Needs
+ * psm_bind_poststeps as well as psm_bind_features (PSM_ERR_STATE names the missing one).
+ * d_dU == NULL: no weighting (then apply_filter == 0 is the plain solve, result = the assembled field). */
+int psm_poisson_step_device(psm_handle* h, const double* d_vel, int32_t n_cases, const double* LU, const float* out_scale,
+                            int32_t apply_filter, const float* d_dU, const float* d_prev,
+                            float* d_result, float* d_change, float* d_next, void* stream);
+/* host buffers, synchronous: vel [n_cases][4][ny*nx] float64 in, float32 fields out; one H2D of the velocities
+ * (+ dU, prev), no image round trip.  Solves again on the general path after a guard trip, like psm_solve_poststeps. */
+int psm_poisson_step(psm_handle* h, const double* vel, int32_t n_cases, const double* LU, const float* out_scale,
+                     int32_t apply_filter, const float* dU, const float* prev, float* result, float* change, float* next);
+
 /* U_to_gradP: integrate the assembled (dp/dx, dp/dy) into p (integrate_field,
  * Eval_dual_Dense_onlycil.py:371-416, and the four-quadrant stitching :597-628).
  * psm_set_integration fixes the geometry: sdfunct [ny*nx] (self.sdfunct[:,:,0], also used by the
@@ -463,7 +492,9 @@ int psm_get_kernel_timing(psm_handle* h, int32_t kernel, double* total_ms, int64
  * *n_kernels the number of distinct kernels (may exceed cap).  While an integration is bound for n_cases cases
  * (psm_bind_integration) the timed step is that of psm_solve_pressure_device: its two launches are stamped too; while
  * post-steps are bound on a c_out == 1 handle (psm_bind_poststeps), that of psm_solve_poststeps_device with the weighting
- * and apply_filter (dU and prev: the handle's scratch). */
+ * and apply_filter (dU and prev: the handle's scratch); with the Poisson features bound for n_cases cases as well
+ * (psm_bind_features), that of psm_poisson_step_device: the two feature launches write the handle's image from its staging
+ * planes and the solve reads that image, not d_grid. */
 int psm_time_kernels(psm_handle* h, const float* d_grid, int32_t n_cases, float* d_fields, int32_t steps, char* names,
                      double* total_ms, int64_t* launches, int32_t cap, int32_t* n_kernels);
 /* The same pass, reported per kernel as the MEDIAN and the 10th / 90th percentile of its dispatch durations in microseconds

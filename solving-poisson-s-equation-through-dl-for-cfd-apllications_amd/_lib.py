@@ -101,6 +101,11 @@ SIGNATURES = {
     "psm_poststeps_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "psm_solve_poststeps_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "psm_solve_poststeps": (C.c_int, [_hp, _f32p, C.c_int32, _f32p, C.c_int32, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "psm_bind_features": (C.c_int, [_hp, _f64p, C.c_int32, C.c_double, _f64p]),
+    "psm_unbind_features": (C.c_int, [_hp]),
+    "psm_features_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, _f64p, C.c_void_p, C.c_void_p]),
+    "psm_poisson_step_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, _f64p, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_poisson_step": (C.c_int, [_hp, _f64p, C.c_int32, _f64p, _f32p, C.c_int32, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
     "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),

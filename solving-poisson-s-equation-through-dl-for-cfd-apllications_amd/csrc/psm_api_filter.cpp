@@ -80,7 +80,7 @@ int poststeps_device(psm_handle* h, const float* d_fields, int n, const PostCall
 }
 
 // state and argument checks shared by the device-resident entries
-static int post_check(psm_handle* h, int n_cases, const PostCall& pc) {
+int post_check(psm_handle* h, int n_cases, const PostCall& pc) {
   if (!h->planned) return fail(h, PSM_ERR_STATE, "psm_plan_grid has not been called");
   if (!h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called (a new plan or model drops the binding)");
   if (n_cases < 1 || n_cases > h->cfg.max_cases) return fail(h, PSM_ERR_ARG, "n_cases outside [1, max_cases]");

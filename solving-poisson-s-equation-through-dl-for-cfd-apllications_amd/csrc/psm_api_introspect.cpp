@@ -52,7 +52,13 @@ static int collect_kernel_samples(psm_handle* h, const float* d_grid, int32_t n_
     PostCall pc;
     const bool post = h->post.ready && h->cfg.c_out == 1;
     if (post) { pc.apply_filter = 1; pc.dU = h->post.d_dU; pc.prev = h->post.d_prev; pc.result = h->post.d_out; pc.change = h->post.d_out + (size_t)h->cfg.max_cases * h->Ny * h->Nx; pc.next = pc.change + (size_t)h->cfg.max_cases * h->Ny * h->Nx; }
-    rc = solve_device(h, d_grid, n_cases, nullptr, d_fields, h->stream, nullptr, integ ? h->integ_dev.d_p : nullptr, post ? &pc : nullptr);
+    // with the Poisson features bound as well (psm_bind_features) it is the step of psm_poisson_step_device: the two feature launches
+    // write the binding's image from its staging planes and scalars (zero velocities, (1, 1) unless a host step left others) and
+    // the solve reads that image instead of d_grid
+    const FeatCall fc{h->feat.d_vel, h->feat.d_grid};
+    const bool feat = post && h->feat.ready && n_cases <= h->feat.n_cases;
+    rc = solve_device(h, feat ? fc.grid : d_grid, n_cases, nullptr, d_fields, h->stream, nullptr, integ ? h->integ_dev.d_p : nullptr, post ? &pc : nullptr,
+                      feat ? &fc : nullptr);
     if (rc == PSM_OK && (i % 64) == 63) rc = drain();
   }
   psm_launch_probe = nullptr;

@@ -122,6 +122,7 @@ void free_plan(psm_handle* h) {
   if (h->mesh_graph) { (void)hipGraphExecDestroy(h->mesh_graph); h->mesh_graph = nullptr; }
   integ_free(h->integ_dev);             // psm_bind_integration is sized by this plan's grid
   post_free(h->post);                   // and so is psm_bind_poststeps
+  feat_free(h->feat);                   // and psm_bind_features
 }
 
 
@@ -354,6 +355,7 @@ int psm_set_pca(psm_handle* h, const double* comp_in, const double* mean_in, con
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->feat.ready = false;                 // and psm_bind_features
   std::vector<float> mi(h->K_in), mo(h->K_out);
   for (int k = 0; k < h->K_in; ++k) mi[k] = (float)mean_in[k];
   for (int k = 0; k < h->K_out; ++k) mo[k] = (float)mean_out[k];
@@ -421,6 +423,7 @@ int psm_set_dense(psm_handle* h, int32_t layer, int32_t n_in, int32_t n_out, con
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->feat.ready = false;                 // and psm_bind_features
   DenseLayer& d = h->dense[layer];
   d.linear = false;                                     // psm_set_attention sets it again after this call
   if (d.ln && (d.n_out != n_out || (d.ln_residual && n_in != n_out))) {      // a LayerNormalization of another width, or its residual x + input on a
@@ -510,6 +513,7 @@ int psm_set_layernorm(psm_handle* h, int32_t layer, int32_t n, const float* gamm
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->feat.ready = false;                 // and psm_bind_features
   // zero-padded to whole 16-byte pieces past the consumer's leading dimension: a Dense launch that applies this normalisation to
   // its input (launch_all) reads gamma / beta with the clamped column index of its operand loads
   std::vector<float> g(round_up(n, 32) + 32, 0.f), b(round_up(n, 32) + 32, 0.f);
@@ -540,6 +544,7 @@ int psm_set_conv1d(psm_handle* h, int32_t layer, int32_t n_layers, int32_t kerne
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->feat.ready = false;                 // and psm_bind_features
   if (!same_stack) {
     for (auto& c : h->conv1d) { dev_free(c.W); dev_free(c.b); }
     h->conv1d.assign(n_layers, Conv1dLayer{});
@@ -568,6 +573,7 @@ int psm_set_scaler(psm_handle* h, const double* in_a, const double* in_b, const 
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->feat.ready = false;                 // and psm_bind_features
   std::vector<float> ia(h->ld_in, 0.f), ib(h->ld_in, 0.f), sa(h->ld_out, 0.f), sb(h->ld_out, 0.f);
   // x_in = coeff*ia + ib ; res' = res*sa + sb  (affine forms of SMD:505-539, evaluated in f64 here)
   for (int p = 0; p < h->cfg.p_in; ++p) {

@@ -417,7 +417,7 @@ static int prepare_scale(psm_handle* h, Workspace& w, const float* out_scale, in
 // count, whether a row scale is uploaded, whether the bound geometry applies and, for the ring, the DMA / pull form.  Everything
 // else the route depends on is fixed while cached graphs live, because what changes it drops them: psm_plan_grid (free_plan), the
 // model setters, psm_bind_geometry* / psm_unbind_geometry and a guard trip (destroy_graphs, which calls ring_drop_graphs), the
-// integration and post-step bind / unbind entries (the graphs that hold their tables); timed and profiled solves are never captured.
+// integration, post-step and feature bind / unbind entries (the graphs that hold their tables); timed and profiled solves are never captured.
 // PSM_SDF_FOLD, which the route also reads per solve, IS part of the key (fold_applies): a sequence captured with the folded encode is
 // never replayed under PSM_SDF_FOLD=0, nor the other way round.
 // NOT covered: PSM_LN_FUSE, which the route reads per solve -- a graph captured under one value is replayed under the other.
@@ -444,7 +444,7 @@ int capture_graph(psm_handle* h, hipStream_t st, const char* label, const std::f
 
 
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
-                 hipStream_t st, hipEvent_t* prof, float* d_p, const PostCall* post) {
+                 hipStream_t st, hipEvent_t* prof, float* d_p, const PostCall* post, const FeatCall* feat) {
   if (!h) return PSM_ERR_ARG;
   if (!h->planned) return fail(h, PSM_ERR_STATE, "psm_plan_grid has not been called");
   if (!d_grid || !d_fields) return fail(h, PSM_ERR_ARG, "null buffer");
@@ -457,15 +457,16 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
   rc = prepare_scale(h, h->ws0, out_scale, n_cases, st, &d_scale);
   if (rc) return rc;
   h->last_cases = n_cases;
-  // the solve, then the two integration launches (d_p) or the post-steps' (at most four): one linear chain
+  // the two feature launches (feat), the solve, then the two integration launches (d_p) or the post-steps' (at most four): one linear chain
   auto sequence = [&](hipStream_t on, hipEvent_t* ev) {
-    int rs = launch_all(h, h->ws0, d_grid, n_cases, d_fields, d_scale, on, ev);
+    int rs = feat ? features_device(h, feat->vel, n_cases, feat->grid, on) : PSM_OK;
+    if (!rs) rs = launch_all(h, h->ws0, d_grid, n_cases, d_fields, d_scale, on, ev);
     if (!rs && d_p) rs = integrate_device(h, d_fields, n_cases, d_p, on);
     if (!rs && post) rs = poststeps_device(h, d_fields, n_cases, *post, on);
     return rs;
   };
   if (prof || h->timed_kernel >= 0 || !h->use_graph) return sequence(st, prof);
-  const GraphKey key{sequence_key(h, n_cases, out_scale != nullptr), d_grid, d_fields, d_p, post ? *post : PostCall{}};
+  const GraphKey key{sequence_key(h, n_cases, out_scale != nullptr), d_grid, d_fields, d_p, post ? *post : PostCall{}, feat ? feat->vel : nullptr};
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     if (h->graphs.size() > 64) destroy_graphs(h);

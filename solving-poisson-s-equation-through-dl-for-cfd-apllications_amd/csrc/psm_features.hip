@@ -9,6 +9,10 @@
 // written as float32 NHWC, the layout the encode kernel reads.  Two launches: the term plus
 // per-workgroup (sum, sum of squares) partials in a fixed order, then every workgroup of the
 // second launch folds the partials the same way (deterministic) and transforms its pixels.
+// A case batch is ONE launch per stage: the case is the grid's second dimension, every plane, the term scratch, the partials and
+// the image have a per-case stride, and mean / standard deviation are folded from that case's own partials only.  The per-step
+// scalars (L, U) of the batched form come from device memory (PsmFeatureArgs::lu), so a captured launch is replayed with new values.
+#include "psm_launch.h"
 #include "psm_mesh.h"
 
 namespace {
@@ -54,22 +58,28 @@ __device__ __forceinline__ double block_sum(double v, double* red) {    // fixed
 
 __global__ __launch_bounds__(FT) void psm_poisson_term_kernel(PsmFeatureArgs a) {
   __shared__ double red[FT];
+  const int c = blockIdx.y;
   const int64_t pix = (int64_t)blockIdx.x * FT + threadIdx.x, n = (int64_t)a.ny * a.nx;
+  const double L = a.lu ? a.lu[2 * c] : a.L, U = a.lu ? a.lu[2 * c + 1] : a.U;
+  const double *ux = a.ux + c * a.vel_stride, *uy = a.uy + c * a.vel_stride, *sdf = a.sdf + c * a.sdf_stride;
   double t = 0.0;
   if (pix < n) {
     const int y = (int)(pix / a.nx), x = (int)(pix - (int64_t)y * a.nx);
-    t = grad_term(a.ux, a.uy, a.sdf, y, x, a.ny, a.nx, a.L * a.L / (a.U * a.U));   // (...) * L**2 / U**2, SMP:635
-    a.term[pix] = t;
+    t = grad_term(ux, uy, sdf, y, x, a.ny, a.nx, L * L / (U * U));   // (...) * L**2 / U**2, SMP:635
+    a.term[c * n + pix] = t;
   }
   const double s1 = block_sum(t, red), s2 = block_sum(t * t, red);
-  if (threadIdx.x == 0) { a.partial[2 * blockIdx.x] = s1; a.partial[2 * blockIdx.x + 1] = s2; }
+  double* partial = a.partial + (int64_t)c * 2 * gridDim.x;          // this case's partials: never mixed with another's
+  if (threadIdx.x == 0) { partial[2 * blockIdx.x] = s1; partial[2 * blockIdx.x + 1] = s2; }
 }
 
 __global__ __launch_bounds__(FT) void psm_poisson_grid_kernel(PsmFeatureArgs a) {
   __shared__ double red[FT];
+  const int c = blockIdx.y;
   const int nwg = gridDim.x;
+  const double* partial = a.partial + (int64_t)c * 2 * nwg;
   double s1 = 0.0, s2 = 0.0;
-  for (int w = threadIdx.x; w < nwg; w += FT) { s1 += a.partial[2 * w]; s2 += a.partial[2 * w + 1]; }
+  for (int w = threadIdx.x; w < nwg; w += FT) { s1 += partial[2 * w]; s2 += partial[2 * w + 1]; }
   s1 = block_sum(s1, red);
   s2 = block_sum(s2, red);
   const int64_t n = (int64_t)a.ny * a.nx;
@@ -80,28 +90,29 @@ __global__ __launch_bounds__(FT) void psm_poisson_grid_kernel(PsmFeatureArgs a) 
   const double lo = mean - a.k * sd, hi = mean + a.k * sd;
   const int64_t pix = (int64_t)blockIdx.x * FT + threadIdx.x;
   if (pix >= n) return;
-  const double t = a.term[pix];
+  const double U = a.lu ? a.lu[2 * c + 1] : a.U;
+  const double t = a.term[c * n + pix];
   double sc;
   if (t < lo) sc = -1.0 - (t - lo) / lo;                    // SMP:50
   else if (t > hi) sc = 1.0 + (t - hi) / hi;                // SMP:52
   else sc = 2.0 * (t - lo) / (hi - lo) - 1.0;               // SMP:54
   double f0 = asinh(sc);                                    // SMP:60
-  double f1 = a.dux[pix] / a.U, f2 = a.duy[pix] / a.U, f3 = a.sdf[pix];
+  double f1 = a.dux[c * a.vel_stride + pix] / U, f2 = a.duy[c * a.vel_stride + pix] / U, f3 = a.sdf[c * a.sdf_stride + pix];
   f0 = (f0 != f0) ? 0.0 : f0; f1 = (f1 != f1) ? 0.0 : f1;   // grid[np.isnan(grid)] = 0, SMP:704
   f2 = (f2 != f2) ? 0.0 : f2; f3 = (f3 != f3) ? 0.0 : f3;
   float4 o;
   o.x = (float)(f0 / a.max_abs[0]); o.y = (float)(f1 / a.max_abs[1]);
   o.z = (float)(f2 / a.max_abs[2]); o.w = (float)(f3 / a.max_abs[3]);
-  reinterpret_cast<float4*>(a.grid)[pix] = o;
+  reinterpret_cast<float4*>(a.grid)[c * n + pix] = o;
 }
 }  // namespace
 
 hipError_t psm_launch_poisson_features(const PsmFeatureArgs& a, hipStream_t st) {
   const int64_t n = (int64_t)a.ny * a.nx;
-  const unsigned nwg = (unsigned)((n + FT - 1) / FT);
-  hipLaunchKernelGGL(psm_poisson_term_kernel, dim3(nwg), dim3(FT), 0, st, a);
+  const dim3 grid((unsigned)((n + FT - 1) / FT), (unsigned)(a.n_cases > 0 ? a.n_cases : 1));
+  PSM_LAUNCH(psm_poisson_term_kernel, grid, dim3(FT), 0, st, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(psm_poisson_grid_kernel, dim3(nwg), dim3(FT), 0, st, a);
+  PSM_LAUNCH(psm_poisson_grid_kernel, grid, dim3(FT), 0, st, a);
   return hipGetLastError();
 }

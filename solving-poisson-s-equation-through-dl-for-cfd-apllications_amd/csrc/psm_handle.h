@@ -1,11 +1,12 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in seven files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in eight files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, graph capture and key, psm_solve_grid*
 //   psm_api_ring.cpp        the pinned submission ring (psm_ring_*, psm_submit_grid*, psm_wait_grid) and registered host memory (psm_host_*)
 //   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*), evaluator helpers (labels, block error, filters), the gradP integration (host entry and device-resident U -> p)
 //   psm_api_filter.cpp      the Gaussian post-steps: psm_gaussian_filter (host entry), psm_bind_poststeps and the device-resident / case-batched entries
+//   psm_api_features.cpp    the pressureSM_Poisson input features on the device: psm_bind_features, psm_features_device and the whole step psm_poisson_step*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -106,11 +107,19 @@ struct PostCall {
   auto tie() const { return std::tie(apply_filter, dU, prev, result, change, next); }
 };
 
+// The Poisson input features in front of a solve (psm_poisson_step*): both pointers are part of the captured launches.
+struct FeatCall {
+  const double* vel = nullptr;          // [n_cases][4][ny*nx] velocity planes; nullptr: no features stage
+  float* grid = nullptr;                // the image the two launches write and the solve reads
+};
+
 struct GraphKey {
   int n; const void* g; void* f;        // n: sequence_key()
   void* p = nullptr;                    // psm_solve_pressure*: where the integration behind the solve writes p (null: the solve alone)
   PostCall post{};                      // psm_solve_poststeps*: the post-steps behind the solve (apply_filter == -1: none)
-  bool operator<(const GraphKey& o) const { return std::tie(n, g, f, p) < std::tie(o.n, o.g, o.f, o.p) || (std::tie(n, g, f, p) == std::tie(o.n, o.g, o.f, o.p) && post.tie() < o.post.tie()); }
+  const void* vel = nullptr;            // psm_poisson_step*: the velocity planes of the features in front of the solve (g is their image)
+  auto head() const { return std::tie(n, g, f, p, vel); }
+  bool operator<(const GraphKey& o) const { return head() < o.head() || (head() == o.head() && post.tie() < o.post.tie()); }
 };
 
 // Everything ONE in-flight solve writes.  The handle owns one for the synchronous / device entries (ws0) and one per
@@ -151,6 +160,22 @@ struct PostSet {
   float* d_fields = nullptr;                             // the solve's field in front of the post-steps [max_cases][npix][c_out]
   float *d_dU = nullptr, *d_prev = nullptr, *d_out = nullptr;       // staging of the host entry (and of psm_time_kernels): [max_cases][npix], d_out x 3
 };
+
+// Binding of the pressureSM_Poisson input features to the planned grid (psm_bind_features): the SDF planes of the case slots, the
+// bind-time constants and every buffer a step touches, so that a step allocates nothing.
+struct FeatureSet {
+  static constexpr int RING = 8;
+  bool ready = false;
+  int n_cases = 0;
+  double k = 0.0, max_abs[4] = {1, 1, 1, 1};
+  double *d_sdf = nullptr, *d_term = nullptr, *d_partial = nullptr;   // [n_cases][npix], [n_cases][npix], [n_cases][2 * workgroups]
+  double* d_lu = nullptr;                                // [n_cases][2] (L, U) of the step: uploaded in front of every call, outside the graph
+  float* d_grid = nullptr;                               // the image of psm_poisson_step* [n_cases][npix][4]
+  double* d_vel = nullptr;                               // staging of the host entry (and of psm_time_kernels) [n_cases][4][npix]
+  double* h_lu = nullptr;                                // pinned upload ring [RING][n_cases][2]
+  hipEvent_t lu_ev[RING] = {};
+  int lu_pos = 0;
+};
 }  // namespace psm_impl
 using namespace psm_impl;
 
@@ -189,6 +214,7 @@ struct psm_handle {
   // batch on the planned grid (psm_bind_integration, device buffers)
   IntegSet integ_host, integ_dev;
   PostSet post;                         // Gaussian post-steps on the planned grid (psm_bind_poststeps)
+  FeatureSet feat;                      // Poisson input features on the planned grid (psm_bind_features)
   double *h_cells = nullptr, *h_p = nullptr;
   const double* pinned_cells = nullptr;   // caller buffers registered with psm_pin_buffers (DMA without staging copies)
   double* pinned_p = nullptr;
@@ -329,6 +355,9 @@ void integ_free(IntegSet& s);
 int integrate_device(psm_handle* h, const float* d_gradp, int n_cases, float* d_p, hipStream_t st);
 void post_free(PostSet& s);
 int poststeps_device(psm_handle* h, const float* d_fields, int n_cases, const PostCall& pc, hipStream_t st);
+int post_check(psm_handle* h, int n_cases, const PostCall& pc);
+void feat_free(FeatureSet& s);
+int features_device(psm_handle* h, const double* d_vel, int n_cases, float* d_grid, hipStream_t st);
 std::vector<uint16_t> pack_comp_in_bf16(const double* comp, int P, int K, int c_in, int S, int NT);
 std::vector<uint16_t> pack_comp_out_bf16(const double* comp, int P, int K_out, int G);
 bool model_complete(const psm_handle* h);
@@ -345,9 +374,10 @@ PsmStripArgs strip_args(const psm_handle* h, const Workspace& w, const float* d_
 PsmChainArgs chain_args(const psm_handle* h, const Workspace& w);
 PsmPasteArgs paste_args(const psm_handle* h, const Workspace& w, float* d_fields);
 // d_p != nullptr: the bound integration (psm_bind_integration) of d_fields into d_p follows in the same stream / the same graph;
-// post (apply_filter >= 0): the bound post-steps (psm_bind_poststeps) of d_fields follow likewise
+// post (apply_filter >= 0): the bound post-steps (psm_bind_poststeps) of d_fields follow likewise;
+// feat (vel != nullptr): the bound features (psm_bind_features) write d_grid == feat->grid in front of the solve, likewise
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
-                 hipStream_t st, hipEvent_t* prof, float* d_p = nullptr, const PostCall* post = nullptr);
+                 hipStream_t st, hipEvent_t* prof, float* d_p = nullptr, const PostCall* post = nullptr, const FeatCall* feat = nullptr);
 bool guard_take(psm_handle* h, Workspace& w);
 int guard_drop(psm_handle* h, const char* where);
 int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases = 1);

@@ -497,6 +497,79 @@ class GridSurrogate:
                                                _p(result, C.c_float), opt(change), opt(nxt)))
         return result, change, nxt
 
+    # -- pressureSM_Poisson input features on the device (SM_call.py:588-711): psm_bind_features once, then one call per step
+    _feat_bound = False
+
+    def bind_features(self, sdfunct, k: float, max_abs):
+        """SDF planes of the case slots (``sdfunct`` [Ny,Nx] or [n,Ny,Nx] float64, raw, 0 in solids), ``k`` and the four
+        ``max_abs`` scales of ``poisson_features``, and every buffer a step touches: after it a step allocates nothing.  Needs
+        a four-channel model with the SDF last."""
+        sd = _f64(np.asarray(sdfunct))
+        if sd.ndim == 2:
+            sd = sd[None]
+        if sd.ndim != 3 or sd.shape[1:] != (self.ny, self.nx):
+            raise ValueError(f"sdfunct must be [{self.ny},{self.nx}] or [n,{self.ny},{self.nx}]")
+        ma = _f64(np.asarray(max_abs, np.float64).reshape(-1))
+        if ma.shape != (4,):
+            raise ValueError("max_abs must hold 4 scales")
+        self._feat_bound = False
+        self._chk(self.lib.psm_bind_features(self.h, _p(sd, C.c_double), sd.shape[0], float(k), _p(ma, C.c_double)))
+        self._feat_bound = True
+
+    def unbind_features(self):
+        self._feat_bound = False
+        self._chk(self.lib.psm_unbind_features(self.h))
+
+    def _lu(self, LU, n_cases: int) -> np.ndarray:
+        lu = _f64(np.asarray(LU, np.float64).reshape(-1, 2))
+        if lu.shape != (n_cases, 2):
+            raise ValueError("LU must be [n_cases][2] = (L, U) per case")
+        return lu
+
+    def features_device(self, d_vel: int, n_cases: int, LU, d_grid: int, stream: int = 0):
+        """Velocity planes [n,4,Ny*Nx] float64 (ux, uy, dux, duy) -> image [n,Ny,Nx,4] float32 on raw device pointers,
+        asynchronous on ``stream``: two launches for the batch.  ``LU`` [n][2] = (L, U) per case, a host array."""
+        lu = self._lu(LU, n_cases)
+        self._chk(self.lib.psm_features_device(self.h, C.c_void_p(d_vel), n_cases, _p(lu, C.c_double), C.c_void_p(d_grid),
+                                               C.c_void_p(stream)))
+
+    def poisson_step_device(self, d_vel: int, n_cases: int, LU, d_result: int, apply_filter: bool = True, d_dU: int = 0,
+                            d_prev: int = 0, d_change: int = 0, d_next: int = 0, stream: int = 0,
+                            out_scale: Optional[Sequence[float]] = None):
+        """A whole Poisson time step as one graph replay on raw device pointers: velocity planes [n,4,Ny*Nx] float64 ->
+        features -> solve -> post-steps -> result (and change / next) [n,Ny,Nx]."""
+        lu = self._lu(LU, n_cases)
+        sc = _f32(np.broadcast_to(out_scale, (n_cases,))) if out_scale is not None else None
+        self._chk(self.lib.psm_poisson_step_device(self.h, C.c_void_p(d_vel), n_cases, _p(lu, C.c_double),
+                                                   _p(sc, C.c_float) if sc is not None else None, int(bool(apply_filter)),
+                                                   C.c_void_p(d_dU or None), C.c_void_p(d_prev or None), C.c_void_p(d_result),
+                                                   C.c_void_p(d_change or None), C.c_void_p(d_next or None), C.c_void_p(stream)))
+
+    def poisson_step(self, vel: np.ndarray, LU, out_scale: Optional[Sequence[float]] = None, apply_filter: bool = False,
+                     dU=None, prev=None):
+        """Host buffers, synchronous: vel [n,4,Ny,Nx] (or [4,Ny,Nx]) float64 -> (result [n,Ny,Nx,c_out], change, next); change
+        and next [n,Ny,Nx] are None without ``dU`` / ``prev`` [n,Ny,Nx]."""
+        v = np.asarray(vel)
+        if v.ndim == 3:
+            v = v[None]
+        if v.ndim != 4 or v.shape[1:] != (4, self.ny, self.nx):
+            raise ValueError(f"vel must be [n,4,{self.ny},{self.nx}]")
+        v = _f64(v)
+        n = v.shape[0]
+        lu = self._lu(LU, n)
+        if (dU is None) != (prev is None):
+            raise ValueError("dU and prev go together")
+        result = np.empty((n, self.ny, self.nx, self.model.c_out), np.float32)
+        change = nxt = None
+        if dU is not None:
+            dU, prev = (_f32(np.asarray(a, np.float32).reshape(n, self.ny, self.nx)) for a in (dU, prev))
+            change, nxt = np.empty((n, self.ny, self.nx), np.float32), np.empty((n, self.ny, self.nx), np.float32)
+        sc = _f32(np.broadcast_to(out_scale, (n,))) if out_scale is not None else None
+        opt = lambda a: _p(a, C.c_float) if a is not None else None
+        self._chk(self.lib.psm_poisson_step(self.h, _p(v, C.c_double), n, _p(lu, C.c_double), opt(sc), int(bool(apply_filter)),
+                                            opt(dU), opt(prev), _p(result, C.c_float), opt(change), opt(nxt)))
+        return result, change, nxt
+
     # -- introspection
     def stage(self, name: str, n_cases: int = 1, layer: int = 0) -> np.ndarray:
         """An intermediate of the last solve; ``name='hidden'``: the output of hidden Dense layer ``layer`` (the handle must have
