@@ -344,6 +344,41 @@ int psm_solve_end(psm_handle* h);
  * write `cells` or read `p_out` between psm_solve_begin and psm_solve_end. */
 int psm_pin_buffers(psm_handle* h, const double* cells, double* p_out);
 int psm_unpin_buffers(psm_handle* h);
+/* ---- the solver boundary for a CASE BATCH: K meshes, one handle, one step ------------
+ * The ensemble of PISO cases as one launch chain instead of one handle, stream and chain per case: K cases, each with its
+ * own mesh and obstacle, all on ONE grid shape, advanced by one call -- per-case U_max (two-level device reduction, never on
+ * the host), mesh -> grid for all cases, the batched solve, grid -> mesh for all cases.
+ * psm_set_geometry_cases takes the tables of psm_set_geometry once per case: n_cells [n_cases] and n_cases pointers per
+ * table (vertex indices address the case's own cells); maxs, normalise_sdf, fill_input and wall_threshold are shared.
+ * All-or-nothing: every table is validated like psm_set_geometry's (the message names the case) before the handle is
+ * touched; then the grid is planned, the per-case tables are uploaded and every per-step buffer is reserved (a step
+ * allocates nothing).  Needs 1 <= n_cases <= max_cases (PSM_ERR_ARG), c_in == 3 and c_out == 1 (PSM_ERR_UNSUPPORTED) and
+ * the grid -> mesh tables of every case (PSM_ERR_ARG).  The K geometries are bound for this entry only (the scope
+ * psm_set_geometry gives its one; a configuration outside the bound path solves on the general path; PSM_NO_BIND=1 keeps
+ * the general path); with n_cases == 1 the route -- and every bit of p -- is that of psm_solve.
+ * A handle holds EITHER the single mesh of psm_set_geometry OR a case set: setting one drops the other, psm_solve* on a case
+ * set and psm_solve_cases* on a single mesh are PSM_ERR_STATE.  psm_plan_grid and the model setters drop the case set. */
+int psm_set_geometry_cases(psm_handle* h, int32_t n_cases, const int64_t* n_cells, int32_t ny, int32_t nx,
+                           const int32_t* const* vtx_m2g, const double* const* wts_m2g, const int32_t* const* indices,
+                           const double* const* sdfunct, const int32_t* const* vtx_g2m, const double* const* wts_g2m,
+                           const double* maxs, int32_t normalise_sdf, int32_t fill_input, double wall_threshold);
+/* psm_init_geometry per case (tables built in C++ with the constants of psm_set_case), then psm_set_geometry_cases.
+ * cells[k] [n[k],5], top[k] [n_top[k],2], obst[k] [n_obst[k],2].  PSM_ERR_ARG names the first case whose grid shape
+ * differs from case 0's. */
+int psm_init_geometry_cases(psm_handle* h, int32_t n_cases, const double* const* cells, const int64_t* n,
+                            const double* const* top, const int64_t* n_top, const double* const* obst, const int64_t* n_obst);
+/* One step of all cases.  The cell-side arrays are the cases' concatenated in case order: cells [sum n_i, 5] float64 ->
+ * p [sum n_i] float64 (psm_mesh_cases gives the offsets).  A case's result does not depend on the other cases' cells.
+ * _device: device pointers (8-byte aligned), asynchronous on `stream` (NULL: the handle's), copies nothing.
+ * psm_solve_cases: host buffers, synchronous -- one H2D copy of the cells and one D2H copy of p, through the handle's
+ * pinned staging or straight from / into ranges registered with psm_host_register.  _begin / _end: the same in two halves
+ * (one step in flight per handle; a second begin, or an end without a begin, is PSM_ERR_STATE). */
+int psm_solve_cases_device(psm_handle* h, const double* d_cells, double* d_p, void* stream);
+int psm_solve_cases(psm_handle* h, const double* cells, double* p_out);
+int psm_solve_cases_begin(psm_handle* h, const double* cells, double* p_out);
+int psm_solve_cases_end(psm_handle* h);
+/* The case set of the handle: *n_cases and cell_off [n_cases + 1] (either may be NULL).  PSM_ERR_STATE without one. */
+int psm_mesh_cases(const psm_handle* h, int32_t* n_cases, int64_t* cell_off);
 /* Generic mesh -> grid step of the evaluators (interpolate_fill + scatter, SM_call.py:419-436,
  * pressureSM_Poisson/SM_call.py:580-600): values [n_cells, k] float64 row-major (k columns of cell
  * data) -> grid_out [ny*nx, k] float64 holding, per image cell, the interpolated value of the grid

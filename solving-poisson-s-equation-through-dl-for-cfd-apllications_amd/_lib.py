@@ -90,6 +90,15 @@ SIGNATURES = {
     "psm_solve": (C.c_int, [_hp, _f64p, C.c_int64, C.c_int32, _f64p]),
     "psm_solve_begin": (C.c_int, [_hp, _f64p, C.c_int64, C.c_int32, _f64p]),
     "psm_solve_end": (C.c_int, [_hp]),
+    "psm_set_geometry_cases": (C.c_int, [_hp, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32] + [C.POINTER(C.c_void_p)] * 6 +
+                                         [_f64p, C.c_int32, C.c_int32, C.c_double]),
+    "psm_init_geometry_cases": (C.c_int, [_hp, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "psm_solve_cases_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_solve_cases": (C.c_int, [_hp, _f64p, _f64p]),
+    "psm_solve_cases_begin": (C.c_int, [_hp, _f64p, _f64p]),
+    "psm_solve_cases_end": (C.c_int, [_hp]),
+    "psm_mesh_cases": (C.c_int, [_hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "psm_poisson_features": (C.c_int, [_hp, _f64p, _f64p, _f64p, _f64p, _f64p, C.c_int32, C.c_int32, _f64p, _f32p]),
     "psm_pin_buffers": (C.c_int, [_hp, _f64p, _f64p]),
     "psm_unpin_buffers": (C.c_int, [_hp]),

@@ -1,5 +1,6 @@
 // psm_api_mesh.cpp -- C-ABI of libpsm_hip.so (include/psm.h): solver boundary (mesh <-> grid) and evaluator helpers.  See psm_handle.h for the map of the files.
 #include "psm_handle.h"
+#include "psm_mesh_tables.h"
 
 namespace psm_impl {
 
@@ -119,6 +120,30 @@ int integrate_device(psm_handle* h, const float* d_gradp, int n_cases, float* d_
   return PSM_OK;
 }
 
+// ---- the case set of psm_set_geometry_cases -----------------------------------------------------------------------
+// state checks shared by the step entries
+static int cases_check(psm_handle* h) {
+  if (h->have_geometry && !h->mcs.ready)
+    return fail(h, PSM_ERR_STATE, "the handle holds the single mesh of psm_set_geometry: psm_solve_cases* needs a case set (psm_set_geometry_cases)");
+  if (!h->mcs.ready || !h->planned)
+    return fail(h, PSM_ERR_STATE, "psm_set_geometry_cases has not been called (or its case set was dropped by a later psm_set_* / psm_plan_grid)");
+  return PSM_OK;
+}
+
+// One step of the case set, a linear chain on `st`: U_max partials, to_grid, the batched solve, to_mesh.  Plain launches (like
+// psm_solve; the solve inside replays its graph under PSM_GRAPH=1); copies nothing.
+static int cases_sequence(psm_handle* h, const double* d_cells, double* d_p, hipStream_t st) {
+  PsmMeshCasesArgs a = h->mcs.args;
+  a.cells = d_cells; a.p_out = d_p;
+  HIPCHK(h, psm_launch_umax_cases(a, st));
+  HIPCHK(h, psm_launch_to_grid_cases(a, st));
+  h->in_mesh_solve = true;
+  const int rc = solve_device(h, h->d_grid_stage, h->mcs.n_cases, nullptr, h->d_fields_stage, st, nullptr);
+  h->in_mesh_solve = false;
+  if (rc) return rc;
+  HIPCHK(h, psm_launch_to_mesh_cases(a, st));
+  return PSM_OK;
+}
 
 }  // namespace psm_impl
 
@@ -330,6 +355,7 @@ int psm_solve_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank,
   (void)rank;
   if (!h) return PSM_ERR_ARG;
   if (h->mesh_inflight) return fail(h, PSM_ERR_STATE, "a psm_solve_begin is already in flight on this handle: call psm_solve_end first");
+  if (h->mcs.ready) return fail(h, PSM_ERR_STATE, "the handle holds the case set of psm_set_geometry_cases: psm_solve needs the single mesh of psm_set_geometry (use psm_solve_cases*)");
   if (!h->have_geometry || !h->planned)
     return fail(h, PSM_ERR_STATE, "psm_set_geometry has not been called (or the plan it belonged to was dropped by a later psm_set_* / psm_plan_grid)");
   if (h->cfg.c_in != 3 || h->cfg.c_out != 1) return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292)");
@@ -440,6 +466,158 @@ int psm_solve_end(psm_handle* h) {
 int psm_solve(psm_handle* h, const double* cells, int64_t n, int32_t rank, double* p_out) {
   int rc = psm_solve_begin(h, cells, n, rank, p_out);
   return rc ? rc : psm_solve_end(h);
+}
+
+
+int psm_set_geometry_cases(psm_handle* h, int32_t n_cases, const int64_t* n_cells, int32_t ny, int32_t nx,
+                           const int32_t* const* vtx_m2g, const double* const* wts_m2g, const int32_t* const* indices,
+                           const double* const* sdfunct, const int32_t* const* vtx_g2m, const double* const* wts_g2m,
+                           const double* maxs, int32_t normalise_sdf, int32_t fill_input, double wall_threshold) {
+  if (!h) return PSM_ERR_ARG;
+  if (!n_cells || !vtx_m2g || !wts_m2g || !indices || !sdfunct || !vtx_g2m || !wts_g2m || !maxs) return fail(h, PSM_ERR_ARG, "null geometry table");
+  if (n_cases < 1 || n_cases > h->cfg.max_cases) return fail(h, PSM_ERR_ARG, "n_cases outside [1, max_cases]");
+  if (h->cfg.c_in != 3 || h->cfg.c_out != 1) return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292)");
+  if (ny < 1 || nx < 1) return fail(h, PSM_ERR_ARG, "bad grid shape");
+  // everything that needs no device first: a bad table leaves the handle as it was
+  std::vector<PsmMeshCaseInput> in(n_cases);
+  for (int k = 0; k < n_cases; ++k) in[k] = PsmMeshCaseInput{n_cells[k], vtx_m2g[k], wts_m2g[k], indices[k], sdfunct[k], vtx_g2m[k], wts_g2m[k]};
+  PsmMeshCaseTables t;
+  std::string why;
+  if (psm_build_mesh_case_tables(n_cases, in.data(), ny, nx, normalise_sdf ? 1.0 / maxs[2] : 1.0, wall_threshold, t, why)) return fail(h, PSM_ERR_ARG, why);
+  int rc = psm_plan_grid(h, ny, nx);
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  free_geometry(h);                                         // the single mesh goes, and an earlier case set
+  MeshCaseSet& m = h->mcs;
+  for (int k = 0; k < 4; ++k) h->maxs[k] = maxs[k];
+  h->normalise_sdf = normalise_sdf; h->fill_input = fill_input;
+  const int n_parts = (int)std::min<int64_t>(PSM_MESH_CASE_PARTS, (t.max_cells + 4095) / 4096);
+  const size_t total = (size_t)t.total;
+  hipError_t e = hipSuccess;
+  if ((rc = dev_upload(h, &m.d_off, t.cell_off)) || (rc = dev_upload(h, &m.d_vtx_m2g, t.vtx_m2g)) || (rc = dev_upload(h, &m.d_wts_m2g, t.wts_m2g)) ||
+      (rc = dev_upload(h, &m.d_src_of_cell, t.src_of_cell)) || (rc = dev_upload(h, &m.d_cell_of_point, t.cell_of_point)) ||
+      (rc = dev_upload(h, &m.d_sdf, t.sdf)) || (rc = dev_upload(h, &m.d_vtx_g2m, t.vtx_g2m)) || (rc = dev_upload(h, &m.d_wts_g2m, t.wts_g2m)) ||
+      (rc = dev_upload(h, &m.d_near_wall, t.near_wall)) || (rc = dev_alloc(h, &m.d_cells, total * 5)) || (rc = dev_alloc(h, &m.d_p, total)) ||
+      (rc = dev_alloc(h, &m.d_umax, (size_t)n_cases)) || (rc = dev_alloc(h, &m.d_umax_part, (size_t)n_cases * n_parts))) { mesh_cases_free(h); return rc; }
+  if ((e = hipHostMalloc((void**)&m.h_cells, total * 5 * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
+      (e = hipHostMalloc((void**)&m.h_p, total * sizeof(double), hipHostMallocDefault)) != hipSuccess) {
+    mesh_cases_free(h);
+    return fail(h, PSM_ERR_NOMEM, std::string("hipHostMalloc(case set staging): ") + hipGetErrorString(e));
+  }
+  PsmMeshCasesArgs& a = m.args;
+  a = PsmMeshCasesArgs{};
+  a.cell_off = m.d_off; a.umax_part = m.d_umax_part; a.umax = m.d_umax; a.n_parts = n_parts; a.n_cases = n_cases;
+  a.vtx_m2g = m.d_vtx_m2g; a.wts_m2g = m.d_wts_m2g; a.src_of_cell = m.d_src_of_cell; a.sdf = m.d_sdf; a.grid = h->d_grid_stage;
+  a.n_grid = t.n_grid; a.max_abs_ux = maxs[0]; a.max_abs_uy = maxs[1]; a.sdf_scale = normalise_sdf ? 1.0 / maxs[2] : 1.0;
+  a.c_in = h->cfg.c_in; a.fill = fill_input;
+  a.vtx_g2m = m.d_vtx_g2m; a.wts_g2m = m.d_wts_g2m; a.cell_of_point = m.d_cell_of_point; a.field = h->d_fields_stage;
+  a.near_wall = m.d_near_wall; a.max_cells = t.max_cells; a.max_abs_p = maxs[3]; a.c_out = h->cfg.c_out;
+  m.off = t.cell_off; m.n_cases = n_cases;
+  // The entry builds its K images from THESE sdfuncts at every step: bind the K geometries for psm_solve_cases* only (scope 1,
+  // like psm_set_geometry binds its one; a single case takes the single-case binding and with it the route of psm_solve).
+  if (h->cfg.sdf_channel == 2 && getenv("PSM_NO_BIND") == nullptr) {
+    HIPCHK(h, psm_copy_h2d(h->d_grid_stage, t.sdf_image.data(), t.sdf_image.size() * sizeof(float)));
+    h->bound_scope = 1;
+    rc = bind_geometry_device(h, h->d_grid_stage, n_cases);
+    if (rc == PSM_ERR_UNSUPPORTED) h->err.clear();           // configuration outside the fused path: general path
+    else if (rc) { mesh_cases_free(h); return rc; }
+  }
+  if ((rc = ensure_encode_aux(h, n_cases))) { mesh_cases_free(h); return rc; }   // once, outside any capture (psm_solve_begin does the same)
+  m.ready = true;
+  return PSM_OK;
+}
+
+
+int psm_init_geometry_cases(psm_handle* h, int32_t n_cases, const double* const* cells, const int64_t* n, const double* const* top,
+                            const int64_t* n_top, const double* const* obst, const int64_t* n_obst) {
+  if (!h) return PSM_ERR_ARG;
+  if (!cells || !n || !top || !n_top || !obst || !n_obst) return fail(h, PSM_ERR_ARG, "null buffer");
+  if (n_cases < 1 || n_cases > h->cfg.max_cases) return fail(h, PSM_ERR_ARG, "n_cases outside [1, max_cases]");
+  int32_t ny = 0, nx = 0;
+  for (int k = 0; k < n_cases; ++k) {
+    if (!cells[k] || !top[k] || !obst[k]) return fail(h, PSM_ERR_ARG, "case " + std::to_string(k) + ": null buffer");
+    int32_t nyk = 0, nxk = 0;
+    if (psm_geometry_shape(cells[k], n[k], h->case_delta, &nyk, &nxk, nullptr) != PSM_OK)
+      return fail(h, PSM_ERR_ARG, "case " + std::to_string(k) + ": " + psm_geometry_last_error());
+    if (k == 0) { ny = nyk; nx = nxk; }
+    else if (nyk != ny || nxk != nx)
+      return fail(h, PSM_ERR_ARG, "case " + std::to_string(k) + ": grid shape " + std::to_string(nyk) + " x " + std::to_string(nxk) + " differs from case 0's " +
+                                      std::to_string(ny) + " x " + std::to_string(nx));
+  }
+  const size_t ng = (size_t)ny * nx;
+  std::vector<std::vector<int32_t>> v1(n_cases), idx(n_cases), v2(n_cases);
+  std::vector<std::vector<double>> w1(n_cases), sdf(n_cases), w2(n_cases);
+  std::vector<const int32_t*> pv1(n_cases), pidx(n_cases), pv2(n_cases);
+  std::vector<const double*> pw1(n_cases), psdf(n_cases), pw2(n_cases);
+  for (int k = 0; k < n_cases; ++k) {
+    v1[k].resize(ng * 3); w1[k].resize(ng * 3); idx[k].resize(ng * 2); sdf[k].resize(ng); v2[k].resize((size_t)n[k] * 3); w2[k].resize((size_t)n[k] * 3);
+    const int rc = psm_geometry_build(cells[k], n[k], top[k], n_top[k], obst[k], n_obst[k], h->case_delta, h->case_every, v1[k].data(), w1[k].data(),
+                                      idx[k].data(), sdf[k].data(), v2[k].data(), w2[k].data());
+    if (rc) return fail(h, rc, "case " + std::to_string(k) + ": " + psm_geometry_last_error());
+    pv1[k] = v1[k].data(); pw1[k] = w1[k].data(); pidx[k] = idx[k].data(); psdf[k] = sdf[k].data(); pv2[k] = v2[k].data(); pw2[k] = w2[k].data();
+  }
+  return psm_set_geometry_cases(h, n_cases, n, ny, nx, pv1.data(), pw1.data(), pidx.data(), psdf.data(), pv2.data(), pw2.data(), h->case_maxs, 0, 0,
+                                h->case_wall);
+}
+
+
+int psm_mesh_cases(const psm_handle* h, int32_t* n_cases, int64_t* cell_off) {
+  if (!h) return PSM_ERR_ARG;
+  if (!h->mcs.ready || !h->planned) return PSM_ERR_STATE;
+  if (n_cases) *n_cases = h->mcs.n_cases;
+  if (cell_off) std::copy(h->mcs.off.begin(), h->mcs.off.end(), cell_off);
+  return PSM_OK;
+}
+
+
+int psm_solve_cases_device(psm_handle* h, const double* d_cells, double* d_p, void* stream) {
+  if (!h) return PSM_ERR_ARG;
+  int rc = cases_check(h);
+  if (rc) return rc;
+  if (h->mcs.inflight) return fail(h, PSM_ERR_STATE, "a psm_solve_cases_begin is in flight on this handle: call psm_solve_cases_end first");
+  if (!d_cells || !d_p) return fail(h, PSM_ERR_ARG, "null buffer");
+  if ((reinterpret_cast<uintptr_t>(d_cells) | reinterpret_cast<uintptr_t>(d_p)) & 7) return fail(h, PSM_ERR_ARG, "device buffers must be 8-byte aligned");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  return cases_sequence(h, d_cells, d_p, stream ? (hipStream_t)stream : h->stream);
+}
+
+
+int psm_solve_cases_begin(psm_handle* h, const double* cells, double* p_out) {
+  if (!h) return PSM_ERR_ARG;
+  if (h->mcs.inflight) return fail(h, PSM_ERR_STATE, "a psm_solve_cases_begin is already in flight on this handle: call psm_solve_cases_end first");
+  int rc = cases_check(h);
+  if (rc) return rc;
+  if (!cells || !p_out) return fail(h, PSM_ERR_ARG, "null buffer");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  MeshCaseSet& m = h->mcs;
+  hipStream_t st = h->stream;
+  const size_t total = (size_t)m.off[m.n_cases], in_bytes = total * 5 * sizeof(double), out_bytes = total * sizeof(double);
+  // one H2D of the concatenated cells, one D2H of p: straight from / into arrays registered with psm_host_register, else through the pinned staging
+  const bool reg_in = host_registered(h, cells, in_bytes), reg_out = host_registered(h, p_out, out_bytes);
+  if (!reg_in) memcpy(m.h_cells, cells, in_bytes);
+  HIPCHK(h, hipMemcpyAsync(m.d_cells, reg_in ? cells : m.h_cells, in_bytes, hipMemcpyHostToDevice, st));
+  if ((rc = cases_sequence(h, m.d_cells, m.d_p, st))) return rc;
+  HIPCHK(h, hipMemcpyAsync(reg_out ? p_out : m.h_p, m.d_p, out_bytes, hipMemcpyDeviceToHost, st));
+  m.copy_out = reg_out ? nullptr : p_out;
+  m.inflight = true;
+  return PSM_OK;
+}
+
+
+int psm_solve_cases_end(psm_handle* h) {
+  if (!h) return PSM_ERR_ARG;
+  if (!h->mcs.inflight) return fail(h, PSM_ERR_STATE, "no psm_solve_cases_begin in flight");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  h->mcs.inflight = false;
+  HIPCHK(h, wait_stream(h->stream));
+  if (h->mcs.copy_out) memcpy(h->mcs.copy_out, h->mcs.h_p, (size_t)h->mcs.off[h->mcs.n_cases] * sizeof(double));
+  return PSM_OK;
+}
+
+
+int psm_solve_cases(psm_handle* h, const double* cells, double* p_out) {
+  int rc = psm_solve_cases_begin(h, cells, p_out);
+  return rc ? rc : psm_solve_cases_end(h);
 }
 
 

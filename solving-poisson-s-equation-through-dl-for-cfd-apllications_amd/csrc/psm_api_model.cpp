@@ -119,6 +119,7 @@ void free_plan(psm_handle* h) {
   // psm_solve / psm_mesh_to_grid must fail with PSM_ERR_STATE until psm_set_geometry runs again, not launch on null buffers.
   // (The registered host arrays stay registered; the graph that holds their addresses goes with the plan.)
   h->have_geometry = false;
+  mesh_cases_free(h);                   // the case set of psm_set_geometry_cases likewise
   if (h->mesh_graph) { (void)hipGraphExecDestroy(h->mesh_graph); h->mesh_graph = nullptr; }
   integ_free(h->integ_dev);             // psm_bind_integration is sized by this plan's grid
   post_free(h->post);                   // and so is psm_bind_poststeps
@@ -175,8 +176,20 @@ void unpin_buffers(psm_handle* h) {
 }
 
 
+void mesh_cases_free(psm_handle* h) {
+  MeshCaseSet& m = h->mcs;
+  dev_free(m.d_off); dev_free(m.d_vtx_m2g); dev_free(m.d_src_of_cell); dev_free(m.d_vtx_g2m); dev_free(m.d_cell_of_point);
+  dev_free(m.d_wts_m2g); dev_free(m.d_sdf); dev_free(m.d_wts_g2m); dev_free(m.d_near_wall);
+  dev_free(m.d_cells); dev_free(m.d_p); dev_free(m.d_umax); dev_free(m.d_umax_part);
+  if (m.h_cells) { (void)hipHostFree(m.h_cells); m.h_cells = nullptr; }
+  if (m.h_p) { (void)hipHostFree(m.h_p); m.h_p = nullptr; }
+  m.ready = false; m.inflight = false; m.n_cases = 0; m.off.clear();
+}
+
+
 void free_geometry(psm_handle* h) {
   unpin_buffers(h);
+  mesh_cases_free(h);
   dev_free(h->d_vtx_m2g); dev_free(h->d_src_of_cell); dev_free(h->d_vtx_g2m); dev_free(h->d_cell_of_point);
   dev_free(h->d_wts_m2g); dev_free(h->d_sdf); dev_free(h->d_wts_g2m); dev_free(h->d_cells); dev_free(h->d_p);
   dev_free(h->d_umax); dev_free(h->d_umax_part); dev_free(h->d_near_wall);
@@ -355,6 +368,7 @@ int psm_set_pca(psm_handle* h, const double* comp_in, const double* mean_in, con
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   std::vector<float> mi(h->K_in), mo(h->K_out);
   for (int k = 0; k < h->K_in; ++k) mi[k] = (float)mean_in[k];
@@ -423,6 +437,7 @@ int psm_set_dense(psm_handle* h, int32_t layer, int32_t n_in, int32_t n_out, con
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   DenseLayer& d = h->dense[layer];
   d.linear = false;                                     // psm_set_attention sets it again after this call
@@ -513,6 +528,7 @@ int psm_set_layernorm(psm_handle* h, int32_t layer, int32_t n, const float* gamm
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   // zero-padded to whole 16-byte pieces past the consumer's leading dimension: a Dense launch that applies this normalisation to
   // its input (launch_all) reads gamma / beta with the clamped column index of its operand loads
@@ -544,6 +560,7 @@ int psm_set_conv1d(psm_handle* h, int32_t layer, int32_t n_layers, int32_t kerne
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   if (!same_stack) {
     for (auto& c : h->conv1d) { dev_free(c.W); dev_free(c.b); }
@@ -573,6 +590,7 @@ int psm_set_scaler(psm_handle* h, const double* in_a, const double* in_b, const 
   h->fold_bound = false;
   h->integ_dev.ready = false;            // psm_bind_integration belongs to one model + plan, like the geometry binding
   h->post.ready = false;                 // and so does psm_bind_poststeps
+  h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   std::vector<float> ia(h->ld_in, 0.f), ib(h->ld_in, 0.f), sa(h->ld_out, 0.f), sb(h->ld_out, 0.f);
   // x_in = coeff*ia + ib ; res' = res*sa + sb  (affine forms of SMD:505-539, evaluated in f64 here)

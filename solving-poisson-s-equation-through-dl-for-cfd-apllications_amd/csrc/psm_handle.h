@@ -4,7 +4,7 @@
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, graph capture and key, psm_solve_grid*
 //   psm_api_ring.cpp        the pinned submission ring (psm_ring_*, psm_submit_grid*, psm_wait_grid) and registered host memory (psm_host_*)
-//   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*), evaluator helpers (labels, block error, filters), the gradP integration (host entry and device-resident U -> p)
+//   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*; the case batch psm_set_geometry_cases / psm_solve_cases*, host tables in psm_mesh_tables.cpp), evaluator helpers (labels, block error, filters), the gradP integration (host entry and device-resident U -> p)
 //   psm_api_filter.cpp      the Gaussian post-steps: psm_gaussian_filter (host entry), psm_bind_poststeps and the device-resident / case-batched entries
 //   psm_api_features.cpp    the pressureSM_Poisson input features on the device: psm_bind_features, psm_features_device and the whole step psm_poisson_step*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
@@ -149,6 +149,23 @@ struct IntegSet {
   PsmIntegArgs args{};
 };
 
+// The case set of psm_set_geometry_cases: K meshes on the planned grid, their tables in the layout of PsmMeshCasesArgs and every
+// buffer a step touches, so that a step allocates nothing.  A handle holds this or the single mesh of psm_set_geometry.
+struct MeshCaseSet {
+  bool ready = false;
+  int n_cases = 0;
+  std::vector<int64_t> off;             // [n_cases + 1] host copy of d_off
+  int64_t* d_off = nullptr;
+  int32_t *d_vtx_m2g = nullptr, *d_src_of_cell = nullptr, *d_vtx_g2m = nullptr, *d_cell_of_point = nullptr;
+  double *d_wts_m2g = nullptr, *d_sdf = nullptr, *d_wts_g2m = nullptr;
+  uint8_t* d_near_wall = nullptr;
+  double *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;   // staged cells, p, U_max[K], partials [K][n_parts]
+  double *h_cells = nullptr, *h_p = nullptr;   // pinned staging of the host entries
+  PsmMeshCasesArgs args{};              // everything but cells / p_out, which are the call's
+  bool inflight = false;                // psm_solve_cases_begin enqueued, psm_solve_cases_end not yet called
+  double* copy_out = nullptr;           // where psm_solve_cases_end copies p to (null: it was DMA'd into the caller's registered array)
+};
+
 // Binding of the Gaussian post-steps to the planned grid (psm_bind_poststeps): the four tap tables and per-case scratch for
 // max_cases cases, so that a step allocates nothing and copies nothing.
 struct PostSet {
@@ -210,6 +227,7 @@ struct psm_handle {
   int32_t *d_vtx_m2g = nullptr, *d_src_of_cell = nullptr, *d_vtx_g2m = nullptr, *d_cell_of_point = nullptr;
   double *d_wts_m2g = nullptr, *d_sdf = nullptr, *d_wts_g2m = nullptr, *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;
   uint8_t* d_near_wall = nullptr;
+  MeshCaseSet mcs;                      // or a case set (psm_set_geometry_cases): setting one drops the other
   // U_to_gradP integration: the evaluator's single geometry of any size (psm_set_integration, host buffers) and the case
   // batch on the planned grid (psm_bind_integration, device buffers)
   IntegSet integ_host, integ_dev;
@@ -351,6 +369,7 @@ std::vector<float4> pack_comp_in(const double* comp, int P, int K, int c_in, int
 std::vector<float4> pack_comp_out(const double* comp, int P, int K_out, int Gd);
 void unpin_buffers(psm_handle* h);
 void free_geometry(psm_handle* h);
+void mesh_cases_free(psm_handle* h);
 void integ_free(IntegSet& s);
 int integrate_device(psm_handle* h, const float* d_gradp, int n_cases, float* d_p, hipStream_t st);
 void post_free(PostSet& s);

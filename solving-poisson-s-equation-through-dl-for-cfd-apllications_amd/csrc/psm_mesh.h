@@ -46,6 +46,40 @@ hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st);
 hipError_t psm_launch_interp_to_grid(const double* values, int k, const int32_t* vtx, const double* wts, const int32_t* src_of_cell,
                                      int fill, double* out, int64_t n_grid, hipStream_t st);
 
+// ---- the mesh ends for a case batch (psm_set_geometry_cases): K meshes on one planned grid, the case is launch dimension y.
+// Cell-side arrays are the cases' concatenated ([sum n_i, ...], case i at rows cell_off[i] .. cell_off[i + 1]), grid-side tables
+// are [K][n_grid, ...]; vertex indices are case-local as the caller gave them (the kernels add the case's offset).
+constexpr int PSM_MESH_CASE_PARTS = 256;   // capacity of one case's row of partial maxima (every to_grid workgroup folds a row)
+struct PsmMeshCasesArgs {
+  const double* cells;          // [sum n_i, 5]
+  const int64_t* cell_off;      // [K + 1]
+  double* umax_part;            // [K][n_parts] maxima of the SQUARED speed over a fixed partition of the case's cells
+  double* umax;                 // [K] written by workgroup 0 of every case in to_grid, read by to_mesh
+  int n_parts, n_cases;
+  // to_grid
+  const int32_t* vtx_m2g;       // [K][n_grid, 3]
+  const double* wts_m2g;        // [K][n_grid, 3]
+  const int32_t* src_of_cell;   // [K][n_grid]
+  const double* sdf;            // [K][n_grid]
+  float* grid;                  // [K][n_grid][c_in]
+  int64_t n_grid;
+  double max_abs_ux, max_abs_uy, sdf_scale;
+  int c_in, fill;
+  // to_mesh
+  const int32_t* vtx_g2m;       // [sum n_i, 3]
+  const double* wts_g2m;        // [sum n_i, 3]
+  const int32_t* cell_of_point; // [K][n_grid]
+  const float* field;           // [K][n_grid][c_out]
+  const uint8_t* near_wall;     // [sum n_i]
+  double* p_out;                // [sum n_i]
+  int64_t max_cells;            // largest n_i: sizes launch dimension x of the two cell-side launches
+  double max_abs_p;
+  int c_out;
+};
+hipError_t psm_launch_umax_cases(const PsmMeshCasesArgs& a, hipStream_t st);
+hipError_t psm_launch_to_grid_cases(const PsmMeshCasesArgs& a, hipStream_t st);
+hipError_t psm_launch_to_mesh_cases(const PsmMeshCasesArgs& a, hipStream_t st);
+
 // ---- Gaussian post-steps (SMD:353-363, UGP:366-367), case-batched: one launch per separable pass, see psm_filter.hip
 struct PsmGaussJob {
   const float* in;           // [n_cases][ny][nx][c]

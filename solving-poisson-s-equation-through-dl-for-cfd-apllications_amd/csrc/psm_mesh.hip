@@ -267,6 +267,119 @@ hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------
+// The mesh ends of a case batch (psm_solve_cases*, PsmMeshCasesArgs in psm_mesh.h): K meshes with their own obstacles on one
+// planned grid.  Three launches around the batched solve, the case is launch dimension y everywhere; a workgroup reads its
+// case's range from cell_off and its case's tables only, so a case's result does not depend on what the other slots hold.
+// The per-thread arithmetic is that of the single-mesh kernels above, statement for statement: one case through these
+// kernels gives the bits of psm_solve (tests/test_mesh_cases.py holds them to that).
+
+// U_max, level one: the maximum of the SQUARED speed over part blockIdx.x of case blockIdx.y.  The partition is fixed by the
+// launch (n_parts parts, cell c of a case belongs to part (c / 1024) % n_parts); a maximum does not depend on it anyway.
+__global__ __launch_bounds__(1024) void psm_umax_partial_kernel(PsmMeshCasesArgs a) {
+  __shared__ double red[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, cs = blockIdx.y;
+  const int64_t c0 = a.cell_off[cs], n = a.cell_off[cs + 1] - c0;
+  const double* cells = a.cells + c0 * 5;
+  double m = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 1024 + tid; i < n; i += (int64_t)gridDim.x * 1024) {
+    const double ux = cells[i * 5], uy = cells[i * 5 + 1];
+    m = nanmax2(m, speed2_np(ux, uy));
+  }
+  for (int o = 32; o > 0; o >>= 1) m = nanmax2(m, __shfl_down(m, o, 64));
+  if (lane == 0) red[wave] = m;
+  __syncthreads();
+  if (tid == 0) {
+    double r = red[0];
+    for (int w = 1; w < 16; ++w) r = nanmax2(r, red[w]);
+    a.umax_part[(int64_t)cs * a.n_parts + blockIdx.x] = r;
+  }
+}
+
+// Level two + mesh -> grid: every workgroup folds its case's row of partials (like psm_to_grid_kernel does with the single
+// mesh's), workgroup 0 of the case leaves U_max[case] for the batched psm_to_mesh_kernel; then the body of psm_to_grid_kernel on
+// the case's tables, into image `case` of the staging grid.
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmMeshCasesArgs a) {
+  __shared__ double um_s[4];
+  const int cs = blockIdx.y;
+  double m = a.umax_part[(int64_t)cs * a.n_parts + min((int)threadIdx.x, a.n_parts - 1)];
+  for (int o = 32; o > 0; o >>= 1) m = nanmax2(m, __shfl_down(m, o, 64));
+  if ((threadIdx.x & 63) == 0) um_s[threadIdx.x >> 6] = m;
+  __syncthreads();
+  const double umax_v = sqrt_rn(nanmax2(nanmax2(um_s[0], um_s[1]), nanmax2(um_s[2], um_s[3])));
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.umax[cs] = umax_v;
+  const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (cell >= a.n_grid) return;
+  const int64_t g0 = (int64_t)cs * a.n_grid;
+  const double* cells = a.cells + a.cell_off[cs] * 5;
+  const int src = a.src_of_cell[g0 + cell];
+  float ux = 0.f, uy = 0.f;
+  if (src >= 0) {
+    const double inv = 1.0 / umax_v;
+    const int32_t* v = a.vtx_m2g + (g0 + src) * 3;
+    const double* w = a.wts_m2g + (g0 + src) * 3;
+    double sx = 0.0, sy = 0.0;
+    bool neg = false;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double* c = cells + (int64_t)v[j] * 5;
+      sx += (c[0] * inv) * w[j];
+      sy += (c[1] * inv) * w[j];
+      neg = neg || (w[j] < 0.0);
+    }
+    if (a.fill && neg) { sx = NAN; sy = NAN; }
+    sx /= a.max_abs_ux;
+    sy /= a.max_abs_uy;
+    ux = (sx != sx) ? 0.f : (float)sx;
+    uy = (sy != sy) ? 0.f : (float)sy;
+  }
+  const double sd = a.sdf[g0 + cell] * a.sdf_scale;
+  float* g = a.grid + (g0 + cell) * a.c_in;
+  g[0] = ux;
+  g[1] = uy;
+  g[2] = (sd != sd) ? 0.f : (float)sd;
+}
+
+// grid -> mesh for all sum n_i cells in one launch.  The case is launch dimension y (x covers the largest case) and not a
+// search of cell_off per thread: a workgroup then reads its range with two uniform loads and gathers from one case's image
+// only, and what it costs is the workgroups beyond a shorter case's end, which return at once -- the cases of an ensemble
+// are meshes of one channel with different obstacles, a few per cent apart in size.
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmMeshCasesArgs a) {
+  const int cs = blockIdx.y;
+  const int64_t c0 = a.cell_off[cs], local = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (local >= a.cell_off[cs + 1] - c0) return;
+  const int64_t n = c0 + local, g0 = (int64_t)cs * a.n_grid;
+  const int32_t* v = a.vtx_g2m + n * 3;
+  const double* w = a.wts_g2m + n * 3;
+  double acc = 0.0;
+  bool neg = false;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int cell = a.cell_of_point[g0 + v[j]];
+    acc += (double)a.field[(g0 + cell) * a.c_out] * w[j];
+    neg = neg || (w[j] < 0.0);
+  }
+  const double um = a.umax[cs];
+  double p = acc * a.max_abs_p * (um * um);
+  const double prev = a.cells[n * 5 + 4];
+  if (a.near_wall[n] || neg || acc != acc) p = prev;
+  a.p_out[n] = p;
+}
+
+typedef void (*PsmCasesKernel)(PsmMeshCasesArgs);
+hipError_t psm_launch_umax_cases(const PsmMeshCasesArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(static_cast<PsmCasesKernel>(psm_umax_partial_kernel), dim3(a.n_parts, a.n_cases), dim3(1024), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_to_grid_cases(const PsmMeshCasesArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(static_cast<PsmCasesKernel>(psm_to_grid_kernel), dim3((unsigned)((a.n_grid + 255) / 256), a.n_cases), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_to_mesh_cases(const PsmMeshCasesArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(static_cast<PsmCasesKernel>(psm_to_mesh_kernel), dim3((unsigned)((a.max_cells + 255) / 256), a.n_cases), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // a8 (evaluation only): label blocks with the per-block mean over the flow cells removed --
 //   y_array[step, ..., c][x_array[step, ..., sdf] != 0] -= mean(y_array[step, ..., c][x_array[step, ..., sdf] != 0])
 // (SM_call.py:487-488; Eval_dual_Dense_onlycil.py:509-511).  One workgroup per (block, channel); float64 sums like the

@@ -1334,3 +1334,99 @@ class SolverModule:
         self._sur._chk(self._sur.lib.psm_solve(self._sur.h, _p(a, C.c_double), a.shape[0], int(placeholder),
                                                 _p(out, C.c_double)))
         return out
+
+
+class SolverEnsemble:
+    """``SolverModule`` for an ensemble of cases that share one grid shape: K meshes with their own obstacles on ONE handle,
+    all advanced by one call (``psm_set_geometry_cases`` / ``psm_solve_cases``: one launch chain per step instead of one per
+    case).  ``init_func`` takes one (array, top, obst) per case, ``py_func`` one ``[N_i,5]`` array per case and returns the
+    list of ``p_i``.  ``geometry``: 'native' (``psm_init_geometry_cases``, the library's C++ table builder) or 'scipy'
+    (``geometry.build_geometry`` per case, handed over with ``psm_set_geometry_cases``) -- see :class:`SolverModule`."""
+
+    def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), max_cases: int = 8, geometry: str = "native",
+                 device: int = 0, delta: float = 5e-3):
+        if geometry not in ("scipy", "native"):
+            raise ValueError("geometry must be 'scipy' or 'native'")
+        self.model, self.maxs, self.max_cases = model, tuple(float(v) for v in maxs), int(max_cases)
+        self.geometry, self.device, self.delta = geometry, device, delta
+        self._sur = None
+        self.tables = None
+        self.cell_off = None
+        self._inflight = None
+
+    @staticmethod
+    def _ptrs(arrays):
+        return (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+    def init_func(self, arrays, tops, obsts):
+        """One-time tables of every case; all cases must give the same grid shape.  Returns 0."""
+        if not (len(arrays) == len(tops) == len(obsts)) or not 1 <= len(arrays) <= self.max_cases:
+            raise ValueError("one (array, top, obst) per case, 1..max_cases cases")
+        lib = _lib.load()
+        K = len(arrays)
+        a, t, o = [_f64(x) for x in arrays], [_f64(x) for x in tops], [_f64(x) for x in obsts]
+        mx = _f64(self.maxs)
+        if self.geometry == "native":
+            ny, nx = C.c_int32(), C.c_int32()
+            if lib.psm_geometry_shape(_p(a[0], C.c_double), a[0].shape[0], self.delta, C.byref(ny), C.byref(nx), None):
+                raise ValueError(lib.psm_geometry_last_error().decode())
+            ny, nx, tables = ny.value, nx.value, "native"
+        else:
+            from .geometry import build_geometry
+            tables = [build_geometry(a[k], t[k], o[k], self.delta) for k in range(K)]
+            ny, nx = tables[0].ny, tables[0].nx
+            if any((g.ny, g.nx) != (ny, nx) for g in tables):
+                raise ValueError("the cases of an ensemble must share one grid shape")
+        if self._sur is not None:
+            self._sur.close()
+        self._sur = sur = GridSurrogate(self.model, ny, nx, self.max_cases, self.device)
+        n = (C.c_int64 * K)(*[x.shape[0] for x in a])
+        if self.geometry == "native":
+            sur._chk(lib.psm_set_case(sur.h, _p(mx, C.c_double), self.delta, 10, 0.05))
+            sur._chk(lib.psm_init_geometry_cases(sur.h, K, self._ptrs(a), n, self._ptrs(t), (C.c_int64 * K)(*[x.shape[0] for x in t]),
+                                                 self._ptrs(o), (C.c_int64 * K)(*[x.shape[0] for x in o])))
+        else:
+            keep = [[np.ascontiguousarray(getattr(g, f), dt) for g in tables]
+                    for f, dt in (("vtx_m2g", np.int32), ("wts_m2g", np.float64), ("indices", np.int32), ("sdfunct", np.float64),
+                                  ("vtx_g2m", np.int32), ("wts_g2m", np.float64))]
+            sur._chk(lib.psm_set_geometry_cases(sur.h, K, n, ny, nx, *[self._ptrs(col) for col in keep], _p(mx, C.c_double), 0, 0, 0.05))
+        off = (C.c_int64 * (K + 1))()
+        sur._chk(lib.psm_mesh_cases(sur.h, None, off))
+        self.cell_off = [int(v) for v in off]
+        self.tables = tables
+        return 0
+
+    def _pack(self, arrays):
+        if self.tables is None:
+            raise RuntimeError("init_func has not been called")
+        K = len(self.cell_off) - 1
+        if len(arrays) != K:
+            raise ValueError(f"{K} cases were initialised")
+        cells = np.empty((self.cell_off[-1], 5), np.float64)
+        for k, x in enumerate(arrays):
+            x = np.asarray(x)
+            if x.shape != (self.cell_off[k + 1] - self.cell_off[k], 5):
+                raise ValueError("array must be [N,5] = (Ux, Uy, Cx, Cy, p) with the cell count of init_func")
+            cells[self.cell_off[k]:self.cell_off[k + 1]] = x
+        return cells, np.empty(self.cell_off[-1], np.float64)
+
+    def _split(self, p):
+        return [p[self.cell_off[k]:self.cell_off[k + 1]] for k in range(len(self.cell_off) - 1)]
+
+    def py_func_begin(self, arrays):
+        """First half of :meth:`py_func` (psm_solve_cases_begin): enqueue the step of all cases and return."""
+        cells, p = self._pack(arrays)
+        self._sur._chk(self._sur.lib.psm_solve_cases_begin(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
+        self._inflight = (cells, p)                     # keeps both arrays alive until the end call
+
+    def py_func_end(self):
+        self._sur._chk(self._sur.lib.psm_solve_cases_end(self._sur.h))
+        cells, p = self._inflight
+        self._inflight = None
+        return self._split(p)
+
+    def py_func(self, arrays):
+        """One step of every case: list of cells [N_i,5] float64 -> list of p_i [N_i] float64."""
+        cells, p = self._pack(arrays)
+        self._sur._chk(self._sur.lib.psm_solve_cases(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
+        return self._split(p)
