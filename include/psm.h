@@ -464,6 +464,40 @@ int psm_poisson_step_device(psm_handle* h, const double* d_vel, int32_t n_cases,
 int psm_poisson_step(psm_handle* h, const double* vel, int32_t n_cases, const double* LU, const float* out_scale,
                      int32_t apply_filter, const float* dU, const float* prev, float* result, float* change, float* next);
 
+/* Frames of cell columns on the single mesh of psm_set_geometry (its grid -> mesh tables are not needed), on the device: the
+ * mesh -> grid step of psm_mesh_to_grid for n_frames arrays at once, every column into a plane of its own, and the Poisson
+ * evaluator's whole frame behind it.  One launch for the batch (the frame is a launch dimension); statements, summation order,
+ * `fill` and the 0 of a cell nobody writes are those of psm_mesh_to_grid, so a float64 plane holds the bits of that entry's
+ * column and a float32 plane their plain cast (NaN stays NaN).  Every stored plane is written completely: no memset needed.
+ * psm_bind_frames: after psm_set_geometry; n_frames in [1, max_cases], k in [1, 16] (PSM_ERR_ARG otherwise); PSM_ERR_STATE
+ * without a mesh or on a case set (psm_set_geometry_cases).  Reserves the device and pinned staging the host entry goes
+ * through (columns, extra planes, fields) for n_frames frames of k columns: after it a step allocates nothing.  A new mesh,
+ * psm_plan_grid or a model change drops the binding. */
+typedef struct { void* dst; int64_t frame_stride; int32_t as_f32; } psm_frame_col;   /* dst NULL: column not stored; stride in elements */
+int psm_bind_frames(psm_handle* h, int32_t n_frames, int32_t k);
+int psm_unbind_frames(psm_handle* h);
+/* The stage alone.  d_cols [n_frames][n_cells][k] float64, row-major (per frame the array psm_mesh_to_grid takes); out: HOST
+ * array [k], column c of frame f goes to out[c].dst + f * out[c].frame_stride + cell, as float64 or (as_f32) float32.  Device
+ * pointers, asynchronous on `stream` (NULL: the handle's), nothing is copied: the descriptors travel in the launch.
+ * PSM_ERR_ARG and nothing enqueued: k outside [1, 16], n_frames outside [1, bound count], a destination that is not aligned
+ * to its element (8 / 4 bytes), a negative stride, every destination NULL. */
+int psm_frames_to_grid_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, int32_t fill,
+                              const psm_frame_col* out, void* stream);
+/* The Poisson evaluator's frames as ONE graph replay: planes -> psm_poisson_step_device, with fill = 1.  Columns 0-3 =
+ * (Ux, Uy, dUx, dUy) go to the velocity planes of the feature binding; with weighting != 0 the last two columns (dU-change
+ * weight, delta_p_prev) go as float32 to the post-steps' dU / prev buffers of the handle; the columns between go as float64 to
+ * d_extra [n_frames][n_extra][ny*nx] (NULL: not stored).  k in [4, 16], with the weighting [6, 16].  weighting == 0: d_change
+ * and d_next are not used.  Needs psm_bind_features, psm_bind_poststeps and psm_bind_frames (PSM_ERR_STATE names the missing
+ * one); n_frames within every bound count.  LU [n_frames][2] and out_scale [n_frames] are HOST arrays copied before return. */
+int psm_poisson_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const double* LU,
+                              const float* out_scale, int32_t apply_filter, int32_t weighting, double* d_extra,
+                              float* d_result, float* d_change, float* d_next, void* stream);
+/* host buffers, synchronous: one H2D of cols (k at most the bound count), D2H of the fields and (extra != NULL) of the extra
+ * planes; no plane or image round trip.  Solves again on the general path after a guard trip, like psm_poisson_step. */
+int psm_poisson_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, const double* LU,
+                       const float* out_scale, int32_t apply_filter, int32_t weighting, double* extra,
+                       float* result, float* change, float* next);
+
 /* U_to_gradP: integrate the assembled (dp/dx, dp/dy) into p (integrate_field,
  * Eval_dual_Dense_onlycil.py:371-416, and the four-quadrant stitching :597-628).
  * psm_set_integration fixes the geometry: sdfunct [ny*nx] (self.sdfunct[:,:,0], also used by the

@@ -42,6 +42,11 @@ class psm_config(C.Structure):
         "sdf_channel", "device", "max_cases", "strict_degenerate", "precision")]
 
 
+class psm_frame_col(C.Structure):
+    """One column's destination plane of psm_frames_to_grid_device (psm.h)."""
+    _fields_ = [("dst", C.c_void_p), ("frame_stride", C.c_int64), ("as_f32", C.c_int32)]
+
+
 _f32p, _f64p, _i32p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)
 _hp = C.c_void_p
 
@@ -115,6 +120,12 @@ SIGNATURES = {
     "psm_features_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, _f64p, C.c_void_p, C.c_void_p]),
     "psm_poisson_step_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, _f64p, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "psm_poisson_step": (C.c_int, [_hp, _f64p, C.c_int32, _f64p, _f32p, C.c_int32, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "psm_bind_frames": (C.c_int, [_hp, C.c_int32, C.c_int32]),
+    "psm_unbind_frames": (C.c_int, [_hp]),
+    "psm_frames_to_grid_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(psm_frame_col), C.c_void_p]),
+    "psm_poisson_frames_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_poisson_frames": (C.c_int, [_hp, _f64p, C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, C.c_int32, _f64p, _f32p, _f32p, _f32p]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
     "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),

@@ -60,8 +60,10 @@ static PostCall post_call(int apply_filter, const float* dU, const float* prev, 
   return pc;
 }
 
-// every check of one whole step, then its scalars and the one graph replay: features into the binding's image, solve, post-steps
-static int step_device(psm_handle* h, const double* d_vel, int n_cases, const double* LU, const float* out_scale, const PostCall& pc, hipStream_t st) {
+// every check of one whole step, then its scalars and the one graph replay: (frames -> planes,) features into the binding's image, solve,
+// post-steps
+int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const double* LU, const float* out_scale, const PostCall& pc, hipStream_t st,
+                        const FrameCall* frames) {
   int rc = feat_check(h, n_cases, LU);
   if (rc) return rc;
   if (!h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: a Poisson step needs it as well as psm_bind_features");
@@ -71,7 +73,7 @@ static int step_device(psm_handle* h, const double* d_vel, int n_cases, const do
   if (!st) st = h->stream;
   if ((rc = upload_lu(h, LU, n_cases, st))) return rc;
   const FeatCall fc{d_vel, h->feat.d_grid};
-  return solve_device(h, fc.grid, n_cases, out_scale, h->post.d_fields, st, nullptr, nullptr, &pc, &fc);
+  return solve_device(h, fc.grid, n_cases, out_scale, h->post.d_fields, st, nullptr, nullptr, &pc, &fc, frames);
 }
 
 }  // namespace psm_impl
@@ -145,7 +147,7 @@ int psm_poisson_step_device(psm_handle* h, const double* d_vel, int32_t n_cases,
                             int32_t apply_filter, const float* d_dU, const float* d_prev, float* d_result, float* d_change,
                             float* d_next, void* stream) {
   if (!h) return PSM_ERR_ARG;
-  return step_device(h, d_vel, n_cases, LU, out_scale, post_call(apply_filter, d_dU, d_prev, d_result, d_change, d_next), (hipStream_t)stream);
+  return poisson_step_device(h, d_vel, n_cases, LU, out_scale, post_call(apply_filter, d_dU, d_prev, d_result, d_change, d_next), (hipStream_t)stream);
 }
 
 
@@ -180,7 +182,7 @@ int psm_poisson_step(psm_handle* h, const double* vel, int32_t n_cases, const do
     HIPCHK(h, hipMemcpyAsync(s.d_prev, p_prev, pb, hipMemcpyHostToDevice, st));
   }
   for (int pass = 0; pass < 2; ++pass) {
-    if ((rc = step_device(h, h->feat.d_vel, n_cases, LU, out_scale, pc, st))) return rc;
+    if ((rc = poisson_step_device(h, h->feat.d_vel, n_cases, LU, out_scale, pc, st))) return rc;
     for (int k = 0; k < 3; ++k)
       if (dst[k]) HIPCHK(h, hipMemcpyAsync(p_out[k], src[k], k ? pb : fb, hipMemcpyDeviceToHost, st));
     HIPCHK(h, wait_stream(st));

@@ -1,0 +1,191 @@
+// psm_api_frames.cpp -- C-ABI of libpsm_hip.so (include/psm.h): frames of cell columns on the single mesh of psm_set_geometry, on the
+// device.  psm_frames_to_grid_device is the mesh -> grid stage alone (interpolate_fill + last-writer scatter of k columns per frame,
+// every column into a plane of its own, one launch for the batch); psm_poisson_frames* put it in front of the Poisson time step of
+// psm_api_features.cpp, column convention of the pressureSM_Poisson evaluator, as one graph replay:
+// d_cols -> planes -> features -> solve -> post-steps.  Kernel: the PsmFrameArgs overload of psm_interp_to_grid_kernel (psm_mesh.hip).
+// See psm_handle.h for the map of the files.
+#include "psm_handle.h"
+
+namespace psm_impl {
+
+// captured step graphs (GraphKey::frames) hold the addresses of the mesh tables and of the column array
+static void drop_frame_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.frames.cols != nullptr; }); }
+
+void frames_free(psm_handle* h) {
+  FrameSet& s = h->frames;
+  drop_frame_graphs(h);
+  dev_free(s.d_cols); dev_free(s.d_extra);
+  if (s.h_cols) { (void)hipHostFree(s.h_cols); s.h_cols = nullptr; }
+  if (s.h_extra) { (void)hipHostFree(s.h_extra); s.h_extra = nullptr; }
+  if (s.h_out) { (void)hipHostFree(s.h_out); s.h_out = nullptr; }
+  s.ready = false; s.n_frames = 0; s.k = 0;
+}
+
+// The one launch of the stage on `st`: the mesh's tables, the call's columns and plane descriptors.
+int frames_device(psm_handle* h, const FrameCall& fc, int n_frames, hipStream_t st) {
+  PsmFrameArgs a{};
+  a.cols = fc.cols; a.vtx = h->d_vtx_m2g; a.wts = h->d_wts_m2g; a.src_of_cell = h->d_src_of_cell;
+  a.n_grid = (int64_t)h->Ny * h->Nx; a.n_cells = h->n_cells;
+  a.k = fc.k; a.fill = fc.fill ? 1 : 0; a.n_frames = n_frames;
+  for (int c = 0; c < fc.k; ++c) a.out[c] = fc.out[c];
+  HIPCHK(h, psm_launch_frames_to_grid(a, st));
+  return PSM_OK;
+}
+
+// the mesh and the binding every entry below needs
+static int frames_state(psm_handle* h) {
+  if (h->mcs.ready) return fail(h, PSM_ERR_STATE, "the handle holds a case set (psm_set_geometry_cases): frames take the single mesh of psm_set_geometry");
+  if (!h->have_geometry || !h->planned) return fail(h, PSM_ERR_STATE, "psm_set_geometry has not been called (a new plan drops the mesh)");
+  if (!h->frames.ready) return fail(h, PSM_ERR_STATE, "psm_bind_frames has not been called (a new mesh, plan or model drops the binding)");
+  return PSM_OK;
+}
+
+static int frames_count_check(psm_handle* h, int n_frames) {
+  if (n_frames < 1 || n_frames > h->frames.n_frames) return fail(h, PSM_ERR_ARG, "n_frames outside [1, frames bound with psm_bind_frames]");
+  return PSM_OK;
+}
+
+// The evaluator's column convention as plane descriptors: 0-3 -> the feature binding's velocity planes, the last two (weighting) ->
+// the post-steps' dU / prev as float32, the columns between -> d_extra (nullptr: not stored).
+static int poisson_frame_call(psm_handle* h, const double* d_cols, int n_frames, int k, int weighting, double* d_extra, FrameCall& fc) {
+  int rc = frames_state(h);
+  if (rc) return rc;
+  if (!h->feat.ready) return fail(h, PSM_ERR_STATE, "psm_bind_features has not been called: the frames step needs it as well as psm_bind_frames");
+  if (!h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: the frames step needs it as well as psm_bind_frames");
+  const int k_min = weighting ? 6 : 4;
+  if (k < k_min || k > PSM_FRAME_MAX_COLS) return fail(h, PSM_ERR_ARG, "k outside [4 (6 with the weighting), 16]: (Ux, Uy, dUx, dUy), extra columns, (dU-change weight, delta_p_prev)");
+  if ((rc = frames_count_check(h, n_frames))) return rc;
+  if (!d_cols) return fail(h, PSM_ERR_ARG, "null buffer");
+  if (reinterpret_cast<uintptr_t>(d_extra) & 7) return fail(h, PSM_ERR_ARG, "d_extra must be 8-byte aligned");
+  const int64_t npix = (int64_t)h->Ny * h->Nx;
+  const int n_extra = k - k_min;
+  fc = FrameCall{};
+  fc.cols = d_cols; fc.k = k; fc.fill = 1;
+  for (int c = 0; c < 4; ++c) fc.out[c] = PsmFramePlane{h->feat.d_vel + c * npix, 4 * npix, 0};
+  for (int e = 0; e < n_extra; ++e) fc.out[4 + e] = PsmFramePlane{d_extra ? d_extra + e * npix : nullptr, n_extra * npix, 0};
+  if (weighting) {
+    fc.out[k - 2] = PsmFramePlane{h->post.d_dU, npix, 1};
+    fc.out[k - 1] = PsmFramePlane{h->post.d_prev, npix, 1};
+  }
+  return PSM_OK;
+}
+
+}  // namespace psm_impl
+
+// ============================================================================
+extern "C" {
+
+
+int psm_bind_frames(psm_handle* h, int32_t n_frames, int32_t k) {
+  if (!h) return PSM_ERR_ARG;
+  if (h->mcs.ready) return fail(h, PSM_ERR_STATE, "the handle holds a case set (psm_set_geometry_cases): frames take the single mesh of psm_set_geometry");
+  if (!h->have_geometry || !h->planned) return fail(h, PSM_ERR_STATE, "psm_set_geometry has not been called (a new plan drops the mesh)");
+  if (n_frames < 1 || n_frames > h->cfg.max_cases) return fail(h, PSM_ERR_ARG, "n_frames outside [1, max_cases]");
+  if (k < 1 || k > PSM_FRAME_MAX_COLS) return fail(h, PSM_ERR_ARG, "1..16 columns");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));           // a step in flight reads the staging that is replaced
+  frames_free(h);
+  FrameSet& s = h->frames;
+  const size_t npix = (size_t)h->Ny * h->Nx, n = (size_t)n_frames;
+  const size_t n_cols = n * (size_t)h->n_cells * k, n_extra = n * (size_t)k * npix, n_out = n * npix * ((size_t)h->cfg.c_out + 2);
+  int rc;
+  if ((rc = dev_alloc(h, &s.d_cols, n_cols)) || (rc = dev_alloc(h, &s.d_extra, n_extra))) { frames_free(h); return rc; }
+  hipError_t e = hipHostMalloc((void**)&s.h_cols, n_cols * sizeof(double), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_extra, n_extra * sizeof(double), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_out, n_out * sizeof(float), hipHostMallocDefault);
+  if (e != hipSuccess) { frames_free(h); return fail(h, PSM_ERR_NOMEM, std::string("psm_bind_frames: ") + hipGetErrorString(e)); }
+  s.n_frames = n_frames; s.k = k;
+  s.ready = true;
+  return PSM_OK;
+}
+
+
+int psm_unbind_frames(psm_handle* h) {
+  if (!h) return PSM_ERR_ARG;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  frames_free(h);
+  return PSM_OK;
+}
+
+
+int psm_frames_to_grid_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, int32_t fill, const psm_frame_col* out,
+                              void* stream) {
+  if (!h) return PSM_ERR_ARG;
+  int rc = frames_state(h);
+  if (rc) return rc;
+  if (k < 1 || k > PSM_FRAME_MAX_COLS) return fail(h, PSM_ERR_ARG, "1..16 columns");
+  if ((rc = frames_count_check(h, n_frames))) return rc;
+  if (!d_cols || !out) return fail(h, PSM_ERR_ARG, "null argument");
+  FrameCall fc;
+  fc.cols = d_cols; fc.k = k; fc.fill = fill ? 1 : 0;
+  bool any = false;
+  for (int c = 0; c < k; ++c) {
+    if (!out[c].dst) continue;
+    any = true;
+    if (reinterpret_cast<uintptr_t>(out[c].dst) & (out[c].as_f32 ? 3 : 7))
+      return fail(h, PSM_ERR_ARG, "a destination plane is misaligned (8 bytes for float64, 4 for float32)");
+    if (out[c].frame_stride < 0) return fail(h, PSM_ERR_ARG, "frame_stride must not be negative");
+    fc.out[c] = PsmFramePlane{out[c].dst, out[c].frame_stride, out[c].as_f32 ? 1 : 0};
+  }
+  if (!any) return fail(h, PSM_ERR_ARG, "every destination is NULL: nothing to store");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  return frames_device(h, fc, n_frames, stream ? (hipStream_t)stream : h->stream);
+}
+
+
+int psm_poisson_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const double* LU, const float* out_scale,
+                              int32_t apply_filter, int32_t weighting, double* d_extra, float* d_result, float* d_change, float* d_next,
+                              void* stream) {
+  if (!h) return PSM_ERR_ARG;
+  FrameCall fc;
+  int rc = poisson_frame_call(h, d_cols, n_frames, k, weighting, d_extra, fc);
+  if (rc) return rc;
+  PostCall pc;
+  pc.apply_filter = apply_filter ? 1 : 0; pc.result = d_result;
+  if (weighting) { pc.dU = h->post.d_dU; pc.prev = h->post.d_prev; pc.change = d_change; pc.next = d_next; }
+  return poisson_step_device(h, h->feat.d_vel, n_frames, LU, out_scale, pc, (hipStream_t)stream, &fc);
+}
+
+
+int psm_poisson_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, const double* LU, const float* out_scale,
+                       int32_t apply_filter, int32_t weighting, double* extra, float* result, float* change, float* next) {
+  if (!h) return PSM_ERR_ARG;
+  if (!cols || !result) return fail(h, PSM_ERR_ARG, "null buffer");
+  FrameSet& F = h->frames;
+  FrameCall fc;
+  int rc = poisson_frame_call(h, F.d_cols, n_frames, k, weighting, extra ? F.d_extra : nullptr, fc);
+  if (rc) return rc;
+  if (k > F.k) return fail(h, PSM_ERR_ARG, "more columns than psm_bind_frames reserved staging for");
+  PostSet& s = h->post;
+  const size_t cap = (size_t)h->cfg.max_cases * h->Ny * h->Nx * h->cfg.c_out;
+  PostCall pc;
+  pc.apply_filter = apply_filter ? 1 : 0; pc.result = s.d_out;
+  if (weighting) { pc.dU = s.d_dU; pc.prev = s.d_prev; pc.change = change ? s.d_out + cap : nullptr; pc.next = next ? s.d_out + 2 * cap : nullptr; }
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  hipStream_t st = h->stream;
+  const size_t npix = (size_t)h->Ny * h->Nx, n_extra = (size_t)k - (weighting ? 6 : 4);
+  const size_t cb = (size_t)n_frames * h->n_cells * k * sizeof(double), pb = (size_t)n_frames * npix * sizeof(float), fb = pb * h->cfg.c_out;
+  const size_t eb = extra ? (size_t)n_frames * n_extra * npix * sizeof(double) : 0;
+  float* p_out[3] = {F.h_out, F.h_out + fb / 4, F.h_out + fb / 4 + pb / 4};
+  float* const dst[3] = {result, pc.change ? change : nullptr, pc.next ? next : nullptr};
+  const float* const src[3] = {pc.result, pc.change, pc.next};
+  memcpy(F.h_cols, cols, cb);
+  HIPCHK(h, hipMemcpyAsync(F.d_cols, F.h_cols, cb, hipMemcpyHostToDevice, st));
+  for (int pass = 0; pass < 2; ++pass) {
+    if ((rc = poisson_step_device(h, h->feat.d_vel, n_frames, LU, out_scale, pc, st, &fc))) return rc;
+    for (int q = 0; q < 3; ++q)
+      if (dst[q]) HIPCHK(h, hipMemcpyAsync(p_out[q], src[q], q ? pb : fb, hipMemcpyDeviceToHost, st));
+    if (eb && pass == 0) HIPCHK(h, hipMemcpyAsync(F.h_extra, F.d_extra, eb, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, wait_stream(st));
+    if (pass == 1 || !guard_take(h, h->ws0)) break;     // not the bound geometry: the field is NaN -- drop the binding, solve again on the general path
+    if ((rc = guard_drop(h, "psm_poisson_frames"))) return rc;
+    h->err += " (solved on the general path)";
+  }
+  for (int q = 0; q < 3; ++q)
+    if (dst[q]) memcpy(dst[q], p_out[q], q ? pb : fb);
+  if (eb) memcpy(extra, F.h_extra, eb);
+  return PSM_OK;
+}
+
+}  // extern "C"

@@ -124,6 +124,7 @@ void free_plan(psm_handle* h) {
   integ_free(h->integ_dev);             // psm_bind_integration is sized by this plan's grid
   post_free(h->post);                   // and so is psm_bind_poststeps
   feat_free(h->feat);                   // and psm_bind_features
+  frames_free(h);                       // psm_bind_frames belongs to the mesh that went with the plan
 }
 
 
@@ -190,6 +191,7 @@ void mesh_cases_free(psm_handle* h) {
 void free_geometry(psm_handle* h) {
   unpin_buffers(h);
   mesh_cases_free(h);
+  frames_free(h);                       // the frame batch reads this mesh's tables
   dev_free(h->d_vtx_m2g); dev_free(h->d_src_of_cell); dev_free(h->d_vtx_g2m); dev_free(h->d_cell_of_point);
   dev_free(h->d_wts_m2g); dev_free(h->d_sdf); dev_free(h->d_wts_g2m); dev_free(h->d_cells); dev_free(h->d_p);
   dev_free(h->d_umax); dev_free(h->d_umax_part); dev_free(h->d_near_wall);
@@ -370,6 +372,7 @@ int psm_set_pca(psm_handle* h, const double* comp_in, const double* mean_in, con
   h->post.ready = false;                 // and so does psm_bind_poststeps
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
+  h->frames.ready = false;               // and psm_bind_frames
   std::vector<float> mi(h->K_in), mo(h->K_out);
   for (int k = 0; k < h->K_in; ++k) mi[k] = (float)mean_in[k];
   for (int k = 0; k < h->K_out; ++k) mo[k] = (float)mean_out[k];
@@ -439,6 +442,7 @@ int psm_set_dense(psm_handle* h, int32_t layer, int32_t n_in, int32_t n_out, con
   h->post.ready = false;                 // and so does psm_bind_poststeps
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
+  h->frames.ready = false;               // and psm_bind_frames
   DenseLayer& d = h->dense[layer];
   d.linear = false;                                     // psm_set_attention sets it again after this call
   if (d.ln && (d.n_out != n_out || (d.ln_residual && n_in != n_out))) {      // a LayerNormalization of another width, or its residual x + input on a
@@ -530,6 +534,7 @@ int psm_set_layernorm(psm_handle* h, int32_t layer, int32_t n, const float* gamm
   h->post.ready = false;                 // and so does psm_bind_poststeps
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
+  h->frames.ready = false;               // and psm_bind_frames
   // zero-padded to whole 16-byte pieces past the consumer's leading dimension: a Dense launch that applies this normalisation to
   // its input (launch_all) reads gamma / beta with the clamped column index of its operand loads
   std::vector<float> g(round_up(n, 32) + 32, 0.f), b(round_up(n, 32) + 32, 0.f);
@@ -562,6 +567,7 @@ int psm_set_conv1d(psm_handle* h, int32_t layer, int32_t n_layers, int32_t kerne
   h->post.ready = false;                 // and so does psm_bind_poststeps
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
+  h->frames.ready = false;               // and psm_bind_frames
   if (!same_stack) {
     for (auto& c : h->conv1d) { dev_free(c.W); dev_free(c.b); }
     h->conv1d.assign(n_layers, Conv1dLayer{});
@@ -592,6 +598,7 @@ int psm_set_scaler(psm_handle* h, const double* in_a, const double* in_b, const 
   h->post.ready = false;                 // and so does psm_bind_poststeps
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
+  h->frames.ready = false;               // and psm_bind_frames
   std::vector<float> ia(h->ld_in, 0.f), ib(h->ld_in, 0.f), sa(h->ld_out, 0.f), sb(h->ld_out, 0.f);
   // x_in = coeff*ia + ib ; res' = res*sa + sb  (affine forms of SMD:505-539, evaluated in f64 here)
   for (int p = 0; p < h->cfg.p_in; ++p) {

@@ -444,7 +444,7 @@ int capture_graph(psm_handle* h, hipStream_t st, const char* label, const std::f
 
 
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
-                 hipStream_t st, hipEvent_t* prof, float* d_p, const PostCall* post, const FeatCall* feat) {
+                 hipStream_t st, hipEvent_t* prof, float* d_p, const PostCall* post, const FeatCall* feat, const FrameCall* frames) {
   if (!h) return PSM_ERR_ARG;
   if (!h->planned) return fail(h, PSM_ERR_STATE, "psm_plan_grid has not been called");
   if (!d_grid || !d_fields) return fail(h, PSM_ERR_ARG, "null buffer");
@@ -457,16 +457,19 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
   rc = prepare_scale(h, h->ws0, out_scale, n_cases, st, &d_scale);
   if (rc) return rc;
   h->last_cases = n_cases;
-  // the two feature launches (feat), the solve, then the two integration launches (d_p) or the post-steps' (at most four): one linear chain
+  // the mesh -> grid launch (frames), the two feature launches (feat), the solve, then the two integration launches (d_p) or the
+  // post-steps' (at most four): one linear chain
   auto sequence = [&](hipStream_t on, hipEvent_t* ev) {
-    int rs = feat ? features_device(h, feat->vel, n_cases, feat->grid, on) : PSM_OK;
+    int rs = frames ? frames_device(h, *frames, n_cases, on) : PSM_OK;
+    if (!rs && feat) rs = features_device(h, feat->vel, n_cases, feat->grid, on);
     if (!rs) rs = launch_all(h, h->ws0, d_grid, n_cases, d_fields, d_scale, on, ev);
     if (!rs && d_p) rs = integrate_device(h, d_fields, n_cases, d_p, on);
     if (!rs && post) rs = poststeps_device(h, d_fields, n_cases, *post, on);
     return rs;
   };
   if (prof || h->timed_kernel >= 0 || !h->use_graph) return sequence(st, prof);
-  const GraphKey key{sequence_key(h, n_cases, out_scale != nullptr), d_grid, d_fields, d_p, post ? *post : PostCall{}, feat ? feat->vel : nullptr};
+  const GraphKey key{sequence_key(h, n_cases, out_scale != nullptr), d_grid, d_fields, d_p, post ? *post : PostCall{}, feat ? feat->vel : nullptr,
+                     frames ? *frames : FrameCall{}};
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     if (h->graphs.size() > 64) destroy_graphs(h);

@@ -1,5 +1,5 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in eight files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in nine files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, graph capture and key, psm_solve_grid*
@@ -7,6 +7,7 @@
 //   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*; the case batch psm_set_geometry_cases / psm_solve_cases*, host tables in psm_mesh_tables.cpp), evaluator helpers (labels, block error, filters), the gradP integration (host entry and device-resident U -> p)
 //   psm_api_filter.cpp      the Gaussian post-steps: psm_gaussian_filter (host entry), psm_bind_poststeps and the device-resident / case-batched entries
 //   psm_api_features.cpp    the pressureSM_Poisson input features on the device: psm_bind_features, psm_features_device and the whole step psm_poisson_step*
+//   psm_api_frames.cpp      frames of cell columns -> planes on the device: psm_bind_frames, psm_frames_to_grid_device and the evaluator's step psm_poisson_frames*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -17,6 +18,7 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <thread>
 #include <cmath>
@@ -113,13 +115,34 @@ struct FeatCall {
   float* grid = nullptr;                // the image the two launches write and the solve reads
 };
 
+// The mesh -> grid stage in front of the features (psm_poisson_frames*): the launch holds the column array and the k plane descriptors.
+struct FrameCall {
+  const double* cols = nullptr;         // [n_frames][n_cells][k]; nullptr: no frame stage
+  int k = 0, fill = 1;
+  PsmFramePlane out[PSM_FRAME_MAX_COLS] = {};
+  auto key() const {                    // everything the captured launch holds, as one comparable value
+    std::array<int64_t, 3 + 3 * PSM_FRAME_MAX_COLS> a{};
+    a[0] = (int64_t)reinterpret_cast<intptr_t>(cols); a[1] = k; a[2] = fill;
+    for (int c = 0; c < k && c < PSM_FRAME_MAX_COLS; ++c) {
+      a[3 + 3 * c] = (int64_t)reinterpret_cast<intptr_t>(out[c].dst); a[4 + 3 * c] = out[c].frame_stride; a[5 + 3 * c] = out[c].as_f32;
+    }
+    return a;
+  }
+};
+
 struct GraphKey {
   int n; const void* g; void* f;        // n: sequence_key()
   void* p = nullptr;                    // psm_solve_pressure*: where the integration behind the solve writes p (null: the solve alone)
   PostCall post{};                      // psm_solve_poststeps*: the post-steps behind the solve (apply_filter == -1: none)
   const void* vel = nullptr;            // psm_poisson_step*: the velocity planes of the features in front of the solve (g is their image)
+  FrameCall frames{};                   // psm_poisson_frames*: the mesh -> grid stage in front of the features (cols == nullptr: none)
   auto head() const { return std::tie(n, g, f, p, vel); }
-  bool operator<(const GraphKey& o) const { return head() < o.head() || (head() == o.head() && post.tie() < o.post.tie()); }
+  bool operator<(const GraphKey& o) const {
+    if (head() != o.head()) return head() < o.head();
+    if (post.tie() != o.post.tie()) return post.tie() < o.post.tie();
+    if (!frames.cols && !o.frames.cols) return false;       // no frame stage on either side: nothing more to compare
+    return frames.key() < o.frames.key();
+  }
 };
 
 // Everything ONE in-flight solve writes.  The handle owns one for the synchronous / device entries (ws0) and one per
@@ -193,6 +216,17 @@ struct FeatureSet {
   hipEvent_t lu_ev[RING] = {};
   int lu_pos = 0;
 };
+
+// Binding of the frame batch to the single mesh of psm_set_geometry (psm_bind_frames): what the host entry psm_poisson_frames stages
+// through, so that a step allocates nothing.  The device entries hold no table of their own: they read the mesh's.
+struct FrameSet {
+  bool ready = false;
+  int n_frames = 0, k = 0;
+  double* d_cols = nullptr;             // [n_frames][n_cells][k]
+  double* d_extra = nullptr;            // [n_frames][k][npix]: the float64 planes of the columns between the velocities and the weighting pair
+  double *h_cols = nullptr, *h_extra = nullptr;   // pinned copies of the two
+  float* h_out = nullptr;               // pinned [n_frames][npix][c_out + 2]: result, change, next
+};
 }  // namespace psm_impl
 using namespace psm_impl;
 
@@ -233,6 +267,7 @@ struct psm_handle {
   IntegSet integ_host, integ_dev;
   PostSet post;                         // Gaussian post-steps on the planned grid (psm_bind_poststeps)
   FeatureSet feat;                      // Poisson input features on the planned grid (psm_bind_features)
+  FrameSet frames;                      // frame batch on the single mesh (psm_bind_frames)
   double *h_cells = nullptr, *h_p = nullptr;
   const double* pinned_cells = nullptr;   // caller buffers registered with psm_pin_buffers (DMA without staging copies)
   double* pinned_p = nullptr;
@@ -376,6 +411,10 @@ void post_free(PostSet& s);
 int poststeps_device(psm_handle* h, const float* d_fields, int n_cases, const PostCall& pc, hipStream_t st);
 int post_check(psm_handle* h, int n_cases, const PostCall& pc);
 void feat_free(FeatureSet& s);
+void frames_free(psm_handle* h);
+int frames_device(psm_handle* h, const FrameCall& fc, int n_frames, hipStream_t st);
+int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const double* LU, const float* out_scale, const PostCall& pc,
+                        hipStream_t st, const FrameCall* frames = nullptr);
 int features_device(psm_handle* h, const double* d_vel, int n_cases, float* d_grid, hipStream_t st);
 std::vector<uint16_t> pack_comp_in_bf16(const double* comp, int P, int K, int c_in, int S, int NT);
 std::vector<uint16_t> pack_comp_out_bf16(const double* comp, int P, int K_out, int G);
@@ -394,9 +433,11 @@ PsmChainArgs chain_args(const psm_handle* h, const Workspace& w);
 PsmPasteArgs paste_args(const psm_handle* h, const Workspace& w, float* d_fields);
 // d_p != nullptr: the bound integration (psm_bind_integration) of d_fields into d_p follows in the same stream / the same graph;
 // post (apply_filter >= 0): the bound post-steps (psm_bind_poststeps) of d_fields follow likewise;
-// feat (vel != nullptr): the bound features (psm_bind_features) write d_grid == feat->grid in front of the solve, likewise
+// feat (vel != nullptr): the bound features (psm_bind_features) write d_grid == feat->grid in front of the solve, likewise;
+// frames (with feat): the mesh -> grid launch of psm_poisson_frames* writes feat->vel (and the post-steps' inputs) in front of the features
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
-                 hipStream_t st, hipEvent_t* prof, float* d_p = nullptr, const PostCall* post = nullptr, const FeatCall* feat = nullptr);
+                 hipStream_t st, hipEvent_t* prof, float* d_p = nullptr, const PostCall* post = nullptr, const FeatCall* feat = nullptr,
+                 const FrameCall* frames = nullptr);
 bool guard_take(psm_handle* h, Workspace& w);
 int guard_drop(psm_handle* h, const char* where);
 int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases = 1);

@@ -46,6 +46,25 @@ hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st);
 hipError_t psm_launch_interp_to_grid(const double* values, int k, const int32_t* vtx, const double* wts, const int32_t* src_of_cell,
                                      int fill, double* out, int64_t n_grid, hipStream_t st);
 
+// ---- frame-batched, plane-writing form of psm_launch_interp_to_grid (psm_frames_to_grid_device): n_frames arrays of cell columns on
+// the single mesh of psm_set_geometry, the frame is launch dimension y, every column goes to a plane of its own.
+constexpr int PSM_FRAME_MAX_COLS = 16;
+struct PsmFramePlane {
+  void* dst;                    // plane of frame 0, nullptr: the column is not stored
+  int64_t frame_stride;         // elements of the plane's type from one frame's plane to the next frame's
+  int32_t as_f32;               // 0: float64; else float32 by a plain cast (NaN stays NaN)
+};
+struct PsmFrameArgs {
+  const double* cols;           // [n_frames][n_cells][k] row-major, the layout psm_mesh_to_grid takes per frame
+  const int32_t* vtx;           // [n_grid,3] mesh->grid simplices, shared by the frames
+  const double* wts;            // [n_grid,3]
+  const int32_t* src_of_cell;   // [n_grid]
+  int64_t n_grid, n_cells;
+  int k, fill, n_frames;
+  PsmFramePlane out[PSM_FRAME_MAX_COLS];
+};
+hipError_t psm_launch_frames_to_grid(const PsmFrameArgs& a, hipStream_t st);
+
 // ---- the mesh ends for a case batch (psm_set_geometry_cases): K meshes on one planned grid, the case is launch dimension y.
 // Cell-side arrays are the cases' concatenated ([sum n_i, ...], case i at rows cell_off[i] .. cell_off[i + 1]), grid-side tables
 // are [K][n_grid, ...]; vertex indices are case-local as the caller gave them (the kernels add the case's offset).

@@ -261,6 +261,49 @@ hipError_t psm_launch_interp_to_grid(const double* values, int k, const int32_t*
   return hipGetLastError();
 }
 
+// The same step for n_frames arrays of cell columns at once (PsmFrameArgs in psm_mesh.h), every column into a plane of its own:
+// frame blockIdx.y, one thread per image cell.  A thread reads its cell's source point, simplex and weights once -- they are the
+// frames' common tables -- and then repeats the statements of the kernel above per column: the sum over the three vertices in the
+// same order from s = 0, NaN for a negative weight under `fill`, 0 for a cell nobody writes (in EVERY stored plane, so the planes
+// need no memset and a replay over reused buffers is complete).  A float64 plane therefore holds the bits of that kernel's column;
+// a float32 plane holds their plain cast.  The k descriptors are kernel arguments: nothing is copied for a launch.
+__global__ __launch_bounds__(256) void psm_interp_to_grid_kernel(PsmFrameArgs a) {
+  const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (cell >= a.n_grid) return;
+  const int64_t frame = blockIdx.y;
+  const int k = a.k;
+  const double* values = a.cols + frame * a.n_cells * k;
+  const int src = a.src_of_cell[cell];
+  int32_t v[3] = {0, 0, 0};
+  double w[3] = {0.0, 0.0, 0.0};
+  if (src >= 0) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { v[j] = a.vtx[(int64_t)src * 3 + j]; w[j] = a.wts[(int64_t)src * 3 + j]; }
+  }
+  const bool neg = (w[0] < 0.0) || (w[1] < 0.0) || (w[2] < 0.0);
+  for (int c = 0; c < k; ++c) {
+    const PsmFramePlane o = a.out[c];
+    if (!o.dst) continue;
+    double r = 0.0;
+    if (src >= 0) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) s += values[(int64_t)v[j] * k + c] * w[j];
+      r = (a.fill && neg) ? NAN : s;
+    }
+    const int64_t at = frame * o.frame_stride + cell;
+    if (o.as_f32) static_cast<float*>(o.dst)[at] = (float)r;
+    else static_cast<double*>(o.dst)[at] = r;
+  }
+}
+
+hipError_t psm_launch_frames_to_grid(const PsmFrameArgs& a, hipStream_t st) {
+  if (a.n_frames < 1 || a.k < 1 || a.k > PSM_FRAME_MAX_COLS || a.n_grid < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmFrameArgs)>(psm_interp_to_grid_kernel), dim3((unsigned)((a.n_grid + 255) / 256), (unsigned)a.n_frames),
+                     dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(psm_to_mesh_kernel, dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
   return hipGetLastError();

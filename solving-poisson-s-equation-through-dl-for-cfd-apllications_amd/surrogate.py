@@ -570,6 +570,108 @@ class GridSurrogate:
                                             opt(dU), opt(prev), _p(result, C.c_float), opt(change), opt(nxt)))
         return result, change, nxt
 
+    # -- frames of cell columns on the single mesh (psm_set_geometry), on the device: psm_bind_frames once, then one call per batch
+    _frames_bound = False
+    mesh_cells = None               # cells of the mesh the handle holds (set_mesh / Evaluation.computeOnlyOnce)
+
+    def set_mesh(self, vtx_m2g, wts_m2g, indices, sdfunct, n_cells: int, maxs=(1.0, 1.0, 1.0, 1.0)):
+        """The mesh -> grid tables of one mesh on the planned grid (psm_set_geometry without the grid -> mesh side): what
+        ``psm_mesh_to_grid`` and the frame entries read.  ``vtx_m2g`` / ``wts_m2g`` [Ny*Nx,3], ``indices`` [Ny*Nx,2] (row, column),
+        ``sdfunct`` [Ny,Nx].  Re-plans the grid, so every binding made before it is dropped."""
+        v, w = np.ascontiguousarray(vtx_m2g, np.int32), _f64(wts_m2g)
+        idx, sdf = np.ascontiguousarray(indices, np.int32), _f64(sdfunct)
+        npix = self.ny * self.nx
+        if v.shape != (npix, 3) or w.shape != (npix, 3) or idx.shape != (npix, 2) or sdf.size != npix:
+            raise ValueError(f"tables must be [{npix},3], [{npix},3], [{npix},2] and sdfunct [{self.ny},{self.nx}]")
+        mx = _f64(np.asarray(maxs, np.float64).reshape(-1)[:4])
+        self.mesh_cells = None
+        self._frames_bound = self._feat_bound = self._post_bound = False
+        self._bound_mask = self._bound_sdf = None
+        self._chk(self.lib.psm_set_geometry(self.h, int(n_cells), self.ny, self.nx, _p(v, C.c_int32), _p(w, C.c_double),
+                                            _p(idx, C.c_int32), _p(sdf, C.c_double), None, None, _p(mx, C.c_double), 1, 1, 0.05))
+        self.mesh_cells = int(n_cells)
+
+    def bind_frames(self, n_frames: int, k: int):
+        """Staging for ``n_frames`` (<= max_cases) frames of ``k`` (<= 16) cell columns on the handle's mesh: after it a batch
+        allocates nothing."""
+        self._frames_bound = False
+        self._chk(self.lib.psm_bind_frames(self.h, int(n_frames), int(k)))
+        self._frames_bound = True
+
+    def unbind_frames(self):
+        self._frames_bound = False
+        self._chk(self.lib.psm_unbind_frames(self.h))
+
+    def frames_to_grid_device(self, d_cols: int, n_frames: int, k: int, outs, fill: bool = True, stream: int = 0):
+        """interpolate_fill + last-writer scatter of ``k`` cell columns of ``n_frames`` frames in one launch, on raw device
+        pointers: ``d_cols`` [n,n_cells,k] float64; ``outs`` = one ``(device pointer or 0, frame_stride, as_f32)`` per column --
+        column c of frame f goes to plane ``pointer + f * frame_stride`` (elements) as float64, or float32 with ``as_f32``; 0: the
+        column is not stored.  Asynchronous on ``stream``."""
+        outs = list(outs)
+        if len(outs) != k:
+            raise ValueError("outs must hold one (pointer, frame_stride, as_f32) per column")
+        desc = (_lib.psm_frame_col * max(k, 1))()
+        for c, (ptr, stride, as_f32) in enumerate(outs):
+            desc[c].dst, desc[c].frame_stride, desc[c].as_f32 = (ptr or None), int(stride), int(bool(as_f32))
+        self._chk(self.lib.psm_frames_to_grid_device(self.h, C.c_void_p(d_cols), n_frames, k, int(bool(fill)), desc, C.c_void_p(stream)))
+
+    @staticmethod
+    def _frame_columns(k: int, weighting: bool) -> int:
+        """Number of extra columns of the evaluator's convention: (Ux, Uy, dUx, dUy), extra..., [dU-change weight, delta_p_prev]."""
+        if k < 4:
+            raise ValueError("frames need at least the 4 columns (Ux, Uy, dUx, dUy)")
+        if weighting and k < 6:
+            raise ValueError("with the weighting the last two of at least 6 columns are (dU-change weight, delta_p_prev)")
+        if k > 16:
+            raise ValueError("at most 16 columns")
+        return k - (6 if weighting else 4)
+
+    def poisson_frames_device(self, d_cols: int, n_frames: int, k: int, LU, d_result: int, apply_filter: bool = True,
+                              weighting: bool = True, d_extra: int = 0, d_change: int = 0, d_next: int = 0, stream: int = 0,
+                              out_scale: Optional[Sequence[float]] = None):
+        """The Poisson evaluator's frames as one graph replay on raw device pointers: ``d_cols`` [n,n_cells,k] float64 with columns
+        (Ux, Uy, dUx, dUy, extra..., [dU-change weight, delta_p_prev]) -> planes -> features -> solve -> post-steps -> result (and
+        change / next) [n,Ny,Nx]; the extra columns' float64 planes go to ``d_extra`` [n,n_extra,Ny*Nx] (0: not stored)."""
+        self._frame_columns(k, weighting)
+        lu = self._lu(LU, n_frames)
+        sc = _f32(np.broadcast_to(out_scale, (n_frames,))) if out_scale is not None else None
+        self._chk(self.lib.psm_poisson_frames_device(self.h, C.c_void_p(d_cols), n_frames, k, _p(lu, C.c_double),
+                                                     _p(sc, C.c_float) if sc is not None else None, int(bool(apply_filter)),
+                                                     int(bool(weighting)), C.c_void_p(d_extra or None), C.c_void_p(d_result),
+                                                     C.c_void_p(d_change or None), C.c_void_p(d_next or None), C.c_void_p(stream)))
+
+    def poisson_frames(self, cols: np.ndarray, LU, out_scale: Optional[Sequence[float]] = None, apply_filter: bool = False,
+                       weighting: bool = True, want_extra: bool = True):
+        """Host buffers, synchronous: ``cols`` [n,n_cells,k] (or [n_cells,k]) float64 -> (result [n,Ny,Nx,c_out], change, next,
+        extra); change and next [n,Ny,Nx] are None without the weighting, extra [n,n_extra,Ny,Nx] float64 (NaNs of
+        interpolate_fill kept) is None without ``want_extra`` or without extra columns."""
+        v = np.asarray(cols)
+        if v.ndim == 2:
+            v = v[None]
+        if v.ndim != 3:
+            raise ValueError("cols must be [n,n_cells,k]")
+        n, n_cells, k = v.shape
+        n_extra = self._frame_columns(k, weighting)
+        if self.mesh_cells is None:
+            raise RuntimeError("the handle holds no mesh (set_mesh / computeOnlyOnce)")
+        if n < 1 or n_cells != self.mesh_cells:
+            raise ValueError(f"cols must be [n >= 1, {self.mesh_cells} cells, k]")
+        lu = self._lu(LU, n)
+        if out_scale is not None and np.size(out_scale) not in (1, n):
+            raise ValueError("out_scale must hold one value per frame")
+        v = _f64(v)
+        result = np.empty((n, self.ny, self.nx, self.model.c_out), np.float32)
+        change = nxt = extra = None
+        if weighting:
+            change, nxt = np.empty((n, self.ny, self.nx), np.float32), np.empty((n, self.ny, self.nx), np.float32)
+        if want_extra and n_extra:
+            extra = np.empty((n, n_extra, self.ny, self.nx), np.float64)
+        sc = _f32(np.broadcast_to(np.asarray(out_scale, np.float32).reshape(-1), (n,))) if out_scale is not None else None
+        opt = lambda a, t=C.c_float: _p(a, t) if a is not None else None
+        self._chk(self.lib.psm_poisson_frames(self.h, _p(v, C.c_double), n, k, _p(lu, C.c_double), opt(sc), int(bool(apply_filter)),
+                                              int(bool(weighting)), opt(extra, C.c_double), _p(result, C.c_float), opt(change), opt(nxt)))
+        return result, change, nxt, extra
+
     # -- introspection
     def stage(self, name: str, n_cases: int = 1, layer: int = 0) -> np.ndarray:
         """An intermediate of the last solve; ``name='hidden'``: the output of hidden Dense layer ``layer`` (the handle must have
@@ -730,6 +832,7 @@ class Evaluation:
     variant = "deltas"
 
     c_in_expected, sdf_ch_expected = 3, 2
+    max_frames = 1                  # case slots of the surrogate (EvaluationPoisson: frames one timeSteps call sends at once)
 
     def __init__(self, delta, shape, overlap, var_p, var_in, dataset_path, model_path, max_num_PC,
                  standardization_method, model: SurrogateModel = None, device: int = 0, artifact_dir: str = None):
@@ -756,7 +859,7 @@ class Evaluation:
         if self._sur is None or (self._sur.ny, self._sur.nx) != (ny, nx):
             if self._sur is not None:
                 self._sur.close()
-            self._sur = GridSurrogate(self.artifacts, ny, nx, 1, self.device)
+            self._sur = GridSurrogate(self.artifacts, ny, nx, self.max_frames, self.device)
             self._sur.check_bound = True          # timeStep_grid takes arbitrary grids: a foreign geometry drops the binding
         return self._sur
 
@@ -780,6 +883,8 @@ class Evaluation:
         mx = _f64(np.asarray(self.maxs if self.maxs is not None else (1.0, 1.0, 1.0, 1.0), np.float64)[:4])
         sur._chk(sur.lib.psm_set_geometry(sur.h, int(self.indice), t.ny, t.nx, _p(v1, C.c_int32), _p(w1, C.c_double),
                                           _p(idx, C.c_int32), _p(sdf, C.c_double), None, None, _p(mx, C.c_double), 1, 1, 0.05))
+        sur.mesh_cells = int(self.indice)
+        sur._frames_bound = sur._feat_bound = sur._post_bound = False      # the new plan dropped them
         self.tables = t
         self._bind_simulation_geometry(sur, t.sdfunct, float(mx[2]))
         return 0
@@ -956,15 +1061,17 @@ def call_SM_main(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num
 
 def call_SM_main_Poisson(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num_PC, dataset_path,
                          plot_intermediate_fields, standardization_method, k, save_plots, show_plots, apply_filter, create_GIF,
-                         n_sims, n_ts, phis_fn, device: int = 0, artifact_dir: str = None, sim_offset: int = 1, time_offset: int = 16):
+                         n_sims, n_ts, phis_fn, device: int = 0, artifact_dir: str = None, sim_offset: int = 1, time_offset: int = 16,
+                         frames_per_call: int = 1):
     """``pressureSM_Poisson.SM_call.call_SM_main`` (pressureSM_Poisson/SM_call.py:1069-1170), same argument list: evaluates
     frames ``time_offset .. time_offset + n_ts`` of simulations ``sim_offset .. sim_offset + n_sims`` (the reference's
     ``sim += 1`` / ``time += 16``, :1095, :1104) with ``phi = phi_list[sim]`` from ``phis_fn`` and returns the three error
     summaries it prints -- delta-p with the deltaU-change weighting, delta-p without it, and p -- per simulation (last
-    ``n_ts`` frames, :1110-1116) and overall.  Plots and GIFs are not produced."""
+    ``n_ts`` frames, :1110-1116) and overall.  Plots and GIFs are not produced.  ``frames_per_call`` > 1: the frames of a
+    simulation go through ``EvaluationPoisson.timeSteps``, that many per call, instead of one ``timeStep`` each."""
     overlap = int(overlap_ratio * shape)
     ev = EvaluationPoisson(delta, shape, overlap, var_p, var_in, dataset_path, model_name, max_num_PC, standardization_method,
-                           k, phis_fn, device=device, artifact_dir=artifact_dir)
+                           k, phis_fn, device=device, artifact_dir=artifact_dir, max_frames=frames_per_call)
     for sfx in ("", "_deltap_crude", "_p"):
         setattr(ev, "pred_minus_true" + sfx, [])
         setattr(ev, "pred_minus_true_squared" + sfx, [])
@@ -975,7 +1082,9 @@ def call_SM_main_Poisson(delta, model_name, shape, overlap_ratio, var_p, var_in,
         ev.computeOnlyOnce(sim)
         phi = phi_list[sim]
         n0 = len(ev.pred_minus_true)
-        for time in range(n_ts):
+        if frames_per_call > 1:
+            ev.timeSteps(sim, [time + time_offset for time in range(n_ts)], apply_filter, phi)
+        for time in range(n_ts if frames_per_call == 1 else 0):
             ev.timeStep(sim, time + time_offset, plot_intermediate_fields, save_plots, show_plots, apply_filter, phi)
         if len(ev.pred_minus_true) > n0:
             out["sims"].append({"sim": sim, "phi": float(phi),
@@ -1029,9 +1138,12 @@ class EvaluationPoisson(Evaluation):
 
     def __init__(self, delta, shape, overlap, var_p, var_in, dataset_path, model_path, max_num_PC,
                  standardization_method, k, phis_fn, model: SurrogateModel = None, device: int = 0,
-                 max_abs=None, artifact_dir: str = None):
+                 max_abs=None, artifact_dir: str = None, max_frames: int = 1):
         super().__init__(delta, shape, overlap, var_p, var_in, dataset_path, model_path, max_num_PC,
                          standardization_method, model, device, artifact_dir)
+        if int(max_frames) < 1:
+            raise ValueError("max_frames must be at least 1")
+        self.max_frames = int(max_frames)                        # the surrogate's max_cases: frames one timeSteps call sends at once
         model = self.artifacts
         if model.c_in != 4 or model.sdf_ch != 3:
             raise ValueError("the Poisson surrogate takes 4 input channels with the SDF in channel 3")
@@ -1077,6 +1189,81 @@ class EvaluationPoisson(Evaluation):
         self._record_errors(self.deltap_res, self.cfd_results, self.no_flow_bool, "_deltap_crude", "Error in delta_p - no weighting")
         self._record_errors(self.p_pred, p_grid, self.no_flow_bool, "_p", "Error in p")
         return field_deltap
+
+    def _bind_simulation_geometry(self, sur, sdfunct: np.ndarray, max_abs_dist: float):
+        """One frame at a time: as the base class.  ``max_frames`` > 1: the simulation's obstacle in every one of the slots, with
+        the SDF channel as the features write it (float32 of sdfunct / max_abs_dist), so that a full batch takes the bound route."""
+        if self.max_frames == 1:
+            return super()._bind_simulation_geometry(sur, sdfunct, max_abs_dist)
+        g = np.zeros((self.max_frames, sur.ny, sur.nx, self.artifacts.c_in), np.float32)
+        sd = np.asarray(sdfunct, np.float64) / self.max_abs_dist
+        g[..., self.artifacts.sdf_ch] = np.where(np.isnan(sd), 0.0, sd).astype(np.float32)[None]
+        sur.bind_geometry(g)
+
+    FRAME_COLUMNS = 8               # Ux, Uy, dUx, dUy | delta_p, p (the label planes) | dU-change weight, delta_p_prev
+
+    def _bind_frames(self, sur):
+        """What timeSteps needs on the handle, once per computeOnlyOnce (whose new plan drops all three): the features with the
+        simulation's SDF plane in every slot, the post-steps (SM_call.py:353, :360) and the frame staging."""
+        if getattr(self, "_frames_tables", None) is self.tables and sur._frames_bound and sur._feat_bound and sur._post_bound:
+            return
+        sur.bind_features(np.repeat(np.asarray(self.sdfunct[..., 0], np.float64)[None], self.max_frames, axis=0), self.k,
+                          (self.max_abs_Poisson_term_1, self.max_abs_delta_Ux, self.max_abs_delta_Uy, self.max_abs_dist))
+        sur.bind_poststeps((10, 10), (50, 50))
+        sur.bind_frames(self.max_frames, self.FRAME_COLUMNS)
+        self._frames_tables = self.tables
+
+    def timeSteps(self, sim, times, apply_filter=False, phi=1.0):
+        """``timeStep`` for several frames of one simulation, the relevant ones sent ``max_frames`` at a time as ONE call each
+        (``poisson_frames``: cell columns -> planes -> features -> solve -> post-steps on the device).  The per-frame host scalars
+        and the three error blocks are those of ``timeStep``, in frame order; returns the list of ``field_deltap`` with 0 for an
+        irrelevant frame.  Afterwards the attributes hold what ``timeStep`` leaves on the last relevant frame, and
+        ``self.label_planes`` the interpolated (delta_p, p) planes [2,Ny,Nx] float64 of every frame (None: irrelevant)."""
+        from . import formats
+        if getattr(self, "tables", None) is None:
+            raise RuntimeError("computeOnlyOnce has not been called")
+        times = [int(t) for t in times]
+        out, cols, Us, slot = [0] * len(times), [], [], []
+        self.label_planes = [None] * len(times)
+        for i, time in enumerate(times):
+            data, _, _ = formats.read_dataset(self.dataset_path, sim, time)
+            d = data[0, 0, :self.indice]
+            Ux, Uy, p = d[:, 0:1], d[:, 1:2], d[:, 2:3]
+            delta_U, delta_p = d[:, 5:7], d[:, 7:8]
+            delta_U_prev, delta_p_prev = d[:, 8:10], d[:, 10:11]
+            deltaU_changed = np.abs(delta_U - delta_U_prev).sum(axis=-1)
+            deltaU_changed = deltaU_changed / deltaU_changed.max()
+            U_max_norm = np.max(np.sqrt(np.square(Ux) + np.square(Uy)))
+            deltaU_max_norm = np.max(np.sqrt(np.square(delta_U[:, 0:1]) + np.square(delta_U[:, 1:2])))
+            if (deltaU_max_norm / U_max_norm) < 1e-4 or deltaU_max_norm < 1e-6 or U_max_norm < 1e-6:      # :562-567
+                continue
+            cols.append(np.concatenate([Ux, Uy, delta_U, delta_p, p, deltaU_changed[:, None], delta_p_prev], axis=1).astype(np.float64))
+            Us.append(float(U_max_norm))
+            slot.append(i)
+        if not cols:
+            return out
+        sur = self._surrogate(self.grid_shape_y, self.grid_shape_x)
+        self._bind_frames(sur)
+        sd = np.nan_to_num(self.sdfunct[..., 0], nan=0.0) / self.max_abs_dist
+        for c0 in range(0, len(cols), self.max_frames):
+            chunk, U_chunk = np.stack(cols[c0:c0 + self.max_frames]), Us[c0:c0 + self.max_frames]
+            res, _, nxt, extra = sur.poisson_frames(chunk, [[phi, U] for U in U_chunk],
+                                                    out_scale=[self.max_abs_delta_p * U ** 2 for U in U_chunk],    # :816
+                                                    apply_filter=apply_filter, weighting=True, want_extra=True)
+            for j, U in enumerate(U_chunk):
+                field_deltap = nxt[j]
+                self.U_max_norm = U
+                self.deltap_res = res[j, :, :, 0]
+                delta_p_grid = np.nan_to_num(extra[j, 0] / pow(U, 2.0), nan=0.0) / self.max_abs_delta_p
+                p_grid = np.nan_to_num(extra[j, 1], nan=0.0)
+                self.cfd_results = delta_p_grid * self.max_abs_delta_p * pow(U, 2.0)
+                self.no_flow_bool = sd == 0
+                self.p_pred = (p_grid - self.cfd_results) + field_deltap
+                self._record_errors(field_deltap, self.cfd_results, self.no_flow_bool, "", "Error in delta_p")
+                self._record_errors(self.deltap_res, self.cfd_results, self.no_flow_bool, "_deltap_crude", "Error in delta_p - no weighting")
+                self._record_errors(self.p_pred, p_grid, self.no_flow_bool, "_p", "Error in p")
+                out[slot[c0 + j]], self.label_planes[slot[c0 + j]] = field_deltap, extra[j]
+        return out
 
     def build_features(self, ux_grid, uy_grid, delta_ux_grid, delta_uy_grid, sdfunct, phi, U_max_norm) -> np.ndarray:
         """SM_call.py:588-711 (after the interpolation to the grid): -> grid [Ny,Nx,4] float32."""
