@@ -498,6 +498,46 @@ int psm_poisson_frames(psm_handle* h, const double* cols, int32_t n_frames, int3
                        const float* out_scale, int32_t apply_filter, int32_t weighting, double* extra,
                        float* result, float* change, float* next);
 
+/* The per-frame error blocks of assembled fields on the device: what every evaluator of the reference prints per frame
+ * (pressureSM_Poisson/SM_call.py:962-1043; SM_call.py:696-724) as eight float64 sums per (frame, pair), so that a metrics-only
+ * sweep copies no field back.  raw[n_frames][n_pairs][8] = n, s1, s2 (count, sum, sum of squares of the non-NaN differences),
+ * tmin, tmax (truth over the flow cells), pmin, pmax (non-NaN effective prediction), tnan (NaN truths on flow cells).  Per pixel:
+ *     flow cell  iff  mask != 0 && mask == mask          (a NaN mask value is no flow: nan_to_num(sdfunct) / max_abs_dist == 0)
+ *     truth    = plane, NaN -> 0 with truth_nan_to_zero
+ *     pred_eff = (nan0(add) - nan0(sub)) + (double)pred  (add / sub: optional planes, ptr NULL = absent = 0)
+ *     d        = pred_eff - truth;  a NaN d is left out of n, s1, s2
+ * A plane is {ptr, frame_stride, elem_stride, as_f32}: pixel i of frame f is element ptr[f * frame_stride + i * elem_stride] of
+ * float64 or (as_f32) float32 -- an [npix][c_out] field has elem_stride c_out.  Two launches (csrc/psm_mesh.hip), no atomics, one
+ * fixed summation tree: raw is bit-reproducible from run to run; n = 0 leaves tmin = +inf, tmax = -inf.
+ * psm_field_errors_device: the stage alone on a PLANNED handle (ny * nx pixels per plane), device pointers, plain launches,
+ * asynchronous on `stream` (NULL: the handle's).  mask and pairs are HOST arrays that travel in the launch; the partial sums use
+ * scratch of the plan (max_cases x PSM_ERR_MAX_PAIRS rows): a call allocates nothing, and calls on one handle must be ordered
+ * by their streams.  PSM_ERR_ARG and nothing enqueued: a NULL or misaligned (8 / 4 bytes) mask, pred or truth plane, a misaligned
+ * add / sub, n_pairs outside [1, PSM_ERR_MAX_PAIRS], n_frames outside [1, max_cases], a negative stride, d_raw not 8-byte aligned. */
+#define PSM_ERR_MAX_PAIRS 4
+typedef struct { const void* ptr; int64_t frame_stride; int64_t elem_stride; int32_t as_f32; } psm_err_plane;   /* strides in elements */
+typedef struct { psm_err_plane pred, truth, add, sub; int32_t truth_nan_to_zero; } psm_err_pair;
+int psm_field_errors_device(psm_handle* h, const psm_err_plane* mask, const psm_err_pair* pairs, int32_t n_pairs,
+                            int32_t n_frames, double* d_raw, void* stream);
+/* psm_poisson_frames_device (the same graph replay, unchanged) and the stage behind it on the same stream, with the Poisson
+ * evaluator's three pairs, in this order: (next, nan0(extra 0)) = delta-p with the weighting, (result, nan0(extra 0)) = delta-p
+ * without it, (next + nan0(extra 1) - nan0(extra 0), nan0(extra 1)) = p; extra 0 / 1 are the delta-p and p label columns, the mask
+ * is the SDF plane of the feature binding.  d_raw [n_frames][3][8].  PSM_ERR_ARG and nothing enqueued: weighting == 0, k < 8 (no
+ * two label columns), d_raw NULL or not 8-byte aligned, d_extra / d_result / d_next NULL; otherwise the errors of
+ * psm_poisson_frames_device.  The device truth of delta-p is nan0(plane); the reference's nan_to_num(x / U^2) / m * m * U^2
+ * differs from it by at most 4 ulp per element. */
+int psm_poisson_frames_errors_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const double* LU,
+                                     const float* out_scale, int32_t apply_filter, int32_t weighting, double* d_extra,
+                                     float* d_result, float* d_change, float* d_next, double* d_raw, void* stream);
+/* host buffers, synchronous: one H2D of cols, the step, the stage, and a D2H of n_frames * 3 * 8 doubles -- fields, change and
+ * label planes stay in the handle's buffers.  Solves again on the general path after a guard trip, like psm_poisson_frames. */
+int psm_poisson_frames_errors(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, const double* LU,
+                              const float* out_scale, int32_t apply_filter, int32_t weighting, double* raw);
+/* Host arithmetic, no GPU and no handle: one raw row -> out[6] = normVal, biasNorm, stdeNorm, rmseNorm (percent), mean_err,
+ * mean_sq_err, as the reference computes them from the arrays: norm = tmax - tmin, NaN when tnan > 0 (np.max of a truth with a
+ * NaN); stde = sqrt(rmse^2 - bias^2), NaN when negative.  n == 0 (NumPy raises on the empty selection): out is all NaN, PSM_OK. */
+int psm_error_metrics_from_sums(const double raw[8], double out[6]);
+
 /* U_to_gradP: integrate the assembled (dp/dx, dp/dy) into p (integrate_field,
  * Eval_dual_Dense_onlycil.py:371-416, and the four-quadrant stitching :597-628).
  * psm_set_integration fixes the geometry: sdfunct [ny*nx] (self.sdfunct[:,:,0], also used by the

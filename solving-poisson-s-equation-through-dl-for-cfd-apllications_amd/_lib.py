@@ -47,6 +47,18 @@ class psm_frame_col(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("frame_stride", C.c_int64), ("as_f32", C.c_int32)]
 
 
+class psm_err_plane(C.Structure):
+    """One plane of psm_field_errors_device (psm.h): pixel i of frame f is element ptr[f * frame_stride + i * elem_stride]."""
+    _fields_ = [("ptr", C.c_void_p), ("frame_stride", C.c_int64), ("elem_stride", C.c_int64), ("as_f32", C.c_int32)]
+
+
+class psm_err_pair(C.Structure):
+    """One (prediction, truth) pair of psm_field_errors_device (psm.h)."""
+    _fields_ = [("pred", psm_err_plane), ("truth", psm_err_plane), ("add", psm_err_plane), ("sub", psm_err_plane),
+                ("truth_nan_to_zero", C.c_int32)]
+
+
+PSM_ERR_MAX_PAIRS = 4
 _f32p, _f64p, _i32p = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)
 _hp = C.c_void_p
 
@@ -126,6 +138,11 @@ SIGNATURES = {
     "psm_poisson_frames_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, C.c_int32, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "psm_poisson_frames": (C.c_int, [_hp, _f64p, C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, C.c_int32, _f64p, _f32p, _f32p, _f32p]),
+    "psm_field_errors_device": (C.c_int, [_hp, C.POINTER(psm_err_plane), C.POINTER(psm_err_pair), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "psm_poisson_frames_errors_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, C.c_int32, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_poisson_frames_errors": (C.c_int, [_hp, _f64p, C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, C.c_int32, _f64p]),
+    "psm_error_metrics_from_sums": (C.c_int, [_f64p, _f64p]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
     "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),

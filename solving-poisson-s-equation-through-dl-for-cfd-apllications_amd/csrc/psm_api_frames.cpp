@@ -14,10 +14,11 @@ static void drop_frame_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphK
 void frames_free(psm_handle* h) {
   FrameSet& s = h->frames;
   drop_frame_graphs(h);
-  dev_free(s.d_cols); dev_free(s.d_extra);
+  dev_free(s.d_cols); dev_free(s.d_extra); dev_free(s.d_raw);
   if (s.h_cols) { (void)hipHostFree(s.h_cols); s.h_cols = nullptr; }
   if (s.h_extra) { (void)hipHostFree(s.h_extra); s.h_extra = nullptr; }
   if (s.h_out) { (void)hipHostFree(s.h_out); s.h_out = nullptr; }
+  if (s.h_raw) { (void)hipHostFree(s.h_raw); s.h_raw = nullptr; }
   s.ready = false; s.n_frames = 0; s.k = 0;
 }
 
@@ -47,7 +48,7 @@ static int frames_count_check(psm_handle* h, int n_frames) {
 
 // The evaluator's column convention as plane descriptors: 0-3 -> the feature binding's velocity planes, the last two (weighting) ->
 // the post-steps' dU / prev as float32, the columns between -> d_extra (nullptr: not stored).
-static int poisson_frame_call(psm_handle* h, const double* d_cols, int n_frames, int k, int weighting, double* d_extra, FrameCall& fc) {
+int poisson_frame_call(psm_handle* h, const double* d_cols, int n_frames, int k, int weighting, double* d_extra, FrameCall& fc) {
   int rc = frames_state(h);
   if (rc) return rc;
   if (!h->feat.ready) return fail(h, PSM_ERR_STATE, "psm_bind_features has not been called: the frames step needs it as well as psm_bind_frames");
@@ -89,10 +90,12 @@ int psm_bind_frames(psm_handle* h, int32_t n_frames, int32_t k) {
   const size_t npix = (size_t)h->Ny * h->Nx, n = (size_t)n_frames;
   const size_t n_cols = n * (size_t)h->n_cells * k, n_extra = n * (size_t)k * npix, n_out = n * npix * ((size_t)h->cfg.c_out + 2);
   int rc;
-  if ((rc = dev_alloc(h, &s.d_cols, n_cols)) || (rc = dev_alloc(h, &s.d_extra, n_extra))) { frames_free(h); return rc; }
+  const size_t n_raw = n * 3 * PSM_ERR_RAW;             // psm_poisson_frames_errors: the three error blocks of every frame
+  if ((rc = dev_alloc(h, &s.d_cols, n_cols)) || (rc = dev_alloc(h, &s.d_extra, n_extra)) || (rc = dev_alloc(h, &s.d_raw, n_raw))) { frames_free(h); return rc; }
   hipError_t e = hipHostMalloc((void**)&s.h_cols, n_cols * sizeof(double), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_extra, n_extra * sizeof(double), hipHostMallocDefault);
   if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_out, n_out * sizeof(float), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_raw, n_raw * sizeof(double), hipHostMallocDefault);
   if (e != hipSuccess) { frames_free(h); return fail(h, PSM_ERR_NOMEM, std::string("psm_bind_frames: ") + hipGetErrorString(e)); }
   s.n_frames = n_frames; s.k = k;
   s.ready = true;

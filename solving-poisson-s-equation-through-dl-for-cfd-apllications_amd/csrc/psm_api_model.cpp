@@ -111,7 +111,7 @@ void free_plan(psm_handle* h) {
   h->d_keep.clear();
   dev_free(h->d_row_base); dev_free(h->d_ones); dev_free(h->d_strips);
   dev_free(h->d_blk); dev_free(h->d_owner); dev_free(h->d_shiftA); dev_free(h->d_shiftB); dev_free(h->d_shiftOwnA); dev_free(h->d_shiftOwnB); dev_free(h->d_shiftW); dev_free(h->d_blocks);
-  dev_free(h->d_stamps); dev_free(h->d_grid_stage); dev_free(h->d_fields_stage);
+  dev_free(h->d_stamps); dev_free(h->d_err_part); dev_free(h->d_grid_stage); dev_free(h->d_fields_stage);
   if (h->h_grid) { (void)hipHostFree(h->h_grid); h->h_grid = nullptr; }
   if (h->h_fields) { (void)hipHostFree(h->h_fields); h->h_fields = nullptr; }
   h->planned = false;

@@ -311,6 +311,7 @@ int psm_plan_grid(psm_handle* h, int32_t ny, int32_t nx) {
   }
   if ((rc = dev_alloc(h, &h->d_stamps, (size_t)16))) return rc;
   HIPCHK(h, hipMemset(h->d_stamps, 0, 16 * sizeof(unsigned long long)));
+  if ((rc = dev_alloc(h, &h->d_err_part, (size_t)h->cfg.max_cases * PSM_FIELD_ERR_MAX_PAIRS * psm_field_error_workgroups((int64_t)npix) * 8))) return rc;
   if ((rc = dev_alloc(h, &h->d_grid_stage, (size_t)h->cfg.max_cases * npix * h->cfg.c_in))) return rc;
   if ((rc = dev_alloc(h, &h->d_fields_stage, (size_t)h->cfg.max_cases * npix * h->cfg.c_out))) return rc;
   HIPCHK(h, hipHostMalloc((void**)&h->h_grid, (size_t)h->cfg.max_cases * npix * h->cfg.c_in * sizeof(float), hipHostMallocDefault));

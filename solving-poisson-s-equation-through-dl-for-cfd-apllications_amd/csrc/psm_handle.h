@@ -1,5 +1,5 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in nine files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in ten files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, graph capture and key, psm_solve_grid*
@@ -8,6 +8,7 @@
 //   psm_api_filter.cpp      the Gaussian post-steps: psm_gaussian_filter (host entry), psm_bind_poststeps and the device-resident / case-batched entries
 //   psm_api_features.cpp    the pressureSM_Poisson input features on the device: psm_bind_features, psm_features_device and the whole step psm_poisson_step*
 //   psm_api_frames.cpp      frames of cell columns -> planes on the device: psm_bind_frames, psm_frames_to_grid_device and the evaluator's step psm_poisson_frames*
+//   psm_api_errors.cpp      the per-frame error blocks of assembled fields on the device: psm_field_errors_device and the metrics-only frame step psm_poisson_frames_errors* (host arithmetic: psm_errors.cpp)
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -35,6 +36,7 @@
 #include "psm_mesh.h"
 #include "psm_plan.h"
 #include "psm_fold.h"
+#include "psm_errors.h"
 
 namespace psm_impl __attribute__((visibility("hidden"))) {
 extern thread_local std::string g_create_error;   // message of the last failed psm_create (psm_api_model.cpp)
@@ -226,6 +228,7 @@ struct FrameSet {
   double* d_extra = nullptr;            // [n_frames][k][npix]: the float64 planes of the columns between the velocities and the weighting pair
   double *h_cols = nullptr, *h_extra = nullptr;   // pinned copies of the two
   float* h_out = nullptr;               // pinned [n_frames][npix][c_out + 2]: result, change, next
+  double *d_raw = nullptr, *h_raw = nullptr;   // psm_poisson_frames_errors: [n_frames][3][8] sums, device and pinned
 };
 }  // namespace psm_impl
 using namespace psm_impl;
@@ -255,6 +258,7 @@ struct psm_handle {
   PsmBlock* d_blocks = nullptr;
   int n_bands = 0;
   unsigned long long* d_stamps = nullptr;
+  double* d_err_part = nullptr;         // partials of psm_field_errors_device: [max_cases][PSM_FIELD_ERR_MAX_PAIRS][workgroups][8], sized by the plan
   // mesh-side tables (psm_set_geometry)
   bool have_geometry = false, have_g2m = false;
   int64_t n_cells = 0;
@@ -413,6 +417,8 @@ int post_check(psm_handle* h, int n_cases, const PostCall& pc);
 void feat_free(FeatureSet& s);
 void frames_free(psm_handle* h);
 int frames_device(psm_handle* h, const FrameCall& fc, int n_frames, hipStream_t st);
+int poisson_frame_call(psm_handle* h, const double* d_cols, int n_frames, int k, int weighting, double* d_extra, FrameCall& fc);
+int field_errors_device(psm_handle* h, const PsmFieldErrorArgs& stage, double* d_raw, hipStream_t st);
 int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const double* LU, const float* out_scale, const PostCall& pc,
                         hipStream_t st, const FrameCall* frames = nullptr);
 int features_device(psm_handle* h, const double* d_vel, int n_cases, float* d_grid, hipStream_t st);

@@ -502,3 +502,128 @@ hipError_t psm_launch_block_error(const float* grid, const float* pred, const fl
   hipLaunchKernelGGL(psm_block_error_kernel, dim3(B), dim3(256), 0, st, grid, pred, label_blocks, row_scale, blk_y0x0, part, S, c_in, c_out, sdf_ch, Nx);
   return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------
+// The same eight sums for ASSEMBLED fields (psm_field_errors_device; PsmFieldErrorArgs in psm_mesh.h): the three error blocks the
+// Poisson evaluator prints per frame (pressureSM_Poisson/SM_call.py:962-1043) without the fields leaving the device.  HBM-bound:
+// a pair reads up to five planes once.  Launch 1, grid (workgroups over pixels, pair, frame): a thread takes 4 consecutive pixels
+// per round -- one 16-byte load per float32 plane, two per float64 plane where the frame's plane is dense and 16-byte aligned,
+// else one load per pixel (result [npix][c_out], odd plane offsets, the tail) --, sums in float64 like the reference's arrays,
+// then wave shuffle -> LDS -> 8 doubles per workgroup.  Launch 2 folds a row of partials.  No atomics; pixel -> thread -> lane ->
+// wave -> workgroup is a fixed tree, the same on either load path: a result depends on the inputs alone, bit for bit.
+typedef float psm_f4 __attribute__((ext_vector_type(4)));
+
+struct PsmErrSrc { const char* base; int64_t es; bool f32, dense; };   // one frame's plane (base == nullptr: absent)
+
+__device__ __forceinline__ PsmErrSrc err_src(const PsmErrPlane& p, int64_t frame) {
+  PsmErrSrc s;
+  s.f32 = p.as_f32 != 0; s.es = p.elem_stride;
+  s.base = p.ptr ? static_cast<const char*>(p.ptr) + frame * p.frame_stride * (s.f32 ? 4 : 8) : nullptr;
+  s.dense = s.base && s.es == 1 && (reinterpret_cast<uintptr_t>(s.base) & 15) == 0;
+  return s;
+}
+
+// pixels pix .. pix + 3 (pix a multiple of 4) as doubles; a pixel beyond the image or of an absent plane reads as 0
+__device__ __forceinline__ void err_load4(const PsmErrSrc& s, int64_t pix, int64_t npix, double (&v)[4]) {
+  v[0] = v[1] = v[2] = v[3] = 0.0;
+  if (!s.base) return;
+  if (s.dense && pix + 3 < npix) {
+    if (s.f32) {
+      const psm_f4 q = *reinterpret_cast<const psm_f4*>(s.base + pix * 4);
+      v[0] = (double)q.x; v[1] = (double)q.y; v[2] = (double)q.z; v[3] = (double)q.w;
+    } else {
+      const psm_d2 q0 = *reinterpret_cast<const psm_d2*>(s.base + pix * 8), q1 = *reinterpret_cast<const psm_d2*>(s.base + pix * 8 + 16);
+      v[0] = q0.x; v[1] = q0.y; v[2] = q1.x; v[3] = q1.y;
+    }
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (pix + e >= npix) continue;
+    const int64_t at = (pix + e) * s.es;
+    v[e] = s.f32 ? (double)reinterpret_cast<const float*>(s.base)[at] : reinterpret_cast<const double*>(s.base)[at];
+  }
+}
+
+__device__ __forceinline__ double nan0(double x) { return x != x ? 0.0 : x; }
+
+__global__ __launch_bounds__(256) void psm_block_error_kernel(PsmFieldErrorArgs a) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, pi = blockIdx.y;
+  const int64_t frame = blockIdx.z;
+  const PsmFieldErrorPair& pr = a.pair[pi];
+  const PsmErrSrc mask = err_src(a.mask, frame), pred = err_src(pr.pred, frame), truth = err_src(pr.truth, frame),
+                  add = err_src(pr.add, frame), sub = err_src(pr.sub, frame);
+  const bool t0 = pr.truth_nan_to_zero != 0;
+  double n = 0.0, s1 = 0.0, s2 = 0.0, tmin = INFINITY, tmax = -INFINITY, pmin = INFINITY, pmax = -INFINITY, tnan = 0.0;
+#pragma unroll
+  for (int j = 0; j < PSM_FIELD_ERR_SPAN / 1024; ++j) {
+    const int64_t pix = (int64_t)blockIdx.x * PSM_FIELD_ERR_SPAN + j * 1024 + t * 4;
+    if (pix >= a.npix) continue;
+    double m[4], p[4], tr[4], ad[4], sb[4];
+    err_load4(mask, pix, a.npix, m); err_load4(pred, pix, a.npix, p); err_load4(truth, pix, a.npix, tr);
+    err_load4(add, pix, a.npix, ad); err_load4(sub, pix, a.npix, sb);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (!(m[e] != 0.0 && m[e] == m[e])) continue;          // no flow, and every pixel beyond the image (its mask read as 0)
+      const double tv = t0 ? nan0(tr[e]) : tr[e];
+      const double pe = (nan0(ad[e]) - nan0(sb[e])) + p[e];
+      if (tv != tv) tnan += 1.0; else { tmin = fmin(tmin, tv); tmax = fmax(tmax, tv); }
+      if (pe == pe) { pmin = fmin(pmin, pe); pmax = fmax(pmax, pe); }
+      const double d = pe - tv;
+      if (d == d) { n += 1.0; s1 += d; s2 += d * d; }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n += __shfl_down(n, o, 64); s1 += __shfl_down(s1, o, 64); s2 += __shfl_down(s2, o, 64); tnan += __shfl_down(tnan, o, 64);
+    tmin = fmin(tmin, __shfl_down(tmin, o, 64)); tmax = fmax(tmax, __shfl_down(tmax, o, 64));
+    pmin = fmin(pmin, __shfl_down(pmin, o, 64)); pmax = fmax(pmax, __shfl_down(pmax, o, 64));
+  }
+  __shared__ double red[4][8];
+  if (lane == 0) {
+    double* r = red[wave];
+    r[0] = n; r[1] = s1; r[2] = s2; r[3] = tmin; r[4] = tmax; r[5] = pmin; r[6] = pmax; r[7] = tnan;
+  }
+  __syncthreads();
+  if (t < 8) {
+    double r = red[0][t];
+    for (int w = 1; w < 4; ++w) r = (t == 3 || t == 5) ? fmin(r, red[w][t]) : (t == 4 || t == 6) ? fmax(r, red[w][t]) : r + red[w][t];
+    a.part[((frame * a.n_pairs + pi) * a.n_wg + blockIdx.x) * 8 + t] = r;
+  }
+}
+
+// one wave per (pair, frame): lane l folds partials l, l + 64, ... in order, then the same shuffle tree
+__global__ __launch_bounds__(64) void psm_block_error_kernel(PsmFieldErrorFinalArgs a) {
+  const int lane = threadIdx.x;
+  const int64_t row = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;        // frame * n_pairs + pair
+  const double* part = a.part + row * a.n_wg * 8;
+  double n = 0.0, s1 = 0.0, s2 = 0.0, tmin = INFINITY, tmax = -INFINITY, pmin = INFINITY, pmax = -INFINITY, tnan = 0.0;
+  for (int w = lane; w < a.n_wg; w += 64) {
+    const double* q = part + (int64_t)w * 8;
+    n += q[0]; s1 += q[1]; s2 += q[2]; tnan += q[7];
+    tmin = fmin(tmin, q[3]); tmax = fmax(tmax, q[4]); pmin = fmin(pmin, q[5]); pmax = fmax(pmax, q[6]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    n += __shfl_down(n, o, 64); s1 += __shfl_down(s1, o, 64); s2 += __shfl_down(s2, o, 64); tnan += __shfl_down(tnan, o, 64);
+    tmin = fmin(tmin, __shfl_down(tmin, o, 64)); tmax = fmax(tmax, __shfl_down(tmax, o, 64));
+    pmin = fmin(pmin, __shfl_down(pmin, o, 64)); pmax = fmax(pmax, __shfl_down(pmax, o, 64));
+  }
+  if (lane == 0) {
+    double* r = a.raw + row * 8;
+    r[0] = n; r[1] = s1; r[2] = s2; r[3] = tmin; r[4] = tmax; r[5] = pmin; r[6] = pmax; r[7] = tnan;
+  }
+}
+
+hipError_t psm_launch_field_errors(const PsmFieldErrorArgs& a, hipStream_t st) {
+  if (a.npix < 1 || a.n_pairs < 1 || a.n_pairs > PSM_FIELD_ERR_MAX_PAIRS || a.n_frames < 1 || a.n_wg != psm_field_error_workgroups(a.npix) || !a.part)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmFieldErrorArgs)>(psm_block_error_kernel), dim3((unsigned)a.n_wg, (unsigned)a.n_pairs, (unsigned)a.n_frames),
+                     dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_field_errors_final(const PsmFieldErrorFinalArgs& a, int n_pairs, int n_frames, hipStream_t st) {
+  if (n_pairs < 1 || n_frames < 1 || a.n_wg < 1 || !a.part || !a.raw) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmFieldErrorFinalArgs)>(psm_block_error_kernel), dim3((unsigned)n_pairs, (unsigned)n_frames), dim3(64), 0, st, a);
+  return hipGetLastError();
+}

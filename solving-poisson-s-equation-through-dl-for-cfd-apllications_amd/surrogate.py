@@ -672,6 +672,109 @@ class GridSurrogate:
                                               int(bool(weighting)), opt(extra, C.c_double), _p(result, C.c_float), opt(change), opt(nxt)))
         return result, change, nxt, extra
 
+    # -- the per-frame error blocks of assembled fields on the device: eight float64 sums per (frame, pair) instead of the fields
+    RAW_SUMS = ("n", "s1", "s2", "tmin", "tmax", "pmin", "pmax", "tnan")
+    METRICS = ("normVal", "biasNorm", "stdeNorm", "rmseNorm", "mean_err", "mean_sq_err")
+
+    @staticmethod
+    def _err_plane(desc, what: str, optional: bool = False):
+        """``(device pointer, frame_stride, elem_stride, as_f32)`` -> psm_err_plane; None (or pointer 0) where ``optional``: absent."""
+        out = _lib.psm_err_plane()
+        if desc is None or not desc[0]:
+            if not optional:
+                raise ValueError(f"{what}: a plane (pointer, frame_stride, elem_stride, as_f32) is needed")
+            return out
+        ptr, frame_stride, elem_stride, as_f32 = desc
+        if int(frame_stride) < 0 or int(elem_stride) < 0:
+            raise ValueError(f"{what}: strides must not be negative")
+        if int(ptr) % (4 if as_f32 else 8):
+            raise ValueError(f"{what}: the plane is not aligned to its element")
+        out.ptr, out.frame_stride, out.elem_stride, out.as_f32 = int(ptr), int(frame_stride), int(elem_stride), int(bool(as_f32))
+        return out
+
+    def field_errors_device(self, mask, pairs, n_frames: int, d_raw: int, stream: int = 0):
+        """The error sums of up to four (prediction, truth) pairs over ``n_frames`` frames of planes on the planned grid, on raw
+        device pointers, asynchronous on ``stream``: ``d_raw`` [n_frames][len(pairs)][8] float64 = ``RAW_SUMS``.  A plane is
+        ``(pointer, frame_stride, elem_stride, as_f32)`` with strides in elements; ``mask``: flow cell iff != 0 and not NaN;
+        a pair is ``(pred, truth, add, sub, truth_nan_to_zero)``, ``add`` / ``sub`` may be None:
+        d = ((nan0(add) - nan0(sub)) + pred) - truth over the flow cells, NaN d left out."""
+        pairs = list(pairs)
+        if not 1 <= len(pairs) <= _lib.PSM_ERR_MAX_PAIRS:
+            raise ValueError(f"1..{_lib.PSM_ERR_MAX_PAIRS} pairs")
+        if not 1 <= int(n_frames) <= self.max_cases:
+            raise ValueError("n_frames outside [1, max_cases]")
+        if not d_raw or int(d_raw) % 8:
+            raise ValueError("d_raw must be an 8-byte aligned device pointer")
+        m = self._err_plane(mask, "mask")
+        desc = (_lib.psm_err_pair * len(pairs))()
+        for i, pair in enumerate(pairs):
+            if len(pair) != 5:
+                raise ValueError("a pair is (pred, truth, add, sub, truth_nan_to_zero)")
+            desc[i].pred, desc[i].truth = self._err_plane(pair[0], f"pair {i} pred"), self._err_plane(pair[1], f"pair {i} truth")
+            desc[i].add, desc[i].sub = self._err_plane(pair[2], f"pair {i} add", True), self._err_plane(pair[3], f"pair {i} sub", True)
+            desc[i].truth_nan_to_zero = int(bool(pair[4]))
+        self._chk(self.lib.psm_field_errors_device(self.h, C.byref(m), desc, len(pairs), int(n_frames), C.c_void_p(d_raw), C.c_void_p(stream)))
+
+    def poisson_frames_errors_device(self, d_cols: int, n_frames: int, k: int, LU, d_extra: int, d_result: int, d_next: int, d_raw: int,
+                                     apply_filter: bool = True, d_change: int = 0, stream: int = 0,
+                                     out_scale: Optional[Sequence[float]] = None):
+        """``poisson_frames_device`` with the weighting (the same graph replay) and, behind it on the same stream, the evaluator's
+        three error blocks of every frame: ``d_raw`` [n][3][8] float64 -- delta-p with the weighting, delta-p without it, p -- from
+        next, result and the two label planes (columns 4 and 5) in ``d_extra``; the mask is the bound SDF plane."""
+        if self._frame_columns(k, True) < 2:
+            raise ValueError("the error blocks need the two label columns (delta_p, p): at least 8 columns")
+        if not (d_extra and d_result and d_next):
+            raise ValueError("the error blocks read d_extra, d_result and d_next: none of them may be 0")
+        if not d_raw or int(d_raw) % 8:
+            raise ValueError("d_raw must be an 8-byte aligned device pointer")
+        lu = self._lu(LU, n_frames)
+        sc = _f32(np.broadcast_to(out_scale, (n_frames,))) if out_scale is not None else None
+        self._chk(self.lib.psm_poisson_frames_errors_device(self.h, C.c_void_p(d_cols), n_frames, k, _p(lu, C.c_double),
+                                                            _p(sc, C.c_float) if sc is not None else None, int(bool(apply_filter)), 1,
+                                                            C.c_void_p(d_extra), C.c_void_p(d_result), C.c_void_p(d_change or None),
+                                                            C.c_void_p(d_next), C.c_void_p(d_raw), C.c_void_p(stream)))
+
+    def poisson_frames_errors(self, cols: np.ndarray, LU, out_scale: Optional[Sequence[float]] = None,
+                              apply_filter: bool = False) -> np.ndarray:
+        """Host buffers, synchronous: ``cols`` [n,n_cells,k >= 8] (or [n_cells,k]) float64 -> raw [n,3,8] float64, the sums of
+        the three error blocks per frame (``metrics_from_sums`` turns a row into the metrics).  Nothing else comes back: the
+        fields and label planes stay on the device."""
+        v = np.asarray(cols)
+        if v.ndim == 2:
+            v = v[None]
+        if v.ndim != 3:
+            raise ValueError("cols must be [n,n_cells,k]")
+        n, n_cells, k = v.shape
+        if self._frame_columns(k, True) < 2:
+            raise ValueError("the error blocks need the two label columns (delta_p, p): at least 8 columns")
+        if self.mesh_cells is None:
+            raise RuntimeError("the handle holds no mesh (set_mesh / computeOnlyOnce)")
+        if n < 1 or n_cells != self.mesh_cells:
+            raise ValueError(f"cols must be [n >= 1, {self.mesh_cells} cells, k]")
+        lu = self._lu(LU, n)
+        if out_scale is not None and np.size(out_scale) not in (1, n):
+            raise ValueError("out_scale must hold one value per frame")
+        v = _f64(v)
+        raw = np.empty((n, 3, len(self.RAW_SUMS)), np.float64)
+        sc = _f32(np.broadcast_to(np.asarray(out_scale, np.float32).reshape(-1), (n,))) if out_scale is not None else None
+        self._chk(self.lib.psm_poisson_frames_errors(self.h, _p(v, C.c_double), n, k, _p(lu, C.c_double),
+                                                     _p(sc, C.c_float) if sc is not None else None, int(bool(apply_filter)), 1,
+                                                     _p(raw, C.c_double)))
+        return raw
+
+    @classmethod
+    def metrics_from_sums(cls, raw) -> dict:
+        """One row of raw sums -> the dict of ``error_metrics`` (psm_error_metrics_from_sums: host arithmetic, no GPU).  ValueError
+        when no finite difference was counted (n == 0), where NumPy raises on the empty selection."""
+        r = _f64(np.asarray(raw, np.float64).reshape(-1))
+        if r.size != len(cls.RAW_SUMS):
+            raise ValueError(f"a raw row holds {len(cls.RAW_SUMS)} sums: {', '.join(cls.RAW_SUMS)}")
+        if not r[0] > 0:
+            raise ValueError("no finite difference over the flow cells (n == 0): the metrics are undefined")
+        out = np.empty(len(cls.METRICS), np.float64)
+        _lib.check(_lib.load().psm_error_metrics_from_sums(_p(r, C.c_double), _p(out, C.c_double)))
+        return {key: float(v) for key, v in zip(cls.METRICS, out)}
+
     # -- introspection
     def stage(self, name: str, n_cases: int = 1, layer: int = 0) -> np.ndarray:
         """An intermediate of the last solve; ``name='hidden'``: the output of hidden Dense layer ``layer`` (the handle must have
@@ -962,7 +1065,10 @@ class Evaluation:
         """SM_call.py:696-724: normalised bias / squared error of the assembled field over the flow cells, appended to
         ``pred_minus_true<suffix>`` / ``pred_minus_true_squared<suffix>`` (what the mains average); the frame's
         normVal / biasNorm / stdeNorm / rmseNorm are kept in ``self.last_metrics[suffix or 'delta_p']``."""
-        m = error_metrics(field, truth, no_flow_bool)
+        return self._record_metrics(error_metrics(field, truth, no_flow_bool), suffix, title)
+
+    def _record_metrics(self, m: dict, suffix: str = "", title: str = None):
+        """The bookkeeping of ``_record_errors`` for metrics that exist already (``timeSteps(fields=False)``: from device sums)."""
         for name in ("pred_minus_true" + suffix, "pred_minus_true_squared" + suffix):
             if not hasattr(self, name):
                 setattr(self, name, [])
@@ -1062,13 +1168,14 @@ def call_SM_main(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num
 def call_SM_main_Poisson(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num_PC, dataset_path,
                          plot_intermediate_fields, standardization_method, k, save_plots, show_plots, apply_filter, create_GIF,
                          n_sims, n_ts, phis_fn, device: int = 0, artifact_dir: str = None, sim_offset: int = 1, time_offset: int = 16,
-                         frames_per_call: int = 1):
+                         frames_per_call: int = 1, fields: bool = True):
     """``pressureSM_Poisson.SM_call.call_SM_main`` (pressureSM_Poisson/SM_call.py:1069-1170), same argument list: evaluates
     frames ``time_offset .. time_offset + n_ts`` of simulations ``sim_offset .. sim_offset + n_sims`` (the reference's
     ``sim += 1`` / ``time += 16``, :1095, :1104) with ``phi = phi_list[sim]`` from ``phis_fn`` and returns the three error
     summaries it prints -- delta-p with the deltaU-change weighting, delta-p without it, and p -- per simulation (last
     ``n_ts`` frames, :1110-1116) and overall.  Plots and GIFs are not produced.  ``frames_per_call`` > 1: the frames of a
-    simulation go through ``EvaluationPoisson.timeSteps``, that many per call, instead of one ``timeStep`` each."""
+    simulation go through ``EvaluationPoisson.timeSteps``, that many per call, instead of one ``timeStep`` each.  ``fields=False``:
+    the same summaries from ``timeSteps(..., fields=False)``, whose error sums are taken on the device: no field is copied back."""
     overlap = int(overlap_ratio * shape)
     ev = EvaluationPoisson(delta, shape, overlap, var_p, var_in, dataset_path, model_name, max_num_PC, standardization_method,
                            k, phis_fn, device=device, artifact_dir=artifact_dir, max_frames=frames_per_call)
@@ -1082,9 +1189,10 @@ def call_SM_main_Poisson(delta, model_name, shape, overlap_ratio, var_p, var_in,
         ev.computeOnlyOnce(sim)
         phi = phi_list[sim]
         n0 = len(ev.pred_minus_true)
-        if frames_per_call > 1:
-            ev.timeSteps(sim, [time + time_offset for time in range(n_ts)], apply_filter, phi)
-        for time in range(n_ts if frames_per_call == 1 else 0):
+        batched = frames_per_call > 1 or not fields
+        if batched:
+            ev.timeSteps(sim, [time + time_offset for time in range(n_ts)], apply_filter, phi, fields=fields)
+        for time in range(0 if batched else n_ts):
             ev.timeStep(sim, time + time_offset, plot_intermediate_fields, save_plots, show_plots, apply_filter, phi)
         if len(ev.pred_minus_true) > n0:
             out["sims"].append({"sim": sim, "phi": float(phi),
@@ -1213,12 +1321,19 @@ class EvaluationPoisson(Evaluation):
         sur.bind_frames(self.max_frames, self.FRAME_COLUMNS)
         self._frames_tables = self.tables
 
-    def timeSteps(self, sim, times, apply_filter=False, phi=1.0):
+    ERROR_BLOCKS = (("", "Error in delta_p"), ("_deltap_crude", "Error in delta_p - no weighting"), ("_p", "Error in p"))
+
+    def timeSteps(self, sim, times, apply_filter=False, phi=1.0, fields=True):
         """``timeStep`` for several frames of one simulation, the relevant ones sent ``max_frames`` at a time as ONE call each
         (``poisson_frames``: cell columns -> planes -> features -> solve -> post-steps on the device).  The per-frame host scalars
         and the three error blocks are those of ``timeStep``, in frame order; returns the list of ``field_deltap`` with 0 for an
         irrelevant frame.  Afterwards the attributes hold what ``timeStep`` leaves on the last relevant frame, and
-        ``self.label_planes`` the interpolated (delta_p, p) planes [2,Ny,Nx] float64 of every frame (None: irrelevant)."""
+        ``self.label_planes`` the interpolated (delta_p, p) planes [2,Ny,Nx] float64 of every frame (None: irrelevant).
+        ``fields=False``: a metrics-only sweep -- the chunks go through ``poisson_frames_errors``, which brings back the sums of the
+        three error blocks and no field; the six lists and ``last_metrics`` are filled as above, the return is one
+        ``{suffix: metrics}`` dict per frame ('' / '_deltap_crude' / '_p'; 0 for an irrelevant frame), and ``deltap_res``,
+        ``cfd_results``, ``p_pred`` and ``label_planes`` are None.  The device takes nan0(label plane) as the delta-p truth where the
+        host chain writes nan_to_num(x / U^2) / m * m * U^2: at most 4 ulp per element apart."""
         from . import formats
         if getattr(self, "tables", None) is None:
             raise RuntimeError("computeOnlyOnce has not been called")
@@ -1247,6 +1362,14 @@ class EvaluationPoisson(Evaluation):
         sd = np.nan_to_num(self.sdfunct[..., 0], nan=0.0) / self.max_abs_dist
         for c0 in range(0, len(cols), self.max_frames):
             chunk, U_chunk = np.stack(cols[c0:c0 + self.max_frames]), Us[c0:c0 + self.max_frames]
+            if not fields:
+                raw = sur.poisson_frames_errors(chunk, [[phi, U] for U in U_chunk],
+                                                out_scale=[self.max_abs_delta_p * U ** 2 for U in U_chunk], apply_filter=apply_filter)
+                for j, U in enumerate(U_chunk):
+                    self.U_max_norm = U
+                    out[slot[c0 + j]] = {sfx: self._record_metrics(sur.metrics_from_sums(raw[j, q]), sfx, title)
+                                         for q, (sfx, title) in enumerate(self.ERROR_BLOCKS)}
+                continue
             res, _, nxt, extra = sur.poisson_frames(chunk, [[phi, U] for U in U_chunk],
                                                     out_scale=[self.max_abs_delta_p * U ** 2 for U in U_chunk],    # :816
                                                     apply_filter=apply_filter, weighting=True, want_extra=True)
@@ -1263,6 +1386,9 @@ class EvaluationPoisson(Evaluation):
                 self._record_errors(self.deltap_res, self.cfd_results, self.no_flow_bool, "_deltap_crude", "Error in delta_p - no weighting")
                 self._record_errors(self.p_pred, p_grid, self.no_flow_bool, "_p", "Error in p")
                 out[slot[c0 + j]], self.label_planes[slot[c0 + j]] = field_deltap, extra[j]
+        if not fields:
+            self.no_flow_bool = sd == 0
+            self.deltap_res = self.cfd_results = self.p_pred = self.label_planes = None
         return out
 
     def build_features(self, ux_grid, uy_grid, delta_ux_grid, delta_uy_grid, sdfunct, phi, U_max_norm) -> np.ndarray:
