@@ -1,6 +1,6 @@
 // psm_api_errors.cpp -- C-ABI of libpsm_hip.so (include/psm.h): the per-frame error blocks of assembled fields on the device.
 // psm_field_errors_device is the stage alone -- two plain launches (the PsmFieldErrorArgs / PsmFieldErrorFinalArgs overloads of
-// psm_block_error_kernel, psm_mesh.hip) that leave raw[n_frames][n_pairs][8] sums for psm_error_metrics_from_sums (psm_errors.cpp);
+// psm_block_error_kernel, psm_eval.hip) that leave raw[n_frames][n_pairs][8] sums for psm_error_metrics_from_sums (psm_errors.cpp);
 // psm_poisson_frames_errors* put it behind the Poisson evaluator's frame step of psm_api_frames.cpp with the three pairs the
 // reference prints (pressureSM_Poisson/SM_call.py:962-1043), so that a metrics-only sweep returns 24 doubles per frame and no field.
 // See psm_handle.h for the map of the files.
@@ -8,7 +8,7 @@
 
 namespace psm_impl {
 
-static_assert(PSM_ERR_MAX_PAIRS == PSM_FIELD_ERR_MAX_PAIRS, "psm.h and psm_mesh.h disagree on the pairs of one call");
+static_assert(PSM_ERR_MAX_PAIRS == PSM_FIELD_ERR_MAX_PAIRS, "psm.h and psm_eval.h disagree on the pairs of one call");
 static_assert(sizeof(psm_err_plane) == 32 && sizeof(psm_err_pair) == 136, "layout of the public descriptors (mirrored by _lib.py)");
 
 static PsmErrPlane plane_of(const psm_err_plane& p) { return PsmErrPlane{p.ptr, p.frame_stride, p.elem_stride, p.as_f32 ? 1 : 0}; }

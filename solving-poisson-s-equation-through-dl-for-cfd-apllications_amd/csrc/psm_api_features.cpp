@@ -1,6 +1,6 @@
 // psm_api_features.cpp -- C-ABI of libpsm_hip.so (include/psm.h): the pressureSM_Poisson input features on the device, case-batched
 // (psm_bind_features, psm_features_device) and the whole Poisson time step behind them as one graph replay (psm_poisson_step*):
-// d_vel -> features -> solve -> post-steps.  The host entry psm_poisson_features stays in psm_api_mesh.cpp.  Kernels: psm_features.hip.
+// d_vel -> features -> solve -> post-steps.  The host entry psm_poisson_features (one case, host arrays) is the first entry below.  Kernels: psm_features.hip.
 // See psm_handle.h for the map of the files.
 #include "psm_handle.h"
 
@@ -80,6 +80,41 @@ int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const d
 
 // ============================================================================
 extern "C" {
+
+
+int psm_poisson_features(psm_handle* h, const double* ux, const double* uy, const double* dux, const double* duy,
+                         const double* sdfunct, int32_t ny, int32_t nx, const double* params, float* grid_out) {
+  if (!h) return PSM_ERR_ARG;
+  if (!ux || !uy || !dux || !duy || !sdfunct || !params || !grid_out) return fail(h, PSM_ERR_ARG, "null argument");
+  if (ny < 2 || nx < 2 || (int64_t)ny * nx > ((int64_t)1 << 26)) return fail(h, PSM_ERR_ARG, "grid must be at least 2x2 (np.gradient)");
+  if (!(params[1] != 0.0)) return fail(h, PSM_ERR_ARG, "U must be non-zero");
+  for (int q = 3; q < 7; ++q)
+    if (!(params[q] != 0.0)) return fail(h, PSM_ERR_ARG, "max_abs scales must be non-zero");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  hipStream_t st = h->stream;
+  const size_t n = (size_t)ny * nx, nwg = (n + 255) / 256;
+  int rc;
+  const size_t ib = 5 * n * sizeof(double), gb = 4 * n * sizeof(float);
+  if ((rc = scratch_reserve(h, carve_size({ib, n * sizeof(double), 2 * nwg * sizeof(double), gb}), carve_size({ib, gb})))) return rc;
+  Carver cd{(char*)h->scr_dev}, cp{(char*)h->scr_pin};
+  double* d_in = cd.take<double>(5 * n); double* d_term = cd.take<double>(n); double* d_part = cd.take<double>(2 * nwg);
+  float* d_grid = cd.take<float>(4 * n);
+  double* p_in = cp.take<double>(5 * n); float* p_grid = cp.take<float>(4 * n);
+  const double* src[5] = {ux, uy, dux, duy, sdfunct};
+  for (int q = 0; q < 5; ++q) memcpy(p_in + q * n, src[q], n * sizeof(double));
+  hipError_t e = hipMemcpyAsync(d_in, p_in, ib, hipMemcpyHostToDevice, st);
+  PsmFeatureArgs fa{};
+  fa.ux = d_in; fa.uy = d_in + n; fa.dux = d_in + 2 * n; fa.duy = d_in + 3 * n; fa.sdf = d_in + 4 * n;
+  fa.term = d_term; fa.partial = d_part; fa.grid = d_grid; fa.ny = ny; fa.nx = nx;
+  fa.L = params[0]; fa.U = params[1]; fa.k = params[2];
+  for (int q = 0; q < 4; ++q) fa.max_abs[q] = params[3 + q];
+  if (e == hipSuccess) e = psm_launch_poisson_features(fa, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(p_grid, d_grid, gb, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = wait_stream(st);
+  if (e == hipSuccess) memcpy(grid_out, p_grid, gb);
+  if (e != hipSuccess) return fail(h, PSM_ERR_HIP, std::string("poisson features: ") + hipGetErrorString(e));
+  return PSM_OK;
+}
 
 
 int psm_bind_features(psm_handle* h, const double* sdfunct, int32_t n_cases, double k, const double* max_abs) {

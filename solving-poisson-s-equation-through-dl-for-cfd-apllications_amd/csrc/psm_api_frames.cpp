@@ -25,7 +25,7 @@ void frames_free(psm_handle* h) {
 // The one launch of the stage on `st`: the mesh's tables, the call's columns and plane descriptors.
 int frames_device(psm_handle* h, const FrameCall& fc, int n_frames, hipStream_t st) {
   PsmFrameArgs a{};
-  a.cols = fc.cols; a.vtx = h->d_vtx_m2g; a.wts = h->d_wts_m2g; a.src_of_cell = h->d_src_of_cell;
+  a.cols = fc.cols; a.vtx = h->mesh.t.vtx_m2g; a.wts = h->mesh.t.wts_m2g; a.src_of_cell = h->mesh.t.src_of_cell;
   a.n_grid = (int64_t)h->Ny * h->Nx; a.n_cells = h->n_cells;
   a.k = fc.k; a.fill = fc.fill ? 1 : 0; a.n_frames = n_frames;
   for (int c = 0; c < fc.k; ++c) a.out[c] = fc.out[c];

@@ -67,7 +67,7 @@ int scratch_reserve(psm_handle* h, size_t dev_bytes, size_t pin_bytes) {
 
 void destroy_graphs(psm_handle* h) {
   drop_graphs_if(h, [](const GraphKey&) { return true; });
-  if (h->mesh_graph) { (void)hipGraphExecDestroy(h->mesh_graph); h->mesh_graph = nullptr; }
+  if (h->mesh.graph) { (void)hipGraphExecDestroy(h->mesh.graph); h->mesh.graph = nullptr; }
   ring_drop_graphs(h);
 }
 
@@ -120,7 +120,7 @@ void free_plan(psm_handle* h) {
   // (The registered host arrays stay registered; the graph that holds their addresses goes with the plan.)
   h->have_geometry = false;
   mesh_cases_free(h);                   // the case set of psm_set_geometry_cases likewise
-  if (h->mesh_graph) { (void)hipGraphExecDestroy(h->mesh_graph); h->mesh_graph = nullptr; }
+  if (h->mesh.graph) { (void)hipGraphExecDestroy(h->mesh.graph); h->mesh.graph = nullptr; }
   integ_free(h->integ_dev);             // psm_bind_integration is sized by this plan's grid
   post_free(h->post);                   // and so is psm_bind_poststeps
   feat_free(h->feat);                   // and psm_bind_features
@@ -170,17 +170,16 @@ std::vector<float4> pack_comp_out(const double* comp, int P, int K_out, int Gd) 
 
 
 void unpin_buffers(psm_handle* h) {
-  if (h->mesh_graph) { (void)hipGraphExecDestroy(h->mesh_graph); h->mesh_graph = nullptr; }      // it holds the registered addresses
-  h->pinned_cells_dev = nullptr;
-  if (h->pinned_cells) { (void)hipHostUnregister((void*)h->pinned_cells); h->pinned_cells = nullptr; }
-  if (h->pinned_p) { (void)hipHostUnregister((void*)h->pinned_p); h->pinned_p = nullptr; h->pinned_p_dev = nullptr; }
+  if (h->mesh.graph) { (void)hipGraphExecDestroy(h->mesh.graph); h->mesh.graph = nullptr; }      // it holds the registered addresses
+  h->mesh.pinned_cells_dev = nullptr;
+  if (h->mesh.pinned_cells) { (void)hipHostUnregister((void*)h->mesh.pinned_cells); h->mesh.pinned_cells = nullptr; }
+  if (h->mesh.pinned_p) { (void)hipHostUnregister((void*)h->mesh.pinned_p); h->mesh.pinned_p = nullptr; h->mesh.pinned_p_dev = nullptr; }
 }
 
 
 void mesh_cases_free(psm_handle* h) {
   MeshCaseSet& m = h->mcs;
-  dev_free(m.d_off); dev_free(m.d_vtx_m2g); dev_free(m.d_src_of_cell); dev_free(m.d_vtx_g2m); dev_free(m.d_cell_of_point);
-  dev_free(m.d_wts_m2g); dev_free(m.d_sdf); dev_free(m.d_wts_g2m); dev_free(m.d_near_wall);
+  mesh_tables_free(m.t);
   dev_free(m.d_cells); dev_free(m.d_p); dev_free(m.d_umax); dev_free(m.d_umax_part);
   if (m.h_cells) { (void)hipHostFree(m.h_cells); m.h_cells = nullptr; }
   if (m.h_p) { (void)hipHostFree(m.h_p); m.h_p = nullptr; }
@@ -192,12 +191,12 @@ void free_geometry(psm_handle* h) {
   unpin_buffers(h);
   mesh_cases_free(h);
   frames_free(h);                       // the frame batch reads this mesh's tables
-  dev_free(h->d_vtx_m2g); dev_free(h->d_src_of_cell); dev_free(h->d_vtx_g2m); dev_free(h->d_cell_of_point);
-  dev_free(h->d_wts_m2g); dev_free(h->d_sdf); dev_free(h->d_wts_g2m); dev_free(h->d_cells); dev_free(h->d_p);
-  dev_free(h->d_umax); dev_free(h->d_umax_part); dev_free(h->d_near_wall);
+  MeshSingle& m = h->mesh;
+  mesh_tables_free(m.t);
+  dev_free(m.d_cells); dev_free(m.d_p); dev_free(m.d_umax); dev_free(m.d_umax_part);
   integ_free(h->integ_host); integ_free(h->integ_dev);
-  if (h->h_cells) { (void)hipHostFree(h->h_cells); h->h_cells = nullptr; }
-  if (h->h_p) { (void)hipHostFree(h->h_p); h->h_p = nullptr; }
+  if (m.h_cells) { (void)hipHostFree(m.h_cells); m.h_cells = nullptr; }
+  if (m.h_p) { (void)hipHostFree(m.h_p); m.h_p = nullptr; }
   h->have_geometry = false;
 }
 

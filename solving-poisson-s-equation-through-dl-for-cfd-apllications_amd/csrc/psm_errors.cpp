@@ -1,5 +1,5 @@
 // psm_errors.cpp -- the error summary every evaluator of the reference prints per frame (pressureSM_Poisson/SM_call.py:962-994;
-// SM_call.py:696-724) from the eight sums the device reduction leaves (psm_block_error_kernel, psm_mesh.hip): over the flow cells,
+// SM_call.py:696-724) from the eight sums the device reduction leaves (psm_block_error_kernel, psm_eval.hip): over the flow cells,
 // with norm = max - min of the truth there and NaN differences left out,
 //   BIAS = mean(pred - true) / norm, RMSE = sqrt(mean((pred - true)^2)) / norm, STDE = sqrt(RMSE^2 - BIAS^2), in percent,
 // and the two values the reference appends to pred_minus_true / pred_minus_true_squared.  Statement for statement what

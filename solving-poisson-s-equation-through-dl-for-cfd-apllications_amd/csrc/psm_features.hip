@@ -13,7 +13,7 @@
 // the image have a per-case stride, and mean / standard deviation are folded from that case's own partials only.  The per-step
 // scalars (L, U) of the batched form come from device memory (PsmFeatureArgs::lu), so a captured launch is replayed with new values.
 #include "psm_launch.h"
-#include "psm_mesh.h"
+#include "psm_features.h"
 
 namespace {
 constexpr int FT = 256;

@@ -27,7 +27,7 @@
 #include <algorithm>
 
 #include "psm_launch.h"
-#include "psm_mesh.h"
+#include "psm_filter.h"
 
 namespace {
 

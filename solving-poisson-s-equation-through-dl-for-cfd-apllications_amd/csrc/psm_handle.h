@@ -1,12 +1,14 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in ten files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in twelve files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, graph capture and key, psm_solve_grid*
 //   psm_api_ring.cpp        the pinned submission ring (psm_ring_*, psm_submit_grid*, psm_wait_grid) and registered host memory (psm_host_*)
-//   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*; the case batch psm_set_geometry_cases / psm_solve_cases*, host tables in psm_mesh_tables.cpp), evaluator helpers (labels, block error, filters), the gradP integration (host entry and device-resident U -> p)
+//   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*; the case batch psm_set_geometry_cases / psm_solve_cases*; host tables of both in psm_mesh_tables.cpp), psm_mesh_to_grid
+//   psm_api_eval.cpp        evaluator helpers on the planned grid: psm_reassemble, psm_label_blocks, psm_block_error
+//   psm_api_integ.cpp       the gradP integration: tables, host entry and the device-resident U -> p (psm_set_integration ... psm_solve_pressure)
 //   psm_api_filter.cpp      the Gaussian post-steps: psm_gaussian_filter (host entry), psm_bind_poststeps and the device-resident / case-batched entries
-//   psm_api_features.cpp    the pressureSM_Poisson input features on the device: psm_bind_features, psm_features_device and the whole step psm_poisson_step*
+//   psm_api_features.cpp    the pressureSM_Poisson input features: the host entry psm_poisson_features; on the device psm_bind_features, psm_features_device and the whole step psm_poisson_step*
 //   psm_api_frames.cpp      frames of cell columns -> planes on the device: psm_bind_frames, psm_frames_to_grid_device and the evaluator's step psm_poisson_frames*
 //   psm_api_errors.cpp      the per-frame error blocks of assembled fields on the device: psm_field_errors_device and the metrics-only frame step psm_poisson_frames_errors* (host arithmetic: psm_errors.cpp)
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
@@ -34,9 +36,15 @@
 #include "../../include/psm.h"
 #include "psm_kernels.h"
 #include "psm_mesh.h"
+#include "psm_eval.h"
+#include "psm_filter.h"
+#include "psm_integ.h"
+#include "psm_features.h"
 #include "psm_plan.h"
 #include "psm_fold.h"
 #include "psm_errors.h"
+
+struct PsmMeshCaseTables;   // psm_mesh_tables.h
 
 namespace psm_impl __attribute__((visibility("hidden"))) {
 extern thread_local std::string g_create_error;   // message of the last failed psm_create (psm_api_model.cpp)
@@ -163,7 +171,7 @@ struct Workspace {
   int gidx = 0;                       // this workspace's word in the handle's mapped guard page (0 = ws0, 1 + i = ring slot i)
 };
 
-// Device tables of one integration binding (PsmIntegArgs, psm_mesh.h) and the handle's own gradient / pressure buffers.
+// Device tables of one integration binding (PsmIntegArgs, psm_integ.h) and the handle's own gradient / pressure buffers.
 struct IntegSet {
   bool ready = false;
   int n_cases = 0;
@@ -174,16 +182,37 @@ struct IntegSet {
   PsmIntegArgs args{};
 };
 
+// The device tables of a mesh, or of K meshes concatenated in the layout of PsmMeshCasesArgs (host side: PsmMeshCaseTables,
+// psm_mesh_tables.h): uploaded by mesh_tables_upload, released by mesh_tables_free (both in psm_api_mesh.cpp).
+struct MeshTablesDev {
+  int64_t* off = nullptr;               // [K + 1]
+  int32_t *vtx_m2g = nullptr, *src_of_cell = nullptr, *vtx_g2m = nullptr, *cell_of_point = nullptr;
+  double *wts_m2g = nullptr, *sdf = nullptr, *wts_g2m = nullptr;
+  uint8_t* near_wall = nullptr;
+};
+
+// The single mesh of psm_set_geometry: its tables and every buffer a psm_solve touches, so that a step allocates nothing.
+struct MeshSingle {
+  MeshTablesDev t;
+  double *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;   // staged cells, p, U_max, <= 256 partials
+  double *h_cells = nullptr, *h_p = nullptr;   // pinned staging
+  const double* pinned_cells = nullptr;   // caller buffers registered with psm_pin_buffers (DMA without staging copies)
+  double* pinned_p = nullptr;
+  double* pinned_p_dev = nullptr;       // device-side address of the registered output (the last kernel writes p straight into it)
+  const double* pinned_cells_dev = nullptr;   // device-side address of the registered input (psm_stage_cells_kernel reads it over PCIe)
+  hipGraphExec_t graph = nullptr;       // psm_solve on registered buffers: stage + to_grid + the solve + to_mesh as ONE graph replay
+  Ws0Solve graph_left;                  // what `graph` leaves on ws0
+  bool inflight = false;                // psm_solve_begin enqueued, psm_solve_end not yet called
+  double* copy_out = nullptr;           // where psm_solve_end copies p to (null: it was DMA'd / stored into the caller's registered array)
+};
+
 // The case set of psm_set_geometry_cases: K meshes on the planned grid, their tables in the layout of PsmMeshCasesArgs and every
 // buffer a step touches, so that a step allocates nothing.  A handle holds this or the single mesh of psm_set_geometry.
 struct MeshCaseSet {
   bool ready = false;
   int n_cases = 0;
-  std::vector<int64_t> off;             // [n_cases + 1] host copy of d_off
-  int64_t* d_off = nullptr;
-  int32_t *d_vtx_m2g = nullptr, *d_src_of_cell = nullptr, *d_vtx_g2m = nullptr, *d_cell_of_point = nullptr;
-  double *d_wts_m2g = nullptr, *d_sdf = nullptr, *d_wts_g2m = nullptr;
-  uint8_t* d_near_wall = nullptr;
+  std::vector<int64_t> off;             // [n_cases + 1] host copy of t.off
+  MeshTablesDev t;
   double *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;   // staged cells, p, U_max[K], partials [K][n_parts]
   double *h_cells = nullptr, *h_p = nullptr;   // pinned staging of the host entries
   PsmMeshCasesArgs args{};              // everything but cells / p_out, which are the call's
@@ -262,9 +291,7 @@ struct psm_handle {
   // mesh-side tables (psm_set_geometry)
   bool have_geometry = false, have_g2m = false;
   int64_t n_cells = 0;
-  int32_t *d_vtx_m2g = nullptr, *d_src_of_cell = nullptr, *d_vtx_g2m = nullptr, *d_cell_of_point = nullptr;
-  double *d_wts_m2g = nullptr, *d_sdf = nullptr, *d_wts_g2m = nullptr, *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;
-  uint8_t* d_near_wall = nullptr;
+  MeshSingle mesh;
   MeshCaseSet mcs;                      // or a case set (psm_set_geometry_cases): setting one drops the other
   // U_to_gradP integration: the evaluator's single geometry of any size (psm_set_integration, host buffers) and the case
   // batch on the planned grid (psm_bind_integration, device buffers)
@@ -272,13 +299,6 @@ struct psm_handle {
   PostSet post;                         // Gaussian post-steps on the planned grid (psm_bind_poststeps)
   FeatureSet feat;                      // Poisson input features on the planned grid (psm_bind_features)
   FrameSet frames;                      // frame batch on the single mesh (psm_bind_frames)
-  double *h_cells = nullptr, *h_p = nullptr;
-  const double* pinned_cells = nullptr;   // caller buffers registered with psm_pin_buffers (DMA without staging copies)
-  double* pinned_p = nullptr;
-  double* pinned_p_dev = nullptr;       // device-side address of the registered output (the last kernel writes p straight into it)
-  const double* pinned_cells_dev = nullptr;   // device-side address of the registered input (psm_stage_cells_kernel reads it over PCIe)
-  hipGraphExec_t mesh_graph = nullptr;  // psm_solve on registered buffers: stage + to_grid + the solve + to_mesh as ONE graph replay
-  Ws0Solve mesh_graph_left;             // what mesh_graph leaves on ws0
   double maxs[4] = {1, 1, 1, 1};
   int normalise_sdf = 0, fill_input = 0;
   double case_maxs[4] = {1, 1, 1, 1}, case_delta = 5e-3, case_wall = 0.05;   // psm_set_case (PM:106-109, 195, 494)
@@ -333,8 +353,6 @@ struct psm_handle {
   bool bound = false, bound_zero_fill = false;
   int bound_scope = 0;                  // 2: every single-case solve (psm_bind_geometry); 1: psm_solve only (bound by psm_set_geometry)
   bool in_mesh_solve = false;
-  bool mesh_inflight = false;           // psm_solve_begin enqueued, psm_solve_end not yet called
-  double* mesh_copy_out = nullptr;      // where psm_solve_end copies p to (null: it was DMA'd / stored into the caller's registered array)
   int bound_rows = 0;                   // table rows per case
   int bound_cases = 0;                  // cases bound (solves with exactly this many cases take the bound path)
   float *d_comp_nat = nullptr;          // comp_out in natural layout [ld_out][K_out] (f32 precision only)
@@ -409,6 +427,8 @@ std::vector<float4> pack_comp_out(const double* comp, int P, int K_out, int Gd);
 void unpin_buffers(psm_handle* h);
 void free_geometry(psm_handle* h);
 void mesh_cases_free(psm_handle* h);
+int mesh_tables_upload(psm_handle* h, MeshTablesDev& dev, const PsmMeshCaseTables& t);
+void mesh_tables_free(MeshTablesDev& dev);
 void integ_free(IntegSet& s);
 int integrate_device(psm_handle* h, const float* d_gradp, int n_cases, float* d_p, hipStream_t st);
 void post_free(PostSet& s);
@@ -437,6 +457,10 @@ PsmDotsArgs dots_args(const psm_handle* h, const Workspace& w, bool cf, int n_ca
 PsmStripArgs strip_args(const psm_handle* h, const Workspace& w, const float* d_grid);
 PsmChainArgs chain_args(const psm_handle* h, const Workspace& w);
 PsmPasteArgs paste_args(const psm_handle* h, const Workspace& w, float* d_fields);
+// the two ends of psm_solve on the single mesh (psm_api_mesh.cpp).  U_max: the device scalar d_umax, else umax_val; to_grid folds
+// n_partials > 0 partial maxima itself and leaves the scalar in the mesh's d_umax
+PsmToGridArgs to_grid_args(const psm_handle* h, const double* d_umax, double umax_val, int n_partials);
+PsmToMeshArgs to_mesh_args(const psm_handle* h, const double* d_umax, double umax_val, double* p_out);
 // d_p != nullptr: the bound integration (psm_bind_integration) of d_fields into d_p follows in the same stream / the same graph;
 // post (apply_filter >= 0): the bound post-steps (psm_bind_poststeps) of d_fields follow likewise;
 // feat (vel != nullptr): the bound features (psm_bind_features) write d_grid == feat->grid in front of the solve, likewise;

@@ -22,7 +22,7 @@
 //   An empty selection gives 0 / 0 = NaN like np.mean.
 // No thread loops serially over a row or a column, no intermediate image; no LDS in launch 1, 0.2 KiB in launch 2.
 #include "psm_launch.h"
-#include "psm_mesh.h"
+#include "psm_integ.h"
 
 namespace {
 

@@ -1,7 +1,8 @@
 // CPU-only check of the host side of psm_set_geometry_cases (csrc/psm_mesh_tables.cpp) under AddressSanitizer + UBSan:
 // random case sets of unequal cell counts on small grids -- offsets, the concatenated layout, last-writer and near-wall
 // tables against a straightforward restatement, every index the kernels follow inside its table -- and every class of bad
-// table refused with a message that names the case, leaving the output untouched.
+// table refused with a message that names the case, leaving the output untouched.  The single mesh of psm_set_geometry goes
+// through the same builder (one case, `single`): with and without the grid->mesh tables, each against a plain loop written here.
 // Built and run by tests/test_mesh_cases.py with g++ -fsanitize=address,undefined.
 #include <algorithm>
 #include <cstdio>
@@ -36,6 +37,53 @@ static Case make_case(std::mt19937& rng, int ny, int nx) {
 }
 
 #define REQUIRE(cond, msg) do { if (!(cond)) { std::printf("FAILED: %s (line %d)\n", msg, __LINE__); return 1; } } while (0)
+
+// One mesh as psm_set_geometry hands it over, with (g2m) or without the grid->mesh pair: every table against the loops
+// psm_set_geometry used to run inline; refusals carry no "case k: " prefix.
+static int single_mesh(std::mt19937& rng, int ny, int nx, bool g2m, double scale, double wall) {
+  const int64_t ng = (int64_t)ny * nx;
+  const Case c = make_case(rng, ny, nx);
+  PsmMeshCaseInput in = c.in();
+  if (!g2m) { in.vtx_g2m = nullptr; in.wts_g2m = nullptr; }
+  PsmMeshCaseTables t;
+  std::string why;
+  REQUIRE(psm_build_mesh_case_tables(1, &in, ny, nx, scale, wall, t, why, true) == 0, why.c_str());
+  REQUIRE(t.n_cases == 1 && t.have_g2m == g2m && t.n_grid == ng && t.total == c.n && t.max_cells == c.n, "single: header");
+  REQUIRE(t.cell_off == (std::vector<int64_t>{0, c.n}), "single: offsets");
+  std::vector<int32_t> src(ng, -1), cop(ng);
+  for (int64_t p = 0; p < ng; ++p) {
+    const int64_t cell = (int64_t)c.idx[p * 2] * nx + c.idx[p * 2 + 1];
+    src[cell] = (int32_t)p;
+    cop[p] = (int32_t)cell;
+  }
+  REQUIRE(t.src_of_cell == src && t.cell_of_point == cop, "single: last writer / cell of point");
+  REQUIRE(t.vtx_m2g == c.v1 && t.wts_m2g == c.w1 && t.sdf == c.sdf, "single: mesh->grid tables");
+  REQUIRE(t.sdf_image.size() == (size_t)ng * 3, "single: image size");
+  for (int64_t p = 0; p < ng; ++p) {
+    const double sdv = c.sdf[p] * scale;
+    REQUIRE(t.sdf_image[p * 3] == 0.f && t.sdf_image[p * 3 + 1] == 0.f && t.sdf_image[p * 3 + 2] == ((sdv != sdv) ? 0.f : (float)sdv), "single: bound image");
+  }
+  REQUIRE(t.vtx_g2m.size() == (size_t)c.n * 3 && t.wts_g2m.size() == (size_t)c.n * 3 && t.near_wall.size() == (size_t)c.n, "single: grid->mesh sizes");
+  for (int64_t n = 0; n < c.n; ++n) {
+    double acc = 0.0; bool neg = false;
+    for (int j = 0; j < 3; ++j) {
+      REQUIRE(t.vtx_g2m[n * 3 + j] == (g2m ? c.v2[n * 3 + j] : 0) && t.wts_g2m[n * 3 + j] == (g2m ? c.w2[n * 3 + j] : 0.0), "single: grid->mesh tables (absent: zero-filled)");
+      acc += c.sdf[c.v2[n * 3 + j]] * c.w2[n * 3 + j]; neg = neg || c.w2[n * 3 + j] < 0.0;
+    }
+    REQUIRE(t.near_wall[n] == (g2m && !neg && acc < wall ? 1 : 0), "single: near wall (absent: all 0)");
+  }
+  // refusals: the texts of psm_set_geometry, no case named, the earlier result untouched
+  Case b = c;
+  b.v1[(rng() % ng) * 3 + 2] = (int32_t)b.n;
+  in = b.in();
+  REQUIRE(psm_build_mesh_case_tables(1, &in, ny, nx, scale, wall, t, why, true) == -1 && why == "mesh->grid vertex index out of range", "single: bad vertex");
+  in = c.in(); in.wts_g2m = nullptr;
+  REQUIRE(psm_build_mesh_case_tables(1, &in, ny, nx, scale, wall, t, why, true) == -1 && why == "vtx_g2m and wts_g2m go together", "single: half a pair");
+  in = c.in();
+  REQUIRE(psm_build_mesh_case_tables(1, &in, ny, 0, scale, wall, t, why, true) == -1 && why == "bad case set", "single: a shape no grid has");
+  REQUIRE(t.cell_off == (std::vector<int64_t>{0, c.n}) && t.src_of_cell == src, "single: a refused mesh changed the output");
+  return 0;
+}
 
 int main() {
   std::mt19937 rng(11);
@@ -105,6 +153,11 @@ int main() {
   PsmMeshCaseTables t;
   std::string why;
   REQUIRE(psm_build_mesh_case_tables(0, nullptr, 4, 4, 1.0, 0.05, t, why) != 0 && !why.empty(), "an empty set was accepted");
-  std::printf("case sets built: %d, refused: %d\n", sets, refused);
+  int singles = 0;
+  for (int trial = 0; trial < 20; ++trial, ++singles) {
+    const int ny = 3 + (int)(rng() % 20), nx = 3 + (int)(rng() % 30);
+    if (single_mesh(rng, ny, nx, trial % 2 == 1, trial % 4 < 2 ? 1.0 : 1.0 / 0.999023, 0.05)) return 1;
+  }
+  std::printf("case sets built: %d, refused: %d, single meshes: %d\n", sets, refused, singles);
   return 0;
 }

@@ -141,8 +141,8 @@ def test_null_handle_is_refused():
 
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 def test_case_tables_are_clean_under_asan_ubsan(tmp_path):
-    """Validation, offsets and derived tables of psm_set_geometry_cases (csrc/psm_mesh_tables.cpp: no device needed) in a
-    stand-alone program under AddressSanitizer + UBSan."""
+    """Validation, offsets and derived tables of psm_set_geometry_cases and of the single mesh of psm_set_geometry, with and
+    without its grid->mesh tables (csrc/psm_mesh_tables.cpp: no device needed), in a stand-alone program under AddressSanitizer + UBSan."""
     exe = str(tmp_path / "mesh_cases_sanitized")
     b = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
                         os.path.join(ROOT, "tests", "native", "mesh_cases_sanitized.cpp"), os.path.join(CSRC, "psm_mesh_tables.cpp"),
@@ -151,7 +151,7 @@ def test_case_tables_are_clean_under_asan_ubsan(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0"))
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
-    assert "case sets built: 60, refused: 60" in r.stdout
+    assert "case sets built: 60, refused: 60, single meshes: 20" in r.stdout
 
 
 def _build_example(out):

@@ -8,6 +8,10 @@ the same order (--dispatches prints a trace as one line per dispatch, to be comp
     python tools/route_matrix.py --dispatches DIR/.../*_kernel_trace.csv     (no GPU needed)
     python tools/route_matrix.py --table LIST_A LIST_B      two such lists as one numbered table of the distinct lines + each list as numbers
 
+The `boundary` configurations (--only boundary, or one of BOUNDARY by name) hash the mesh ends of the library at the smallest shapes
+that can go wrong: every one runs in a child process of its own with its switches in the environment (they are read once per
+process) and prints one SHA-256 line per output.
+
 --lib: the library to load (default: the tree's libpsm_hip.so), e.g. the parent commit's build.  PSM_MESH_GRAPH is read once per
 process: the `mesh` configuration runs in the mode --mesh-graph sets (default 2), so the three modes take three runs.
 """
@@ -43,6 +47,20 @@ GRID_CONFIGS = {
     "deltas_bound_100_blocks": ("deltas", 3, (900, 900), 32, 32, 1, "f32", {}, True),        # more than 64 blocks: chain launch + batch paste for one case
     "gradp_bound_bf16_n5": ("gradp", 3, (256, 256), 48, 64, 5, "bf16", {}, True),
     "deltas_bound_n17_spread": ("deltas", 3, (256, 256), 32, 32, 17, "f32", {}, True),       # 272 guard workgroups: dealt over the Dense launches
+}
+# name: environment of the child process.  psm_solve on the 138 x 300 mesh case unless the name says otherwise.
+BOUNDARY = {
+    "solve_host_umax": {},                                   # unregistered arrays: U_max on the host
+    "solve_device_umax": {"PSM_DEVICE_UMAX": "1"},           # unregistered, psm_umax_kernel
+    "solve_partials": {},                                    # 32769 + 37 cells on synthetic tables: psm_umax_partial_kernel, folded by to_grid
+    "solve_registered_graph1": {"PSM_MESH_GRAPH": "1"},      # registered arrays: stage kernel + partials, one graph replay
+    "solve_registered_graph2": {"PSM_MESH_GRAPH": "2"},      # the same as plain launches
+    "solve_nan": {},                                         # one NaN velocity: U_max and with it every pressure
+    "cases_k1": {}, "cases_k3": {},                          # psm_solve_cases: 16021 / 16165 / 15838 cells, none a multiple of 256
+    "mesh_to_grid": {},                                      # psm_mesh_to_grid k = 1 and 3, fill 0 / 1, on hand-made tables (130 x 131)
+    "frames_to_grid": {},                                    # psm_frames_to_grid_device: 2 frames, a float64 plane, a float32 plane, a skipped column
+    "block_error": {},                                       # psm_block_error behind a solve: label blocks + the per-block sums
+    "field_errors": {},                                      # psm_field_errors_device: 17030 pixels (no multiple of 4), dense aligned / odd-offset / strided planes
 }
 OTHER = ["attention_ln_deferred", "attention_ln_launched", "conv1d_head", "mesh", "ring", "pressure", "poststeps"]
 _lines = []
@@ -186,6 +204,166 @@ def other_config(name):
         say(f"{'mesh':28s} solve1={h[0]} solve2={h[1]} solve3={h[2]}  psm_solve on the 140x300 mesh case, PSM_MESH_GRAPH={os.environ['PSM_MESH_GRAPH']}")
 
 
+def hand_mesh(sur, ny, nx, n_cells, seed=1301):
+    """Mesh -> grid tables made by hand on `sur` (psm_set_geometry without the grid -> mesh side): random simplices, a quarter of the
+    grid points with a negative weight, 15 % of the points redirected to another cell (several writers there, possibly none at home)."""
+    import numpy as np
+    ng, rng = ny * nx, np.random.default_rng(seed)
+    vtx = rng.integers(0, n_cells, (ng, 3)).astype(np.int32)
+    w = rng.random((ng, 2)) * 0.5
+    wts = np.c_[w, 1.0 - w.sum(axis=1)]
+    neg = rng.random(ng) < 0.25
+    wts[neg, 0] = -wts[neg, 0]
+    wts[neg, 2] = 1.0 - wts[neg, 0] - wts[neg, 1]
+    cell = np.arange(ng)
+    moved = rng.random(ng) < 0.15
+    cell[moved] = rng.integers(0, ng, int(moved.sum()))
+    sur.set_mesh(vtx, np.ascontiguousarray(wts), np.c_[cell // nx, cell % nx].astype(np.int32), np.ones((ny, nx)), n_cells)
+
+
+def boundary_config(name):
+    """Runs in the child process: one line per output."""
+    import numpy as np
+    import cases
+    from hipmem import DeviceArray
+    from psm_amd import GridSurrogate, SolverEnsemble, SolverModule, synthetic
+    from psm_amd.surrogate import _p
+    line = lambda what, a: say(f"{name:28s} {what:18s} {sha(a)}")
+    HY, HX, HN = 130, 131, 200                               # the hand-made mesh: 17030 pixels, 200 cells
+    if name.startswith("solve_") and name != "solve_partials":
+        array, top, obst, model, maxs = cases.build_mesh_case()
+        sm = SolverModule(model, maxs)
+        sm.init_func(array, top, obst)
+        cells, out = np.ascontiguousarray(array, np.float64).copy(), np.empty(array.shape[0], np.float64)
+        if name == "solve_nan":
+            cells[array.shape[0] // 3, 1] = np.nan
+        if "registered" in name:
+            sm.pin(cells, out)
+        for k in range(2):
+            line(f"p solve{k + 1}", sm.py_func(cells, out=out).copy())
+        if "registered" in name:
+            sm.unpin()
+    elif name == "solve_partials":
+        _, _, _, model, maxs = cases.build_mesh_case()
+        ny, nx, n = 138, 300, 32769 + 37
+        ng, rng = ny * nx, np.random.default_rng(1501)
+
+        def simplices(rows, hi):                             # random simplices, a tenth with a negative weight
+            v = rng.integers(0, hi, (rows, 3)).astype(np.int32)
+            w = rng.random((rows, 2)) * 0.5
+            w = np.c_[w, 1.0 - w.sum(axis=1)]
+            neg = rng.random(rows) < 0.1
+            w[neg, 0] = -w[neg, 0]
+            w[neg, 2] = 1.0 - w[neg, 0] - w[neg, 1]
+            return v, np.ascontiguousarray(w)
+        v1, w1 = simplices(ng, n)
+        v2, w2 = simplices(n, ng)
+        cell = np.arange(ng)
+        moved = rng.random(ng) < 0.15
+        cell[moved] = rng.integers(0, ng, int(moved.sum()))
+        idx = np.ascontiguousarray(np.c_[cell // nx, cell % nx], np.int32)
+        sdf = np.ascontiguousarray(np.abs(rng.standard_normal((ny, nx))) * (rng.random((ny, nx)) > 0.1))
+        mx = np.ascontiguousarray(maxs, np.float64)
+        cells = np.ascontiguousarray(rng.standard_normal((n, 5)))
+        out = np.empty(n, np.float64)
+        with GridSurrogate(model, ny, nx, 1) as sur:
+            sur._chk(sur.lib.psm_set_geometry(sur.h, n, ny, nx, _p(v1, C.c_int32), _p(w1, C.c_double), _p(idx, C.c_int32), _p(sdf, C.c_double),
+                                              _p(v2, C.c_int32), _p(w2, C.c_double), _p(mx, C.c_double), 0, 0, 0.05))
+            for k in range(2):
+                sur._chk(sur.lib.psm_solve(sur.h, _p(cells, C.c_double), n, 0, _p(out, C.c_double)))
+                line(f"p solve{k + 1}", out.copy())
+    elif name.startswith("cases_"):
+        _, _, _, model, maxs = cases.build_mesh_case()
+        obstacles = (dict(), dict(cx=0.55, cy=0.05, R=0.06), dict(cx=0.9, cy=-0.08, R=0.1, step=2))[:int(name[-1])]
+        mesh = [synthetic.channel_mesh(**kw) for kw in obstacles]
+        se = SolverEnsemble(model, maxs, 4, geometry="native")
+        se.init_func(*zip(*mesh))
+        for step in range(2):
+            for k, p in enumerate(se.py_func([m[0] for m in mesh])):
+                line(f"p step{step + 1} case{k}", p)
+        se._sur.close()
+    elif name == "mesh_to_grid":
+        rng = np.random.default_rng(5)
+        with GridSurrogate(synthetic.make_model("deltas", p_in=32, p_out=32), HY, HX, 1) as sur:
+            hand_mesh(sur, HY, HX, HN)
+            for k in (1, 3):
+                values = np.ascontiguousarray(rng.standard_normal((HN, k)))
+                values[7, 0] = np.nan
+                for fill in (0, 1):
+                    out = np.empty((HY, HX, k), np.float64)
+                    sur._chk(sur.lib.psm_mesh_to_grid(sur.h, _p(values, C.c_double), HN, k, fill, _p(out, C.c_double)))
+                    line(f"k={k} fill={fill}", out)
+    elif name == "frames_to_grid":
+        rng = np.random.default_rng(6)
+        nf, k, npix = 2, 3, HY * HX
+        cols = np.ascontiguousarray(rng.standard_normal((nf, HN, k)))
+        cols[1, 3, 0] = cols[1, HN // 2, 1] = np.nan
+        with GridSurrogate(synthetic.make_model("deltas", p_in=32, p_out=32), HY, HX, nf) as sur:
+            hand_mesh(sur, HY, HX, HN)
+            sur.bind_frames(nf, k)
+            d_cols = DeviceArray(cols)
+            d64, d32 = DeviceArray(np.full((nf, npix), -7.5, np.float64)), DeviceArray(np.full((nf, npix + 1), -7.5, np.float32))
+            # column 0 -> a float64 plane, column 1 -> a float32 plane that starts 4- but not 8-byte aligned, column 2 is not stored
+            sur.frames_to_grid_device(d_cols.ptr, nf, k, [(d64.ptr, npix, False), (d32.ptr + 4, npix + 1, True), (0, 0, 0)], fill=True)
+            sur.synchronize()
+            line("float64 planes", d64.numpy())
+            line("float32 planes", d32.numpy())
+            d_cols.free(), d64.free(), d32.free()
+    elif name == "block_error":
+        model = synthetic.make_model("deltas", p_in=32, p_out=32)
+        grid = synthetic.channel_grid(256, 256, seed=9).astype(np.float32)
+        labels = np.random.default_rng(10).standard_normal((256, 256, model.c_out)).astype(np.float32)
+        with GridSurrogate(model, 256, 256, 1) as sur:
+            sur.solve(grid[None])
+            out = (C.c_double * 5)()
+            sur._chk(sur.lib.psm_block_error(sur.h, _p(grid, C.c_float), _p(labels, C.c_float), out))
+            line("5 doubles", np.array(list(out)))
+            line("label blocks", sur.label_blocks(grid, labels))
+    elif name == "field_errors":
+        rng = np.random.default_rng(12)
+        nf, npix = 2, HY * HX                                # 17030 = 4 * 4257 + 2: a ragged tail of the 4-pixel rounds
+        f64 = lambda: rng.standard_normal((nf, npix))
+        mask = f64() * (rng.random((nf, npix)) > 0.2)
+        mask[0, 5] = np.nan                                  # a NaN SDF is no flow cell
+        truth, add = f64(), f64()
+        truth[1, 11] = truth[0, npix - 1] = np.nan
+        add[0, 17] = np.nan
+        sub = np.zeros((nf, npix + 1))                       # its planes start at element 1: dense, 8- but not 16-byte aligned
+        sub[:, 1:] = f64()
+        pred = rng.standard_normal((nf, npix)).astype(np.float32)
+        pred[1, 23] = np.nan
+        field = rng.standard_normal((nf, npix, 2)).astype(np.float32)      # a strided plane: channel 1 of an [npix][2] field
+        with GridSurrogate(synthetic.make_model("deltas", p_in=32, p_out=32), HY, HX, nf) as sur:
+            d = {k: DeviceArray(np.ascontiguousarray(v)) for k, v in dict(mask=mask, truth=truth, add=add, sub=sub, pred=pred, field=field).items()}
+            d_raw = DeviceArray(np.zeros((nf, 2, 8)))
+            dense = lambda a, f32=False: (d[a].ptr, npix, 1, f32)
+            pairs = [(dense("pred", True), dense("truth"), None, None, False),
+                     ((d["field"].ptr + 4, 2 * npix, 2, True), dense("truth"), dense("add"), (d["sub"].ptr + 8, npix + 1, 1, False), True)]
+            sur.field_errors_device(dense("mask"), pairs, nf, d_raw.ptr)
+            sur.synchronize()
+            line("raw sums", d_raw.numpy())
+            for a in list(d.values()) + [d_raw]:
+                a.free()
+
+
+def boundary(names, lib):
+    """One child process per configuration, its switches in its environment; the children's lines are repeated here."""
+    import subprocess
+    for name in names:
+        env = dict(os.environ, **BOUNDARY[name])
+        for k in ("PSM_DEVICE_UMAX", "PSM_MESH_GRAPH"):
+            if k not in BOUNDARY[name]:
+                env.pop(k, None)
+        cmd = [sys.executable, os.path.abspath(__file__), "--boundary-child", name] + (["--lib", lib] if lib else [])
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        for ln in r.stdout.splitlines():
+            say(ln)
+        if r.returncode:
+            say(f"{name:28s} FAILED exit {r.returncode}: {r.stderr.strip().splitlines()[-1] if r.stderr.strip() else ''}")
+            return r.returncode                              # nothing more on the GPU after a child that died
+    return 0
+
+
 def dispatches(paths):
     """The dispatches of rocprofv3 kernel traces in the order they started: kernel name, grid, workgroup, LDS and scratch bytes."""
     import csv
@@ -221,6 +399,7 @@ def main():
     ap.add_argument("--only")
     ap.add_argument("--mesh-graph", default="2", choices=["0", "1", "2"])
     ap.add_argument("--out")
+    ap.add_argument("--boundary-child", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.dispatches:
         return dispatches(args.dispatches)
@@ -228,6 +407,17 @@ def main():
         return table(args.table)
     if args.lib:
         os.environ["PSM_LIB"] = os.path.abspath(args.lib)
+    if args.boundary_child:
+        return boundary_config(args.boundary_child)
+    only = args.only.split(",") if args.only else []
+    if only and all(n == "boundary" or n in BOUNDARY for n in only):     # the parent process never opens the GPU
+        say(f"# tools/route_matrix.py boundary lib={args.lib or 'libpsm_hip.so of the tree'}")
+        rc = boundary([b for n in only for b in (BOUNDARY if n == "boundary" else [n])], args.lib)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write("\n".join(_lines) + "\n")
+        return rc
     os.environ["PSM_MESH_GRAPH"] = args.mesh_graph
     for k in ("PSM_X6", "PSM_LN_FUSE", "PSM_KEEP_HIDDEN", "PSM_NO_BIND", "PSM_RING_GRAPH"):
         os.environ.pop(k, None)
@@ -244,4 +434,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
