@@ -538,6 +538,54 @@ int psm_poisson_frames_errors(psm_handle* h, const double* cols, int32_t n_frame
  * NaN); stde = sqrt(rmse^2 - bias^2), NaN when negative.  n == 0 (NumPy raises on the empty selection): out is all NaN, PSM_OK. */
 int psm_error_metrics_from_sums(const double raw[8], double out[6]);
 
+/* The frame batch of the pressureSM_deltas evaluator (SM_call.py:367-724) on the device: cell columns -> planes -> the solve's image,
+ * label and truth planes -> solve (-> filter) -> the frame's two error blocks, without an image, a label or a field leaving the
+ * device.  Columns of a frame: (dUx / U, dUy / U, dp / U^2, ...); columns beyond 2 are not stored.
+ * psm_bind_deltas_frames: after psm_bind_frames, on a three-channel image with the SDF last and a one-channel field (c_in == 3,
+ * sdf_channel == 2, c_out == 1; PSM_ERR_STATE otherwise, and without a frame binding).  sdfunct [ny*nx] float64 is the simulation's
+ * raw SDF plane (NaNs allowed), max_abs = (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p), each finite and non-zero (PSM_ERR_ARG).
+ * Keeps nan0(sdfunct) / max_abs_dist in float64 on the device -- channel 2 of every image, and the mask of the field errors (flow
+ * cell iff != 0) -- and reserves image, label, truth, field, block partials, raw sums and pinned slots for the frame count bound
+ * with psm_bind_frames: after it a step allocates nothing.  psm_bind_frames / psm_unbind_frames, a new mesh, psm_plan_grid or a
+ * model change drop the binding. */
+int psm_bind_deltas_frames(psm_handle* h, const double* sdfunct, const double* max_abs);
+int psm_unbind_deltas_frames(psm_handle* h);
+/* The image stage alone: psm_frames_to_grid_device (fill = 1) of columns 0-2 into the binding's planes, then one pack launch:
+ *     d_grid  [n][ny][nx][3] float32 = (float)(nan0(v_c) / max_abs_c), c = 0, 1; channel 2 = (float)(nan0(sdfunct) / max_abs_dist)
+ *     d_label [n][ny*nx]     float32 = (float)(nan0(v_2) / max_abs_p)                                  (NULL: not stored)
+ *     d_truth [n][ny*nx]     float64 = (nan0(v_2) / max_abs_p) * max_abs_p * U2[f], left to right      (NULL: not stored)
+ * -- divisions in float64, the cast behind them: the bits of the reference's NumPy statements (SM_call.py:439-445, :580).  U2
+ * [n_frames] is a HOST array copied before return (may be NULL with d_truth NULL).  Device pointers aligned to their element,
+ * asynchronous on `stream` (NULL: the handle's).  PSM_ERR_ARG and nothing enqueued: k outside [3, 16], n_frames outside [1, bound
+ * count], d_cols or d_grid NULL, a misaligned destination, d_truth without U2. */
+int psm_deltas_image_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const double* U2, float* d_grid,
+                            float* d_label, double* d_truth, void* stream);
+/* compute_in_block_error (utils.py:210-243; what psm_block_error gives for case 0 of the last solve) for n_frames frames on the
+ * device: the decoded blocks of the LAST synchronous or device solve of at least n_frames cases on the handle's workspace (decoded
+ * again from its network output, with its row scale) against the de-meaned label blocks of d_label [n][ny*nx] * row scale, over
+ * the flow cells of d_grid [n][ny][nx][3] (SDF channel != 0).  d_raw [n_frames][8], 8-byte aligned: the sums of
+ * psm_field_errors_device's layout, per frame the bits psm_block_error adds up on the host; psm_error_metrics_from_sums turns a row
+ * into the metrics (mean_err / mean_sq_err = psm_block_error's out[0] / out[1]).  Three launches, no atomics, one fixed tree.
+ * PSM_ERR_STATE: no deltas binding, no solve yet, the last solve ran on the ring, or it had fewer than n_frames cases. */
+int psm_block_errors_device(psm_handle* h, const float* d_grid, const float* d_label, int32_t n_frames, double* d_raw, void* stream);
+/* The whole step: planes -> image -> solve (-> the sigma_field filter of psm_bind_poststeps with apply_filter != 0; PSM_ERR_STATE
+ * without that binding) as ONE graph replay.  Inside it the frames are solved one by one, each as the single case the evaluator's
+ * per-frame call solves -- with a geometry bound for ONE case (psm_bind_geometry) the 6-launch route --, so a frame's field holds
+ * the bits of psm_solve_grid on its image whatever the batch; every frame's network output is kept in the binding for the block
+ * stage (psm_read_stage then shows the last frame's solve).  Then, with d_raw != NULL, plain launches on the same stream that leave
+ * d_raw [n_frames][2][8]: row 0 = the (filtered) field against the truth plane over the cells with nan0(sdfunct) / max_abs_dist != 0
+ * (psm_field_errors_device), row 1 = the blocks (psm_block_errors_device: always the unfiltered decoded blocks, as in the
+ * reference).  d_result [n][ny*nx] float32 and d_truth [n][ny*nx] float64 may be NULL: the binding's buffers are used.  U2 and
+ * out_scale [n_frames] are HOST arrays copied before return (out_scale NULL: 1).  k in [3, 16]. */
+int psm_deltas_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const double* U2,
+                             const float* out_scale, int32_t apply_filter, float* d_result, double* d_truth, double* d_raw,
+                             void* stream);
+/* host buffers, synchronous: one H2D of cols (k at most the count bound with psm_bind_frames), D2H of what is non-NULL only --
+ * result [n][ny*nx] float32, truth [n][ny*nx] float64, raw [n][2][8] (at least one of them).  Solves again on the general path
+ * after a guard trip, like psm_poisson_frames. */
+int psm_deltas_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, const double* U2, const float* out_scale,
+                      int32_t apply_filter, float* result, double* truth, double* raw);
+
 /* U_to_gradP: integrate the assembled (dp/dx, dp/dy) into p (integrate_field,
  * Eval_dual_Dense_onlycil.py:371-416, and the four-quadrant stitching :597-628).
  * psm_set_integration fixes the geometry: sdfunct [ny*nx] (self.sdfunct[:,:,0], also used by the

@@ -143,6 +143,13 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "psm_poisson_frames_errors": (C.c_int, [_hp, _f64p, C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, C.c_int32, _f64p]),
     "psm_error_metrics_from_sums": (C.c_int, [_f64p, _f64p]),
+    "psm_bind_deltas_frames": (C.c_int, [_hp, _f64p, _f64p]),
+    "psm_unbind_deltas_frames": (C.c_int, [_hp]),
+    "psm_deltas_image_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, _f64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_block_errors_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "psm_deltas_frames_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "psm_deltas_frames": (C.c_int, [_hp, _f64p, C.c_int32, C.c_int32, _f64p, _f32p, C.c_int32, _f32p, _f64p, _f64p]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
     "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),

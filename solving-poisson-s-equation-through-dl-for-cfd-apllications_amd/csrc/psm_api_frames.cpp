@@ -13,6 +13,7 @@ static void drop_frame_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphK
 
 void frames_free(psm_handle* h) {
   FrameSet& s = h->frames;
+  deltas_free(h);                       // psm_bind_deltas_frames stands on this binding
   drop_frame_graphs(h);
   dev_free(s.d_cols); dev_free(s.d_extra); dev_free(s.d_raw);
   if (s.h_cols) { (void)hipHostFree(s.h_cols); s.h_cols = nullptr; }
@@ -34,14 +35,14 @@ int frames_device(psm_handle* h, const FrameCall& fc, int n_frames, hipStream_t 
 }
 
 // the mesh and the binding every entry below needs
-static int frames_state(psm_handle* h) {
+int frames_state(psm_handle* h) {
   if (h->mcs.ready) return fail(h, PSM_ERR_STATE, "the handle holds a case set (psm_set_geometry_cases): frames take the single mesh of psm_set_geometry");
   if (!h->have_geometry || !h->planned) return fail(h, PSM_ERR_STATE, "psm_set_geometry has not been called (a new plan drops the mesh)");
   if (!h->frames.ready) return fail(h, PSM_ERR_STATE, "psm_bind_frames has not been called (a new mesh, plan or model drops the binding)");
   return PSM_OK;
 }
 
-static int frames_count_check(psm_handle* h, int n_frames) {
+int frames_count_check(psm_handle* h, int n_frames) {
   if (n_frames < 1 || n_frames > h->frames.n_frames) return fail(h, PSM_ERR_ARG, "n_frames outside [1, frames bound with psm_bind_frames]");
   return PSM_OK;
 }

@@ -11,6 +11,28 @@ hipError_t psm_launch_label_blocks(const float* grid, const float* labels, const
 hipError_t psm_launch_block_error(const float* grid, const float* pred, const float* label_blocks, const float* row_scale,
                                   const int32_t* blk_y0x0, double* part, int B, int S, int c_in, int c_out, int sdf_ch, int Nx, hipStream_t st);
 
+// ---- compute_in_block_error for a batch of frames on the device (psm_block_errors_device): the two launches above in one, per
+// (block, frame), from the frame's label PLANE -- no label block is stored --, then a fold of every frame's B partial rows in block
+// order, as psm_block_error's host loop adds them.  c_out == 1.  See psm_eval.hip.
+struct PsmBlockErrorBatchArgs {
+  const float* grid;            // [n_frames][npix][c_in] the solve's image (flow cell: its SDF channel != 0)
+  const float* label;           // [n_frames][npix] label plane in the network's normalised output units
+  const float* pred;            // [n_frames * B][S*S] decoded blocks
+  const float* row_scale;       // [n_frames * B]
+  const int32_t* blk_y0x0;      // [B][2]
+  double* part;                 // [n_frames][B][8]
+  int64_t npix;
+  int S, c_in, sdf_ch, Nx, B, n_frames;
+};
+struct PsmBlockErrorFoldArgs {
+  const double* part;           // [n_frames][B][8]
+  const double* field_raw;      // [n_frames][8] sums of the assembled field, copied to row 0 of the frame (nullptr: raw holds the block row alone)
+  double* raw;                  // field_raw ? [n_frames][2][8] : [n_frames][8]
+  int B;
+};
+hipError_t psm_launch_block_error_batch(const PsmBlockErrorBatchArgs& a, hipStream_t st);
+hipError_t psm_launch_block_error_fold(const PsmBlockErrorFoldArgs& a, int n_frames, hipStream_t st);
+
 // ---- the same eight sums for assembled fields (psm_field_errors_device): whole images instead of decoded blocks, several
 // (prediction, truth) pairs and frames per call, two launches, no atomics.  Launch 1: grid (workgroups over pixels, pair, frame),
 // every workgroup leaves 8 doubles of partials over its PSM_FIELD_ERR_SPAN pixels; launch 2: one workgroup per (pair, frame) folds

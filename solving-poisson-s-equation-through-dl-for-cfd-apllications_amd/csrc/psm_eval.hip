@@ -213,3 +213,87 @@ hipError_t psm_launch_field_errors_final(const PsmFieldErrorFinalArgs& a, int n_
   hipLaunchKernelGGL(static_cast<void (*)(PsmFieldErrorFinalArgs)>(psm_block_error_kernel), dim3((unsigned)n_pairs, (unsigned)n_frames), dim3(64), 0, st, a);
   return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------
+// compute_in_block_error for a batch of frames (psm_block_errors_device; PsmBlockErrorBatchArgs in psm_eval.h): workgroup (block,
+// frame) does what psm_label_blocks_kernel and the first psm_block_error_kernel above do for case 0 in two launches, without the
+// label block in between.  Pass 1 is the mean of psm_label_blocks_kernel -- its pixel -> thread partition (i = t, t + 256, ...), its
+// float64 sums, its LDS tree --, so (float)(label - mean) holds the bits that kernel stores; pass 2 is the first kernel's loop and
+// tree on (double)pred against (double)that float * row_scale[frame * B + block].  A frame's row of B partials therefore holds the
+// bits psm_block_error sums for that frame.  The partition is kept for that reason: a wave reads 64 consecutive pixels of a block
+// row per access (the image channel at a stride of c_in floats); pass 2 reads the block's label and mask a second time, from L2.
+__global__ __launch_bounds__(256) void psm_block_error_kernel(PsmBlockErrorBatchArgs a) {
+  const int b = blockIdx.x, t = threadIdx.x, S = a.S;
+  const int64_t frame = blockIdx.y;
+  const int y0 = a.blk_y0x0[2 * b], x0 = a.blk_y0x0[2 * b + 1];
+  const float* grid = a.grid + frame * a.npix * a.c_in;
+  const float* labels = a.label + frame * a.npix;
+  const int64_t row = frame * a.B + b;
+  const float* pred = a.pred + row * S * S;
+  __shared__ double sh[8][256];
+  double sum = 0.0, cnt = 0.0;
+  for (int i = t; i < S * S; i += 256) {
+    const int64_t pix = (int64_t)(y0 + i / S) * a.Nx + x0 + i % S;
+    if (grid[pix * a.c_in + a.sdf_ch] != 0.f) { sum += (double)labels[pix]; cnt += 1.0; }
+  }
+  sh[0][t] = sum; sh[1][t] = cnt;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) { sh[0][t] += sh[0][t + s]; sh[1][t] += sh[1][t + s]; }
+    __syncthreads();
+  }
+  const double mean = sh[1][0] > 0.0 ? sh[0][0] / sh[1][0] : 0.0;
+  __syncthreads();                                      // every thread has read the mean before the tree's rows are written again
+  const double sc = (double)a.row_scale[row];
+  PsmErrSums sums;
+  for (int i = t; i < S * S; i += 256) {
+    const int64_t pix = (int64_t)(y0 + i / S) * a.Nx + x0 + i % S;
+    if (!(grid[pix * a.c_in + a.sdf_ch] != 0.f)) continue;
+    const float lb = (float)((double)labels[pix] - mean);
+    sums.add((double)pred[i], (double)lb * sc);
+  }
+  sums.store(&sh[0][t], 256);
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) {
+      sh[0][t] += sh[0][t + s]; sh[1][t] += sh[1][t + s]; sh[2][t] += sh[2][t + s]; sh[7][t] += sh[7][t + s];
+      sh[3][t] = fmin(sh[3][t], sh[3][t + s]); sh[4][t] = fmax(sh[4][t], sh[4][t + s]);
+      sh[5][t] = fmin(sh[5][t], sh[5][t + s]); sh[6][t] = fmax(sh[6][t], sh[6][t + s]);
+    }
+    __syncthreads();
+  }
+  if (t < 8) a.part[row * 8 + t] = sh[t][0];
+}
+
+// One workgroup per frame: thread q < 8 adds slot q of the frame's B partial rows in block order -- the statements of
+// psm_block_error's host loop (sums from 0, std::min / std::max from +-inf) -- into the frame's block row of raw; threads 8-15
+// copy the frame's field row in front of it where there is one.
+__global__ __launch_bounds__(64) void psm_block_error_kernel(PsmBlockErrorFoldArgs a) {
+  const int t = threadIdx.x;
+  const int64_t frame = blockIdx.x;
+  const int rows = a.field_raw ? 2 : 1;
+  if (t < 8) {
+    const double* q = a.part + frame * a.B * 8 + t;
+    const bool lo = t == 3 || t == 5, hi = t == 4 || t == 6;
+    double r = lo ? INFINITY : hi ? -INFINITY : 0.0;
+    for (int b = 0; b < a.B; ++b) {
+      const double v = q[(int64_t)b * 8];
+      r = lo ? (v < r ? v : r) : hi ? (r < v ? v : r) : r + v;
+    }
+    a.raw[(frame * rows + rows - 1) * 8 + t] = r;
+  } else if (t < 16 && a.field_raw) {
+    a.raw[frame * 16 + t - 8] = a.field_raw[frame * 8 + t - 8];
+  }
+}
+
+hipError_t psm_launch_block_error_batch(const PsmBlockErrorBatchArgs& a, hipStream_t st) {
+  if (a.n_frames < 1 || a.B < 1 || a.S < 1 || a.npix < 1 || !a.grid || !a.label || !a.pred || !a.row_scale || !a.blk_y0x0 || !a.part)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmBlockErrorBatchArgs)>(psm_block_error_kernel), dim3((unsigned)a.B, (unsigned)a.n_frames), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_block_error_fold(const PsmBlockErrorFoldArgs& a, int n_frames, hipStream_t st) {
+  if (n_frames < 1 || a.B < 1 || !a.part || !a.raw) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmBlockErrorFoldArgs)>(psm_block_error_kernel), dim3((unsigned)n_frames), dim3(64), 0, st, a);
+  return hipGetLastError();
+}

@@ -1,5 +1,5 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in twelve files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in thirteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, graph capture and key, psm_solve_grid*
@@ -11,6 +11,7 @@
 //   psm_api_features.cpp    the pressureSM_Poisson input features: the host entry psm_poisson_features; on the device psm_bind_features, psm_features_device and the whole step psm_poisson_step*
 //   psm_api_frames.cpp      frames of cell columns -> planes on the device: psm_bind_frames, psm_frames_to_grid_device and the evaluator's step psm_poisson_frames*
 //   psm_api_errors.cpp      the per-frame error blocks of assembled fields on the device: psm_field_errors_device and the metrics-only frame step psm_poisson_frames_errors* (host arithmetic: psm_errors.cpp)
+//   psm_api_deltas_frames.cpp  the deltas evaluator's frame batch on the device: psm_bind_deltas_frames, the image pack psm_deltas_image_device, the batched block errors psm_block_errors_device and the step psm_deltas_frames*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -84,6 +85,7 @@ struct Ws0Solve {
   // demand) / left its last hidden activation in MFMA operand order (PsmDenseArgs::out_packed: readers take d_act_rows)
   bool pred_stored = false, used_cf = false, act_packed = false;
   const float* row_scale = nullptr;     // its row scale
+  const float* res = nullptr;           // where its network output rows [cases * B][ld_out] are when not in ws0.d_res (psm_deltas_frames*: one solve per frame)
 };
 
 // Every decision of one solve's launch sequence, made once by choose_route (psm_api_solve.cpp) from the handle, the workspace, the grid
@@ -140,16 +142,28 @@ struct FrameCall {
   }
 };
 
+// The image pack between the mesh -> grid stage and the solve (psm_deltas_frames*): every pointer is part of the captured launch; the
+// SDF plane, the scales and the per-frame U^2 array are the binding's (DeltasSet), which drops these graphs when it goes.
+struct DeltasCall {
+  const double* planes = nullptr;       // [n_frames][3][npix] what the frame stage wrote; nullptr: no pack stage
+  float *grid = nullptr, *label = nullptr;
+  double* truth = nullptr;
+  float* res = nullptr;                 // the binding's copy of every frame's network output rows (the frames are solved one by one)
+  auto tie() const { return std::tie(planes, grid, label, truth); }
+};
+
 struct GraphKey {
   int n; const void* g; void* f;        // n: sequence_key()
   void* p = nullptr;                    // psm_solve_pressure*: where the integration behind the solve writes p (null: the solve alone)
   PostCall post{};                      // psm_solve_poststeps*: the post-steps behind the solve (apply_filter == -1: none)
   const void* vel = nullptr;            // psm_poisson_step*: the velocity planes of the features in front of the solve (g is their image)
   FrameCall frames{};                   // psm_poisson_frames*: the mesh -> grid stage in front of the features (cols == nullptr: none)
+  DeltasCall deltas{};                  // psm_deltas_frames*: the image pack behind the mesh -> grid stage (planes == nullptr: none)
   auto head() const { return std::tie(n, g, f, p, vel); }
   bool operator<(const GraphKey& o) const {
     if (head() != o.head()) return head() < o.head();
     if (post.tie() != o.post.tie()) return post.tie() < o.post.tie();
+    if (deltas.tie() != o.deltas.tie()) return deltas.tie() < o.deltas.tie();
     if (!frames.cols && !o.frames.cols) return false;       // no frame stage on either side: nothing more to compare
     return frames.key() < o.frames.key();
   }
@@ -259,6 +273,28 @@ struct FrameSet {
   float* h_out = nullptr;               // pinned [n_frames][npix][c_out + 2]: result, change, next
   double *d_raw = nullptr, *h_raw = nullptr;   // psm_poisson_frames_errors: [n_frames][3][8] sums, device and pinned
 };
+
+// Binding of the deltas evaluator's frame batch (psm_bind_deltas_frames, behind psm_bind_frames): the simulation's normalised SDF
+// plane, the scales, and every buffer a step touches for the bound frame count, so that a step allocates nothing.  The columns go
+// through the frame binding's staging (FrameSet::d_cols / h_cols).
+struct DeltasSet {
+  static constexpr int RING = 8;
+  bool ready = false;
+  int n_frames = 0;
+  double max_abs[4] = {1, 1, 1, 1};     // max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p
+  double* d_sdn = nullptr;              // [npix] nan0(sdfunct) / max_abs_dist in float64: channel 2 of the image, and the field errors' mask
+  double* d_planes = nullptr;           // [n_frames][3][npix] float64 planes of columns 0-2
+  float *d_grid = nullptr, *d_label = nullptr, *d_result = nullptr;   // image [n][npix][3], label plane [n][npix], field [n][npix]
+  double* d_truth = nullptr;            // [n][npix]
+  float* d_res = nullptr;               // [round_up(n * B, 32)][ld_out] network output rows of the step's frames, for the block stage
+  double *d_part = nullptr, *d_fraw = nullptr;   // block partials [n][B][8]; the field's sums [n][8] in front of the fold
+  double *d_raw = nullptr, *h_raw = nullptr;     // [n][2][8], device and pinned (host entry)
+  float* h_result = nullptr;            // pinned [n][npix]
+  double* h_truth = nullptr;            // pinned [n][npix]
+  double *d_u2 = nullptr, *h_u2 = nullptr;       // U^2 of the step's frames [n]; pinned upload ring [RING][n]
+  hipEvent_t u2_ev[RING] = {};
+  int u2_pos = 0;
+};
 }  // namespace psm_impl
 using namespace psm_impl;
 
@@ -299,6 +335,7 @@ struct psm_handle {
   PostSet post;                         // Gaussian post-steps on the planned grid (psm_bind_poststeps)
   FeatureSet feat;                      // Poisson input features on the planned grid (psm_bind_features)
   FrameSet frames;                      // frame batch on the single mesh (psm_bind_frames)
+  DeltasSet deltas;                     // the deltas evaluator's frame batch behind it (psm_bind_deltas_frames)
   double maxs[4] = {1, 1, 1, 1};
   int normalise_sdf = 0, fill_input = 0;
   double case_maxs[4] = {1, 1, 1, 1}, case_delta = 5e-3, case_wall = 0.05;   // psm_set_case (PM:106-109, 195, 494)
@@ -436,6 +473,9 @@ int poststeps_device(psm_handle* h, const float* d_fields, int n_cases, const Po
 int post_check(psm_handle* h, int n_cases, const PostCall& pc);
 void feat_free(FeatureSet& s);
 void frames_free(psm_handle* h);
+void deltas_free(psm_handle* h);
+int frames_state(psm_handle* h);
+int frames_count_check(psm_handle* h, int n_frames);
 int frames_device(psm_handle* h, const FrameCall& fc, int n_frames, hipStream_t st);
 int poisson_frame_call(psm_handle* h, const double* d_cols, int n_frames, int k, int weighting, double* d_extra, FrameCall& fc);
 int field_errors_device(psm_handle* h, const PsmFieldErrorArgs& stage, double* d_raw, hipStream_t st);
@@ -464,10 +504,12 @@ PsmToMeshArgs to_mesh_args(const psm_handle* h, const double* d_umax, double uma
 // d_p != nullptr: the bound integration (psm_bind_integration) of d_fields into d_p follows in the same stream / the same graph;
 // post (apply_filter >= 0): the bound post-steps (psm_bind_poststeps) of d_fields follow likewise;
 // feat (vel != nullptr): the bound features (psm_bind_features) write d_grid == feat->grid in front of the solve, likewise;
-// frames (with feat): the mesh -> grid launch of psm_poisson_frames* writes feat->vel (and the post-steps' inputs) in front of the features
+// frames (with feat): the mesh -> grid launch of psm_poisson_frames* writes feat->vel (and the post-steps' inputs) in front of the features;
+// deltas (with frames, without feat): the image pack of psm_deltas_frames* turns the planes the mesh -> grid launch wrote into d_grid
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
                  hipStream_t st, hipEvent_t* prof, float* d_p = nullptr, const PostCall* post = nullptr, const FeatCall* feat = nullptr,
-                 const FrameCall* frames = nullptr);
+                 const FrameCall* frames = nullptr, const DeltasCall* deltas = nullptr);
+int deltas_pack_device(psm_handle* h, const DeltasCall& dc, int n_frames, hipStream_t st);
 bool guard_take(psm_handle* h, Workspace& w);
 int guard_drop(psm_handle* h, const char* where);
 int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases = 1);

@@ -65,6 +65,23 @@ struct PsmFrameArgs {
 };
 hipError_t psm_launch_frames_to_grid(const PsmFrameArgs& a, hipStream_t st);
 
+// ---- the image pack of the deltas evaluator's frame batch (psm_deltas_image_device): the float64 planes the launch above leaves for
+// columns 0-2 (dUx / U, dUy / U, dp / U^2; NaNs of interpolate_fill kept) -> the solve's image, the label plane and the truth plane,
+// the statements of pressureSM_deltas/SM_call.py:439-445 and :580 per pixel.  One launch, the frame is launch dimension y.
+struct PsmDeltasPackArgs {
+  const double* planes;         // [n_frames][3][npix]
+  const double* sdn;            // [npix] nan0(sdfunct) / max_abs_dist of the simulation, shared by the frames (float64, made at bind)
+  const double* u2;             // [n_frames] U_max_norm^2 of the frame (read only with truth)
+  float* grid;                  // [n_frames][npix][3] = (float)(nan0(v) / max_abs) per channel, channel 2 = (float)sdn
+  float* label;                 // [n_frames][npix]    = (float)(nan0(v2) / max_abs_p); nullptr: not stored
+  double* truth;                // [n_frames][npix]    = (nan0(v2) / max_abs_p) * max_abs_p * u2[f], left to right; nullptr: not stored
+  int64_t npix;
+  double max_abs_ux, max_abs_uy, max_abs_p;
+  int n_frames;
+};
+constexpr int PSM_DELTAS_PACK_SPAN = 1024;   // pixels per workgroup: 256 threads x 4 consecutive pixels
+hipError_t psm_launch_deltas_pack(const PsmDeltasPackArgs& a, hipStream_t st);
+
 // ---- the mesh ends for a case batch (psm_set_geometry_cases): K meshes on one planned grid, the case is launch dimension y.
 // Cell-side arrays are the cases' concatenated ([sum n_i, ...], case i at rows cell_off[i] .. cell_off[i + 1]), grid-side tables
 // are [K][n_grid, ...]; vertex indices are case-local as the caller gave them (the kernels add the case's offset).

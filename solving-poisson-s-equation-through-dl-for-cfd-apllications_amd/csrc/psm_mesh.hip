@@ -327,6 +327,82 @@ hipError_t psm_launch_frames_to_grid(const PsmFrameArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// The image pack of the deltas evaluator's frame batch (PsmDeltasPackArgs in psm_mesh.h): what Evaluation.timeStep does on the host
+// between psm_mesh_to_grid and the solve, per pixel and in its order -- NaN -> 0, the division by max_abs in float64, then the float32
+// cast of the solve's entry (SM_call.py:439-445) -- and the frame's truth image (:580).  Two float64 multiplications in a row and no
+// addition: nothing for the compiler to contract, and IEEE division, so the three outputs hold the bits of the NumPy statements.
+// HBM-bound stream: frame blockIdx.y, a thread takes 4 consecutive pixels -- two 16-byte loads per float64 plane, three 16-byte
+// stores of the 12 image floats, one of the labels, two of the truths where the frame's plane starts 16-byte aligned; else (odd
+// plane sizes, shifted destinations, the tail) one access per element.  The values do not depend on the path.
+typedef float psm_pack_f4 __attribute__((ext_vector_type(4)));
+typedef double psm_pack_d2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void pack_load4(const double* p, int64_t pix, int n, bool vec, double (&v)[4]) {
+  if (vec) {
+    const psm_pack_d2 q0 = *reinterpret_cast<const psm_pack_d2*>(p + pix), q1 = *reinterpret_cast<const psm_pack_d2*>(p + pix + 2);
+    v[0] = q0.x; v[1] = q0.y; v[2] = q1.x; v[3] = q1.y;
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = e < n ? p[pix + e] : 0.0;
+}
+
+__device__ __forceinline__ bool pack_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmDeltasPackArgs a) {
+  const int64_t frame = blockIdx.y;
+  const int64_t pix = (int64_t)blockIdx.x * PSM_DELTAS_PACK_SPAN + threadIdx.x * 4;
+  if (pix >= a.npix) return;
+  const int n = (int)min((int64_t)4, a.npix - pix);
+  const double* pl = a.planes + frame * 3 * a.npix;
+  double v0[4], v1[4], v2[4], sd[4];
+  pack_load4(pl, pix, n, n == 4 && pack_aligned(pl), v0);
+  pack_load4(pl + a.npix, pix, n, n == 4 && pack_aligned(pl + a.npix), v1);
+  pack_load4(pl + 2 * a.npix, pix, n, n == 4 && pack_aligned(pl + 2 * a.npix), v2);
+  pack_load4(a.sdn, pix, n, n == 4 && pack_aligned(a.sdn), sd);
+  float g[12], lb[4];
+  double tr[4];
+  const double u2 = a.truth ? a.u2[frame] : 0.0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const double x = (v0[e] != v0[e] ? 0.0 : v0[e]) / a.max_abs_ux;
+    const double y = (v1[e] != v1[e] ? 0.0 : v1[e]) / a.max_abs_uy;
+    const double p = (v2[e] != v2[e] ? 0.0 : v2[e]) / a.max_abs_p;
+    g[3 * e] = (float)x; g[3 * e + 1] = (float)y; g[3 * e + 2] = (float)sd[e];
+    lb[e] = (float)p;
+    const double pm = p * a.max_abs_p;
+    tr[e] = pm * u2;
+  }
+  float* go = a.grid + (frame * a.npix + pix) * 3;
+  if (n == 4 && pack_aligned(go)) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) reinterpret_cast<psm_pack_f4*>(go)[q] = psm_pack_f4{g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]};
+  } else {
+    for (int e = 0; e < 3 * n; ++e) go[e] = g[e];
+  }
+  if (a.label) {
+    float* lo = a.label + frame * a.npix + pix;
+    if (n == 4 && pack_aligned(lo)) *reinterpret_cast<psm_pack_f4*>(lo) = psm_pack_f4{lb[0], lb[1], lb[2], lb[3]};
+    else for (int e = 0; e < n; ++e) lo[e] = lb[e];
+  }
+  if (a.truth) {
+    double* to = a.truth + frame * a.npix + pix;
+    if (n == 4 && pack_aligned(to)) {
+      reinterpret_cast<psm_pack_d2*>(to)[0] = psm_pack_d2{tr[0], tr[1]};
+      reinterpret_cast<psm_pack_d2*>(to)[1] = psm_pack_d2{tr[2], tr[3]};
+    } else {
+      for (int e = 0; e < n; ++e) to[e] = tr[e];
+    }
+  }
+}
+
+hipError_t psm_launch_deltas_pack(const PsmDeltasPackArgs& a, hipStream_t st) {
+  if (a.n_frames < 1 || a.npix < 1 || !a.planes || !a.sdn || !a.grid || (a.truth && !a.u2)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmDeltasPackArgs)>(psm_to_grid_kernel),
+                     dim3((unsigned)((a.npix + PSM_DELTAS_PACK_SPAN - 1) / PSM_DELTAS_PACK_SPAN), (unsigned)a.n_frames), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(psm_to_mesh_kernel, dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
   return hipGetLastError();

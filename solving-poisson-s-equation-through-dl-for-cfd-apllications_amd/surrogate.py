@@ -585,7 +585,7 @@ class GridSurrogate:
             raise ValueError(f"tables must be [{npix},3], [{npix},3], [{npix},2] and sdfunct [{self.ny},{self.nx}]")
         mx = _f64(np.asarray(maxs, np.float64).reshape(-1)[:4])
         self.mesh_cells = None
-        self._frames_bound = self._feat_bound = self._post_bound = False
+        self._frames_bound = self._feat_bound = self._post_bound = self._deltas_bound = False
         self._bound_mask = self._bound_sdf = None
         self._chk(self.lib.psm_set_geometry(self.h, int(n_cells), self.ny, self.nx, _p(v, C.c_int32), _p(w, C.c_double),
                                             _p(idx, C.c_int32), _p(sdf, C.c_double), None, None, _p(mx, C.c_double), 1, 1, 0.05))
@@ -594,12 +594,12 @@ class GridSurrogate:
     def bind_frames(self, n_frames: int, k: int):
         """Staging for ``n_frames`` (<= max_cases) frames of ``k`` (<= 16) cell columns on the handle's mesh: after it a batch
         allocates nothing."""
-        self._frames_bound = False
+        self._frames_bound = self._deltas_bound = False
         self._chk(self.lib.psm_bind_frames(self.h, int(n_frames), int(k)))
         self._frames_bound = True
 
     def unbind_frames(self):
-        self._frames_bound = False
+        self._frames_bound = self._deltas_bound = False
         self._chk(self.lib.psm_unbind_frames(self.h))
 
     def frames_to_grid_device(self, d_cols: int, n_frames: int, k: int, outs, fill: bool = True, stream: int = 0):
@@ -761,6 +761,137 @@ class GridSurrogate:
                                                      _p(sc, C.c_float) if sc is not None else None, int(bool(apply_filter)), 1,
                                                      _p(raw, C.c_double)))
         return raw
+
+    # -- the frame batch of the pressureSM_deltas evaluator on the device: columns -> image, label, truth -> solve -> two error blocks
+    _deltas_bound = False
+
+    def bind_deltas_frames(self, sdfunct, max_abs):
+        """After ``bind_frames``, on a three-channel model with the SDF last and a one-channel field: the simulation's raw SDF plane
+        ``sdfunct`` [Ny,Nx] float64 (NaNs allowed) and ``max_abs`` = (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p), each finite
+        and non-zero.  Reserves everything a step touches for the frame count bound with ``bind_frames``."""
+        m = self.model
+        if m.c_in != 3 or m.sdf_ch != 2 or m.c_out != 1:
+            raise ValueError("the deltas frames take a model with 3 input channels, the SDF in channel 2, and 1 output channel")
+        if not getattr(self, "_frames_bound", False):
+            raise RuntimeError("bind_frames has not been called")
+        sdf = _f64(sdfunct)
+        if sdf.size != self.ny * self.nx:
+            raise ValueError(f"sdfunct must be [{self.ny},{self.nx}]")
+        mx = _f64(np.asarray(max_abs, np.float64).reshape(-1))
+        if mx.size != 4 or not np.all(np.isfinite(mx)) or np.any(mx == 0):
+            raise ValueError("max_abs must hold four finite non-zero scales: (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p)")
+        self._deltas_bound = False
+        self._chk(self.lib.psm_bind_deltas_frames(self.h, _p(sdf, C.c_double), _p(mx, C.c_double)))
+        self._deltas_bound = True
+
+    def unbind_deltas_frames(self):
+        self._deltas_bound = False
+        self._chk(self.lib.psm_unbind_deltas_frames(self.h))
+
+    def _deltas_call(self, n_frames, k, U2, need_u2: bool = True):
+        """The argument checks the deltas frame entries share -> U2 as a float64 array (None where it is optional and absent)."""
+        if not self._deltas_bound:
+            raise RuntimeError("bind_deltas_frames has not been called (bind_frames and a new mesh drop the binding)")
+        if not 3 <= int(k) <= 16:
+            raise ValueError("frames take 3..16 columns: (dUx / U, dUy / U, dp / U^2), further columns are not stored")
+        if not 1 <= int(n_frames) <= self.max_cases:
+            raise ValueError("n_frames outside [1, max_cases]")
+        if U2 is None:
+            if need_u2:
+                raise ValueError("U2 must hold one value per frame")
+            return None
+        u2 = _f64(np.asarray(U2, np.float64).reshape(-1))
+        if u2.size != int(n_frames) or not np.all(np.isfinite(u2)):
+            raise ValueError("U2 must hold one finite value per frame")
+        return u2
+
+    @staticmethod
+    def _dev_ptr(ptr, align: int, what: str, optional: bool = False) -> int:
+        if not ptr:
+            if not optional:
+                raise ValueError(f"{what} must be a device pointer")
+            return 0
+        if int(ptr) % align:
+            raise ValueError(f"{what} must be {align}-byte aligned")
+        return int(ptr)
+
+    def _frame_scale(self, out_scale, n: int):
+        if out_scale is None:
+            return None
+        if np.size(out_scale) not in (1, n):
+            raise ValueError("out_scale must hold one value per frame")
+        return _f32(np.broadcast_to(np.asarray(out_scale, np.float32).reshape(-1), (n,)))
+
+    def deltas_image_device(self, d_cols: int, n_frames: int, k: int, U2, d_grid: int, d_label: int = 0, d_truth: int = 0, stream: int = 0):
+        """The image stage alone on raw device pointers, asynchronous on ``stream``: ``d_cols`` [n,n_cells,k] float64 -> ``d_grid``
+        [n,Ny,Nx,3] float32, ``d_label`` [n,Ny*Nx] float32 and ``d_truth`` [n,Ny*Nx] float64 (0: not stored), bit for bit the host
+        statements of ``Evaluation.timeStep``.  ``U2`` [n]: U_max_norm^2 per frame (None without ``d_truth``)."""
+        u2 = self._deltas_call(n_frames, k, U2, need_u2=bool(d_truth))
+        d_cols = self._dev_ptr(d_cols, 8, "d_cols")
+        d_grid, d_label = self._dev_ptr(d_grid, 4, "d_grid"), self._dev_ptr(d_label, 4, "d_label", True)
+        d_truth = self._dev_ptr(d_truth, 8, "d_truth", True)
+        self._chk(self.lib.psm_deltas_image_device(self.h, C.c_void_p(d_cols), int(n_frames), int(k), _p(u2, C.c_double) if u2 is not None else None,
+                                                   C.c_void_p(d_grid), C.c_void_p(d_label or None), C.c_void_p(d_truth or None), C.c_void_p(stream)))
+
+    def block_errors_device(self, d_grid: int, d_label: int, n_frames: int, d_raw: int, stream: int = 0):
+        """``utils.compute_in_block_error`` for the first ``n_frames`` cases of the LAST synchronous or device solve, on raw device
+        pointers, asynchronous on ``stream``: the decoded blocks against the de-meaned label blocks of ``d_label`` [n,Ny*Nx] float32
+        times the solve's row scale, over the flow cells of ``d_grid`` [n,Ny,Nx,3].  ``d_raw`` [n,8] float64 = ``RAW_SUMS``."""
+        if not self._deltas_bound:
+            raise RuntimeError("bind_deltas_frames has not been called (bind_frames and a new mesh drop the binding)")
+        if not 1 <= int(n_frames) <= self.max_cases:
+            raise ValueError("n_frames outside [1, max_cases]")
+        d_grid, d_label = self._dev_ptr(d_grid, 4, "d_grid"), self._dev_ptr(d_label, 4, "d_label")
+        d_raw = self._dev_ptr(d_raw, 8, "d_raw")
+        self._chk(self.lib.psm_block_errors_device(self.h, C.c_void_p(d_grid), C.c_void_p(d_label), int(n_frames), C.c_void_p(d_raw), C.c_void_p(stream)))
+
+    def deltas_frames_device(self, d_cols: int, n_frames: int, k: int, U2, d_result: int = 0, d_truth: int = 0, d_raw: int = 0,
+                             apply_filter: bool = False, stream: int = 0, out_scale: Optional[Sequence[float]] = None):
+        """The deltas evaluator's frames as one graph replay on raw device pointers: ``d_cols`` [n,n_cells,k] float64 -> planes ->
+        image -> one single-case solve per frame (-> the ``sigma_field`` filter of ``bind_poststeps`` with ``apply_filter``) -> ``d_result`` [n,Ny*Nx] float32,
+        ``d_truth`` [n,Ny*Nx] float64 (0: the binding's buffers); with ``d_raw`` [n,2,8] float64 the two error blocks behind it:
+        row 0 the field against the truth, row 1 the decoded blocks against the de-meaned label blocks."""
+        u2 = self._deltas_call(n_frames, k, U2)
+        if apply_filter and not getattr(self, "_post_bound", False):
+            raise RuntimeError("apply_filter needs bind_poststeps")
+        d_cols = self._dev_ptr(d_cols, 8, "d_cols")
+        d_result, d_truth = self._dev_ptr(d_result, 4, "d_result", True), self._dev_ptr(d_truth, 8, "d_truth", True)
+        d_raw = self._dev_ptr(d_raw, 8, "d_raw", True)
+        sc = self._frame_scale(out_scale, int(n_frames))
+        self._chk(self.lib.psm_deltas_frames_device(self.h, C.c_void_p(d_cols), int(n_frames), int(k), _p(u2, C.c_double),
+                                                    _p(sc, C.c_float) if sc is not None else None, int(bool(apply_filter)),
+                                                    C.c_void_p(d_result or None), C.c_void_p(d_truth or None), C.c_void_p(d_raw or None),
+                                                    C.c_void_p(stream)))
+
+    def deltas_frames(self, cols: np.ndarray, U2, out_scale: Optional[Sequence[float]] = None, apply_filter: bool = False,
+                      want_result: bool = True, want_truth: bool = True, want_raw: bool = True):
+        """Host buffers, synchronous: ``cols`` [n,n_cells,k] (or [n_cells,k]) float64 -> (result [n,Ny,Nx] float32, truth [n,Ny,Nx]
+        float64, raw [n,2,8] float64); what is not wanted is None and is not copied back -- a metrics-only sweep
+        (``want_result = want_truth = False``) brings back 16 doubles per frame."""
+        v = np.asarray(cols)
+        if v.ndim == 2:
+            v = v[None]
+        if v.ndim != 3:
+            raise ValueError("cols must be [n,n_cells,k]")
+        n, n_cells, k = v.shape
+        u2 = self._deltas_call(n, k, U2)
+        if self.mesh_cells is None:
+            raise RuntimeError("the handle holds no mesh (set_mesh / computeOnlyOnce)")
+        if n_cells != self.mesh_cells:
+            raise ValueError(f"cols must be [n >= 1, {self.mesh_cells} cells, k]")
+        if not (want_result or want_truth or want_raw):
+            raise ValueError("nothing to return")
+        if apply_filter and not getattr(self, "_post_bound", False):
+            raise RuntimeError("apply_filter needs bind_poststeps")
+        sc = self._frame_scale(out_scale, n)
+        v = _f64(v)
+        result = np.empty((n, self.ny, self.nx), np.float32) if want_result else None
+        truth = np.empty((n, self.ny, self.nx), np.float64) if want_truth else None
+        raw = np.empty((n, 2, len(self.RAW_SUMS)), np.float64) if want_raw else None
+        opt = lambda a, t: _p(a, t) if a is not None else None
+        self._chk(self.lib.psm_deltas_frames(self.h, _p(v, C.c_double), n, k, _p(u2, C.c_double), opt(sc, C.c_float), int(bool(apply_filter)),
+                                             opt(result, C.c_float), opt(truth, C.c_double), opt(raw, C.c_double)))
+        return result, truth, raw
 
     @classmethod
     def metrics_from_sums(cls, raw) -> dict:
@@ -938,9 +1069,14 @@ class Evaluation:
     max_frames = 1                  # case slots of the surrogate (EvaluationPoisson: frames one timeSteps call sends at once)
 
     def __init__(self, delta, shape, overlap, var_p, var_in, dataset_path, model_path, max_num_PC,
-                 standardization_method, model: SurrogateModel = None, device: int = 0, artifact_dir: str = None):
+                 standardization_method, model: SurrogateModel = None, device: int = 0, artifact_dir: str = None,
+                 max_frames: int = None):
         if standardization_method not in ("std", "min_max", "max_abs"):
             raise ValueError("Standardization method not valid")
+        if max_frames is not None:
+            if int(max_frames) < 1:
+                raise ValueError("max_frames must be at least 1")
+            self.max_frames = int(max_frames)                    # the surrogate's max_cases: frames one timeSteps call sends at once
         self.maxs = None
         if model is None:
             # like the reference: `maxs`, `ipca_input.pkl`, `ipca_p.pkl` and the scaler files are read from
@@ -987,7 +1123,7 @@ class Evaluation:
         sur._chk(sur.lib.psm_set_geometry(sur.h, int(self.indice), t.ny, t.nx, _p(v1, C.c_int32), _p(w1, C.c_double),
                                           _p(idx, C.c_int32), _p(sdf, C.c_double), None, None, _p(mx, C.c_double), 1, 1, 0.05))
         sur.mesh_cells = int(self.indice)
-        sur._frames_bound = sur._feat_bound = sur._post_bound = False      # the new plan dropped them
+        sur._frames_bound = sur._feat_bound = sur._post_bound = sur._deltas_bound = False      # the new plan dropped them
         self.tables = t
         self._bind_simulation_geometry(sur, t.sdfunct, float(mx[2]))
         return 0
@@ -995,7 +1131,8 @@ class Evaluation:
     def _bind_simulation_geometry(self, sur, sdfunct: np.ndarray, max_abs_dist: float):
         """computeOnlyOnce fixes the obstacle for every timeStep of the simulation: bind its flow-cell pattern (the SDF
         channel exactly as timeStep normalises it) so that the steps take the 6-launch path.  Grids of another
-        geometry passed to timeStep_grid drop the binding again (GridSurrogate._check_bound)."""
+        geometry passed to timeStep_grid drop the binding again (GridSurrogate._check_bound).  The frames of ``timeSteps`` are solved one by
+        one inside their call, so they take this single-case binding too."""
         g = np.zeros((sur.ny, sur.nx, self.artifacts.c_in), np.float32)
         sd = np.asarray(sdfunct, np.float64) / max_abs_dist
         g[..., self.artifacts.sdf_ch] = np.where(np.isnan(sd), 0.0, sd).astype(np.float32)
@@ -1058,6 +1195,82 @@ class Evaluation:
         self.U_max_norm = float(U_max_norm)
         self._record_errors(res, self.cfd_results, self.no_flow_bool)
         return res
+
+    FRAME_COLUMNS = 3               # dUx / U, dUy / U, dp / U^2 (the label column)
+
+    def _bind_frames(self, sur, apply_filter: bool):
+        """What timeSteps needs on the handle, once per computeOnlyOnce (whose new plan drops them): the frame staging, the deltas
+        binding with the simulation's SDF plane, and the post-steps (SM_call.py:353) when a filtered field is asked for."""
+        if apply_filter and not sur._post_bound:
+            sur.bind_poststeps((10, 10), (50, 50))
+        if getattr(self, "_frames_tables", None) is self.tables and sur._frames_bound and sur._deltas_bound:
+            return
+        sur.bind_frames(self.max_frames, self.FRAME_COLUMNS)
+        sur.bind_deltas_frames(self.sdfunct[..., 0], [float(v) for v in self.maxs[:4]])
+        self._frames_tables = self.tables
+
+    def timeSteps(self, sim, times, apply_filter=False, fields=True):
+        """``timeStep`` for several frames of one simulation, the relevant ones sent ``max_frames`` at a time as ONE call each
+        (``deltas_frames``: cell columns -> planes -> image -> solve -> filter -> both error blocks on the device).  The per-frame
+        host scalars and the skip rule are those of ``timeStep``; ``pred_minus_true*``, ``pred_minus_true*_block`` and
+        ``last_metrics`` are filled in frame order.  Returns the list of delta-p images with 0 for an irrelevant frame; afterwards
+        ``cfd_results``, ``no_flow_bool`` and ``U_max_norm`` hold what ``timeStep`` leaves on the last relevant frame (``grid`` and
+        the weighting planes are not produced).  The block errors come from the device sums in either mode.
+        ``fields=False``: a metrics-only sweep -- nothing but the sums comes back, the field's metrics are taken from them too, the
+        return is one ``{'delta_p': metrics, 'blocks': metrics}`` dict per frame (0 for an irrelevant frame) and ``cfd_results`` is
+        None."""
+        from . import formats
+        if getattr(self, "tables", None) is None:
+            raise RuntimeError("computeOnlyOnce has not been called")
+        times = [int(t) for t in times]
+        out, cols, Us, slot = [0] * len(times), [], [], []
+        for i, time in enumerate(times):
+            data, _, _ = formats.read_dataset(self.dataset_path, sim, time)
+            d = data[0, 0, :self.indice]                  # float32 like the file: the reference normalises in float32
+            Ux, Uy = d[:, 0:1], d[:, 1:2]
+            delta_U, delta_p = d[:, 5:7], d[:, 7:8]
+            U_max_norm = np.max(np.sqrt(np.square(Ux) + np.square(Uy)))                      # :407
+            deltaU_max_norm = np.max(np.sqrt(np.square(delta_U[:, 0:1]) + np.square(delta_U[:, 1:2])))
+            if (deltaU_max_norm / U_max_norm) < 1e-4:                                       # :413-421
+                continue
+            cols.append(np.concatenate([delta_U / U_max_norm, delta_p / pow(U_max_norm, 2.0)], axis=1).astype(np.float64))
+            Us.append(U_max_norm)
+            slot.append(i)
+        if not cols:
+            return out
+        sur = self._surrogate(self.grid_shape_y, self.grid_shape_x)
+        self._bind_frames(sur, apply_filter)
+        max_abs_dist, max_abs_p = float(self.maxs[2]), float(self.maxs[3])
+        self.max_abs_p = max_abs_p
+        sd = np.nan_to_num(np.asarray(self.sdfunct[..., 0], np.float64), nan=0.0) / max_abs_dist
+        self.no_flow_bool = sd == 0
+        if not isinstance(getattr(self, "last_metrics", None), dict):
+            self.last_metrics = {}
+        for name in ("pred_minus_true_block", "pred_minus_true_squared_block"):
+            if not hasattr(self, name):
+                setattr(self, name, [])
+        for c0 in range(0, len(cols), self.max_frames):
+            chunk, U_chunk = np.stack(cols[c0:c0 + self.max_frames]), Us[c0:c0 + self.max_frames]
+            res, truth, raw = sur.deltas_frames(chunk, [float(pow(U, 2.0)) for U in U_chunk],       # :580 (float32 square, like the reference)
+                                                out_scale=[max_abs_p * U ** 2 for U in U_chunk], apply_filter=apply_filter,
+                                                want_result=fields, want_truth=fields)
+            for j, U in enumerate(U_chunk):
+                self.U_max_norm = float(U)
+                mb = sur.metrics_from_sums(raw[j, 1])                                          # :553-557, before the assembly
+                mb.update(norm_pred=float(raw[j, 1, 6] - raw[j, 1, 5]), n=int(raw[j, 1, 0]))
+                self.pred_minus_true_block.append(mb["mean_err"])
+                self.pred_minus_true_squared_block.append(mb["mean_sq_err"])
+                self.last_metrics["blocks"] = mb
+                if fields:
+                    self.cfd_results = truth[j]
+                    m = self._record_errors(res[j], self.cfd_results, self.no_flow_bool)
+                    out[slot[c0 + j]] = res[j]
+                else:
+                    m = self._record_metrics(sur.metrics_from_sums(raw[j, 0]))
+                    out[slot[c0 + j]] = {"delta_p": m, "blocks": mb}
+        if not fields:
+            self.cfd_results = None
+        return out
 
     print_metrics = False           # True: print the per-frame error block like the reference's timeStep does
 
@@ -1132,14 +1345,19 @@ class Evaluation:
 
 def call_SM_main(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num_PC, dataset_path,
                  plot_intermediate_fields=False, standardization_method="std", save_plots=False, show_plots=False,
-                 apply_filter=False, create_GIF=False, n_sims=1, n_ts=1, device: int = 0, artifact_dir: str = None):
+                 apply_filter=False, create_GIF=False, n_sims=1, n_ts=1, device: int = 0, artifact_dir: str = None,
+                 frames_per_call: int = 1, fields: bool = True):
     """``pressureSM_deltas.SM_call.call_SM_main`` (SM_call.py:778-900): evaluate ``n_ts`` frames of ``n_sims``
     simulations of the dataset and return the error summary the reference prints -- per simulation and overall
     BIAS / STDE / RMSE [%] of delta-p over the flow cells, and BIAS_block / RSME_block / STDE_block [%] of the decoded blocks
-    before the assembly (SM_call.py:824-826, from ``utils.compute_in_block_error``); plots and GIFs are not produced."""
+    before the assembly (SM_call.py:824-826, from ``utils.compute_in_block_error``); plots and GIFs are not produced.
+    ``frames_per_call`` > 1: the frames of a simulation go through ``Evaluation.timeSteps``, that many per call, instead of one
+    ``timeStep`` each.  ``fields=False``: the same summary from ``timeSteps(..., fields=False)``, whose error sums are taken on the
+    device: no field is copied back."""
     overlap = int(overlap_ratio * shape)
+    batched = frames_per_call > 1 or not fields
     ev = Evaluation(delta, shape, overlap, var_p, var_in, dataset_path, model_name, max_num_PC, standardization_method,
-                    device=device, artifact_dir=artifact_dir)
+                    device=device, artifact_dir=artifact_dir, max_frames=frames_per_call)
     ev.pred_minus_true, ev.pred_minus_true_squared = [], []
     ev.pred_minus_true_block, ev.pred_minus_true_squared_block = [], []
 
@@ -1148,7 +1366,9 @@ def call_SM_main(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num
     for sim in range(n_sims):
         n0 = len(ev.pred_minus_true)
         ev.computeOnlyOnce(sim)
-        for time in range(n_ts):
+        if batched:
+            ev.timeSteps(sim, range(n_ts), apply_filter, fields=fields)
+        for time in range(0 if batched else n_ts):
             ev.timeStep(sim, time, plot_intermediate_fields, save_plots, show_plots, apply_filter)
         if len(ev.pred_minus_true) > n0:
             s = summary(ev.pred_minus_true[n0:], ev.pred_minus_true_squared[n0:])
