@@ -586,6 +586,52 @@ int psm_deltas_frames_device(psm_handle* h, const double* d_cols, int32_t n_fram
 int psm_deltas_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, const double* U2, const float* out_scale,
                       int32_t apply_filter, float* result, double* truth, double* raw);
 
+/* The frame batch of the U_to_gradP evaluator (Eval_dual_Dense_onlycil.py:418-687) on the device: cell columns -> planes -> the
+ * solve's image and the three label planes -> solve (-> filter) -> integration into p -> the frame's four error blocks, without an
+ * image, a label or a field leaving the device.  Columns of a frame: (Ux / U, Uy / U, dPdx (max_x - min_x) / U^2,
+ * dPdy (max_y - min_y) / U^2, p / U^2, ...); columns beyond 4 are not stored.  No dimensional scale enters.
+ * psm_bind_gradp_frames: after psm_bind_frames, on a three-channel image with the SDF last and a two-channel field (c_in == 3,
+ * sdf_channel == 2, c_out == 2; PSM_ERR_STATE otherwise, and without a frame binding).  sdfunct [ny*nx] float64 is the simulation's
+ * raw SDF plane (NaNs allowed), max_abs [5] the scales of grid channels 0-4, each finite and non-zero (PSM_ERR_ARG).  (center_y,
+ * center_x), dx, dy: the cut and the spacings of psm_set_integration, fixed for the simulation; the tables are built once, into a set
+ * of the binding's own, one geometry for every frame -- psm_bind_integration / psm_set_integration neither see nor change them, and
+ * any frame count up to the bound one integrates.  PSM_ERR_UNSUPPORTED where the reference itself raises (see psm_set_integration);
+ * then, as after every error, nothing is bound.  Keeps nan0(sdfunct) / max_abs[2] in float64 on the device -- channel 2 of every
+ * image, and the mask of the field errors (flow cell iff != 0) -- and reserves planes, image, labels, gradient, p, raw sums and
+ * pinned slots for the frame count bound with psm_bind_frames: after it a step allocates nothing.  psm_bind_frames /
+ * psm_unbind_frames, a new mesh, psm_plan_grid or a model change drop the binding. */
+int psm_bind_gradp_frames(psm_handle* h, const double* sdfunct, const double* max_abs, int32_t center_y, int32_t center_x, double dx,
+                          double dy);
+int psm_unbind_gradp_frames(psm_handle* h);
+/* The image stage alone: psm_frames_to_grid_device (fill = 1) of columns 0-4 into the binding's planes, then one pack launch:
+ *     d_grid  [n][ny][nx][3] float32 = ((float)(nan0(v_0) / max_abs_0), (float)(nan0(v_1) / max_abs_1), (float)(nan0(sdfunct) / max_abs_2))
+ *     d_truth [n][3][ny*nx]  float64 = (nan0(v_2) / max_abs_3, nan0(v_3) / max_abs_4, nan0(v_4))             (NULL: not stored)
+ * -- grid channels 3, 4 and 5 of the reference, the pressure label not divided (:463-467 loops over range(5)); divisions in float64,
+ * the cast behind them: the bits of the reference's NumPy statements.  Device pointers aligned to their element, asynchronous on
+ * `stream` (NULL: the handle's).  PSM_ERR_ARG and nothing enqueued: k outside [5, 16], n_frames outside [1, bound count], d_cols or
+ * d_grid NULL, a misaligned destination. */
+int psm_gradp_image_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, float* d_grid, double* d_truth, void* stream);
+/* The whole step as ONE graph replay: planes -> image and labels -> solve (-> the sigma_field filter of psm_bind_poststeps on both
+ * gradient components with apply_filter != 0, in place of the unfiltered gradient; PSM_ERR_STATE without that binding) -> the two
+ * integration launches for the batch with the binding's tables.  Inside it the frames are solved one by one, each as the single
+ * case the evaluator's per-frame call solves -- with a geometry bound for ONE case (psm_bind_geometry) the 6-launch route --, so a
+ * frame's gradient holds the bits of psm_solve_grid (psm_solve_poststeps) on its image whatever the batch, and its p the bits of
+ * psm_integrate_gradp of that gradient (psm_read_stage then shows the last frame's solve).  Then, with d_raw != NULL, the two
+ * launches of psm_field_errors_device on the same stream, over the cells with nan0(sdfunct) / max_abs_2 != 0, that leave d_raw
+ * [n_frames][4][8]: row 0 = p against label plane 0 (the reference's own metric, :667-687: its "true" values are grid channel 3),
+ * row 1 = p against label plane 2 (the pressure label), rows 2 and 3 = gradient components 0 and 1 against label planes 0 and 1.
+ * d_gradp [n][ny*nx][2] float32 (8-byte aligned), d_p [n][ny*nx] float32 and d_truth [n][3][ny*nx] float64 may be NULL: the
+ * binding's buffers are used.  out_scale [n_frames] is a HOST array copied before return (NULL: 1, what the evaluator passes).
+ * PSM_ERR_ARG and nothing enqueued: k outside [5, 16], n_frames outside [1, bound count], d_cols NULL, a misaligned destination
+ * (8 bytes for d_gradp, d_truth and d_raw, 4 for d_p). */
+int psm_gradp_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const float* out_scale,
+                            int32_t apply_filter, float* d_gradp, float* d_p, double* d_truth, double* d_raw, void* stream);
+/* host buffers, synchronous: one H2D of cols (k at most the count bound with psm_bind_frames), D2H of what is non-NULL only --
+ * gradp [n][ny*nx][2] float32, p [n][ny*nx] float32, truth [n][3][ny*nx] float64, raw [n][4][8] (at least one of them).  Solves
+ * again on the general path after a guard trip, like psm_deltas_frames. */
+int psm_gradp_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, const float* out_scale, int32_t apply_filter,
+                     float* gradp, float* p, double* truth, double* raw);
+
 /* U_to_gradP: integrate the assembled (dp/dx, dp/dy) into p (integrate_field,
  * Eval_dual_Dense_onlycil.py:371-416, and the four-quadrant stitching :597-628).
  * psm_set_integration fixes the geometry: sdfunct [ny*nx] (self.sdfunct[:,:,0], also used by the

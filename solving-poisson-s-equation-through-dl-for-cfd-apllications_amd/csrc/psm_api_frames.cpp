@@ -13,7 +13,8 @@ static void drop_frame_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphK
 
 void frames_free(psm_handle* h) {
   FrameSet& s = h->frames;
-  deltas_free(h);                       // psm_bind_deltas_frames stands on this binding
+  deltas_free(h);                       // psm_bind_deltas_frames stands on this binding,
+  gradp_free(h);                        // and psm_bind_gradp_frames
   drop_frame_graphs(h);
   dev_free(s.d_cols); dev_free(s.d_extra); dev_free(s.d_raw);
   if (s.h_cols) { (void)hipHostFree(s.h_cols); s.h_cols = nullptr; }

@@ -1,0 +1,217 @@
+// psm_api_gradp_frames.cpp -- C-ABI of libpsm_hip.so (include/psm.h): the frame batch of the U_to_gradP evaluator on the device.
+// psm_bind_gradp_frames stands on psm_bind_frames and holds integration tables of its own (integ_bind of psm_api_integ.cpp, the
+// simulation's one geometry for every frame slot); psm_gradp_image_device is the image stage alone (the mesh -> grid launch of
+// psm_api_frames.cpp, then the pack: the PsmGradpPackArgs overload of psm_to_grid_kernel, psm_mesh.hip); psm_gradp_frames* put
+// planes -> image, labels -> one solve per frame (-> filter) -> integration into one graph replay (solve_device, psm_api_solve.cpp)
+// and the field-error launches of psm_api_errors.cpp with four pairs behind it, so that a metrics-only sweep returns 32 doubles per
+// frame.  See psm_handle.h for the map of the files.
+#include "psm_handle.h"
+
+namespace psm_impl {
+
+constexpr int GRADP_PAIRS = 4;
+static_assert(GRADP_PAIRS <= PSM_FIELD_ERR_MAX_PAIRS, "the step's error blocks are one call of the field-error stage");
+
+// captured step graphs (GraphKey::gradp) hold the addresses of the binding's planes, SDF plane and integration tables
+static void drop_gradp_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.gradp.planes != nullptr; }); }
+
+void gradp_free(psm_handle* h) {
+  GradpSet& s = h->gradp;
+  drop_gradp_graphs(h);
+  dev_free(s.d_sdn); dev_free(s.d_planes); dev_free(s.d_grid); dev_free(s.d_truth); dev_free(s.d_raw);
+  integ_free(s.integ);
+  if (s.h_raw) { (void)hipHostFree(s.h_raw); s.h_raw = nullptr; }
+  if (s.h_gradp) { (void)hipHostFree(s.h_gradp); s.h_gradp = nullptr; }
+  if (s.h_p) { (void)hipHostFree(s.h_p); s.h_p = nullptr; }
+  if (s.h_truth) { (void)hipHostFree(s.h_truth); s.h_truth = nullptr; }
+  s.ready = false; s.n_frames = 0;
+}
+
+// The pack launch on `st`: the binding's SDF plane and scales, the call's planes and destinations.
+int gradp_pack_device(psm_handle* h, const GradpCall& gc, int n_frames, hipStream_t st) {
+  const GradpSet& G = h->gradp;
+  PsmGradpPackArgs a{};
+  a.planes = gc.planes; a.sdn = G.d_sdn;
+  a.grid = gc.grid; a.truth = gc.truth;
+  a.npix = (int64_t)h->Ny * h->Nx;
+  a.m0 = G.max_abs[0]; a.m1 = G.max_abs[1]; a.m3 = G.max_abs[3]; a.m4 = G.max_abs[4];
+  a.n_frames = n_frames;
+  HIPCHK(h, psm_launch_gradp_pack(a, st));
+  return PSM_OK;
+}
+
+// the mesh, the frame binding and this binding
+static int gradp_state(psm_handle* h) {
+  int rc = frames_state(h);
+  if (rc) return rc;
+  if (!h->gradp.ready) return fail(h, PSM_ERR_STATE, "psm_bind_gradp_frames has not been called (psm_bind_frames, a new mesh, plan or model drop the binding)");
+  return PSM_OK;
+}
+
+// state and arguments of the image stage; the frame stage's descriptors: columns 0-4 into the binding's planes, the rest not stored
+static int image_call(psm_handle* h, const double* d_cols, int n_frames, int k, const float* d_grid, const double* d_truth, FrameCall& fc) {
+  int rc = gradp_state(h);
+  if (rc) return rc;
+  if (k < 5 || k > PSM_FRAME_MAX_COLS) return fail(h, PSM_ERR_ARG, "k outside [5, 16]: (Ux / U, Uy / U, dPdx / U^2, dPdy / U^2, p / U^2), further columns are not stored");
+  if ((rc = frames_count_check(h, n_frames))) return rc;
+  if (!d_cols || !d_grid) return fail(h, PSM_ERR_ARG, "null buffer");
+  if ((reinterpret_cast<uintptr_t>(d_grid) & 3) || (reinterpret_cast<uintptr_t>(d_truth) & 7))
+    return fail(h, PSM_ERR_ARG, "a destination is misaligned (4 bytes for the image, 8 for the label planes)");
+  const int64_t npix = (int64_t)h->Ny * h->Nx;
+  fc = FrameCall{};
+  fc.cols = d_cols; fc.k = k; fc.fill = 1;
+  for (int c = 0; c < 5; ++c) fc.out[c] = PsmFramePlane{h->gradp.d_planes + c * npix, 5 * npix, 0};
+  return PSM_OK;
+}
+
+// The error blocks behind a step: the two field-error launches, four pairs over the binding's SDF plane.
+static int step_errors_device(psm_handle* h, int n_frames, const float* d_gradp, const float* d_p, const double* d_truth, double* d_raw,
+                              hipStream_t st) {
+  const int64_t npix = (int64_t)h->Ny * h->Nx;
+  const PsmErrPlane none{nullptr, 0, 0, 0};
+  const PsmErrPlane p{d_p, npix, 1, 1}, gx{d_gradp, 2 * npix, 2, 1}, gy{d_gradp + 1, 2 * npix, 2, 1};
+  const PsmErrPlane t0{d_truth, 3 * npix, 1, 0}, t1{d_truth + npix, 3 * npix, 1, 0}, t2{d_truth + 2 * npix, 3 * npix, 1, 0};
+  PsmFieldErrorArgs a{};
+  a.mask = PsmErrPlane{h->gradp.d_sdn, 0, 1, 0};          // one plane for every frame
+  a.pair[0] = PsmFieldErrorPair{p, t0, none, none, 0};    // the reference's own metric (:667-687)
+  a.pair[1] = PsmFieldErrorPair{p, t2, none, none, 0};    // p against the pressure label
+  a.pair[2] = PsmFieldErrorPair{gx, t0, none, none, 0};   // the network's own output against its labels
+  a.pair[3] = PsmFieldErrorPair{gy, t1, none, none, 0};
+  a.n_pairs = GRADP_PAIRS; a.n_frames = n_frames;
+  return field_errors_device(h, a, d_raw, st);
+}
+
+// every check of one step, then the one graph replay: frames -> planes -> image, labels -> solve (-> filter) -> integration
+static int step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const float* out_scale, int apply_filter, float* d_gradp,
+                       float* d_p, double* d_truth, const double* d_raw, hipStream_t st) {
+  GradpSet& G = h->gradp;
+  FrameCall fc;
+  int rc = image_call(h, d_cols, n_frames, k, G.d_grid, d_truth, fc);
+  if (rc) return rc;
+  if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_gradp_frames");
+  if ((reinterpret_cast<uintptr_t>(d_gradp) & 7) || (reinterpret_cast<uintptr_t>(d_p) & 3) || (reinterpret_cast<uintptr_t>(d_raw) & 7))
+    return fail(h, PSM_ERR_ARG, "a destination is misaligned (8 bytes for d_gradp and d_raw, 4 for d_p)");
+  const GradpCall gc{G.d_planes, G.d_grid, d_truth, d_p};
+  if (!apply_filter) return solve_device(h, G.d_grid, n_frames, out_scale, d_gradp, st, nullptr, nullptr, nullptr, nullptr, &fc, nullptr, &gc);
+  PostCall pc;
+  pc.apply_filter = 1; pc.result = d_gradp;
+  return solve_device(h, G.d_grid, n_frames, out_scale, h->post.d_fields, st, nullptr, nullptr, &pc, nullptr, &fc, nullptr, &gc);
+}
+
+}  // namespace psm_impl
+
+// ============================================================================
+extern "C" {
+
+
+int psm_bind_gradp_frames(psm_handle* h, const double* sdfunct, const double* max_abs, int32_t center_y, int32_t center_x, double dx,
+                          double dy) {
+  if (!h) return PSM_ERR_ARG;
+  int rc = frames_state(h);
+  if (rc) return rc;
+  if (h->cfg.c_in != 3 || h->cfg.sdf_channel != 2 || h->cfg.c_out != 2)
+    return fail(h, PSM_ERR_STATE, "the gradP frames are a three-channel image with the SDF last and a (dp/dx, dp/dy) field: c_in == 3, sdf_channel == 2, c_out == 2");
+  if (!sdfunct || !max_abs) return fail(h, PSM_ERR_ARG, "null argument");
+  for (int q = 0; q < 5; ++q)
+    if (!(max_abs[q] != 0.0) || !std::isfinite(max_abs[q])) return fail(h, PSM_ERR_ARG, "max_abs scales must be finite and non-zero");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));           // a step in flight reads the buffers that are replaced
+  gradp_free(h);
+  GradpSet& s = h->gradp;
+  const size_t npix = (size_t)h->Ny * h->Nx, n = (size_t)h->frames.n_frames;
+  // the tables first: a geometry the reference cannot process (PSM_ERR_UNSUPPORTED) or a cut outside the grid (PSM_ERR_ARG) binds nothing
+  if ((rc = integ_bind(h, s.integ, h->Ny, h->Nx, sdfunct, (int)n, &center_y, &center_x, dx, dy, true))) { gradp_free(h); return rc; }
+  if ((rc = dev_alloc(h, &s.d_sdn, npix)) || (rc = dev_alloc(h, &s.d_planes, n * 5 * npix)) || (rc = dev_alloc(h, &s.d_grid, n * npix * 3)) ||
+      (rc = dev_alloc(h, &s.d_truth, n * 3 * npix)) || (rc = dev_alloc(h, &s.d_raw, n * GRADP_PAIRS * PSM_ERR_RAW))) { gradp_free(h); return rc; }
+  hipError_t e = hipHostMalloc((void**)&s.h_raw, n * GRADP_PAIRS * PSM_ERR_RAW * sizeof(double), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_gradp, n * npix * 2 * sizeof(float), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_p, n * npix * sizeof(float), hipHostMallocDefault);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_truth, n * 3 * npix * sizeof(double), hipHostMallocDefault);
+  if (e == hipSuccess) {
+    // nan0(sdfunct) / max_abs[2]: the statements of Eval_dual_Dense_onlycil.py:461-465 on the SDF channel, once for the simulation
+    std::vector<double> sdn(npix);
+    for (size_t i = 0; i < npix; ++i) sdn[i] = (sdfunct[i] != sdfunct[i] ? 0.0 : sdfunct[i]) / max_abs[2];
+    e = psm_copy_h2d(s.d_sdn, sdn.data(), npix * sizeof(double));
+  }
+  if (e != hipSuccess) { gradp_free(h); return fail(h, PSM_ERR_NOMEM, std::string("psm_bind_gradp_frames: ") + hipGetErrorString(e)); }
+  s.n_frames = h->frames.n_frames;
+  for (int q = 0; q < 5; ++q) s.max_abs[q] = max_abs[q];
+  s.ready = true;
+  return PSM_OK;
+}
+
+
+int psm_unbind_gradp_frames(psm_handle* h) {
+  if (!h) return PSM_ERR_ARG;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  gradp_free(h);
+  return PSM_OK;
+}
+
+
+int psm_gradp_image_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, float* d_grid, double* d_truth, void* stream) {
+  if (!h) return PSM_ERR_ARG;
+  FrameCall fc;
+  int rc = image_call(h, d_cols, n_frames, k, d_grid, d_truth, fc);
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  if ((rc = frames_device(h, fc, n_frames, st))) return rc;
+  return gradp_pack_device(h, GradpCall{h->gradp.d_planes, d_grid, d_truth, nullptr}, n_frames, st);
+}
+
+
+int psm_gradp_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const float* out_scale,
+                            int32_t apply_filter, float* d_gradp, float* d_p, double* d_truth, double* d_raw, void* stream) {
+  if (!h) return PSM_ERR_ARG;
+  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  if (!d_gradp) d_gradp = h->gradp.integ.d_gradp;
+  if (!d_p) d_p = h->gradp.integ.d_p;
+  if (!d_truth) d_truth = h->gradp.d_truth;
+  int rc = step_device(h, d_cols, n_frames, k, out_scale, apply_filter, d_gradp, d_p, d_truth, d_raw, st);
+  if (rc || !d_raw) return rc;
+  return step_errors_device(h, n_frames, d_gradp, d_p, d_truth, d_raw, st);
+}
+
+
+int psm_gradp_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, const float* out_scale, int32_t apply_filter,
+                     float* gradp, float* p, double* truth, double* raw) {
+  if (!h) return PSM_ERR_ARG;
+  if (!cols || !(gradp || p || truth || raw)) return fail(h, PSM_ERR_ARG, "null buffer");
+  FrameSet& F = h->frames;
+  GradpSet& G = h->gradp;
+  hipStream_t st = h->stream;
+  // every check of the step before the first copy: the step itself repeats them
+  FrameCall fc;
+  int rc = image_call(h, F.d_cols, n_frames, k, G.d_grid, G.d_truth, fc);
+  if (rc) return rc;
+  if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_gradp_frames");
+  if (k > F.k) return fail(h, PSM_ERR_ARG, "more columns than psm_bind_frames reserved staging for");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  const size_t npix = (size_t)h->Ny * h->Nx;
+  const size_t cb = (size_t)n_frames * h->n_cells * k * sizeof(double), pb = (size_t)n_frames * npix * sizeof(float), gb = 2 * pb;
+  const size_t tb = (size_t)n_frames * 3 * npix * sizeof(double), rb = (size_t)n_frames * GRADP_PAIRS * PSM_ERR_RAW * sizeof(double);
+  float *d_g = G.integ.d_gradp, *d_p = G.integ.d_p;
+  memcpy(F.h_cols, cols, cb);
+  HIPCHK(h, hipMemcpyAsync(F.d_cols, F.h_cols, cb, hipMemcpyHostToDevice, st));
+  for (int pass = 0; pass < 2; ++pass) {
+    if ((rc = step_device(h, F.d_cols, n_frames, k, out_scale, apply_filter, d_g, d_p, G.d_truth, G.d_raw, st))) return rc;
+    if (raw && (rc = step_errors_device(h, n_frames, d_g, d_p, G.d_truth, G.d_raw, st))) return rc;
+    if (gradp) HIPCHK(h, hipMemcpyAsync(G.h_gradp, d_g, gb, hipMemcpyDeviceToHost, st));
+    if (p) HIPCHK(h, hipMemcpyAsync(G.h_p, d_p, pb, hipMemcpyDeviceToHost, st));
+    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(G.h_truth, G.d_truth, tb, hipMemcpyDeviceToHost, st));
+    if (raw) HIPCHK(h, hipMemcpyAsync(G.h_raw, G.d_raw, rb, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, wait_stream(st));
+    if (pass == 1 || !guard_take(h, h->ws0)) break;     // not the bound geometry: the gradient is NaN -- drop the binding, solve again on the general path
+    if ((rc = guard_drop(h, "psm_gradp_frames"))) return rc;
+    h->err += " (solved on the general path)";
+  }
+  if (gradp) memcpy(gradp, G.h_gradp, gb);
+  if (p) memcpy(p, G.h_p, pb);
+  if (truth) memcpy(truth, G.h_truth, tb);
+  if (raw) memcpy(raw, G.h_raw, rb);
+  return PSM_OK;
+}
+
+}  // extern "C"

@@ -51,19 +51,21 @@ static int integ_tables(int ny, int nx, const double* sdfunct, int cy, int cx, i
 }
 
 // Build and upload the tables of n_cases geometries on a ny x nx grid into `s`; all-or-nothing: a geometry the reference cannot
-// process leaves `s` as it was (the caller decides whether an earlier binding survives).
-static int integ_bind(psm_handle* h, IntegSet& s, int ny, int nx, const double* sdfunct, int n_cases, const int32_t* cy, const int32_t* cx,
-                      double dx, double dy) {
+// process leaves `s` as it was (the caller decides whether an earlier binding survives).  one_geometry: sdfunct [ny*nx], cy [1] and
+// cx [1] describe ONE geometry, whose tables every case slot gets (psm_bind_gradp_frames: the frames of one simulation).
+int integ_bind(psm_handle* h, IntegSet& s, int ny, int nx, const double* sdfunct, int n_cases, const int32_t* cy, const int32_t* cx,
+               double dx, double dy, bool one_geometry) {
   const size_t npix = (size_t)ny * nx;
   if (npix * n_cases >= ((size_t)1 << 30)) return fail(h, PSM_ERR_ARG, "integration batch too large");
   std::vector<int2> fix((size_t)n_cases * ny * PSM_INTEG_MAX_FIX, make_int2(-1, -1)), cuts(n_cases), npair(n_cases);
   std::vector<uint8_t> mask((size_t)n_cases * ny, 0);
   for (int c = 0; c < n_cases; ++c) {
     std::string why;
-    const int rc = integ_tables(ny, nx, sdfunct + (size_t)c * npix, cy[c], cx[c], fix.data() + (size_t)c * ny * PSM_INTEG_MAX_FIX,
+    const int g = one_geometry ? 0 : c;
+    const int rc = integ_tables(ny, nx, sdfunct + (size_t)g * npix, cy[g], cx[g], fix.data() + (size_t)c * ny * PSM_INTEG_MAX_FIX,
                                 mask.data() + (size_t)c * ny, &npair[c], why);
-    if (rc) return fail(h, rc, n_cases > 1 ? "case " + std::to_string(c) + ": " + why : why);
-    cuts[c] = make_int2(cy[c], cx[c]);
+    if (rc) return fail(h, rc, n_cases > 1 && !one_geometry ? "case " + std::to_string(c) + ": " + why : why);
+    cuts[c] = make_int2(cy[g], cx[g]);
   }
   integ_free(s);
   int rc;
@@ -89,13 +91,17 @@ static int integ_check(psm_handle* h, int n_cases) {
   return PSM_OK;
 }
 
-// the two launches on `st`, from / into caller memory
-int integrate_device(psm_handle* h, const float* d_gradp, int n_cases, float* d_p, hipStream_t st) {
+// the two launches on `st`, from / into caller memory, with the tables of `s` (its first n_cases case slots)
+int integrate_device(psm_handle* h, const IntegSet& s, const float* d_gradp, int n_cases, float* d_p, hipStream_t st) {
   if ((reinterpret_cast<uintptr_t>(d_gradp) & 7) || (reinterpret_cast<uintptr_t>(d_p) & 3)) return fail(h, PSM_ERR_ARG, "gradient buffer must be 8-byte aligned");
-  PsmIntegArgs a = h->integ_dev.args;
+  PsmIntegArgs a = s.args;
   a.gradp = d_gradp; a.p = d_p; a.n_cases = n_cases;
   HIPCHK(h, psm_launch_integrate(a, st));
   return PSM_OK;
+}
+
+int integrate_device(psm_handle* h, const float* d_gradp, int n_cases, float* d_p, hipStream_t st) {
+  return integrate_device(h, h->integ_dev, d_gradp, n_cases, d_p, st);
 }
 
 }  // namespace psm_impl

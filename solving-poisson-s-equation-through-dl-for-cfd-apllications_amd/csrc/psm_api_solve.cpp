@@ -445,7 +445,7 @@ int capture_graph(psm_handle* h, hipStream_t st, const char* label, const std::f
 
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
                  hipStream_t st, hipEvent_t* prof, float* d_p, const PostCall* post, const FeatCall* feat, const FrameCall* frames,
-                 const DeltasCall* deltas) {
+                 const DeltasCall* deltas, const GradpCall* gradp) {
   if (!h) return PSM_ERR_ARG;
   if (!h->planned) return fail(h, PSM_ERR_STATE, "psm_plan_grid has not been called");
   if (!d_grid || !d_fields) return fail(h, PSM_ERR_ARG, "null buffer");
@@ -457,14 +457,21 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
   if (rc) return rc;
   rc = prepare_scale(h, h->ws0, out_scale, n_cases, st, &d_scale);
   if (rc) return rc;
-  h->last_cases = n_cases;
-  // the mesh -> grid launch (frames), the two feature launches (feat) or the image pack (deltas), the solve, then the two integration launches (d_p) or the
-  // post-steps' (at most four): one linear chain
+  h->last_cases = gradp ? 1 : n_cases;  // gradp: ws0 holds the last frame's single-case solve
+  // the mesh -> grid launch (frames), the two feature launches (feat) or the image pack (deltas, gradp), the solve, then the two integration launches (d_p) or the
+  // post-steps' (at most four); gradp: the filter among the post-steps and BEHIND it the integration with the gradp binding's tables: one linear chain
   auto sequence = [&](hipStream_t on, hipEvent_t* ev) {
     int rs = frames ? frames_device(h, *frames, n_cases, on) : PSM_OK;
     if (!rs && feat) rs = features_device(h, feat->vel, n_cases, feat->grid, on);
     if (!rs && deltas) rs = deltas_pack_device(h, *deltas, n_cases, on);
-    if (!rs && deltas) {
+    if (!rs && gradp) rs = gradp_pack_device(h, *gradp, n_cases, on);
+    if (!rs && gradp) {
+      // The U_to_gradP evaluator's frames, solved one by one for the reason given below: a frame's gradient holds the bits of the
+      // single-case solve EvaluationGradP.timeStep runs on its image, whatever the batch.
+      const size_t npix = (size_t)h->Ny * h->Nx;
+      for (int f = 0; f < n_cases && !rs; ++f)
+        rs = launch_all(h, h->ws0, d_grid + f * npix * h->cfg.c_in, 1, d_fields + f * npix * h->cfg.c_out, d_scale + (d_scale == h->d_ones ? 0 : f * h->B), on, ev);
+    } else if (!rs && deltas) {
       // The deltas evaluator's frames are solved ONE BY ONE, each as the single case Evaluation.timeStep solves (with a geometry bound
       // for one case: the 6-launch route with the folded encode), so that a frame's field holds the bits of that call whatever the
       // batch; the network output rows of every frame are kept for the block stage, which decodes them again.
@@ -480,11 +487,12 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
     } else if (!rs) rs = launch_all(h, h->ws0, d_grid, n_cases, d_fields, d_scale, on, ev);
     if (!rs && d_p) rs = integrate_device(h, d_fields, n_cases, d_p, on);
     if (!rs && post) rs = poststeps_device(h, d_fields, n_cases, *post, on);
+    if (!rs && gradp) rs = integrate_device(h, h->gradp.integ, post ? post->result : d_fields, n_cases, gradp->p, on);
     return rs;
   };
   if (prof || h->timed_kernel >= 0 || !h->use_graph) return sequence(st, prof);
   const GraphKey key{sequence_key(h, n_cases, out_scale != nullptr), d_grid, d_fields, d_p, post ? *post : PostCall{}, feat ? feat->vel : nullptr,
-                     frames ? *frames : FrameCall{}, deltas ? *deltas : DeltasCall{}};
+                     frames ? *frames : FrameCall{}, deltas ? *deltas : DeltasCall{}, gradp ? *gradp : GradpCall{}};
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     if (h->graphs.size() > 64) destroy_graphs(h);

@@ -1,5 +1,5 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in thirteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in fourteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, graph capture and key, psm_solve_grid*
@@ -12,6 +12,7 @@
 //   psm_api_frames.cpp      frames of cell columns -> planes on the device: psm_bind_frames, psm_frames_to_grid_device and the evaluator's step psm_poisson_frames*
 //   psm_api_errors.cpp      the per-frame error blocks of assembled fields on the device: psm_field_errors_device and the metrics-only frame step psm_poisson_frames_errors* (host arithmetic: psm_errors.cpp)
 //   psm_api_deltas_frames.cpp  the deltas evaluator's frame batch on the device: psm_bind_deltas_frames, the image pack psm_deltas_image_device, the batched block errors psm_block_errors_device and the step psm_deltas_frames*
+//   psm_api_gradp_frames.cpp   the U_to_gradP evaluator's frame batch on the device: psm_bind_gradp_frames, the image / label pack psm_gradp_image_device and the step psm_gradp_frames* (columns -> p -> errors)
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -152,6 +153,17 @@ struct DeltasCall {
   auto tie() const { return std::tie(planes, grid, label, truth); }
 };
 
+// The image / label pack between the mesh -> grid stage and the solve, and the integration behind the solve (and its filter), of the
+// U_to_gradP evaluator's frame batch (psm_gradp_frames*): every pointer is part of the captured launches; the SDF plane, the scales
+// and the integration tables are the binding's (GradpSet), which drops these graphs when it goes.
+struct GradpCall {
+  const double* planes = nullptr;       // [n_frames][5][npix] what the frame stage wrote; nullptr: no pack stage
+  float* grid = nullptr;
+  double* truth = nullptr;
+  float* p = nullptr;                   // [n_frames][npix] where the binding's integration writes p
+  auto tie() const { return std::tie(planes, grid, truth, p); }
+};
+
 struct GraphKey {
   int n; const void* g; void* f;        // n: sequence_key()
   void* p = nullptr;                    // psm_solve_pressure*: where the integration behind the solve writes p (null: the solve alone)
@@ -159,11 +171,13 @@ struct GraphKey {
   const void* vel = nullptr;            // psm_poisson_step*: the velocity planes of the features in front of the solve (g is their image)
   FrameCall frames{};                   // psm_poisson_frames*: the mesh -> grid stage in front of the features (cols == nullptr: none)
   DeltasCall deltas{};                  // psm_deltas_frames*: the image pack behind the mesh -> grid stage (planes == nullptr: none)
+  GradpCall gradp{};                    // psm_gradp_frames*: the pack behind the mesh -> grid stage, the integration behind the filter (planes == nullptr: none)
   auto head() const { return std::tie(n, g, f, p, vel); }
   bool operator<(const GraphKey& o) const {
     if (head() != o.head()) return head() < o.head();
     if (post.tie() != o.post.tie()) return post.tie() < o.post.tie();
     if (deltas.tie() != o.deltas.tie()) return deltas.tie() < o.deltas.tie();
+    if (gradp.tie() != o.gradp.tie()) return gradp.tie() < o.gradp.tie();
     if (!frames.cols && !o.frames.cols) return false;       // no frame stage on either side: nothing more to compare
     return frames.key() < o.frames.key();
   }
@@ -295,6 +309,24 @@ struct DeltasSet {
   hipEvent_t u2_ev[RING] = {};
   int u2_pos = 0;
 };
+
+// Binding of the U_to_gradP evaluator's frame batch (psm_bind_gradp_frames, behind psm_bind_frames): the simulation's normalised SDF
+// plane, the scales, integration tables OF ITS OWN (the simulation's one geometry and cut, replicated per frame slot so that the
+// integration kernels index them by case as ever; h->integ_dev and h->integ_host are not touched) and every buffer a step touches
+// for the bound frame count, so that a step allocates nothing.  The columns go through the frame binding's staging.
+struct GradpSet {
+  bool ready = false;
+  int n_frames = 0;
+  double max_abs[5] = {1, 1, 1, 1, 1};  // of grid channels 0-4: Ux, Uy, SDF, dPdx label, dPdy label
+  double* d_sdn = nullptr;              // [npix] nan0(sdfunct) / max_abs[2] in float64: channel 2 of the image, and the field errors' mask
+  double* d_planes = nullptr;           // [n_frames][5][npix] float64 planes of columns 0-4
+  float* d_grid = nullptr;              // image [n][npix][3]
+  double* d_truth = nullptr;            // [n][3][npix]: grid channels 3-5
+  IntegSet integ;                       // the tables; integ.d_gradp [n][npix][2] and integ.d_p [n][npix] are the step's gradient and p
+  double *d_raw = nullptr, *h_raw = nullptr;     // [n][4][8], device and pinned (host entry)
+  float *h_gradp = nullptr, *h_p = nullptr;      // pinned [n][npix][2], [n][npix]
+  double* h_truth = nullptr;            // pinned [n][3][npix]
+};
 }  // namespace psm_impl
 using namespace psm_impl;
 
@@ -336,6 +368,7 @@ struct psm_handle {
   FeatureSet feat;                      // Poisson input features on the planned grid (psm_bind_features)
   FrameSet frames;                      // frame batch on the single mesh (psm_bind_frames)
   DeltasSet deltas;                     // the deltas evaluator's frame batch behind it (psm_bind_deltas_frames)
+  GradpSet gradp;                       // the U_to_gradP evaluator's frame batch behind it (psm_bind_gradp_frames)
   double maxs[4] = {1, 1, 1, 1};
   int normalise_sdf = 0, fill_input = 0;
   double case_maxs[4] = {1, 1, 1, 1}, case_delta = 5e-3, case_wall = 0.05;   // psm_set_case (PM:106-109, 195, 494)
@@ -467,13 +500,17 @@ void mesh_cases_free(psm_handle* h);
 int mesh_tables_upload(psm_handle* h, MeshTablesDev& dev, const PsmMeshCaseTables& t);
 void mesh_tables_free(MeshTablesDev& dev);
 void integ_free(IntegSet& s);
+int integ_bind(psm_handle* h, IntegSet& s, int ny, int nx, const double* sdfunct, int n_cases, const int32_t* cy, const int32_t* cx,
+               double dx, double dy, bool one_geometry = false);
 int integrate_device(psm_handle* h, const float* d_gradp, int n_cases, float* d_p, hipStream_t st);
+int integrate_device(psm_handle* h, const IntegSet& s, const float* d_gradp, int n_cases, float* d_p, hipStream_t st);
 void post_free(PostSet& s);
 int poststeps_device(psm_handle* h, const float* d_fields, int n_cases, const PostCall& pc, hipStream_t st);
 int post_check(psm_handle* h, int n_cases, const PostCall& pc);
 void feat_free(FeatureSet& s);
 void frames_free(psm_handle* h);
 void deltas_free(psm_handle* h);
+void gradp_free(psm_handle* h);
 int frames_state(psm_handle* h);
 int frames_count_check(psm_handle* h, int n_frames);
 int frames_device(psm_handle* h, const FrameCall& fc, int n_frames, hipStream_t st);
@@ -505,11 +542,14 @@ PsmToMeshArgs to_mesh_args(const psm_handle* h, const double* d_umax, double uma
 // post (apply_filter >= 0): the bound post-steps (psm_bind_poststeps) of d_fields follow likewise;
 // feat (vel != nullptr): the bound features (psm_bind_features) write d_grid == feat->grid in front of the solve, likewise;
 // frames (with feat): the mesh -> grid launch of psm_poisson_frames* writes feat->vel (and the post-steps' inputs) in front of the features;
-// deltas (with frames, without feat): the image pack of psm_deltas_frames* turns the planes the mesh -> grid launch wrote into d_grid
+// deltas (with frames, without feat): the image pack of psm_deltas_frames* turns the planes the mesh -> grid launch wrote into d_grid;
+// gradp (with frames, without feat, deltas and d_p): the pack of psm_gradp_frames* likewise, the frames solved one by one, and BEHIND
+// the post-steps the integration with the gradp binding's own tables, of post->result where there is a filter, else of d_fields
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
                  hipStream_t st, hipEvent_t* prof, float* d_p = nullptr, const PostCall* post = nullptr, const FeatCall* feat = nullptr,
-                 const FrameCall* frames = nullptr, const DeltasCall* deltas = nullptr);
+                 const FrameCall* frames = nullptr, const DeltasCall* deltas = nullptr, const GradpCall* gradp = nullptr);
 int deltas_pack_device(psm_handle* h, const DeltasCall& dc, int n_frames, hipStream_t st);
+int gradp_pack_device(psm_handle* h, const GradpCall& gc, int n_frames, hipStream_t st);
 bool guard_take(psm_handle* h, Workspace& w);
 int guard_drop(psm_handle* h, const char* where);
 int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases = 1);

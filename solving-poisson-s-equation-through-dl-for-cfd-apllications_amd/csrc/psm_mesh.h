@@ -82,6 +82,21 @@ struct PsmDeltasPackArgs {
 constexpr int PSM_DELTAS_PACK_SPAN = 1024;   // pixels per workgroup: 256 threads x 4 consecutive pixels
 hipError_t psm_launch_deltas_pack(const PsmDeltasPackArgs& a, hipStream_t st);
 
+// ---- the image / label pack of the U_to_gradP evaluator's frame batch (psm_gradp_image_device): the float64 planes of columns 0-4
+// (Ux / U, Uy / U, dPdx (max_x - min_x) / U^2, dPdy (max_y - min_y) / U^2, p / U^2; NaNs of interpolate_fill kept) -> the solve's
+// image and the three float64 label planes, the statements of Eval_dual_Dense_onlycil.py:461-467 per pixel.  One launch, the frame
+// is launch dimension y; 48 bytes in and 36 out per pixel (60 with the labels).
+struct PsmGradpPackArgs {
+  const double* planes;         // [n_frames][5][npix]
+  const double* sdn;            // [npix] nan0(sdfunct) / max_abs[2] of the simulation, shared by the frames (float64, made at bind)
+  float* grid;                  // [n_frames][npix][3] = ((float)(nan0(v0) / m0), (float)(nan0(v1) / m1), (float)sdn)
+  double* truth;                // [n_frames][3][npix] = (nan0(v2) / m3, nan0(v3) / m4, nan0(v4)): grid channels 3-5; nullptr: not stored
+  int64_t npix;
+  double m0, m1, m3, m4;        // max_abs of channels 0, 1, 3, 4; the pressure label (channel 5) is not divided
+  int n_frames;
+};
+hipError_t psm_launch_gradp_pack(const PsmGradpPackArgs& a, hipStream_t st);
+
 // ---- the mesh ends for a case batch (psm_set_geometry_cases): K meshes on one planned grid, the case is launch dimension y.
 // Cell-side arrays are the cases' concatenated ([sum n_i, ...], case i at rows cell_off[i] .. cell_off[i + 1]), grid-side tables
 // are [K][n_grid, ...]; vertex indices are case-local as the caller gave them (the kernels add the case's offset).

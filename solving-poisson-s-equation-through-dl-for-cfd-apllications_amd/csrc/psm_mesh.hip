@@ -403,6 +403,65 @@ hipError_t psm_launch_deltas_pack(const PsmDeltasPackArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// The image / label pack of the U_to_gradP evaluator's frame batch (PsmGradpPackArgs in psm_mesh.h): what EvaluationGradP.timeStep
+// does on the host between psm_mesh_to_grid and the solve, per pixel and in its order -- NaN -> 0, the division by the channel's
+// max_abs in float64, then the float32 cast of the solve's entry (Eval_dual_Dense_onlycil.py:461-467); the label channels 3-5 stay
+// float64, the pressure label undivided.  One IEEE division per value and no addition: nothing to contract, the outputs hold the
+// bits of the NumPy statements.  The access pattern is the deltas pack's: frame blockIdx.y, a thread takes 4 consecutive pixels of
+// every plane, 16-byte accesses where the frame's plane starts 16-byte aligned, one access per element otherwise and in the tail.
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmGradpPackArgs a) {
+  const int64_t frame = blockIdx.y;
+  const int64_t pix = (int64_t)blockIdx.x * PSM_DELTAS_PACK_SPAN + threadIdx.x * 4;
+  if (pix >= a.npix) return;
+  const int n = (int)min((int64_t)4, a.npix - pix);
+  const double* pl = a.planes + frame * 5 * a.npix;
+  double v0[4], v1[4], sd[4];
+  pack_load4(pl, pix, n, n == 4 && pack_aligned(pl), v0);
+  pack_load4(pl + a.npix, pix, n, n == 4 && pack_aligned(pl + a.npix), v1);
+  pack_load4(a.sdn, pix, n, n == 4 && pack_aligned(a.sdn), sd);
+  float g[12];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const double x = (v0[e] != v0[e] ? 0.0 : v0[e]) / a.m0;
+    const double y = (v1[e] != v1[e] ? 0.0 : v1[e]) / a.m1;
+    g[3 * e] = (float)x; g[3 * e + 1] = (float)y; g[3 * e + 2] = (float)sd[e];
+  }
+  float* go = a.grid + (frame * a.npix + pix) * 3;
+  if (n == 4 && pack_aligned(go)) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) reinterpret_cast<psm_pack_f4*>(go)[q] = psm_pack_f4{g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]};
+  } else {
+    for (int e = 0; e < 3 * n; ++e) go[e] = g[e];
+  }
+  if (!a.truth) return;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double* src = pl + (2 + c) * a.npix;
+    const double m = c == 0 ? a.m3 : c == 1 ? a.m4 : 1.0;
+    double v[4], t[4];
+    pack_load4(src, pix, n, n == 4 && pack_aligned(src), v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const double z = v[e] != v[e] ? 0.0 : v[e];
+      t[e] = c < 2 ? z / m : z;
+    }
+    double* to = a.truth + (frame * 3 + c) * a.npix + pix;
+    if (n == 4 && pack_aligned(to)) {
+      reinterpret_cast<psm_pack_d2*>(to)[0] = psm_pack_d2{t[0], t[1]};
+      reinterpret_cast<psm_pack_d2*>(to)[1] = psm_pack_d2{t[2], t[3]};
+    } else {
+      for (int e = 0; e < n; ++e) to[e] = t[e];
+    }
+  }
+}
+
+hipError_t psm_launch_gradp_pack(const PsmGradpPackArgs& a, hipStream_t st) {
+  if (a.n_frames < 1 || a.npix < 1 || !a.planes || !a.sdn || !a.grid) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmGradpPackArgs)>(psm_to_grid_kernel),
+                     dim3((unsigned)((a.npix + PSM_DELTAS_PACK_SPAN - 1) / PSM_DELTAS_PACK_SPAN), (unsigned)a.n_frames), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(psm_to_mesh_kernel, dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
   return hipGetLastError();
