@@ -8,18 +8,15 @@
 
 namespace psm_impl {
 
-// captured step graphs (GraphKey::deltas) hold the addresses of the binding's planes, SDF plane and U^2 array
-static void drop_deltas_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.deltas.planes != nullptr; }); }
+// captured step graphs (StepCall::deltas) hold the addresses of the binding's planes, SDF plane and U^2 array
+static void drop_deltas_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.step.deltas.planes != nullptr; }); }
 
 void deltas_free(psm_handle* h) {
   DeltasSet& s = h->deltas;
   drop_deltas_graphs(h);
   dev_free(s.d_sdn); dev_free(s.d_planes); dev_free(s.d_grid); dev_free(s.d_label); dev_free(s.d_result); dev_free(s.d_truth);
   dev_free(s.d_res); dev_free(s.d_part); dev_free(s.d_fraw); dev_free(s.d_raw); dev_free(s.d_u2);
-  if (s.h_raw) { (void)hipHostFree(s.h_raw); s.h_raw = nullptr; }
-  if (s.h_result) { (void)hipHostFree(s.h_result); s.h_result = nullptr; }
-  if (s.h_truth) { (void)hipHostFree(s.h_truth); s.h_truth = nullptr; }
-  if (s.h_u2) { (void)hipHostFree(s.h_u2); s.h_u2 = nullptr; }
+  pin_free(s.h_raw); pin_free(s.h_result); pin_free(s.h_truth); pin_free(s.h_u2);
   for (auto& e : s.u2_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   s.ready = false; s.n_frames = 0; s.u2_pos = 0;
 }
@@ -124,8 +121,8 @@ static int step_errors_device(psm_handle* h, int n_frames, const float* d_result
 static int step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* out_scale, int apply_filter,
                        float* d_result, double* d_truth, const double* d_raw, hipStream_t st) {
   DeltasSet& D = h->deltas;
-  FrameCall fc;
-  int rc = image_call(h, d_cols, n_frames, k, U2, D.d_grid, D.d_label, d_truth, fc);
+  StepCall step;
+  int rc = image_call(h, d_cols, n_frames, k, U2, D.d_grid, D.d_label, d_truth, step.frames);
   if (rc) return rc;
   if (!U2) return fail(h, PSM_ERR_ARG, "null argument");
   if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_deltas_frames");
@@ -133,11 +130,9 @@ static int step_device(psm_handle* h, const double* d_cols, int n_frames, int k,
     return fail(h, PSM_ERR_ARG, "a destination is misaligned (4 bytes for d_result, 8 for d_raw)");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if ((rc = upload_u2(h, U2, n_frames, st))) return rc;
-  const DeltasCall dc{D.d_planes, D.d_grid, D.d_label, d_truth, D.d_res};
-  if (!apply_filter) return solve_device(h, D.d_grid, n_frames, out_scale, d_result, st, nullptr, nullptr, nullptr, nullptr, &fc, &dc);
-  PostCall pc;
-  pc.apply_filter = 1; pc.result = d_result;
-  return solve_device(h, D.d_grid, n_frames, out_scale, h->post.d_fields, st, nullptr, nullptr, &pc, nullptr, &fc, &dc);
+  step.deltas = DeltasCall{D.d_planes, D.d_grid, D.d_label, d_truth, D.d_res};
+  if (apply_filter) { step.post.apply_filter = 1; step.post.result = d_result; }
+  return solve_device(h, D.d_grid, n_frames, out_scale, apply_filter ? h->post.d_fields : d_result, st, nullptr, step);
 }
 
 }  // namespace psm_impl
@@ -164,17 +159,11 @@ int psm_bind_deltas_frames(psm_handle* h, const double* sdfunct, const double* m
       (rc = dev_alloc(h, &s.d_label, n * npix)) || (rc = dev_alloc(h, &s.d_result, n * npix)) || (rc = dev_alloc(h, &s.d_truth, n * npix)) ||
       (rc = dev_alloc(h, &s.d_res, (size_t)round_up((int)n * h->B, 32) * h->ld_out)) || (rc = dev_alloc(h, &s.d_part, n * h->B * PSM_ERR_RAW)) || (rc = dev_alloc(h, &s.d_fraw, n * PSM_ERR_RAW)) ||
       (rc = dev_alloc(h, &s.d_raw, n * 2 * PSM_ERR_RAW)) || (rc = dev_alloc(h, &s.d_u2, n))) { deltas_free(h); return rc; }
-  hipError_t e = hipHostMalloc((void**)&s.h_raw, n * 2 * PSM_ERR_RAW * sizeof(double), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_result, n * npix * sizeof(float), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_truth, n * npix * sizeof(double), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_u2, DeltasSet::RING * n * sizeof(double), hipHostMallocDefault);
+  if ((rc = pin_alloc(h, &s.h_raw, n * 2 * PSM_ERR_RAW, "psm_bind_deltas_frames")) || (rc = pin_alloc(h, &s.h_result, n * npix, "psm_bind_deltas_frames")) ||
+      (rc = pin_alloc(h, &s.h_truth, n * npix, "psm_bind_deltas_frames")) || (rc = pin_alloc(h, &s.h_u2, DeltasSet::RING * n, "psm_bind_deltas_frames"))) { deltas_free(h); return rc; }
+  hipError_t e = hipSuccess;
   for (auto& ev : s.u2_ev) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-  if (e == hipSuccess) {
-    // nan0(sdfunct) / max_abs_dist: the statements of SM_call.py:439-444 on the SDF channel, once for the simulation
-    std::vector<double> sdn(npix);
-    for (size_t i = 0; i < npix; ++i) sdn[i] = (sdfunct[i] != sdfunct[i] ? 0.0 : sdfunct[i]) / max_abs[2];
-    e = psm_copy_h2d(s.d_sdn, sdn.data(), npix * sizeof(double));
-  }
+  if (e == hipSuccess) e = upload_sdf_plane(h, sdfunct, max_abs[2], s.d_sdn);     // the statements of SM_call.py:439-444 on the SDF channel
   if (e == hipSuccess) e = hipMemset(s.d_res, 0, (size_t)round_up((int)n * h->B, 32) * h->ld_out * sizeof(float));   // the rows the decode pads to
   const std::vector<double> ones(n, 1.0);
   if (e == hipSuccess) e = psm_copy_h2d(s.d_u2, ones.data(), n * sizeof(double));
@@ -187,11 +176,7 @@ int psm_bind_deltas_frames(psm_handle* h, const double* sdfunct, const double* m
 
 
 int psm_unbind_deltas_frames(psm_handle* h) {
-  if (!h) return PSM_ERR_ARG;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  deltas_free(h);
-  return PSM_OK;
+  return unbind(h, [h] { deltas_free(h); });
 }
 
 
@@ -202,7 +187,7 @@ int psm_deltas_image_device(psm_handle* h, const double* d_cols, int32_t n_frame
   int rc = image_call(h, d_cols, n_frames, k, U2, d_grid, d_label, d_truth, fc);
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  hipStream_t st = stream_of(h, stream);
   if (U2 && (rc = upload_u2(h, U2, n_frames, st))) return rc;
   if ((rc = frames_device(h, fc, n_frames, st))) return rc;
   return deltas_pack_device(h, DeltasCall{h->deltas.d_planes, d_grid, d_label, d_truth, nullptr}, n_frames, st);
@@ -219,14 +204,14 @@ int psm_block_errors_device(psm_handle* h, const float* d_grid, const float* d_l
   if (reinterpret_cast<uintptr_t>(d_raw) & 7) return fail(h, PSM_ERR_ARG, "d_raw must be 8-byte aligned");
   if ((rc = block_state(h, n_frames))) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  return block_errors_device(h, d_grid, d_label, n_frames, nullptr, d_raw, stream ? (hipStream_t)stream : h->stream);
+  return block_errors_device(h, d_grid, d_label, n_frames, nullptr, d_raw, stream_of(h, stream));
 }
 
 
 int psm_deltas_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const double* U2, const float* out_scale,
                              int32_t apply_filter, float* d_result, double* d_truth, double* d_raw, void* stream) {
   if (!h) return PSM_ERR_ARG;
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  hipStream_t st = stream_of(h, stream);
   if (!d_result) d_result = h->deltas.d_result;
   if (!d_truth) d_truth = h->deltas.d_truth;
   int rc = step_device(h, d_cols, n_frames, k, U2, out_scale, apply_filter, d_result, d_truth, d_raw, st);
@@ -248,24 +233,18 @@ int psm_deltas_frames(psm_handle* h, const double* cols, int32_t n_frames, int32
   if (rc) return rc;
   if (!U2) return fail(h, PSM_ERR_ARG, "null argument");
   if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_deltas_frames");
-  if (k > F.k) return fail(h, PSM_ERR_ARG, "more columns than psm_bind_frames reserved staging for");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if ((rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
   const size_t npix = (size_t)h->Ny * h->Nx;
-  const size_t cb = (size_t)n_frames * h->n_cells * k * sizeof(double), fb = (size_t)n_frames * npix * sizeof(float), tb = 2 * fb;
-  const size_t rb = (size_t)n_frames * 2 * PSM_ERR_RAW * sizeof(double);
-  memcpy(F.h_cols, cols, cb);
-  HIPCHK(h, hipMemcpyAsync(F.d_cols, F.h_cols, cb, hipMemcpyHostToDevice, st));
-  for (int pass = 0; pass < 2; ++pass) {
-    if ((rc = step_device(h, F.d_cols, n_frames, k, U2, out_scale, apply_filter, D.d_result, D.d_truth, D.d_raw, st))) return rc;
-    if (raw && (rc = step_errors_device(h, n_frames, D.d_result, D.d_truth, D.d_raw, st))) return rc;
+  const size_t fb = (size_t)n_frames * npix * sizeof(float), tb = 2 * fb, rb = (size_t)n_frames * 2 * PSM_ERR_RAW * sizeof(double);
+  rc = guarded_host_step(h, st, "psm_deltas_frames", [&](int pass) {
+    int rs = step_device(h, F.d_cols, n_frames, k, U2, out_scale, apply_filter, D.d_result, D.d_truth, D.d_raw, st);
+    if (rs || (raw && (rs = step_errors_device(h, n_frames, D.d_result, D.d_truth, D.d_raw, st)))) return rs;
     if (result) HIPCHK(h, hipMemcpyAsync(D.h_result, D.d_result, fb, hipMemcpyDeviceToHost, st));
-    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(D.h_truth, D.d_truth, tb, hipMemcpyDeviceToHost, st));
+    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(D.h_truth, D.d_truth, tb, hipMemcpyDeviceToHost, st));   // the labels do not depend on the route
     if (raw) HIPCHK(h, hipMemcpyAsync(D.h_raw, D.d_raw, rb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, wait_stream(st));
-    if (pass == 1 || !guard_take(h, h->ws0)) break;     // not the bound geometry: the field is NaN -- drop the binding, solve again on the general path
-    if ((rc = guard_drop(h, "psm_deltas_frames"))) return rc;
-    h->err += " (solved on the general path)";
-  }
+    return PSM_OK;
+  });
+  if (rc) return rc;
   if (result) memcpy(result, D.h_result, fb);
   if (truth) memcpy(truth, D.h_truth, tb);
   if (raw) memcpy(raw, D.h_raw, rb);

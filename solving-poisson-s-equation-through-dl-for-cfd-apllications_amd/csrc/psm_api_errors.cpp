@@ -86,7 +86,7 @@ int psm_field_errors_device(psm_handle* h, const psm_err_plane* mask, const psm_
                                   pairs[p].truth_nan_to_zero ? 1 : 0};
   a.n_pairs = n_pairs; a.n_frames = n_frames;
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  return field_errors_device(h, a, d_raw, stream ? (hipStream_t)stream : h->stream);
+  return field_errors_device(h, a, d_raw, stream_of(h, stream));
 }
 
 
@@ -102,7 +102,7 @@ int psm_poisson_frames_errors_device(psm_handle* h, const double* d_cols, int32_
   PostCall pc;
   pc.apply_filter = apply_filter ? 1 : 0; pc.result = d_result;
   pc.dU = h->post.d_dU; pc.prev = h->post.d_prev; pc.change = d_change; pc.next = d_next;
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  hipStream_t st = stream_of(h, stream);
   if ((rc = poisson_step_device(h, h->feat.d_vel, n_frames, LU, out_scale, pc, st, &fc))) return rc;
   return field_errors_device(h, poisson_pairs(h, n_frames, k - 6, d_extra, d_result, d_next), d_raw, st);
 }
@@ -117,27 +117,22 @@ int psm_poisson_frames_errors(psm_handle* h, const double* cols, int32_t n_frame
   int rc = poisson_frame_call(h, F.d_cols, n_frames, k, weighting, F.d_extra, fc);
   if (rc) return rc;
   if ((rc = errors_call_check(h, k, weighting, F.d_raw))) return rc;
-  if (k > F.k) return fail(h, PSM_ERR_ARG, "more columns than psm_bind_frames reserved staging for");
   PostSet& s = h->post;
   const size_t cap = (size_t)h->cfg.max_cases * h->Ny * h->Nx * h->cfg.c_out;
   PostCall pc;
   pc.apply_filter = apply_filter ? 1 : 0; pc.result = s.d_out;
   pc.dU = s.d_dU; pc.prev = s.d_prev; pc.change = s.d_out + cap; pc.next = s.d_out + 2 * cap;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
-  const size_t cb = (size_t)n_frames * h->n_cells * k * sizeof(double), rb = (size_t)n_frames * 3 * PSM_ERR_RAW * sizeof(double);
+  const size_t rb = (size_t)n_frames * 3 * PSM_ERR_RAW * sizeof(double);
   const PsmFieldErrorArgs stage = poisson_pairs(h, n_frames, k - 6, F.d_extra, pc.result, pc.next);
-  memcpy(F.h_cols, cols, cb);
-  HIPCHK(h, hipMemcpyAsync(F.d_cols, F.h_cols, cb, hipMemcpyHostToDevice, st));
-  for (int pass = 0; pass < 2; ++pass) {
-    if ((rc = poisson_step_device(h, h->feat.d_vel, n_frames, LU, out_scale, pc, st, &fc))) return rc;
-    if ((rc = field_errors_device(h, stage, F.d_raw, st))) return rc;
+  if ((rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
+  rc = guarded_host_step(h, st, "psm_poisson_frames_errors", [&](int) {
+    int rs = poisson_step_device(h, h->feat.d_vel, n_frames, LU, out_scale, pc, st, &fc);
+    if (rs || (rs = field_errors_device(h, stage, F.d_raw, st))) return rs;
     HIPCHK(h, hipMemcpyAsync(F.h_raw, F.d_raw, rb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, wait_stream(st));
-    if (pass == 1 || !guard_take(h, h->ws0)) break;     // not the bound geometry: the field is NaN -- drop the binding, solve again on the general path
-    if ((rc = guard_drop(h, "psm_poisson_frames_errors"))) return rc;
-    h->err += " (solved on the general path)";
-  }
+    return PSM_OK;
+  });
+  if (rc) return rc;
   memcpy(raw, F.h_raw, rb);
   return PSM_OK;
 }

@@ -8,13 +8,13 @@ namespace psm_impl {
 
 void feat_free(FeatureSet& s) {
   dev_free(s.d_sdf); dev_free(s.d_term); dev_free(s.d_partial); dev_free(s.d_lu); dev_free(s.d_grid); dev_free(s.d_vel);
-  if (s.h_lu) { (void)hipHostFree(s.h_lu); s.h_lu = nullptr; }
+  pin_free(s.h_lu);
   for (auto& e : s.lu_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   s.ready = false; s.n_cases = 0; s.lu_pos = 0;
 }
 
-// captured step graphs (GraphKey::vel) hold the addresses of the binding's planes and scratch
-static void drop_feature_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.vel != nullptr; }); }
+// captured step graphs (StepCall::feat) hold the addresses of the binding's planes and scratch
+static void drop_feature_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.step.feat.vel != nullptr; }); }
 
 // The two feature launches of d_vel [n][4][npix] into d_grid [n][npix][4] on `st`; (L, U) per case are read from the binding's d_lu.
 int features_device(psm_handle* h, const double* d_vel, int n, float* d_grid, hipStream_t st) {
@@ -54,7 +54,7 @@ static int upload_lu(psm_handle* h, const double* LU, int n_cases, hipStream_t s
   return PSM_OK;
 }
 
-static PostCall post_call(int apply_filter, const float* dU, const float* prev, float* result, float* change, float* next) {
+PostCall post_call(int apply_filter, const float* dU, const float* prev, float* result, float* change, float* next) {
   PostCall pc;
   pc.apply_filter = apply_filter ? 1 : 0; pc.dU = dU; pc.prev = prev; pc.result = result; pc.change = change; pc.next = next;
   return pc;
@@ -72,8 +72,11 @@ int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const d
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (!st) st = h->stream;
   if ((rc = upload_lu(h, LU, n_cases, st))) return rc;
-  const FeatCall fc{d_vel, h->feat.d_grid};
-  return solve_device(h, fc.grid, n_cases, out_scale, h->post.d_fields, st, nullptr, nullptr, &pc, &fc, frames);
+  StepCall step;
+  if (frames) step.frames = *frames;
+  step.feat = FeatCall{d_vel, h->feat.d_grid};
+  step.post = pc;
+  return solve_device(h, step.feat.grid, n_cases, out_scale, h->post.d_fields, st, nullptr, step);
 }
 
 }  // namespace psm_impl
@@ -138,8 +141,9 @@ int psm_bind_features(psm_handle* h, const double* sdfunct, int32_t n_cases, dou
       (rc = dev_alloc(h, &s.d_lu, n * 2)) || (rc = dev_alloc(h, &s.d_grid, n * npix * 4)) || (rc = dev_alloc(h, &s.d_vel, n * 4 * npix))) { feat_free(s); return rc; }
   // the host entry's pinned staging (velocities; dU, prev and the three outputs as psm_solve_poststeps): grown here, not in a step
   const size_t pb = n * npix * sizeof(float);
-  if ((rc = scratch_reserve(h, 0, carve_size({n * 4 * npix * sizeof(double), pb, pb, pb * h->cfg.c_out, pb, pb})))) { feat_free(s); return rc; }
-  hipError_t e = hipHostMalloc((void**)&s.h_lu, FeatureSet::RING * n * 2 * sizeof(double), hipHostMallocDefault);
+  if ((rc = scratch_reserve(h, 0, carve_size({n * 4 * npix * sizeof(double), pb, pb, pb * h->cfg.c_out + 2 * pb})))) { feat_free(s); return rc; }
+  if ((rc = pin_alloc(h, &s.h_lu, FeatureSet::RING * n * 2, "psm_bind_features", PSM_ERR_HIP))) { feat_free(s); return rc; }
+  hipError_t e = hipSuccess;
   for (auto& ev : s.lu_ev) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
   if (e == hipSuccess) e = psm_copy_h2d(s.d_sdf, sdfunct, n * npix * sizeof(double));
   // what psm_time_kernels reads as velocities and scalars is defined: zero planes, (L, U) = (1, 1)
@@ -156,12 +160,7 @@ int psm_bind_features(psm_handle* h, const double* sdfunct, int32_t n_cases, dou
 
 
 int psm_unbind_features(psm_handle* h) {
-  if (!h) return PSM_ERR_ARG;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  drop_feature_graphs(h);
-  feat_free(h->feat);
-  return PSM_OK;
+  return unbind(h, [h] { drop_feature_graphs(h); feat_free(h->feat); });
 }
 
 
@@ -172,7 +171,7 @@ int psm_features_device(psm_handle* h, const double* d_vel, int32_t n_cases, con
   if (!d_vel || !d_grid) return fail(h, PSM_ERR_ARG, "null buffer");
   if (reinterpret_cast<uintptr_t>(d_grid) & 15) return fail(h, PSM_ERR_ARG, "the image must be 16-byte aligned");
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  hipStream_t st = stream_of(h, stream);
   if ((rc = upload_lu(h, LU, n_cases, st))) return rc;
   return features_device(h, d_vel, n_cases, d_grid, st);
 }
@@ -202,13 +201,11 @@ int psm_poisson_step(psm_handle* h, const double* vel, int32_t n_cases, const do
   hipStream_t st = h->stream;
   const size_t npix = (size_t)h->Ny * h->Nx;
   const size_t vb = (size_t)n_cases * 4 * npix * sizeof(double), pb = (size_t)n_cases * npix * sizeof(float), fb = pb * h->cfg.c_out;
-  if ((rc = scratch_reserve(h, 0, carve_size({vb, pb, pb, fb, pb, pb})))) return rc;
+  if ((rc = scratch_reserve(h, 0, carve_size({vb, pb, pb, fb + 2 * pb})))) return rc;
   Carver cp{(char*)h->scr_pin};
   double* p_vel = cp.take<double>(vb / 8);
   float* p_dU = cp.take<float>(pb / 4); float* p_prev = cp.take<float>(pb / 4);
-  float* p_out[3] = {cp.take<float>(fb / 4), cp.take<float>(pb / 4), cp.take<float>(pb / 4)};
-  float* const dst[3] = {result, pc.change ? change : nullptr, pc.next ? next : nullptr};
-  const float* const src[3] = {pc.result, pc.change, pc.next};
+  const PostOut out(pc, result, change, next, cp.take<float>((fb + 2 * pb) / 4), fb, pb);
   memcpy(p_vel, vel, vb);
   HIPCHK(h, hipMemcpyAsync(h->feat.d_vel, p_vel, vb, hipMemcpyHostToDevice, st));
   if (dU) {
@@ -216,17 +213,12 @@ int psm_poisson_step(psm_handle* h, const double* vel, int32_t n_cases, const do
     HIPCHK(h, hipMemcpyAsync(s.d_dU, p_dU, pb, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(s.d_prev, p_prev, pb, hipMemcpyHostToDevice, st));
   }
-  for (int pass = 0; pass < 2; ++pass) {
-    if ((rc = poisson_step_device(h, h->feat.d_vel, n_cases, LU, out_scale, pc, st))) return rc;
-    for (int k = 0; k < 3; ++k)
-      if (dst[k]) HIPCHK(h, hipMemcpyAsync(p_out[k], src[k], k ? pb : fb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, wait_stream(st));
-    if (pass == 1 || !guard_take(h, h->ws0)) break;     // not the bound geometry: the field is NaN -- drop the binding, solve again on the general path
-    if ((rc = guard_drop(h, "psm_poisson_step"))) return rc;
-    h->err += " (solved on the general path)";
-  }
-  for (int k = 0; k < 3; ++k)
-    if (dst[k]) memcpy(dst[k], p_out[k], k ? pb : fb);
+  rc = guarded_host_step(h, st, "psm_poisson_step", [&](int) {
+    const int rs = poisson_step_device(h, h->feat.d_vel, n_cases, LU, out_scale, pc, st);
+    return rs ? rs : out.enqueue(h, st);
+  });
+  if (rc) return rc;
+  out.deliver();
   return PSM_OK;
 }
 

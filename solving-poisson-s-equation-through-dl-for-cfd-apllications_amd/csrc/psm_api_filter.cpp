@@ -23,8 +23,8 @@ void post_free(PostSet& s) {
   s.ready = false;
 }
 
-// captured solve + post-step graphs (GraphKey::post) hold the addresses of the binding's tables and scratch
-static void drop_post_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.post.apply_filter >= 0; }); }
+// captured solve + post-step graphs (StepCall::post) hold the addresses of the binding's tables and scratch
+static void drop_post_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.step.post.apply_filter >= 0; }); }
 
 // axis 0 then axis 1 of ONE filter over [n][ny][nx][c]: in -> tmp -> out (in and out may alias)
 static int filter_pair(psm_handle* h, const float* in, int n, int ny, int nx, int c, float* tmp, float* out, const float* wy, int ry,
@@ -161,12 +161,7 @@ int psm_bind_poststeps(psm_handle* h, const double* sigma_field, const double* s
 
 
 int psm_unbind_poststeps(psm_handle* h) {
-  if (!h) return PSM_ERR_ARG;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  drop_post_graphs(h);
-  post_free(h->post);
-  return PSM_OK;
+  return unbind(h, [h] { drop_post_graphs(h); post_free(h->post); });
 }
 
 
@@ -178,33 +173,33 @@ int psm_filter_fields_device(psm_handle* h, const float* d_in, int32_t n_cases, 
   if (rc) return rc;
   if (!d_in) return fail(h, PSM_ERR_ARG, "null buffer");
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  return poststeps_device(h, d_in, n_cases, pc, stream ? (hipStream_t)stream : h->stream);
+  return poststeps_device(h, d_in, n_cases, pc, stream_of(h, stream));
 }
 
 
 int psm_poststeps_device(psm_handle* h, const float* d_fields, int32_t n_cases, int32_t apply_filter, const float* d_dU,
                          const float* d_prev, float* d_result, float* d_change, float* d_next, void* stream) {
   if (!h) return PSM_ERR_ARG;
-  PostCall pc;
-  pc.apply_filter = apply_filter ? 1 : 0; pc.dU = d_dU; pc.prev = d_prev; pc.result = d_result; pc.change = d_change; pc.next = d_next;
+  const PostCall pc = post_call(apply_filter, d_dU, d_prev, d_result, d_change, d_next);
   int rc = post_check(h, n_cases, pc);
   if (rc) return rc;
   if (!d_fields) return fail(h, PSM_ERR_ARG, "null buffer");
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  return poststeps_device(h, d_fields, n_cases, pc, stream ? (hipStream_t)stream : h->stream);
+  return poststeps_device(h, d_fields, n_cases, pc, stream_of(h, stream));
 }
 
 
 int psm_solve_poststeps_device(psm_handle* h, const float* d_grid, int32_t n_cases, const float* out_scale, int32_t apply_filter,
                                const float* d_dU, const float* d_prev, float* d_result, float* d_change, float* d_next, void* stream) {
   if (!h) return PSM_ERR_ARG;
-  PostCall pc;
-  pc.apply_filter = apply_filter ? 1 : 0; pc.dU = d_dU; pc.prev = d_prev; pc.result = d_result; pc.change = d_change; pc.next = d_next;
+  const PostCall pc = post_call(apply_filter, d_dU, d_prev, d_result, d_change, d_next);
   int rc = post_check(h, n_cases, pc);
   if (rc) return rc;
   if (!d_grid) return fail(h, PSM_ERR_ARG, "null buffer");
   // one graph replay: the solve's launches into the handle's field buffer + the post-steps' behind them
-  return solve_device(h, d_grid, n_cases, out_scale, h->post.d_fields, stream ? (hipStream_t)stream : h->stream, nullptr, nullptr, &pc);
+  StepCall step;
+  step.post = pc;
+  return solve_device(h, d_grid, n_cases, out_scale, h->post.d_fields, stream_of(h, stream), nullptr, step);
 }
 
 
@@ -224,12 +219,10 @@ int psm_solve_poststeps(psm_handle* h, const float* grid, int32_t n_cases, const
   hipStream_t st = h->stream;
   const size_t npix = (size_t)h->Ny * h->Nx;
   const size_t gin = (size_t)n_cases * npix * h->cfg.c_in * sizeof(float), pb = (size_t)n_cases * npix * sizeof(float), fb = pb * h->cfg.c_out;
-  if ((rc = scratch_reserve(h, 0, carve_size({pb, pb, fb, pb, pb})))) return rc;
+  if ((rc = scratch_reserve(h, 0, carve_size({pb, pb, fb + 2 * pb})))) return rc;
   Carver cp{(char*)h->scr_pin};
   float* p_dU = cp.take<float>(pb / 4); float* p_prev = cp.take<float>(pb / 4);
-  float* p_out[3] = {cp.take<float>(fb / 4), cp.take<float>(pb / 4), cp.take<float>(pb / 4)};
-  float* const dst[3] = {result, pc.change ? change : nullptr, pc.next ? next : nullptr};
-  const float* const src[3] = {pc.result, pc.change, pc.next};
+  const PostOut out(pc, result, change, next, cp.take<float>((fb + 2 * pb) / 4), fb, pb);
   const bool reg_in = host_registered(h, grid, gin);
   if (!reg_in) memcpy(h->h_grid, grid, gin);
   HIPCHK(h, hipMemcpyAsync(h->d_grid_stage, reg_in ? grid : h->h_grid, gin, hipMemcpyHostToDevice, st));
@@ -238,17 +231,14 @@ int psm_solve_poststeps(psm_handle* h, const float* grid, int32_t n_cases, const
     HIPCHK(h, hipMemcpyAsync(s.d_dU, p_dU, pb, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(s.d_prev, p_prev, pb, hipMemcpyHostToDevice, st));
   }
-  for (int pass = 0; pass < 2; ++pass) {
-    if ((rc = solve_device(h, h->d_grid_stage, n_cases, out_scale, s.d_fields, st, nullptr, nullptr, &pc))) return rc;
-    for (int k = 0; k < 3; ++k)
-      if (dst[k]) HIPCHK(h, hipMemcpyAsync(p_out[k], src[k], k ? pb : fb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, wait_stream(st));
-    if (pass == 1 || !guard_take(h, h->ws0)) break;     // not the bound geometry: the field is NaN -- drop the binding, solve again on the general path
-    if ((rc = guard_drop(h, "psm_solve_poststeps"))) return rc;
-    h->err += " (solved on the general path)";
-  }
-  for (int k = 0; k < 3; ++k)
-    if (dst[k]) memcpy(dst[k], p_out[k], k ? pb : fb);
+  StepCall step;
+  step.post = pc;
+  rc = guarded_host_step(h, st, "psm_solve_poststeps", [&](int) {
+    const int rs = solve_device(h, h->d_grid_stage, n_cases, out_scale, s.d_fields, st, nullptr, step);
+    return rs ? rs : out.enqueue(h, st);
+  });
+  if (rc) return rc;
+  out.deliver();
   return PSM_OK;
 }
 

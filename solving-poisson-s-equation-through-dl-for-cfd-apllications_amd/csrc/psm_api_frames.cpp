@@ -8,8 +8,8 @@
 
 namespace psm_impl {
 
-// captured step graphs (GraphKey::frames) hold the addresses of the mesh tables and of the column array
-static void drop_frame_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.frames.cols != nullptr; }); }
+// captured step graphs (StepCall::frames) hold the addresses of the mesh tables and of the column array
+static void drop_frame_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.step.frames.cols != nullptr; }); }
 
 void frames_free(psm_handle* h) {
   FrameSet& s = h->frames;
@@ -17,10 +17,7 @@ void frames_free(psm_handle* h) {
   gradp_free(h);                        // and psm_bind_gradp_frames
   drop_frame_graphs(h);
   dev_free(s.d_cols); dev_free(s.d_extra); dev_free(s.d_raw);
-  if (s.h_cols) { (void)hipHostFree(s.h_cols); s.h_cols = nullptr; }
-  if (s.h_extra) { (void)hipHostFree(s.h_extra); s.h_extra = nullptr; }
-  if (s.h_out) { (void)hipHostFree(s.h_out); s.h_out = nullptr; }
-  if (s.h_raw) { (void)hipHostFree(s.h_raw); s.h_raw = nullptr; }
+  pin_free(s.h_cols); pin_free(s.h_extra); pin_free(s.h_out); pin_free(s.h_raw);
   s.ready = false; s.n_frames = 0; s.k = 0;
 }
 
@@ -46,6 +43,23 @@ int frames_state(psm_handle* h) {
 int frames_count_check(psm_handle* h, int n_frames) {
   if (n_frames < 1 || n_frames > h->frames.n_frames) return fail(h, PSM_ERR_ARG, "n_frames outside [1, frames bound with psm_bind_frames]");
   return PSM_OK;
+}
+
+int frames_upload_cols(psm_handle* h, const double* cols, int n_frames, int k) {
+  FrameSet& F = h->frames;
+  if (k > F.k) return fail(h, PSM_ERR_ARG, "more columns than psm_bind_frames reserved staging for");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  const size_t cb = (size_t)n_frames * h->n_cells * k * sizeof(double);
+  memcpy(F.h_cols, cols, cb);
+  HIPCHK(h, hipMemcpyAsync(F.d_cols, F.h_cols, cb, hipMemcpyHostToDevice, h->stream));
+  return PSM_OK;
+}
+
+hipError_t upload_sdf_plane(psm_handle* h, const double* sdfunct, double max_abs_dist, double* d_sdn) {
+  const size_t npix = (size_t)h->Ny * h->Nx;
+  std::vector<double> sdn(npix);
+  for (size_t i = 0; i < npix; ++i) sdn[i] = (sdfunct[i] != sdfunct[i] ? 0.0 : sdfunct[i]) / max_abs_dist;
+  return psm_copy_h2d(d_sdn, sdn.data(), npix * sizeof(double));
 }
 
 // The evaluator's column convention as plane descriptors: 0-3 -> the feature binding's velocity planes, the last two (weighting) ->
@@ -94,11 +108,8 @@ int psm_bind_frames(psm_handle* h, int32_t n_frames, int32_t k) {
   int rc;
   const size_t n_raw = n * 3 * PSM_ERR_RAW;             // psm_poisson_frames_errors: the three error blocks of every frame
   if ((rc = dev_alloc(h, &s.d_cols, n_cols)) || (rc = dev_alloc(h, &s.d_extra, n_extra)) || (rc = dev_alloc(h, &s.d_raw, n_raw))) { frames_free(h); return rc; }
-  hipError_t e = hipHostMalloc((void**)&s.h_cols, n_cols * sizeof(double), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_extra, n_extra * sizeof(double), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_out, n_out * sizeof(float), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_raw, n_raw * sizeof(double), hipHostMallocDefault);
-  if (e != hipSuccess) { frames_free(h); return fail(h, PSM_ERR_NOMEM, std::string("psm_bind_frames: ") + hipGetErrorString(e)); }
+  if ((rc = pin_alloc(h, &s.h_cols, n_cols, "psm_bind_frames")) || (rc = pin_alloc(h, &s.h_extra, n_extra, "psm_bind_frames")) ||
+      (rc = pin_alloc(h, &s.h_out, n_out, "psm_bind_frames")) || (rc = pin_alloc(h, &s.h_raw, n_raw, "psm_bind_frames"))) { frames_free(h); return rc; }
   s.n_frames = n_frames; s.k = k;
   s.ready = true;
   return PSM_OK;
@@ -106,11 +117,7 @@ int psm_bind_frames(psm_handle* h, int32_t n_frames, int32_t k) {
 
 
 int psm_unbind_frames(psm_handle* h) {
-  if (!h) return PSM_ERR_ARG;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  frames_free(h);
-  return PSM_OK;
+  return unbind(h, [h] { frames_free(h); });
 }
 
 
@@ -135,7 +142,7 @@ int psm_frames_to_grid_device(psm_handle* h, const double* d_cols, int32_t n_fra
   }
   if (!any) return fail(h, PSM_ERR_ARG, "every destination is NULL: nothing to store");
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  return frames_device(h, fc, n_frames, stream ? (hipStream_t)stream : h->stream);
+  return frames_device(h, fc, n_frames, stream_of(h, stream));
 }
 
 
@@ -161,34 +168,25 @@ int psm_poisson_frames(psm_handle* h, const double* cols, int32_t n_frames, int3
   FrameCall fc;
   int rc = poisson_frame_call(h, F.d_cols, n_frames, k, weighting, extra ? F.d_extra : nullptr, fc);
   if (rc) return rc;
-  if (k > F.k) return fail(h, PSM_ERR_ARG, "more columns than psm_bind_frames reserved staging for");
   PostSet& s = h->post;
   const size_t cap = (size_t)h->cfg.max_cases * h->Ny * h->Nx * h->cfg.c_out;
   PostCall pc;
   pc.apply_filter = apply_filter ? 1 : 0; pc.result = s.d_out;
   if (weighting) { pc.dU = s.d_dU; pc.prev = s.d_prev; pc.change = change ? s.d_out + cap : nullptr; pc.next = next ? s.d_out + 2 * cap : nullptr; }
-  HIPCHK(h, hipSetDevice(h->cfg.device));
   hipStream_t st = h->stream;
   const size_t npix = (size_t)h->Ny * h->Nx, n_extra = (size_t)k - (weighting ? 6 : 4);
-  const size_t cb = (size_t)n_frames * h->n_cells * k * sizeof(double), pb = (size_t)n_frames * npix * sizeof(float), fb = pb * h->cfg.c_out;
+  const size_t pb = (size_t)n_frames * npix * sizeof(float), fb = pb * h->cfg.c_out;
   const size_t eb = extra ? (size_t)n_frames * n_extra * npix * sizeof(double) : 0;
-  float* p_out[3] = {F.h_out, F.h_out + fb / 4, F.h_out + fb / 4 + pb / 4};
-  float* const dst[3] = {result, pc.change ? change : nullptr, pc.next ? next : nullptr};
-  const float* const src[3] = {pc.result, pc.change, pc.next};
-  memcpy(F.h_cols, cols, cb);
-  HIPCHK(h, hipMemcpyAsync(F.d_cols, F.h_cols, cb, hipMemcpyHostToDevice, st));
-  for (int pass = 0; pass < 2; ++pass) {
-    if ((rc = poisson_step_device(h, h->feat.d_vel, n_frames, LU, out_scale, pc, st, &fc))) return rc;
-    for (int q = 0; q < 3; ++q)
-      if (dst[q]) HIPCHK(h, hipMemcpyAsync(p_out[q], src[q], q ? pb : fb, hipMemcpyDeviceToHost, st));
-    if (eb && pass == 0) HIPCHK(h, hipMemcpyAsync(F.h_extra, F.d_extra, eb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, wait_stream(st));
-    if (pass == 1 || !guard_take(h, h->ws0)) break;     // not the bound geometry: the field is NaN -- drop the binding, solve again on the general path
-    if ((rc = guard_drop(h, "psm_poisson_frames"))) return rc;
-    h->err += " (solved on the general path)";
-  }
-  for (int q = 0; q < 3; ++q)
-    if (dst[q]) memcpy(dst[q], p_out[q], q ? pb : fb);
+  const PostOut out(pc, result, change, next, F.h_out, fb, pb);
+  if ((rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
+  rc = guarded_host_step(h, st, "psm_poisson_frames", [&](int pass) {
+    int rs = poisson_step_device(h, h->feat.d_vel, n_frames, LU, out_scale, pc, st, &fc);
+    if (rs || (rs = out.enqueue(h, st))) return rs;
+    if (eb && pass == 0) HIPCHK(h, hipMemcpyAsync(F.h_extra, F.d_extra, eb, hipMemcpyDeviceToHost, st));   // the planes do not depend on the route
+    return PSM_OK;
+  });
+  if (rc) return rc;
+  out.deliver();
   if (eb) memcpy(extra, F.h_extra, eb);
   return PSM_OK;
 }

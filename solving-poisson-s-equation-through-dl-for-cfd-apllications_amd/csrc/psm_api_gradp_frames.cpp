@@ -12,18 +12,15 @@ namespace psm_impl {
 constexpr int GRADP_PAIRS = 4;
 static_assert(GRADP_PAIRS <= PSM_FIELD_ERR_MAX_PAIRS, "the step's error blocks are one call of the field-error stage");
 
-// captured step graphs (GraphKey::gradp) hold the addresses of the binding's planes, SDF plane and integration tables
-static void drop_gradp_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.gradp.planes != nullptr; }); }
+// captured step graphs (StepCall::gradp) hold the addresses of the binding's planes, SDF plane and integration tables
+static void drop_gradp_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.step.gradp.planes != nullptr; }); }
 
 void gradp_free(psm_handle* h) {
   GradpSet& s = h->gradp;
   drop_gradp_graphs(h);
   dev_free(s.d_sdn); dev_free(s.d_planes); dev_free(s.d_grid); dev_free(s.d_truth); dev_free(s.d_raw);
   integ_free(s.integ);
-  if (s.h_raw) { (void)hipHostFree(s.h_raw); s.h_raw = nullptr; }
-  if (s.h_gradp) { (void)hipHostFree(s.h_gradp); s.h_gradp = nullptr; }
-  if (s.h_p) { (void)hipHostFree(s.h_p); s.h_p = nullptr; }
-  if (s.h_truth) { (void)hipHostFree(s.h_truth); s.h_truth = nullptr; }
+  pin_free(s.h_raw); pin_free(s.h_gradp); pin_free(s.h_p); pin_free(s.h_truth);
   s.ready = false; s.n_frames = 0;
 }
 
@@ -85,17 +82,15 @@ static int step_errors_device(psm_handle* h, int n_frames, const float* d_gradp,
 static int step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const float* out_scale, int apply_filter, float* d_gradp,
                        float* d_p, double* d_truth, const double* d_raw, hipStream_t st) {
   GradpSet& G = h->gradp;
-  FrameCall fc;
-  int rc = image_call(h, d_cols, n_frames, k, G.d_grid, d_truth, fc);
+  StepCall step;
+  int rc = image_call(h, d_cols, n_frames, k, G.d_grid, d_truth, step.frames);
   if (rc) return rc;
   if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_gradp_frames");
   if ((reinterpret_cast<uintptr_t>(d_gradp) & 7) || (reinterpret_cast<uintptr_t>(d_p) & 3) || (reinterpret_cast<uintptr_t>(d_raw) & 7))
     return fail(h, PSM_ERR_ARG, "a destination is misaligned (8 bytes for d_gradp and d_raw, 4 for d_p)");
-  const GradpCall gc{G.d_planes, G.d_grid, d_truth, d_p};
-  if (!apply_filter) return solve_device(h, G.d_grid, n_frames, out_scale, d_gradp, st, nullptr, nullptr, nullptr, nullptr, &fc, nullptr, &gc);
-  PostCall pc;
-  pc.apply_filter = 1; pc.result = d_gradp;
-  return solve_device(h, G.d_grid, n_frames, out_scale, h->post.d_fields, st, nullptr, nullptr, &pc, nullptr, &fc, nullptr, &gc);
+  step.gradp = GradpCall{G.d_planes, G.d_grid, d_truth, d_p};
+  if (apply_filter) { step.post.apply_filter = 1; step.post.result = d_gradp; }
+  return solve_device(h, G.d_grid, n_frames, out_scale, apply_filter ? h->post.d_fields : d_gradp, st, nullptr, step);
 }
 
 }  // namespace psm_impl
@@ -123,16 +118,9 @@ int psm_bind_gradp_frames(psm_handle* h, const double* sdfunct, const double* ma
   if ((rc = integ_bind(h, s.integ, h->Ny, h->Nx, sdfunct, (int)n, &center_y, &center_x, dx, dy, true))) { gradp_free(h); return rc; }
   if ((rc = dev_alloc(h, &s.d_sdn, npix)) || (rc = dev_alloc(h, &s.d_planes, n * 5 * npix)) || (rc = dev_alloc(h, &s.d_grid, n * npix * 3)) ||
       (rc = dev_alloc(h, &s.d_truth, n * 3 * npix)) || (rc = dev_alloc(h, &s.d_raw, n * GRADP_PAIRS * PSM_ERR_RAW))) { gradp_free(h); return rc; }
-  hipError_t e = hipHostMalloc((void**)&s.h_raw, n * GRADP_PAIRS * PSM_ERR_RAW * sizeof(double), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_gradp, n * npix * 2 * sizeof(float), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_p, n * npix * sizeof(float), hipHostMallocDefault);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_truth, n * 3 * npix * sizeof(double), hipHostMallocDefault);
-  if (e == hipSuccess) {
-    // nan0(sdfunct) / max_abs[2]: the statements of Eval_dual_Dense_onlycil.py:461-465 on the SDF channel, once for the simulation
-    std::vector<double> sdn(npix);
-    for (size_t i = 0; i < npix; ++i) sdn[i] = (sdfunct[i] != sdfunct[i] ? 0.0 : sdfunct[i]) / max_abs[2];
-    e = psm_copy_h2d(s.d_sdn, sdn.data(), npix * sizeof(double));
-  }
+  if ((rc = pin_alloc(h, &s.h_raw, n * GRADP_PAIRS * PSM_ERR_RAW, "psm_bind_gradp_frames")) || (rc = pin_alloc(h, &s.h_gradp, n * npix * 2, "psm_bind_gradp_frames")) ||
+      (rc = pin_alloc(h, &s.h_p, n * npix, "psm_bind_gradp_frames")) || (rc = pin_alloc(h, &s.h_truth, n * 3 * npix, "psm_bind_gradp_frames"))) { gradp_free(h); return rc; }
+  const hipError_t e = upload_sdf_plane(h, sdfunct, max_abs[2], s.d_sdn);     // the statements of Eval_dual_Dense_onlycil.py:461-465 on the SDF channel
   if (e != hipSuccess) { gradp_free(h); return fail(h, PSM_ERR_NOMEM, std::string("psm_bind_gradp_frames: ") + hipGetErrorString(e)); }
   s.n_frames = h->frames.n_frames;
   for (int q = 0; q < 5; ++q) s.max_abs[q] = max_abs[q];
@@ -142,11 +130,7 @@ int psm_bind_gradp_frames(psm_handle* h, const double* sdfunct, const double* ma
 
 
 int psm_unbind_gradp_frames(psm_handle* h) {
-  if (!h) return PSM_ERR_ARG;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  gradp_free(h);
-  return PSM_OK;
+  return unbind(h, [h] { gradp_free(h); });
 }
 
 
@@ -156,7 +140,7 @@ int psm_gradp_image_device(psm_handle* h, const double* d_cols, int32_t n_frames
   int rc = image_call(h, d_cols, n_frames, k, d_grid, d_truth, fc);
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  hipStream_t st = stream_of(h, stream);
   if ((rc = frames_device(h, fc, n_frames, st))) return rc;
   return gradp_pack_device(h, GradpCall{h->gradp.d_planes, d_grid, d_truth, nullptr}, n_frames, st);
 }
@@ -165,7 +149,7 @@ int psm_gradp_image_device(psm_handle* h, const double* d_cols, int32_t n_frames
 int psm_gradp_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const float* out_scale,
                             int32_t apply_filter, float* d_gradp, float* d_p, double* d_truth, double* d_raw, void* stream) {
   if (!h) return PSM_ERR_ARG;
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+  hipStream_t st = stream_of(h, stream);
   if (!d_gradp) d_gradp = h->gradp.integ.d_gradp;
   if (!d_p) d_p = h->gradp.integ.d_p;
   if (!d_truth) d_truth = h->gradp.d_truth;
@@ -187,26 +171,20 @@ int psm_gradp_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_
   int rc = image_call(h, F.d_cols, n_frames, k, G.d_grid, G.d_truth, fc);
   if (rc) return rc;
   if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_gradp_frames");
-  if (k > F.k) return fail(h, PSM_ERR_ARG, "more columns than psm_bind_frames reserved staging for");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  const size_t npix = (size_t)h->Ny * h->Nx;
-  const size_t cb = (size_t)n_frames * h->n_cells * k * sizeof(double), pb = (size_t)n_frames * npix * sizeof(float), gb = 2 * pb;
+  if ((rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
+  const size_t npix = (size_t)h->Ny * h->Nx, pb = (size_t)n_frames * npix * sizeof(float), gb = 2 * pb;
   const size_t tb = (size_t)n_frames * 3 * npix * sizeof(double), rb = (size_t)n_frames * GRADP_PAIRS * PSM_ERR_RAW * sizeof(double);
   float *d_g = G.integ.d_gradp, *d_p = G.integ.d_p;
-  memcpy(F.h_cols, cols, cb);
-  HIPCHK(h, hipMemcpyAsync(F.d_cols, F.h_cols, cb, hipMemcpyHostToDevice, st));
-  for (int pass = 0; pass < 2; ++pass) {
-    if ((rc = step_device(h, F.d_cols, n_frames, k, out_scale, apply_filter, d_g, d_p, G.d_truth, G.d_raw, st))) return rc;
-    if (raw && (rc = step_errors_device(h, n_frames, d_g, d_p, G.d_truth, G.d_raw, st))) return rc;
+  rc = guarded_host_step(h, st, "psm_gradp_frames", [&](int pass) {
+    int rs = step_device(h, F.d_cols, n_frames, k, out_scale, apply_filter, d_g, d_p, G.d_truth, G.d_raw, st);
+    if (rs || (raw && (rs = step_errors_device(h, n_frames, d_g, d_p, G.d_truth, G.d_raw, st)))) return rs;
     if (gradp) HIPCHK(h, hipMemcpyAsync(G.h_gradp, d_g, gb, hipMemcpyDeviceToHost, st));
     if (p) HIPCHK(h, hipMemcpyAsync(G.h_p, d_p, pb, hipMemcpyDeviceToHost, st));
-    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(G.h_truth, G.d_truth, tb, hipMemcpyDeviceToHost, st));
+    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(G.h_truth, G.d_truth, tb, hipMemcpyDeviceToHost, st));   // the labels do not depend on the route
     if (raw) HIPCHK(h, hipMemcpyAsync(G.h_raw, G.d_raw, rb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, wait_stream(st));
-    if (pass == 1 || !guard_take(h, h->ws0)) break;     // not the bound geometry: the gradient is NaN -- drop the binding, solve again on the general path
-    if ((rc = guard_drop(h, "psm_gradp_frames"))) return rc;
-    h->err += " (solved on the general path)";
-  }
+    return PSM_OK;
+  });
+  if (rc) return rc;
   if (gradp) memcpy(gradp, G.h_gradp, gb);
   if (p) memcpy(p, G.h_p, pb);
   if (truth) memcpy(truth, G.h_truth, tb);

@@ -79,8 +79,8 @@ int integ_bind(psm_handle* h, IntegSet& s, int ny, int nx, const double* sdfunct
   return PSM_OK;
 }
 
-// captured solve + integration graphs (GraphKey::p) hold the addresses of the binding's tables
-static void drop_pressure_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.p != nullptr; }); }
+// captured solve + integration graphs (StepCall::p) hold the addresses of the binding's tables
+static void drop_pressure_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.step.p != nullptr; }); }
 
 // state checks shared by the device-resident entries
 static int integ_check(psm_handle* h, int n_cases) {
@@ -157,12 +157,7 @@ int psm_bind_integration(psm_handle* h, const double* sdfunct, int32_t n_cases, 
 
 
 int psm_unbind_integration(psm_handle* h) {
-  if (!h) return PSM_ERR_ARG;
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  drop_pressure_graphs(h);
-  integ_free(h->integ_dev);
-  return PSM_OK;
+  return unbind(h, [h] { drop_pressure_graphs(h); integ_free(h->integ_dev); });
 }
 
 
@@ -172,7 +167,7 @@ int psm_integrate_gradp_device(psm_handle* h, const float* d_gradp, int32_t n_ca
   int rc = integ_check(h, n_cases);
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  return integrate_device(h, d_gradp, n_cases, d_p, stream ? (hipStream_t)stream : h->stream);
+  return integrate_device(h, d_gradp, n_cases, d_p, stream_of(h, stream));
 }
 
 
@@ -182,10 +177,11 @@ int psm_solve_pressure_device(psm_handle* h, const float* d_grid, int32_t n_case
   if (!d_grid || !d_p) return fail(h, PSM_ERR_ARG, "null buffer");
   int rc = integ_check(h, n_cases);
   if (rc) return rc;
-  hipStream_t st = stream ? (hipStream_t)stream : h->stream;
   float* g = d_gradp ? d_gradp : h->integ_dev.d_gradp;
   if ((reinterpret_cast<uintptr_t>(g) & 7) || (reinterpret_cast<uintptr_t>(d_p) & 3)) return fail(h, PSM_ERR_ARG, "gradient buffer must be 8-byte aligned");
-  return solve_device(h, d_grid, n_cases, out_scale, g, st, nullptr, d_p);       // one graph replay: the solve's launches + the two of the integration
+  StepCall step;
+  step.p = d_p;
+  return solve_device(h, d_grid, n_cases, out_scale, g, stream_of(h, stream), nullptr, step);   // one graph replay: the solve's launches + the two of the integration
 }
 
 
@@ -201,14 +197,15 @@ int psm_solve_pressure(psm_handle* h, const float* grid, int32_t n_cases, const 
   IntegSet& s = h->integ_dev;
   if (!reg_in) memcpy(h->h_grid, grid, gin);
   HIPCHK(h, hipMemcpyAsync(h->d_grid_stage, reg_in ? grid : h->h_grid, gin, hipMemcpyHostToDevice, h->stream));
-  for (int pass = 0; pass < 2; ++pass) {
-    if ((rc = solve_device(h, h->d_grid_stage, n_cases, out_scale, s.d_gradp, h->stream, nullptr, s.d_p))) return rc;
+  StepCall step;
+  step.p = s.d_p;
+  rc = guarded_host_step(h, h->stream, "psm_solve_pressure", [&](int) {
+    const int rs = solve_device(h, h->d_grid_stage, n_cases, out_scale, s.d_gradp, h->stream, nullptr, step);
+    if (rs) return rs;
     HIPCHK(h, hipMemcpyAsync(reg_out ? p : h->h_fields, s.d_p, pout, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, wait_stream(h->stream));
-    if (pass == 1 || !guard_take(h, h->ws0)) break;     // not the bound geometry: the gradient is NaN -- drop the binding, solve again on the general path
-    if ((rc = guard_drop(h, "psm_solve_pressure"))) return rc;
-    h->err += " (solved on the general path)";
-  }
+    return PSM_OK;
+  });
+  if (rc) return rc;
   if (!reg_out) memcpy(p, h->h_fields, pout);
   return PSM_OK;
 }

@@ -49,16 +49,17 @@ static int collect_kernel_samples(psm_handle* h, const float* d_grid, int32_t n_
     const bool integ = h->integ_dev.ready && h->integ_dev.n_cases == n_cases && h->cfg.c_out == 2 && (reinterpret_cast<uintptr_t>(d_fields) & 7) == 0;
     // with post-steps bound on a c_out == 1 handle (psm_bind_poststeps) it is the step of psm_solve_poststeps_device with the
     // weighting; dU and prev are the handle's scratch, whatever it holds
-    PostCall pc;
+    StepCall step;
+    if (integ) step.p = h->integ_dev.d_p;
+    PostCall& pc = step.post;
     const bool post = h->post.ready && h->cfg.c_out == 1;
     if (post) { pc.apply_filter = 1; pc.dU = h->post.d_dU; pc.prev = h->post.d_prev; pc.result = h->post.d_out; pc.change = h->post.d_out + (size_t)h->cfg.max_cases * h->Ny * h->Nx; pc.next = pc.change + (size_t)h->cfg.max_cases * h->Ny * h->Nx; }
     // with the Poisson features bound as well (psm_bind_features) it is the step of psm_poisson_step_device: the two feature launches
     // write the binding's image from its staging planes and scalars (zero velocities, (1, 1) unless a host step left others) and
     // the solve reads that image instead of d_grid
-    const FeatCall fc{h->feat.d_vel, h->feat.d_grid};
     const bool feat = post && h->feat.ready && n_cases <= h->feat.n_cases;
-    rc = solve_device(h, feat ? fc.grid : d_grid, n_cases, nullptr, d_fields, h->stream, nullptr, integ ? h->integ_dev.d_p : nullptr, post ? &pc : nullptr,
-                      feat ? &fc : nullptr);
+    if (feat) step.feat = FeatCall{h->feat.d_vel, h->feat.d_grid};
+    rc = solve_device(h, feat ? step.feat.grid : d_grid, n_cases, nullptr, d_fields, h->stream, nullptr, step);
     if (rc == PSM_OK && (i % 64) == 63) rc = drain();
   }
   psm_launch_probe = nullptr;

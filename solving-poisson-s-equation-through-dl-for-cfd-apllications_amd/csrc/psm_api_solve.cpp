@@ -1,4 +1,4 @@
-// psm_api_solve.cpp -- C-ABI of libpsm_hip.so (include/psm.h): one solve: route, launch sequence, graph capture, host-buffer entries.  See psm_handle.h for the map of the files.
+// psm_api_solve.cpp -- C-ABI of libpsm_hip.so (include/psm.h): one solve: route, argument builders, launch sequence, host-buffer entries (the step around it: psm_api_step.cpp).  See psm_handle.h for the map of the files.
 #include "psm_handle.h"
 
 namespace psm_impl {
@@ -58,14 +58,14 @@ int ensure_encode_aux(psm_handle* h, int n_cases) {
 
 // ---- the route --------------------------------------------------------------------------------------------------
 // The bound geometry applies to a solve of this many cases: THE spelling of "is this solve bound", for the route and for the graph keys.
-static bool bound_applies(const psm_handle* h, int n_cases) {
+bool bound_applies(const psm_handle* h, int n_cases) {
   return h->bound && (h->bound_scope == 2 || h->in_mesh_solve) && n_cases == h->bound_cases;
 }
 
 // The SDF fold applies to a solve of this many cases (psm_handle.h): a float32 single case of one row tile on a geometry bound with
 // psm_bind_geometry (whose guard riders then check the SDF channel's values; not psm_solve's own binding, whose grids nobody checks),
 // float32 MFMA arithmetic.  PSM_SDF_FOLD=0 switches it off; read per solve, and part of sequence_key.
-static bool fold_applies(const psm_handle* h, int n_cases) {
+bool fold_applies(const psm_handle* h, int n_cases) {
   if (!(bound_applies(h, n_cases) && n_cases == 1 && h->bound_scope == 2 && h->fold_bound && h->d_bpack_fold && h->d_ib_fold && h->d_sdf_bound)) return false;
   if (h->cfg.precision != PSM_PRECISION_F32 || h->NT > 4 || round_up(h->B, 32) != 32 || (h->x6_mode >= 0 && (h->x6_mode & 1))) return false;
   const char* e = getenv("PSM_SDF_FOLD");
@@ -396,138 +396,6 @@ int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, fl
   return r.bound ? stage_bound_tail(s) : stage_general_tail(s);
 }
 
-
-static int prepare_scale(psm_handle* h, Workspace& w, const float* out_scale, int n_cases, hipStream_t st, const float** d_scale) {
-  if (!out_scale) { *d_scale = h->d_ones; return PSM_OK; }
-  const int M = n_cases * h->B;
-  const int slot = h->scale_pos;
-  h->scale_pos = (h->scale_pos + 1) % psm_handle::RING;
-  HIPCHK(h, hipEventSynchronize(h->scale_ev[slot]));
-  for (int c = 0; c < n_cases; ++c)
-    for (int b = 0; b < h->B; ++b) h->h_scale[slot][c * h->B + b] = out_scale[c];
-  HIPCHK(h, hipMemcpyAsync(w.d_row_scale, h->h_scale[slot], (size_t)M * sizeof(float), hipMemcpyHostToDevice, st));
-  HIPCHK(h, hipEventRecord(h->scale_ev[slot], st));
-  *d_scale = w.d_row_scale;
-  return PSM_OK;
-}
-
-
-// ---- captured sequences ---------------------------------------------------------------------------------------------
-// The integer part of a captured sequence's cache key (GraphKey::n of solve_device, the key of a ring slot's graphs): the case
-// count, whether a row scale is uploaded, whether the bound geometry applies and, for the ring, the DMA / pull form.  Everything
-// else the route depends on is fixed while cached graphs live, because what changes it drops them: psm_plan_grid (free_plan), the
-// model setters, psm_bind_geometry* / psm_unbind_geometry and a guard trip (destroy_graphs, which calls ring_drop_graphs), the
-// integration, post-step and feature bind / unbind entries (the graphs that hold their tables); timed and profiled solves are never captured.
-// PSM_SDF_FOLD, which the route also reads per solve, IS part of the key (fold_applies): a sequence captured with the folded encode is
-// never replayed under PSM_SDF_FOLD=0, nor the other way round.
-// NOT covered: PSM_LN_FUSE, which the route reads per solve -- a graph captured under one value is replayed under the other.
-int sequence_key(const psm_handle* h, int n_cases, bool scale, bool ring) {
-  const int k = ((n_cases * 2 + (scale ? 1 : 0)) * 2 + (bound_applies(h, n_cases) ? 1 : 0)) * 2 + (fold_applies(h, n_cases) ? 1 : 0);
-  return ring ? k * 2 + (h->ring_dma ? 1 : 0) : k;
-}
-
-// Captures what `enqueue` puts on `st` into an executable graph.  The callable's own error comes first; the graph is destroyed on
-// every arm.
-int capture_graph(psm_handle* h, hipStream_t st, const char* label, const std::function<int()>& enqueue, hipGraphExec_t* exec) {
-  hipGraph_t graph = nullptr;
-  HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-  const int rc = enqueue();
-  hipError_t e = hipStreamEndCapture(st, &graph);
-  hipGraphExec_t made = nullptr;
-  if (!rc && e == hipSuccess) e = hipGraphInstantiate(&made, graph, nullptr, nullptr, 0);
-  if (graph) (void)hipGraphDestroy(graph);
-  if (rc) return rc;
-  if (e != hipSuccess) return fail(h, PSM_ERR_HIP, std::string(label) + " capture: " + hipGetErrorString(e));
-  *exec = made;
-  return PSM_OK;
-}
-
-
-int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
-                 hipStream_t st, hipEvent_t* prof, float* d_p, const PostCall* post, const FeatCall* feat, const FrameCall* frames,
-                 const DeltasCall* deltas, const GradpCall* gradp) {
-  if (!h) return PSM_ERR_ARG;
-  if (!h->planned) return fail(h, PSM_ERR_STATE, "psm_plan_grid has not been called");
-  if (!d_grid || !d_fields) return fail(h, PSM_ERR_ARG, "null buffer");
-  if (n_cases < 1 || n_cases > h->cfg.max_cases) return fail(h, PSM_ERR_ARG, "n_cases outside [1, max_cases]");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  if (!st) st = h->stream;
-  const float* d_scale = nullptr;
-  int rc = ensure_encode_aux(h, n_cases);
-  if (rc) return rc;
-  rc = prepare_scale(h, h->ws0, out_scale, n_cases, st, &d_scale);
-  if (rc) return rc;
-  h->last_cases = gradp ? 1 : n_cases;  // gradp: ws0 holds the last frame's single-case solve
-  // the mesh -> grid launch (frames), the two feature launches (feat) or the image pack (deltas, gradp), the solve, then the two integration launches (d_p) or the
-  // post-steps' (at most four); gradp: the filter among the post-steps and BEHIND it the integration with the gradp binding's tables: one linear chain
-  auto sequence = [&](hipStream_t on, hipEvent_t* ev) {
-    int rs = frames ? frames_device(h, *frames, n_cases, on) : PSM_OK;
-    if (!rs && feat) rs = features_device(h, feat->vel, n_cases, feat->grid, on);
-    if (!rs && deltas) rs = deltas_pack_device(h, *deltas, n_cases, on);
-    if (!rs && gradp) rs = gradp_pack_device(h, *gradp, n_cases, on);
-    if (!rs && gradp) {
-      // The U_to_gradP evaluator's frames, solved one by one for the reason given below: a frame's gradient holds the bits of the
-      // single-case solve EvaluationGradP.timeStep runs on its image, whatever the batch.
-      const size_t npix = (size_t)h->Ny * h->Nx;
-      for (int f = 0; f < n_cases && !rs; ++f)
-        rs = launch_all(h, h->ws0, d_grid + f * npix * h->cfg.c_in, 1, d_fields + f * npix * h->cfg.c_out, d_scale + (d_scale == h->d_ones ? 0 : f * h->B), on, ev);
-    } else if (!rs && deltas) {
-      // The deltas evaluator's frames are solved ONE BY ONE, each as the single case Evaluation.timeStep solves (with a geometry bound
-      // for one case: the 6-launch route with the folded encode), so that a frame's field holds the bits of that call whatever the
-      // batch; the network output rows of every frame are kept for the block stage, which decodes them again.
-      const size_t npix = (size_t)h->Ny * h->Nx, rows = (size_t)h->B * h->ld_out;
-      for (int f = 0; f < n_cases && !rs; ++f) {
-        rs = launch_all(h, h->ws0, d_grid + f * npix * h->cfg.c_in, 1, d_fields + f * npix * h->cfg.c_out, d_scale + (d_scale == h->d_ones ? 0 : f * h->B), on, ev);
-        if (!rs && hipMemcpyAsync(deltas->res + f * rows, h->ws0.d_res, rows * sizeof(float), hipMemcpyDeviceToDevice, on) != hipSuccess)
-          rs = fail(h, PSM_ERR_HIP, "psm_deltas_frames: copy of the network output");
-      }
-      h->last.pred_stored = false;        // ws0.d_pred holds the last frame's blocks at most
-      h->last.row_scale = d_scale;
-      h->last.res = deltas->res;
-    } else if (!rs) rs = launch_all(h, h->ws0, d_grid, n_cases, d_fields, d_scale, on, ev);
-    if (!rs && d_p) rs = integrate_device(h, d_fields, n_cases, d_p, on);
-    if (!rs && post) rs = poststeps_device(h, d_fields, n_cases, *post, on);
-    if (!rs && gradp) rs = integrate_device(h, h->gradp.integ, post ? post->result : d_fields, n_cases, gradp->p, on);
-    return rs;
-  };
-  if (prof || h->timed_kernel >= 0 || !h->use_graph) return sequence(st, prof);
-  const GraphKey key{sequence_key(h, n_cases, out_scale != nullptr), d_grid, d_fields, d_p, post ? *post : PostCall{}, feat ? feat->vel : nullptr,
-                     frames ? *frames : FrameCall{}, deltas ? *deltas : DeltasCall{}, gradp ? *gradp : GradpCall{}};
-  auto it = h->graphs.find(key);
-  if (it == h->graphs.end()) {
-    if (h->graphs.size() > 64) destroy_graphs(h);
-    hipGraphExec_t exec = nullptr;
-    if ((rc = capture_graph(h, h->stream, "solve", [&] { return sequence(h->stream, nullptr); }, &exec))) return rc;
-    it = h->graphs.emplace(key, psm_handle::SolveGraph{exec, h->last}).first;   // launch_all ran for the capture
-  } else {
-    h->last = it->second.left;                    // a replay runs no host code of launch_all
-  }
-  HIPCHK(h, hipGraphLaunch(it->second.exec, st));
-  return PSM_OK;
-}
-
-
-// ---- guard of the bound-geometry contract, host side -------------------------------------------------------------
-// true once per trip: a guard wave of a solve on workspace `w` found a grid whose flow-cell pattern is not the bound one
-bool guard_take(psm_handle* h, Workspace& w) {
-  if (!h->h_guard) return false;
-  volatile int* f = h->h_guard + w.gidx;
-  if (!*f) return false;
-  *f = 0;
-  return true;
-}
-
-// drop the binding: the following solves (and the re-run of the one that tripped) take the general path
-int guard_drop(psm_handle* h, const char* where) {
-  ++h->guard_trips;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  destroy_graphs(h);
-  h->bound = false;
-  h->fold_bound = false;
-  h->err = std::string(where) + ": the grid's flow-cell pattern (SDF channel != 0; with the SDF fold, the SDF channel's values) is not the one bound with psm_bind_geometry; the binding was dropped";
-  return PSM_OK;
-}
-
 }  // namespace psm_impl
 
 // ============================================================================
@@ -551,18 +419,13 @@ int psm_solve_grid(psm_handle* h, const float* grid, int32_t n_cases, const floa
   const bool reg_in = host_registered(h, grid, gin), reg_out = host_registered(h, fields, gout);
   if (!reg_in) memcpy(h->h_grid, grid, gin);
   HIPCHK(h, hipMemcpyAsync(h->d_grid_stage, reg_in ? grid : h->h_grid, gin, hipMemcpyHostToDevice, h->stream));
-  int rc = solve_device(h, h->d_grid_stage, n_cases, out_scale, h->d_fields_stage, h->stream, nullptr);
-  if (rc) return rc;
-  HIPCHK(h, hipMemcpyAsync(reg_out ? fields : h->h_fields, h->d_fields_stage, gout, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(h, wait_stream(h->stream));
-  if (guard_take(h, h->ws0)) {                 // not the bound geometry: the field is NaN -- drop the binding, solve again on the general path
-    if ((rc = guard_drop(h, "psm_solve_grid"))) return rc;
-    const std::string note = h->err;
-    if ((rc = solve_device(h, h->d_grid_stage, n_cases, out_scale, h->d_fields_stage, h->stream, nullptr))) return rc;
+  const int rc = guarded_host_step(h, h->stream, "psm_solve_grid", [&](int) {
+    const int rs = solve_device(h, h->d_grid_stage, n_cases, out_scale, h->d_fields_stage, h->stream, nullptr);
+    if (rs) return rs;
     HIPCHK(h, hipMemcpyAsync(reg_out ? fields : h->h_fields, h->d_fields_stage, gout, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, wait_stream(h->stream));
-    h->err = note + " (solved on the general path)";
-  }
+    return PSM_OK;
+  });
+  if (rc) return rc;
   if (!reg_out) memcpy(fields, h->h_fields, gout);
   return PSM_OK;
 }

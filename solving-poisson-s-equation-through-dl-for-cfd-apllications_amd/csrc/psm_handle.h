@@ -1,8 +1,9 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in fourteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in fifteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
-//   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, graph capture and key, psm_solve_grid*
+//   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, psm_solve_grid*
+//   psm_api_step.cpp        the step around a solve (solve_device: StepCall, step_check, row scale, graph capture and key) and the guarded host loop of every host entry
 //   psm_api_ring.cpp        the pinned submission ring (psm_ring_*, psm_submit_grid*, psm_wait_grid) and registered host memory (psm_host_*)
 //   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*; the case batch psm_set_geometry_cases / psm_solve_cases*; host tables of both in psm_mesh_tables.cpp), psm_mesh_to_grid
 //   psm_api_eval.cpp        evaluator helpers on the planned grid: psm_reassemble, psm_label_blocks, psm_block_error
@@ -126,6 +127,7 @@ struct PostCall {
 struct FeatCall {
   const double* vel = nullptr;          // [n_cases][4][ny*nx] velocity planes; nullptr: no features stage
   float* grid = nullptr;                // the image the two launches write and the solve reads
+  auto tie() const { return std::tie(vel, grid); }
 };
 
 // The mesh -> grid stage in front of the features (psm_poisson_frames*): the launch holds the column array and the k plane descriptors.
@@ -133,13 +135,18 @@ struct FrameCall {
   const double* cols = nullptr;         // [n_frames][n_cells][k]; nullptr: no frame stage
   int k = 0, fill = 1;
   PsmFramePlane out[PSM_FRAME_MAX_COLS] = {};
-  auto key() const {                    // everything the captured launch holds, as one comparable value
+  struct Key {                          // (a type of this namespace: what is instantiated over it stays out of the exported symbols)
     std::array<int64_t, 3 + 3 * PSM_FRAME_MAX_COLS> a{};
+    bool operator<(const Key& o) const { return a < o.a; }
+  };
+  Key key() const {                     // everything the captured launch holds, as one comparable value
+    Key key;
+    auto& a = key.a;
     a[0] = (int64_t)reinterpret_cast<intptr_t>(cols); a[1] = k; a[2] = fill;
     for (int c = 0; c < k && c < PSM_FRAME_MAX_COLS; ++c) {
       a[3 + 3 * c] = (int64_t)reinterpret_cast<intptr_t>(out[c].dst); a[4 + 3 * c] = out[c].frame_stride; a[5 + 3 * c] = out[c].as_f32;
     }
-    return a;
+    return key;
   }
 };
 
@@ -150,7 +157,7 @@ struct DeltasCall {
   float *grid = nullptr, *label = nullptr;
   double* truth = nullptr;
   float* res = nullptr;                 // the binding's copy of every frame's network output rows (the frames are solved one by one)
-  auto tie() const { return std::tie(planes, grid, label, truth); }
+  auto tie() const { return std::tie(planes, grid, label, truth); }   // not res: the binding's buffer, the same for every call
 };
 
 // The image / label pack between the mesh -> grid stage and the solve, and the integration behind the solve (and its filter), of the
@@ -164,23 +171,32 @@ struct GradpCall {
   auto tie() const { return std::tie(planes, grid, truth, p); }
 };
 
-struct GraphKey {
-  int n; const void* g; void* f;        // n: sequence_key()
-  void* p = nullptr;                    // psm_solve_pressure*: where the integration behind the solve writes p (null: the solve alone)
-  PostCall post{};                      // psm_solve_poststeps*: the post-steps behind the solve (apply_filter == -1: none)
-  const void* vel = nullptr;            // psm_poisson_step*: the velocity planes of the features in front of the solve (g is their image)
-  FrameCall frames{};                   // psm_poisson_frames*: the mesh -> grid stage in front of the features (cols == nullptr: none)
-  DeltasCall deltas{};                  // psm_deltas_frames*: the image pack behind the mesh -> grid stage (planes == nullptr: none)
-  GradpCall gradp{};                    // psm_gradp_frames*: the pack behind the mesh -> grid stage, the integration behind the filter (planes == nullptr: none)
-  auto head() const { return std::tie(n, g, f, p, vel); }
-  bool operator<(const GraphKey& o) const {
-    if (head() != o.head()) return head() < o.head();
-    if (post.tie() != o.post.tie()) return post.tie() < o.post.tie();
-    if (deltas.tie() != o.deltas.tie()) return deltas.tie() < o.deltas.tie();
-    if (gradp.tie() != o.gradp.tie()) return gradp.tie() < o.gradp.tie();
-    if (!frames.cols && !o.frames.cols) return false;       // no frame stage on either side: nothing more to compare
-    return frames.key() < o.frames.key();
+// What surrounds ONE solve (solve_device, psm_api_step.cpp), in launch order; every stage keeps its own "absent" value.  A new stage
+// is one member here and one entry in key(): the graph cache compares nothing else, so a stage in the sequence is in the cache key.
+struct StepCall {
+  FrameCall frames{};                   // psm_poisson_frames*, psm_deltas_frames*, psm_gradp_frames*: the mesh -> grid launch (cols == nullptr: none)
+  FeatCall feat{};                      // psm_poisson_step*: the two feature launches write the solve's image (vel == nullptr: none)
+  DeltasCall deltas{};                  // psm_deltas_frames*: the image pack, the frames solved one by one (planes == nullptr: none)
+  GradpCall gradp{};                    // psm_gradp_frames*: likewise, and BEHIND the post-steps the integration with the binding's own tables
+  float* p = nullptr;                   // psm_solve_pressure*: where the bound integration (psm_bind_integration) behind the solve writes p
+  PostCall post{};                      // psm_solve_poststeps*: the bound post-steps behind the solve (apply_filter == -1: none)
+  auto key() const { return std::make_tuple(frames.key(), feat.tie(), deltas.tie(), gradp.tie(), p, post.tie()); }
+  const char* fault() const {           // the combinations the sequence does not define (null: defined); no C entry builds one
+    const bool fr = frames.cols, ft = feat.vel, dl = deltas.planes, gp = gradp.planes;
+    if (dl && gp) return "the deltas and the gradP pack exclude each other";
+    if ((dl || gp) && !fr) return "an image pack reads the planes of the mesh -> grid stage: it needs frames";
+    if (ft && (dl || gp)) return "the features and an image pack both write the solve's image";
+    if (p && gp) return "the gradP frames integrate with their own tables: not the bound integration as well";
+    if (fr && !ft && !dl && !gp) return "frames alone: nothing reads the planes (features or an image pack)";
+    return nullptr;
   }
+};
+
+struct GraphKey {
+  int n; const void* g; void* f;        // n: sequence_key(); the solve's grid and field
+  StepCall step{};
+  auto key() const { return std::make_tuple(n, g, f, step.key()); }
+  bool operator<(const GraphKey& o) const { return key() < o.key(); }
 };
 
 // Everything ONE in-flight solve writes.  The handle owns one for the synchronous / device entries (ws0) and one per
@@ -518,6 +534,7 @@ int poisson_frame_call(psm_handle* h, const double* d_cols, int n_frames, int k,
 int field_errors_device(psm_handle* h, const PsmFieldErrorArgs& stage, double* d_raw, hipStream_t st);
 int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const double* LU, const float* out_scale, const PostCall& pc,
                         hipStream_t st, const FrameCall* frames = nullptr);
+PostCall post_call(int apply_filter, const float* dU, const float* prev, float* result, float* change, float* next);
 int features_device(psm_handle* h, const double* d_vel, int n_cases, float* d_grid, hipStream_t st);
 std::vector<uint16_t> pack_comp_in_bf16(const double* comp, int P, int K, int c_in, int S, int NT);
 std::vector<uint16_t> pack_comp_out_bf16(const double* comp, int P, int K_out, int G);
@@ -526,6 +543,8 @@ int ensure_encode_aux(psm_handle* h, int n_cases);
 SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_grid, int n_cases, bool profiled);
 int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, float* d_fields, const float* d_row_scale,
                hipStream_t st, hipEvent_t* prof);
+bool bound_applies(const psm_handle* h, int n_cases);
+bool fold_applies(const psm_handle* h, int n_cases);
 int sequence_key(const psm_handle* h, int n_cases, bool scale, bool ring = false);
 int capture_graph(psm_handle* h, hipStream_t st, const char* label, const std::function<int()>& enqueue, hipGraphExec_t* exec);
 // one builder per kernel-argument block (psm_api_solve.cpp): the stages of launch_all, psm_read_stage, psm_block_error and psm_reassemble
@@ -538,20 +557,21 @@ PsmPasteArgs paste_args(const psm_handle* h, const Workspace& w, float* d_fields
 // n_partials > 0 partial maxima itself and leaves the scalar in the mesh's d_umax
 PsmToGridArgs to_grid_args(const psm_handle* h, const double* d_umax, double umax_val, int n_partials);
 PsmToMeshArgs to_mesh_args(const psm_handle* h, const double* d_umax, double umax_val, double* p_out);
-// d_p != nullptr: the bound integration (psm_bind_integration) of d_fields into d_p follows in the same stream / the same graph;
-// post (apply_filter >= 0): the bound post-steps (psm_bind_poststeps) of d_fields follow likewise;
-// feat (vel != nullptr): the bound features (psm_bind_features) write d_grid == feat->grid in front of the solve, likewise;
-// frames (with feat): the mesh -> grid launch of psm_poisson_frames* writes feat->vel (and the post-steps' inputs) in front of the features;
-// deltas (with frames, without feat): the image pack of psm_deltas_frames* turns the planes the mesh -> grid launch wrote into d_grid;
-// gradp (with frames, without feat, deltas and d_p): the pack of psm_gradp_frames* likewise, the frames solved one by one, and BEHIND
-// the post-steps the integration with the gradp binding's own tables, of post->result where there is a filter, else of d_fields
+// the stages of `step` and the solve between them on one stream / in one graph replay; the combinations of stages: step_check there
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
-                 hipStream_t st, hipEvent_t* prof, float* d_p = nullptr, const PostCall* post = nullptr, const FeatCall* feat = nullptr,
-                 const FrameCall* frames = nullptr, const DeltasCall* deltas = nullptr, const GradpCall* gradp = nullptr);
+                 hipStream_t st, hipEvent_t* prof, const StepCall& step = {});
 int deltas_pack_device(psm_handle* h, const DeltasCall& dc, int n_frames, hipStream_t st);
 int gradp_pack_device(psm_handle* h, const GradpCall& gc, int n_frames, hipStream_t st);
 bool guard_take(psm_handle* h, Workspace& w);
 int guard_drop(psm_handle* h, const char* where);
+// A host entry's step: `enqueue` puts the step and its device -> host copies on `st`, this waits; a tripped guard drops the binding
+// and the step runs once more (pass 1), on the general path.
+int guarded_host_step(psm_handle* h, hipStream_t st, const char* where, const std::function<int(int pass)>& enqueue);
+int frames_upload_cols(psm_handle* h, const double* cols, int n_frames, int k);   // a frame host entry's columns, through the frame binding's staging
+// nan0(sdfunct) / max_abs_dist in float64 into d_sdn [npix]: the SDF channel of the deltas and the gradP image, once for the simulation
+hipError_t upload_sdf_plane(psm_handle* h, const double* sdfunct, double max_abs_dist, double* d_sdn);
+int unbind(psm_handle* h, const std::function<void()>& free_fn);   // the body of a psm_unbind_* entry: nothing in flight reads what free_fn releases
+inline hipStream_t stream_of(const psm_handle* h, void* stream) { return stream ? (hipStream_t)stream : h->stream; }
 int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases = 1);
 bool host_registered(const psm_handle* h, const void* p, size_t bytes);
 
@@ -608,6 +628,30 @@ int dev_upload(psm_handle* h, T** p, const std::vector<T>& v) {
 
 template <typename T>
 void dev_free(T*& p) { if (p) { (void)psm_dev_free(p); p = nullptr; } }
+
+
+// pinned host memory of a binding: n elements; a failure carries the entry's name (`where`) and the entry's code
+template <typename T>
+int pin_alloc(psm_handle* h, T** p, size_t n, const char* where, int code = PSM_ERR_NOMEM) {
+  const hipError_t e = hipHostMalloc((void**)p, n * sizeof(T), hipHostMallocDefault);
+  return e == hipSuccess ? PSM_OK : fail(h, code, std::string(where) + ": " + hipGetErrorString(e));
+}
+template <typename T>
+void pin_free(T*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } }
+
+
+// result / change / next of a post-step call through pinned memory (result | change | next behind `pinned`): what was asked for
+struct PostOut {
+  float* host[3]; const float* dev[3]; float* pin[3]; size_t bytes[3];
+  PostOut(const PostCall& pc, float* result, float* change, float* next, float* pinned, size_t fb, size_t pb)
+      : host{result, pc.change ? change : nullptr, pc.next ? next : nullptr}, dev{pc.result, pc.change, pc.next},
+        pin{pinned, pinned + fb / 4, pinned + (fb + pb) / 4}, bytes{fb, pb, pb} {}
+  int enqueue(psm_handle* h, hipStream_t st) const {
+    for (int q = 0; q < 3; ++q) if (host[q]) HIPCHK(h, hipMemcpyAsync(pin[q], dev[q], bytes[q], hipMemcpyDeviceToHost, st));
+    return PSM_OK;
+  }
+  void deliver() const { for (int q = 0; q < 3; ++q) if (host[q]) memcpy(host[q], pin[q], bytes[q]); }
+};
 
 
 inline uint16_t f2bf(double v) {             // round-to-nearest-even float -> bf16 (NaN stays NaN)

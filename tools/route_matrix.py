@@ -12,6 +12,12 @@ The `boundary` configurations (--only boundary, or one of BOUNDARY by name) hash
 that can go wrong: every one runs in a child process of its own with its switches in the environment (they are read once per
 process) and prints one SHA-256 line per output.
 
+The `steps` configurations (--only steps, or one of STEPS by name) hash the entries that put stages around a solve (solve_device,
+csrc/psm_api_step.cpp), each in a child process of its own: per variant (with / without out_scale, apply_filter 0 / 1) one call on a
+handle that launches plainly, then a capture and two replays on a PSM_GRAPH=1 handle, one SHA-256 per output; the `_host`
+configurations go through the host entry on a bound geometry and then, with one frame, on a geometry that is not the frames' (one
+guard trip, the re-run on the general path).
+
 --lib: the library to load (default: the tree's libpsm_hip.so), e.g. the parent commit's build.  PSM_MESH_GRAPH is read once per
 process: the `mesh` configuration runs in the mode --mesh-graph sets (default 2), so the three modes take three runs.
 """
@@ -62,6 +68,12 @@ BOUNDARY = {
     "block_error": {},                                       # psm_block_error behind a solve: label blocks + the per-block sums
     "field_errors": {},                                      # psm_field_errors_device: 17030 pixels (no multiple of 4), dense aligned / odd-offset / strided planes
 }
+# name: (entry, frames per call; 0: the host entry, bound and tripping).  Frame entries on hand-made tables of 200 cells: 138 x 300, the
+# evaluator's grid (161 workgroups + 184 pixels); the gradP frames on 320 x 300.  k: 7 = the velocities, one extra plane, the
+# weighting pair (the error blocks need the two label planes: 8); 4 / 6 = one column more than the deltas / gradP pack stores.
+STEPS = {"pressure": None, "poststeps": None, "poisson_step": ("poisson_step", 2)}
+for _e in ("poisson_frames", "poisson_frames_errors", "deltas_frames", "gradp_frames"):
+    STEPS.update({f"{_e}_n1": (_e, 1), f"{_e}_n3": (_e, 3), f"{_e}_host": (_e, 0)})
 OTHER = ["attention_ln_deferred", "attention_ln_launched", "conv1d_head", "mesh", "ring", "pressure", "poststeps"]
 _lines = []
 
@@ -346,15 +358,130 @@ def boundary_config(name):
                 a.free()
 
 
-def boundary(names, lib):
+def steps_config(name):
+    """Runs in the child process: one line per output."""
+    if STEPS[name] is None:                                  # pressure, poststeps: the configurations of OTHER, in a process of their own
+        return other_config(name)
+    import numpy as np
+    import cases
+    from hipmem import DeviceArray
+    from psm_amd import GridSurrogate, synthetic
+    from test_poisson_step_device import K, MAX_ABS, P_SCALE, S_FIELD, S_WEIGHT, model4
+    entry, n = STEPS[name]
+    poisson, NF, CELLS = entry.startswith("poisson"), 3, 200
+    ny, nx = (320, 300) if entry == "gradp_frames" else (138, 300)
+    k = {"poisson_step": 0, "poisson_frames": 7, "poisson_frames_errors": 8, "deltas_frames": 4, "gradp_frames": 6}[entry]
+    npix, rng = ny * nx, np.random.default_rng(1901)
+    vtx = rng.integers(0, CELLS, (npix, 3)).astype(np.int32)                    # the tables of tests/test_field_errors.py:flow_tables on this grid
+    w = rng.random((npix, 2)) * 0.5
+    wts = np.ascontiguousarray(np.c_[w, 1.0 - w.sum(axis=1)])
+    idx = np.c_[np.arange(npix) // nx, np.arange(npix) % nx].astype(np.int32)
+    sdf = 0.05 + 0.2 * rng.random((ny, nx))
+    sdf[40:75, 30:70] = 0.0                                                     # no flow; rolled by 11 columns: the geometry that trips the guard
+    cols = rng.standard_normal((NF, CELLS, max(k, 1))) * (1.0 + 0.3 * np.arange(NF))[:, None, None]
+    if poisson and k:
+        cols[..., 2:4] *= 0.05
+        cols[..., k - 2] = np.abs(cols[..., k - 2]) / np.abs(cols[..., k - 2]).max(axis=1, keepdims=True)
+        cols[..., k - 1] *= 0.1
+        cols[0, 3:6, 4] = np.nan                                                # a label plane with NaN cells
+    cols = np.ascontiguousarray(cols)
+    U = [float(np.sqrt(cols[f, :, 0] ** 2 + cols[f, :, 1] ** 2).max()) for f in range(NF)] if k else [1.3, 1.7, 2.1]
+    lu, u2 = np.array([[0.16, u] for u in U]), [u * u for u in U]
+    scale = [P_SCALE * u * u for u in U]
+    vel = np.ascontiguousarray(rng.standard_normal((NF, 4, ny, nx)) * (sdf != 0))
+    dU, prev = np.abs(rng.standard_normal((NF, ny, nx))).astype(np.float32), (0.1 * rng.standard_normal((NF, ny, nx))).astype(np.float32)
+    if poisson:
+        model, c_in, sdf_scale = model4(), 4, MAX_ABS[3]
+    elif entry == "deltas_frames":
+        model, c_in, sdf_scale = synthetic.make_model("deltas", p_in=48, p_out=40, c_in=3, seed_pca=778, seed_w=6), 3, cases.DATASET_MAXS[2]
+    else:
+        model, c_in, sdf_scale = synthetic.make_model("gradp", p_in=32, p_out=32), 3, cases.GRADP_MAXS[2]
+    model.sdf_ch = c_in - 1
+
+    def handle(graph):
+        os.environ["PSM_GRAPH"] = "1" if graph else "0"                          # read by psm_create
+        sur = GridSurrogate(model, ny, nx, max_cases=NF)
+        sur.set_mesh(vtx, wts, idx, sdf, CELLS)
+        sur.bind_poststeps(S_FIELD, S_WEIGHT)
+        if poisson:
+            sur.bind_features(np.repeat(sdf[None], NF, axis=0), K, MAX_ABS)
+        if k:
+            sur.bind_frames(NF, k)
+        if entry == "deltas_frames":
+            sur.bind_deltas_frames(sdf, cases.DATASET_MAXS)
+        if entry == "gradp_frames":
+            assert sur.bind_gradp_frames(sdf, cases.GRADP_MAXS, 57, 50, 1.0 / nx, 1.0 / ny)
+        return sur
+
+    def bind(sur, frames, other):                            # the frames' own geometry, or one whose flow-cell pattern is another
+        one = not poisson                                    # the deltas and gradP frames are solved one by one: a single case is bound
+        g = np.zeros((1 if one else frames, ny, nx, c_in), np.float32)
+        g[..., c_in - 1] = ((np.roll(sdf, 11, axis=1) if other else sdf) / sdf_scale).astype(np.float32)[None]
+        assert sur.bind_geometry(g[0] if one else g) and sur.geometry_bound
+
+    def host_call(sur, frames, sc, af):
+        c, s = cols[:frames], (scale[:frames] if sc else None)
+        if entry == "poisson_frames":
+            return dict(zip(("result", "change", "next", "extra"), sur.poisson_frames(c, lu[:frames], out_scale=s, apply_filter=af)))
+        if entry == "poisson_frames_errors":
+            return {"raw": sur.poisson_frames_errors(c, lu[:frames], out_scale=s, apply_filter=af)}
+        if entry == "deltas_frames":
+            return dict(zip(("result", "truth", "raw"), sur.deltas_frames(c, u2[:frames], out_scale=s, apply_filter=af)))
+        return dict(zip(("gradp", "p", "truth", "raw"), sur.gradp_frames(c, out_scale=s, apply_filter=af)))
+
+    def device_call(sur, b, sc, af):
+        s = scale[:n] if sc else None
+        if entry == "poisson_step":
+            sur.poisson_step_device(b["vel"].ptr, n, lu[:n], b["result"].ptr, af, b["dU"].ptr, b["prev"].ptr, b["change"].ptr, b["next"].ptr, out_scale=s)
+        elif entry == "poisson_frames":
+            sur.poisson_frames_device(b["cols"].ptr, n, k, lu[:n], b["result"].ptr, af, True, b["extra"].ptr, b["change"].ptr, b["next"].ptr, out_scale=s)
+        elif entry == "poisson_frames_errors":
+            sur.poisson_frames_errors_device(b["cols"].ptr, n, k, lu[:n], b["extra"].ptr, b["result"].ptr, b["next"].ptr, b["raw"].ptr, af, b["change"].ptr, out_scale=s)
+        elif entry == "deltas_frames":
+            sur.deltas_frames_device(b["cols"].ptr, n, k, u2[:n], b["result"].ptr, b["truth"].ptr, b["raw"].ptr, af, out_scale=s)
+        else:
+            sur.gradp_frames_device(b["cols"].ptr, n, k, b["gradp"].ptr, b["p"].ptr, b["truth"].ptr, b["raw"].ptr, af, out_scale=s)
+        sur.synchronize()
+        return {key: b[key].numpy() for key in outputs}
+
+    f32, f64 = np.float32, np.float64
+    outputs = {"poisson_step": ("result", "change", "next"), "poisson_frames": ("result", "change", "next", "extra"),
+               "poisson_frames_errors": ("result", "change", "next", "extra", "raw"), "deltas_frames": ("result", "truth", "raw"),
+               "gradp_frames": ("gradp", "p", "truth", "raw")}[entry]
+    shapes = {"result": ((NF, npix), f32), "change": ((NF, npix), f32), "next": ((NF, npix), f32), "extra": ((NF, max(k - 6, 1), npix), f64),
+              "raw": ((NF, 4, 8), f64), "truth": ((NF, 3, npix), f64), "gradp": ((NF, npix, 2), f32), "p": ((NF, npix), f32)}
+    line = lambda what, outs: [say(f"{name:28s} {what:34s} {key:7s} {sha(a)}") for key, a in outs.items() if a is not None]
+    for graph in (False, True):
+        with handle(graph) as sur:
+            mode = "graph" if graph else "plain"
+            if n == 0:                                       # host entry: bound (3 frames), then one frame on another geometry
+                bind(sur, NF, other=False)
+                line(f"{mode} host bound scale=1 af=1", host_call(sur, NF, True, True))
+                assert sur.guard_trips == 0 and sur.geometry_bound, "the frames' own geometry tripped the guard"
+                bind(sur, 1, other=True)
+                line(f"{mode} host trip scale=0 af=0", host_call(sur, 1, False, False))
+                say(f"{name:28s} {mode} host trip: guard trips {sur.guard_trips}, still bound {sur.geometry_bound}")
+                continue
+            b = {key: DeviceArray(np.zeros(*shapes[key])) for key in outputs}
+            b.update(vel=DeviceArray(vel), dU=DeviceArray(dU), prev=DeviceArray(prev), cols=DeviceArray(cols))
+            for sc in (False, True):
+                for af in (False, True):
+                    for rep in range(3 if graph else 1):     # graph: the capture and two replays
+                        what = ("plain" if not graph else ("capture", "replay1", "replay2")[rep]) + f" scale={int(sc)} af={int(af)}"
+                        line(what, device_call(sur, b, sc, af))
+            for d in b.values():
+                d.free()
+
+
+def children(names, lib, flag, envs):
     """One child process per configuration, its switches in its environment; the children's lines are repeated here."""
     import subprocess
     for name in names:
-        env = dict(os.environ, **BOUNDARY[name])
+        env = dict(os.environ, **envs.get(name, {}))
         for k in ("PSM_DEVICE_UMAX", "PSM_MESH_GRAPH"):
-            if k not in BOUNDARY[name]:
+            if k not in envs.get(name, {}):
                 env.pop(k, None)
-        cmd = [sys.executable, os.path.abspath(__file__), "--boundary-child", name] + (["--lib", lib] if lib else [])
+        cmd = [sys.executable, os.path.abspath(__file__), flag, name] + (["--lib", lib] if lib else [])
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
         for ln in r.stdout.splitlines():
             say(ln)
@@ -362,6 +489,10 @@ def boundary(names, lib):
             say(f"{name:28s} FAILED exit {r.returncode}: {r.stderr.strip().splitlines()[-1] if r.stderr.strip() else ''}")
             return r.returncode                              # nothing more on the GPU after a child that died
     return 0
+
+
+def boundary(names, lib):
+    return children(names, lib, "--boundary-child", BOUNDARY)
 
 
 def dispatches(paths):
@@ -400,6 +531,7 @@ def main():
     ap.add_argument("--mesh-graph", default="2", choices=["0", "1", "2"])
     ap.add_argument("--out")
     ap.add_argument("--boundary-child", help=argparse.SUPPRESS)
+    ap.add_argument("--steps-child", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.dispatches:
         return dispatches(args.dispatches)
@@ -409,10 +541,17 @@ def main():
         os.environ["PSM_LIB"] = os.path.abspath(args.lib)
     if args.boundary_child:
         return boundary_config(args.boundary_child)
+    if args.steps_child:
+        return steps_config(args.steps_child)
     only = args.only.split(",") if args.only else []
-    if only and all(n == "boundary" or n in BOUNDARY for n in only):     # the parent process never opens the GPU
-        say(f"# tools/route_matrix.py boundary lib={args.lib or 'libpsm_hip.so of the tree'}")
-        rc = boundary([b for n in only for b in (BOUNDARY if n == "boundary" else [n])], args.lib)
+    group = next((g for g, names in (("boundary", BOUNDARY), ("steps", STEPS)) if only and all(n == g or n in names for n in only)), None)
+    if group:                                                            # the parent process never opens the GPU
+        if group == "boundary":
+            say(f"# tools/route_matrix.py boundary lib={args.lib or 'libpsm_hip.so of the tree'}")
+            rc = boundary([b for n in only for b in (BOUNDARY if n == "boundary" else [n])], args.lib)
+        else:                                                            # no library path in the output: two libraries' runs are compared with cmp
+            say("# tools/route_matrix.py steps")
+            rc = children([b for n in only for b in (STEPS if n == "steps" else [n])], args.lib, "--steps-child", {})
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
