@@ -632,6 +632,74 @@ int psm_gradp_frames_device(psm_handle* h, const double* d_cols, int32_t n_frame
 int psm_gradp_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, const float* out_scale, int32_t apply_filter,
                      float* gradp, float* p, double* truth, double* raw);
 
+/* A frame's dataset rows in, the per-frame scalars and the columns of the frame entries above made on the device: the head of the
+ * three evaluators' timeSteps (surrogate.py) without per-cell host arithmetic, at half the bytes of the float64 columns.
+ * rows [n_frames][n_cells][width] float32, row-major: the dataset frame cut at `indice`, nothing else done to it (r0, r1 = Ux, Uy;
+ * r2 = p; r5, r6 = delta_U; r7 = delta_p; r8, r9 = delta_U_prev; r10 = delta_p_prev -- the gradP dataset: r6, r7 = dPdx, dPdy).
+ * Two launches for the batch (csrc/psm_rows.hip; the frame is a launch dimension): partial maxima per (frame, 256-cell part), then a
+ * finish launch in which every workgroup folds its frame's partials and writes its cells' columns.  All arithmetic is NumPy's on
+ * float32, each operation rounded on its own (no fma), widened afterwards: U = max sqrt(r0^2 + r1^2), dU = max sqrt(r5^2 + r6^2),
+ * c = max(|r5 - r8| + |r6 - r9|); a NaN anywhere makes a maximum NaN (np.max); U^2 = U * U in float32 (pow(U, 2.0) on a float32
+ * wherever libm's powf rounds correctly; it is documented to within 1 ulp).  No atomics: the scalars are bit-reproducible.
+ * `kind` selects the recipe; the columns d_cols [n_frames][n_cells][k] float64 hold the float32 results, widened:
+ *   PSM_ROWS_DELTAS  k = 3: r5 / U, r6 / U, r7 / U^2
+ *                    relevant = !(dU / U < 1e-4);  out-scale = (float)base * U^2 in float32
+ *   PSM_ROWS_POISSON k = 8: r0, r1, r5, r6, r7, r2, (|r5 - r8| + |r6 - r9|) / c, r10
+ *                    relevant = !(dU / U < 1e-4 || dU < 1e-6 || U < 1e-6) in float32;  out-scale = base * U^2 in float64
+ *   PSM_ROWS_GRADP   k = 5: r0 / U, r1 / U, r6 * ex / U^2, r7 * ey / U^2, r2 / U^2, ex and ey rounded to float32 (what
+ *                    EvaluationGradP holds);  relevant = 1;  out-scale = 1;  dU and c are not taken (0), nor is c for PSM_ROWS_DELTAS
+ * d_scalars [n_frames][8] float64 = U, dU, c, relevant (1 / 0), U^2, out-scale, 0, 0.  A NaN maximum compares false: relevant.
+ * An IRRELEVANT frame keeps its slot: all-zero columns, U = U^2 = 1, out-scale 0, relevant 0 (dU and c as measured); behind a
+ * step its fields and sums are unspecified (they may be NaN), the other frames' bits are what they are without it, and it cannot
+ * trip the bound-geometry guard -- the SDF channel comes from the binding.
+ * psm_bind_rows: after psm_bind_frames; reserves device and pinned staging for the bound frame count x mesh cells x width rows,
+ * the partial maxima and the scalar slots: after it a step allocates nothing.  width in [8, 16] (PSM_ERR_ARG).  Dropped by what
+ * drops the frame binding (psm_bind_frames / psm_unbind_frames, a new mesh, psm_plan_grid, a model change). */
+#define PSM_ROWS_DELTAS  0   /* pressureSM_deltas evaluator:  Evaluation.timeSteps */
+#define PSM_ROWS_POISSON 1   /* pressureSM_Poisson evaluator: EvaluationPoisson.timeSteps */
+#define PSM_ROWS_GRADP   2   /* U_to_gradP evaluator:         EvaluationGradP.timeSteps */
+int psm_bind_rows(psm_handle* h, int32_t width);
+int psm_unbind_rows(psm_handle* h);
+/* The stage alone, as plain launches on device pointers, asynchronous on `stream` (NULL: the handle's).  n_cells in [1, cells of
+ * the mesh]; params [4] = base, phi, ex, ey is a HOST array copied before return (base: PSM_ROWS_DELTAS / _POISSON; ex, ey:
+ * PSM_ROWS_GRADP; phi is not used by the stage alone).  d_cols NULL: the frame binding's column buffer (it must have been bound with
+ * at least k columns); d_scalars NULL: the binding's slots.  PSM_ERR_ARG and nothing enqueued: an unknown kind, width outside
+ * [8, 16] (below 11 for PSM_ROWS_DELTAS / _POISSON), n_frames outside [1, bound count], n_cells outside the mesh, d_rows NULL, a
+ * misaligned pointer (4 bytes for the rows, 8 for columns and scalars), a zero or non-finite base (kinds that use it), a
+ * non-finite phi, ex or ey.  PSM_ERR_STATE names the missing binding. */
+int psm_rows_prepare_device(psm_handle* h, int32_t kind, const float* d_rows, int32_t n_frames, int64_t n_cells, int32_t width,
+                            const double* params, double* d_cols, double* d_scalars, void* stream);
+/* The whole steps: the _frames entries of the same evaluator with the two launches at the head of their ONE graph replay.  rows +
+ * width take the place of cols (the columns go through the frame binding's buffer, bound with at least k columns; the rows cover
+ * the whole mesh), base (phi; ex, ey) the place of U2 / LU / out_scale: the finish launch writes the row scale of the decode, the
+ * U^2 of the deltas pack and the (L, U) = (phi, U) of the feature launches into the device arrays those kernels read, so nothing but
+ * the rows is uploaded in front of a step.  base = max_abs_p (deltas) / max_abs_delta_p (Poisson).  d_scalars [n_frames][8] beside
+ * the other outputs (NULL: the binding's slots).  Every other argument, the bindings needed and the errors are those of the
+ * counterpart (the Poisson entries pass k = 8) plus those of psm_rows_prepare_device; relevant frames hold the bits the counterpart
+ * gives on the host-made columns and scalars. */
+int psm_deltas_rows_device(psm_handle* h, const float* d_rows, int32_t n_frames, int32_t width, double base, int32_t apply_filter,
+                           float* d_result, double* d_truth, double* d_raw, double* d_scalars, void* stream);
+int psm_poisson_rows_device(psm_handle* h, const float* d_rows, int32_t n_frames, int32_t width, double base, double phi,
+                            int32_t apply_filter, int32_t weighting, double* d_extra, float* d_result, float* d_change,
+                            float* d_next, double* d_scalars, void* stream);
+int psm_poisson_rows_errors_device(psm_handle* h, const float* d_rows, int32_t n_frames, int32_t width, double base, double phi,
+                                   int32_t apply_filter, int32_t weighting, double* d_extra, float* d_result, float* d_change,
+                                   float* d_next, double* d_raw, double* d_scalars, void* stream);
+int psm_gradp_rows_device(psm_handle* h, const float* d_rows, int32_t n_frames, int32_t width, double ex, double ey,
+                          int32_t apply_filter, float* d_gradp, float* d_p, double* d_truth, double* d_raw, double* d_scalars,
+                          void* stream);
+/* host buffers, synchronous: one H2D of the float32 rows (width at most the one bound with psm_bind_rows), D2H of what is non-NULL
+ * only; scalars [n_frames][8] may be NULL.  They solve again on the general path after a guard trip, like their counterparts. */
+int psm_deltas_rows(psm_handle* h, const float* rows, int32_t n_frames, int32_t width, double base, int32_t apply_filter,
+                    float* result, double* truth, double* raw, double* scalars);
+int psm_poisson_rows(psm_handle* h, const float* rows, int32_t n_frames, int32_t width, double base, double phi,
+                     int32_t apply_filter, int32_t weighting, double* extra, float* result, float* change, float* next,
+                     double* scalars);
+int psm_poisson_rows_errors(psm_handle* h, const float* rows, int32_t n_frames, int32_t width, double base, double phi,
+                            int32_t apply_filter, int32_t weighting, double* raw, double* scalars);
+int psm_gradp_rows(psm_handle* h, const float* rows, int32_t n_frames, int32_t width, double ex, double ey, int32_t apply_filter,
+                   float* gradp, float* p, double* truth, double* raw, double* scalars);
+
 /* U_to_gradP: integrate the assembled (dp/dx, dp/dy) into p (integrate_field,
  * Eval_dual_Dense_onlycil.py:371-416, and the four-quadrant stitching :597-628).
  * psm_set_integration fixes the geometry: sdfunct [ny*nx] (self.sdfunct[:,:,0], also used by the

@@ -156,6 +156,22 @@ SIGNATURES = {
     "psm_gradp_frames_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "psm_gradp_frames": (C.c_int, [_hp, _f64p, C.c_int32, C.c_int32, _f32p, C.c_int32, _f32p, _f32p, _f64p, _f64p]),
+    "psm_bind_rows": (C.c_int, [_hp, C.c_int32]),
+    "psm_unbind_rows": (C.c_int, [_hp]),
+    "psm_rows_prepare_device": (C.c_int, [_hp, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, _f64p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_deltas_rows_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "psm_deltas_rows": (C.c_int, [_hp, _f32p, C.c_int32, C.c_int32, C.c_double, C.c_int32, _f32p, _f64p, _f64p, _f64p]),
+    "psm_poisson_rows_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_poisson_rows": (C.c_int, [_hp, _f32p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _f64p, _f32p, _f32p, _f32p,
+                                   _f64p]),
+    "psm_poisson_rows_errors_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_poisson_rows_errors": (C.c_int, [_hp, _f32p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _f64p, _f64p]),
+    "psm_gradp_rows_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_gradp_rows": (C.c_int, [_hp, _f32p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _f32p, _f32p, _f64p, _f64p, _f64p]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
     "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),

@@ -104,7 +104,7 @@ static int block_errors_device(psm_handle* h, const float* d_grid, const float* 
 
 // The two error stages behind a step: the field's sums (the existing field-error launches, one pair) into the binding's scratch
 // row, then the block stage, whose fold leaves both rows in d_raw [n][2][8].
-static int step_errors_device(psm_handle* h, int n_frames, const float* d_result, const double* d_truth, double* d_raw, hipStream_t st) {
+int deltas_step_errors_device(psm_handle* h, int n_frames, const float* d_result, const double* d_truth, double* d_raw, hipStream_t st) {
   const DeltasSet& D = h->deltas;
   const int64_t npix = (int64_t)h->Ny * h->Nx;
   const PsmErrPlane none{nullptr, 0, 0, 0};
@@ -118,18 +118,20 @@ static int step_errors_device(psm_handle* h, int n_frames, const float* d_result
 }
 
 // every check of one step, then its scalars and the one graph replay: frames -> planes -> image (label, truth) -> solve (-> filter)
-static int step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* out_scale, int apply_filter,
-                       float* d_result, double* d_truth, const double* d_raw, hipStream_t st) {
+int deltas_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* out_scale, int apply_filter,
+                       float* d_result, double* d_truth, const double* d_raw, hipStream_t st, const RowsCall* rows) {
   DeltasSet& D = h->deltas;
   StepCall step;
-  int rc = image_call(h, d_cols, n_frames, k, U2, D.d_grid, D.d_label, d_truth, step.frames);
+  int rc = image_call(h, d_cols, n_frames, k, U2, D.d_grid, D.d_label, rows ? nullptr : d_truth, step.frames);   // rows: U^2 is made on the device
   if (rc) return rc;
-  if (!U2) return fail(h, PSM_ERR_ARG, "null argument");
+  if (rows && (reinterpret_cast<uintptr_t>(d_truth) & 7)) return fail(h, PSM_ERR_ARG, "a destination is misaligned (8 bytes for the truth plane)");
+  if (!rows && !U2) return fail(h, PSM_ERR_ARG, "null argument");
   if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_deltas_frames");
   if ((reinterpret_cast<uintptr_t>(d_result) & 3) || (reinterpret_cast<uintptr_t>(d_raw) & 7))
     return fail(h, PSM_ERR_ARG, "a destination is misaligned (4 bytes for d_result, 8 for d_raw)");
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  if ((rc = upload_u2(h, U2, n_frames, st))) return rc;
+  if (rows) step.rows = *rows;
+  else if ((rc = upload_u2(h, U2, n_frames, st))) return rc;
   step.deltas = DeltasCall{D.d_planes, D.d_grid, D.d_label, d_truth, D.d_res};
   if (apply_filter) { step.post.apply_filter = 1; step.post.result = d_result; }
   return solve_device(h, D.d_grid, n_frames, out_scale, apply_filter ? h->post.d_fields : d_result, st, nullptr, step);
@@ -214,9 +216,9 @@ int psm_deltas_frames_device(psm_handle* h, const double* d_cols, int32_t n_fram
   hipStream_t st = stream_of(h, stream);
   if (!d_result) d_result = h->deltas.d_result;
   if (!d_truth) d_truth = h->deltas.d_truth;
-  int rc = step_device(h, d_cols, n_frames, k, U2, out_scale, apply_filter, d_result, d_truth, d_raw, st);
+  int rc = deltas_step_device(h, d_cols, n_frames, k, U2, out_scale, apply_filter, d_result, d_truth, d_raw, st);
   if (rc || !d_raw) return rc;
-  return step_errors_device(h, n_frames, d_result, d_truth, d_raw, st);
+  return deltas_step_errors_device(h, n_frames, d_result, d_truth, d_raw, st);
 }
 
 
@@ -237,8 +239,8 @@ int psm_deltas_frames(psm_handle* h, const double* cols, int32_t n_frames, int32
   const size_t npix = (size_t)h->Ny * h->Nx;
   const size_t fb = (size_t)n_frames * npix * sizeof(float), tb = 2 * fb, rb = (size_t)n_frames * 2 * PSM_ERR_RAW * sizeof(double);
   rc = guarded_host_step(h, st, "psm_deltas_frames", [&](int pass) {
-    int rs = step_device(h, F.d_cols, n_frames, k, U2, out_scale, apply_filter, D.d_result, D.d_truth, D.d_raw, st);
-    if (rs || (raw && (rs = step_errors_device(h, n_frames, D.d_result, D.d_truth, D.d_raw, st)))) return rs;
+    int rs = deltas_step_device(h, F.d_cols, n_frames, k, U2, out_scale, apply_filter, D.d_result, D.d_truth, D.d_raw, st);
+    if (rs || (raw && (rs = deltas_step_errors_device(h, n_frames, D.d_result, D.d_truth, D.d_raw, st)))) return rs;
     if (result) HIPCHK(h, hipMemcpyAsync(D.h_result, D.d_result, fb, hipMemcpyDeviceToHost, st));
     if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(D.h_truth, D.d_truth, tb, hipMemcpyDeviceToHost, st));   // the labels do not depend on the route
     if (raw) HIPCHK(h, hipMemcpyAsync(D.h_raw, D.d_raw, rb, hipMemcpyDeviceToHost, st));

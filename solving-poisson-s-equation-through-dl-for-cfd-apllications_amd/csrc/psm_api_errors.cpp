@@ -34,8 +34,7 @@ int field_errors_device(psm_handle* h, const PsmFieldErrorArgs& stage, double* d
 
 // The evaluator's three pairs on what a frame step leaves: delta-p with the weighting (next), without it (result), and p
 // (next + p label - delta-p label against the p label); the labels are the first two extra planes, NaN -> 0 (SM_call.py:687-711).
-static PsmFieldErrorArgs poisson_pairs(const psm_handle* h, int n_frames, int n_extra, const double* d_extra, const float* d_result,
-                                       const float* d_next) {
+PsmFieldErrorArgs poisson_error_pairs(const psm_handle* h, int n_frames, int n_extra, const double* d_extra, const float* d_result, const float* d_next) {
   const int64_t npix = (int64_t)h->Ny * h->Nx;
   const PsmErrPlane none{nullptr, 0, 0, 0};
   const PsmErrPlane dp{d_extra, n_extra * npix, 1, 0}, p{d_extra + npix, n_extra * npix, 1, 0};
@@ -49,7 +48,7 @@ static PsmFieldErrorArgs poisson_pairs(const psm_handle* h, int n_frames, int n_
   return a;
 }
 
-static int errors_call_check(psm_handle* h, int k, int weighting, const void* d_raw) {
+int poisson_errors_call_check(psm_handle* h, int k, int weighting, const void* d_raw) {
   if (!weighting) return fail(h, PSM_ERR_ARG, "the error blocks compare the weighted field: weighting must be on");
   if (k < 8) return fail(h, PSM_ERR_ARG, "the error blocks need the two label columns (delta_p, p) between the velocities and the weighting pair: k >= 8");
   if (!d_raw) return fail(h, PSM_ERR_ARG, "null buffer");
@@ -97,14 +96,14 @@ int psm_poisson_frames_errors_device(psm_handle* h, const double* d_cols, int32_
   FrameCall fc;
   int rc = poisson_frame_call(h, d_cols, n_frames, k, weighting, d_extra, fc);
   if (rc) return rc;
-  if ((rc = errors_call_check(h, k, weighting, d_raw))) return rc;
+  if ((rc = poisson_errors_call_check(h, k, weighting, d_raw))) return rc;
   if (!d_extra || !d_result || !d_next) return fail(h, PSM_ERR_ARG, "the error blocks read d_extra, d_result and d_next: none of them may be NULL");
   PostCall pc;
   pc.apply_filter = apply_filter ? 1 : 0; pc.result = d_result;
   pc.dU = h->post.d_dU; pc.prev = h->post.d_prev; pc.change = d_change; pc.next = d_next;
   hipStream_t st = stream_of(h, stream);
   if ((rc = poisson_step_device(h, h->feat.d_vel, n_frames, LU, out_scale, pc, st, &fc))) return rc;
-  return field_errors_device(h, poisson_pairs(h, n_frames, k - 6, d_extra, d_result, d_next), d_raw, st);
+  return field_errors_device(h, poisson_error_pairs(h, n_frames, k - 6, d_extra, d_result, d_next), d_raw, st);
 }
 
 
@@ -116,7 +115,7 @@ int psm_poisson_frames_errors(psm_handle* h, const double* cols, int32_t n_frame
   FrameCall fc;
   int rc = poisson_frame_call(h, F.d_cols, n_frames, k, weighting, F.d_extra, fc);
   if (rc) return rc;
-  if ((rc = errors_call_check(h, k, weighting, F.d_raw))) return rc;
+  if ((rc = poisson_errors_call_check(h, k, weighting, F.d_raw))) return rc;
   PostSet& s = h->post;
   const size_t cap = (size_t)h->cfg.max_cases * h->Ny * h->Nx * h->cfg.c_out;
   PostCall pc;
@@ -124,7 +123,7 @@ int psm_poisson_frames_errors(psm_handle* h, const double* cols, int32_t n_frame
   pc.dU = s.d_dU; pc.prev = s.d_prev; pc.change = s.d_out + cap; pc.next = s.d_out + 2 * cap;
   hipStream_t st = h->stream;
   const size_t rb = (size_t)n_frames * 3 * PSM_ERR_RAW * sizeof(double);
-  const PsmFieldErrorArgs stage = poisson_pairs(h, n_frames, k - 6, F.d_extra, pc.result, pc.next);
+  const PsmFieldErrorArgs stage = poisson_error_pairs(h, n_frames, k - 6, F.d_extra, pc.result, pc.next);
   if ((rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
   rc = guarded_host_step(h, st, "psm_poisson_frames_errors", [&](int) {
     int rs = poisson_step_device(h, h->feat.d_vel, n_frames, LU, out_scale, pc, st, &fc);

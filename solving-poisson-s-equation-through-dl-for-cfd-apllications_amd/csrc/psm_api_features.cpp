@@ -31,10 +31,15 @@ int features_device(psm_handle* h, const double* d_vel, int n, float* d_grid, hi
 }
 
 // state and argument checks shared by the entries below; nothing is enqueued before they pass
-static int feat_check(psm_handle* h, int n_cases, const double* LU) {
+static int feat_check_state(psm_handle* h, int n_cases) {
   if (!h->planned) return fail(h, PSM_ERR_STATE, "psm_plan_grid has not been called");
   if (!h->feat.ready) return fail(h, PSM_ERR_STATE, "psm_bind_features has not been called (a new plan or model drops the binding)");
   if (n_cases < 1 || n_cases > h->feat.n_cases) return fail(h, PSM_ERR_ARG, "n_cases outside [1, cases bound with psm_bind_features]");
+  return PSM_OK;
+}
+static int feat_check(psm_handle* h, int n_cases, const double* LU) {
+  int rc = feat_check_state(h, n_cases);
+  if (rc) return rc;
   if (!LU) return fail(h, PSM_ERR_ARG, "null argument");
   for (int c = 0; c < n_cases; ++c)
     if (!(LU[2 * c + 1] != 0.0) || !std::isfinite(LU[2 * c + 1])) return fail(h, PSM_ERR_ARG, "U must be finite and non-zero for every case");
@@ -63,16 +68,17 @@ PostCall post_call(int apply_filter, const float* dU, const float* prev, float* 
 // every check of one whole step, then its scalars and the one graph replay: (frames -> planes,) features into the binding's image, solve,
 // post-steps
 int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const double* LU, const float* out_scale, const PostCall& pc, hipStream_t st,
-                        const FrameCall* frames) {
-  int rc = feat_check(h, n_cases, LU);
+                        const FrameCall* frames, const RowsCall* rows) {
+  int rc = rows ? feat_check_state(h, n_cases) : feat_check(h, n_cases, LU);   // rows: (L, U) are made on the device, nothing to check or upload
   if (rc) return rc;
   if (!h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: a Poisson step needs it as well as psm_bind_features");
   if ((rc = post_check(h, n_cases, pc))) return rc;
   if (!d_vel) return fail(h, PSM_ERR_ARG, "null buffer");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (!st) st = h->stream;
-  if ((rc = upload_lu(h, LU, n_cases, st))) return rc;
+  if (!rows && (rc = upload_lu(h, LU, n_cases, st))) return rc;
   StepCall step;
+  if (rows) step.rows = *rows;
   if (frames) step.frames = *frames;
   step.feat = FeatCall{d_vel, h->feat.d_grid};
   step.post = pc;

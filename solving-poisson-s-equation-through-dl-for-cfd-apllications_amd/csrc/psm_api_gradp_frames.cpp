@@ -62,7 +62,7 @@ static int image_call(psm_handle* h, const double* d_cols, int n_frames, int k, 
 }
 
 // The error blocks behind a step: the two field-error launches, four pairs over the binding's SDF plane.
-static int step_errors_device(psm_handle* h, int n_frames, const float* d_gradp, const float* d_p, const double* d_truth, double* d_raw,
+int gradp_step_errors_device(psm_handle* h, int n_frames, const float* d_gradp, const float* d_p, const double* d_truth, double* d_raw,
                               hipStream_t st) {
   const int64_t npix = (int64_t)h->Ny * h->Nx;
   const PsmErrPlane none{nullptr, 0, 0, 0};
@@ -79,8 +79,8 @@ static int step_errors_device(psm_handle* h, int n_frames, const float* d_gradp,
 }
 
 // every check of one step, then the one graph replay: frames -> planes -> image, labels -> solve (-> filter) -> integration
-static int step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const float* out_scale, int apply_filter, float* d_gradp,
-                       float* d_p, double* d_truth, const double* d_raw, hipStream_t st) {
+int gradp_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const float* out_scale, int apply_filter, float* d_gradp,
+                      float* d_p, double* d_truth, const double* d_raw, hipStream_t st, const RowsCall* rows) {
   GradpSet& G = h->gradp;
   StepCall step;
   int rc = image_call(h, d_cols, n_frames, k, G.d_grid, d_truth, step.frames);
@@ -88,6 +88,7 @@ static int step_device(psm_handle* h, const double* d_cols, int n_frames, int k,
   if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_gradp_frames");
   if ((reinterpret_cast<uintptr_t>(d_gradp) & 7) || (reinterpret_cast<uintptr_t>(d_p) & 3) || (reinterpret_cast<uintptr_t>(d_raw) & 7))
     return fail(h, PSM_ERR_ARG, "a destination is misaligned (8 bytes for d_gradp and d_raw, 4 for d_p)");
+  if (rows) step.rows = *rows;
   step.gradp = GradpCall{G.d_planes, G.d_grid, d_truth, d_p};
   if (apply_filter) { step.post.apply_filter = 1; step.post.result = d_gradp; }
   return solve_device(h, G.d_grid, n_frames, out_scale, apply_filter ? h->post.d_fields : d_gradp, st, nullptr, step);
@@ -153,9 +154,9 @@ int psm_gradp_frames_device(psm_handle* h, const double* d_cols, int32_t n_frame
   if (!d_gradp) d_gradp = h->gradp.integ.d_gradp;
   if (!d_p) d_p = h->gradp.integ.d_p;
   if (!d_truth) d_truth = h->gradp.d_truth;
-  int rc = step_device(h, d_cols, n_frames, k, out_scale, apply_filter, d_gradp, d_p, d_truth, d_raw, st);
+  int rc = gradp_step_device(h, d_cols, n_frames, k, out_scale, apply_filter, d_gradp, d_p, d_truth, d_raw, st);
   if (rc || !d_raw) return rc;
-  return step_errors_device(h, n_frames, d_gradp, d_p, d_truth, d_raw, st);
+  return gradp_step_errors_device(h, n_frames, d_gradp, d_p, d_truth, d_raw, st);
 }
 
 
@@ -176,8 +177,8 @@ int psm_gradp_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_
   const size_t tb = (size_t)n_frames * 3 * npix * sizeof(double), rb = (size_t)n_frames * GRADP_PAIRS * PSM_ERR_RAW * sizeof(double);
   float *d_g = G.integ.d_gradp, *d_p = G.integ.d_p;
   rc = guarded_host_step(h, st, "psm_gradp_frames", [&](int pass) {
-    int rs = step_device(h, F.d_cols, n_frames, k, out_scale, apply_filter, d_g, d_p, G.d_truth, G.d_raw, st);
-    if (rs || (raw && (rs = step_errors_device(h, n_frames, d_g, d_p, G.d_truth, G.d_raw, st)))) return rs;
+    int rs = gradp_step_device(h, F.d_cols, n_frames, k, out_scale, apply_filter, d_g, d_p, G.d_truth, G.d_raw, st);
+    if (rs || (raw && (rs = gradp_step_errors_device(h, n_frames, d_g, d_p, G.d_truth, G.d_raw, st)))) return rs;
     if (gradp) HIPCHK(h, hipMemcpyAsync(G.h_gradp, d_g, gb, hipMemcpyDeviceToHost, st));
     if (p) HIPCHK(h, hipMemcpyAsync(G.h_p, d_p, pb, hipMemcpyDeviceToHost, st));
     if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(G.h_truth, G.d_truth, tb, hipMemcpyDeviceToHost, st));   // the labels do not depend on the route

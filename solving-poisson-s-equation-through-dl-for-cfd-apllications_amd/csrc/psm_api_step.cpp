@@ -68,13 +68,16 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
   if (!st) st = h->stream;
   const float* d_scale = nullptr;
   if ((rc = ensure_encode_aux(h, n_cases))) return rc;
-  if ((rc = prepare_scale(h, h->ws0, out_scale, n_cases, st, &d_scale))) return rc;
+  const bool rows = step.rows.rows;
+  if (step.rows.scaled()) d_scale = h->ws0.d_row_scale;   // the finish launch of the rows stage writes it, inside the sequence
+  else if ((rc = prepare_scale(h, h->ws0, out_scale, n_cases, st, &d_scale))) return rc;
   const bool frames = step.frames.cols, feat = step.feat.vel, deltas = step.deltas.planes, gradp = step.gradp.planes, post = step.post.apply_filter >= 0;
   h->last_cases = gradp ? 1 : n_cases;  // gradp: ws0 holds the last frame's single-case solve
-  // the mesh -> grid launch (frames), the two feature launches (feat) or the image pack (deltas, gradp), the solve, then the two integration launches (p) or the
+  // the two rows launches (rows), the mesh -> grid launch (frames), the two feature launches (feat) or the image pack (deltas, gradp), the solve, then the two integration launches (p) or the
   // post-steps' (at most four); gradp: the filter among the post-steps and BEHIND it the integration with the gradp binding's tables: one linear chain
   auto sequence = [&](hipStream_t on, hipEvent_t* ev) {
-    int rs = frames ? frames_device(h, step.frames, n_cases, on) : PSM_OK;
+    int rs = rows ? rows_device(h, step.rows, n_cases, on) : PSM_OK;
+    if (!rs && frames) rs = frames_device(h, step.frames, n_cases, on);
     if (!rs && feat) rs = features_device(h, step.feat.vel, n_cases, step.feat.grid, on);
     if (!rs && deltas) rs = deltas_pack_device(h, step.deltas, n_cases, on);
     if (!rs && gradp) rs = gradp_pack_device(h, step.gradp, n_cases, on);
@@ -101,7 +104,7 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
     return rs;
   };
   if (prof || h->timed_kernel >= 0 || !h->use_graph) return sequence(st, prof);
-  const GraphKey key{sequence_key(h, n_cases, out_scale != nullptr), d_grid, d_fields, step};
+  const GraphKey key{sequence_key(h, n_cases, d_scale != h->d_ones), d_grid, d_fields, step};
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     if (h->graphs.size() > 64) destroy_graphs(h);

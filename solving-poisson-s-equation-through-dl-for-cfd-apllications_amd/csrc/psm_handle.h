@@ -1,5 +1,5 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in fifteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in sixteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, psm_solve_grid*
@@ -14,6 +14,7 @@
 //   psm_api_errors.cpp      the per-frame error blocks of assembled fields on the device: psm_field_errors_device and the metrics-only frame step psm_poisson_frames_errors* (host arithmetic: psm_errors.cpp)
 //   psm_api_deltas_frames.cpp  the deltas evaluator's frame batch on the device: psm_bind_deltas_frames, the image pack psm_deltas_image_device, the batched block errors psm_block_errors_device and the step psm_deltas_frames*
 //   psm_api_gradp_frames.cpp   the U_to_gradP evaluator's frame batch on the device: psm_bind_gradp_frames, the image / label pack psm_gradp_image_device and the step psm_gradp_frames* (columns -> p -> errors)
+//   psm_api_rows.cpp        a frame's dataset rows -> scalars + columns on the device: psm_bind_rows, the stage alone psm_rows_prepare_device and the evaluators' steps behind it, psm_deltas_rows* / psm_poisson_rows* / psm_gradp_rows*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -39,6 +40,7 @@
 #include "../../include/psm.h"
 #include "psm_kernels.h"
 #include "psm_mesh.h"
+#include "psm_rows.h"
 #include "psm_eval.h"
 #include "psm_filter.h"
 #include "psm_integ.h"
@@ -130,6 +132,21 @@ struct FeatCall {
   auto tie() const { return std::tie(vel, grid); }
 };
 
+// The rows -> scalars + columns stage at the head of an evaluator's frame step (psm_*_rows*): everything the two launches hold.  The
+// frame's scalars reach the step's kernels through the device arrays those read anyway (the workspace's row scale, the deltas
+// binding's U^2, the feature binding's (L, U)): with this stage in the step nothing is uploaded in front of the replay.
+struct RowsCall {
+  const float* rows = nullptr;          // [n_frames][n_cells][width]; nullptr: no rows stage
+  int kind = 0, width = 0;
+  double* cols = nullptr;               // [n_frames][n_cells][k] what the mesh -> grid stage reads
+  double* scalars = nullptr;            // [n_frames][8]
+  int64_t n_cells = 0;
+  double base = 1.0, phi = 1.0, ex = 1.0, ey = 1.0;
+  bool wired = false;                   // a step: the finish launch also writes the device arrays the step's kernels read
+  bool scaled() const { return rows && wired && kind != PSM_ROWS_KIND_GRADP; }   // ... among them the solve's row scale
+  auto tie() const { return std::tie(rows, kind, width, cols, scalars, n_cells, base, phi, ex, ey, wired); }
+};
+
 // The mesh -> grid stage in front of the features (psm_poisson_frames*): the launch holds the column array and the k plane descriptors.
 struct FrameCall {
   const double* cols = nullptr;         // [n_frames][n_cells][k]; nullptr: no frame stage
@@ -174,15 +191,17 @@ struct GradpCall {
 // What surrounds ONE solve (solve_device, psm_api_step.cpp), in launch order; every stage keeps its own "absent" value.  A new stage
 // is one member here and one entry in key(): the graph cache compares nothing else, so a stage in the sequence is in the cache key.
 struct StepCall {
+  RowsCall rows{};                      // psm_*_rows*: the two launches that make the columns and the frame scalars (rows == nullptr: none)
   FrameCall frames{};                   // psm_poisson_frames*, psm_deltas_frames*, psm_gradp_frames*: the mesh -> grid launch (cols == nullptr: none)
   FeatCall feat{};                      // psm_poisson_step*: the two feature launches write the solve's image (vel == nullptr: none)
   DeltasCall deltas{};                  // psm_deltas_frames*: the image pack, the frames solved one by one (planes == nullptr: none)
   GradpCall gradp{};                    // psm_gradp_frames*: likewise, and BEHIND the post-steps the integration with the binding's own tables
   float* p = nullptr;                   // psm_solve_pressure*: where the bound integration (psm_bind_integration) behind the solve writes p
   PostCall post{};                      // psm_solve_poststeps*: the bound post-steps behind the solve (apply_filter == -1: none)
-  auto key() const { return std::make_tuple(frames.key(), feat.tie(), deltas.tie(), gradp.tie(), p, post.tie()); }
+  auto key() const { return std::make_tuple(rows.tie(), frames.key(), feat.tie(), deltas.tie(), gradp.tie(), p, post.tie()); }
   const char* fault() const {           // the combinations the sequence does not define (null: defined); no C entry builds one
     const bool fr = frames.cols, ft = feat.vel, dl = deltas.planes, gp = gradp.planes;
+    if (rows.rows && (!fr || rows.cols != frames.cols)) return "the rows stage writes the columns the mesh -> grid stage reads: it needs frames on its columns";
     if (dl && gp) return "the deltas and the gradP pack exclude each other";
     if ((dl || gp) && !fr) return "an image pack reads the planes of the mesh -> grid stage: it needs frames";
     if (ft && (dl || gp)) return "the features and an image pack both write the solve's image";
@@ -304,6 +323,16 @@ struct FrameSet {
   double *d_raw = nullptr, *h_raw = nullptr;   // psm_poisson_frames_errors: [n_frames][3][8] sums, device and pinned
 };
 
+// Binding of the rows stage (psm_bind_rows, behind psm_bind_frames): staging for the bound frame count x mesh cells x width float32
+// rows, the partial maxima and the scalar slots, so that a step allocates nothing.  The columns go to the frame binding's d_cols.
+struct RowsSet {
+  bool ready = false;
+  int n_frames = 0, width = 0;
+  float *d_rows = nullptr, *h_rows = nullptr;     // [n_frames][n_cells][width], device and pinned
+  float* d_part = nullptr;                         // [n_frames][3][PSM_ROWS_PARTS]
+  double *d_scalars = nullptr, *h_scalars = nullptr;   // [n_frames][8], device and pinned
+};
+
 // Binding of the deltas evaluator's frame batch (psm_bind_deltas_frames, behind psm_bind_frames): the simulation's normalised SDF
 // plane, the scales, and every buffer a step touches for the bound frame count, so that a step allocates nothing.  The columns go
 // through the frame binding's staging (FrameSet::d_cols / h_cols).
@@ -383,6 +412,7 @@ struct psm_handle {
   PostSet post;                         // Gaussian post-steps on the planned grid (psm_bind_poststeps)
   FeatureSet feat;                      // Poisson input features on the planned grid (psm_bind_features)
   FrameSet frames;                      // frame batch on the single mesh (psm_bind_frames)
+  RowsSet rows;                         // the rows stage's staging behind it (psm_bind_rows)
   DeltasSet deltas;                     // the deltas evaluator's frame batch behind it (psm_bind_deltas_frames)
   GradpSet gradp;                       // the U_to_gradP evaluator's frame batch behind it (psm_bind_gradp_frames)
   double maxs[4] = {1, 1, 1, 1};
@@ -527,13 +557,15 @@ void feat_free(FeatureSet& s);
 void frames_free(psm_handle* h);
 void deltas_free(psm_handle* h);
 void gradp_free(psm_handle* h);
+void rows_free(psm_handle* h);
+int rows_device(psm_handle* h, const RowsCall& rc, int n_frames, hipStream_t st);
 int frames_state(psm_handle* h);
 int frames_count_check(psm_handle* h, int n_frames);
 int frames_device(psm_handle* h, const FrameCall& fc, int n_frames, hipStream_t st);
 int poisson_frame_call(psm_handle* h, const double* d_cols, int n_frames, int k, int weighting, double* d_extra, FrameCall& fc);
 int field_errors_device(psm_handle* h, const PsmFieldErrorArgs& stage, double* d_raw, hipStream_t st);
 int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const double* LU, const float* out_scale, const PostCall& pc,
-                        hipStream_t st, const FrameCall* frames = nullptr);
+                        hipStream_t st, const FrameCall* frames = nullptr, const RowsCall* rows = nullptr);
 PostCall post_call(int apply_filter, const float* dU, const float* prev, float* result, float* change, float* next);
 int features_device(psm_handle* h, const double* d_vel, int n_cases, float* d_grid, hipStream_t st);
 std::vector<uint16_t> pack_comp_in_bf16(const double* comp, int P, int K, int c_in, int S, int NT);
@@ -562,6 +594,17 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
                  hipStream_t st, hipEvent_t* prof, const StepCall& step = {});
 int deltas_pack_device(psm_handle* h, const DeltasCall& dc, int n_frames, hipStream_t st);
 int gradp_pack_device(psm_handle* h, const GradpCall& gc, int n_frames, hipStream_t st);
+// the evaluators' frame steps and the error stages behind them (psm_api_deltas_frames.cpp, psm_api_gradp_frames.cpp); with `rows` the
+// rows stage heads the step, d_cols are its columns, and U2 / out_scale are not read: the finish launch leaves them on the device
+int deltas_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* out_scale, int apply_filter,
+                       float* d_result, double* d_truth, const double* d_raw, hipStream_t st, const RowsCall* rows = nullptr);
+int deltas_step_errors_device(psm_handle* h, int n_frames, const float* d_result, const double* d_truth, double* d_raw, hipStream_t st);
+int gradp_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const float* out_scale, int apply_filter, float* d_gradp,
+                      float* d_p, double* d_truth, const double* d_raw, hipStream_t st, const RowsCall* rows = nullptr);
+int gradp_step_errors_device(psm_handle* h, int n_frames, const float* d_gradp, const float* d_p, const double* d_truth, double* d_raw,
+                             hipStream_t st);
+PsmFieldErrorArgs poisson_error_pairs(const psm_handle* h, int n_frames, int n_extra, const double* d_extra, const float* d_result, const float* d_next);
+int poisson_errors_call_check(psm_handle* h, int k, int weighting, const void* d_raw);
 bool guard_take(psm_handle* h, Workspace& w);
 int guard_drop(psm_handle* h, const char* where);
 // A host entry's step: `enqueue` puts the step and its device -> host copies on `st`, this waits; a tripped guard drops the binding

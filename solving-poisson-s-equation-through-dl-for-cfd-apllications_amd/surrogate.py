@@ -585,7 +585,7 @@ class GridSurrogate:
             raise ValueError(f"tables must be [{npix},3], [{npix},3], [{npix},2] and sdfunct [{self.ny},{self.nx}]")
         mx = _f64(np.asarray(maxs, np.float64).reshape(-1)[:4])
         self.mesh_cells = None
-        self._frames_bound = self._feat_bound = self._post_bound = self._deltas_bound = self._gradp_bound = False
+        self._frames_bound = self._feat_bound = self._post_bound = self._deltas_bound = self._gradp_bound = False; self._rows_bound = 0
         self._bound_mask = self._bound_sdf = None
         self._chk(self.lib.psm_set_geometry(self.h, int(n_cells), self.ny, self.nx, _p(v, C.c_int32), _p(w, C.c_double),
                                             _p(idx, C.c_int32), _p(sdf, C.c_double), None, None, _p(mx, C.c_double), 1, 1, 0.05))
@@ -594,12 +594,12 @@ class GridSurrogate:
     def bind_frames(self, n_frames: int, k: int):
         """Staging for ``n_frames`` (<= max_cases) frames of ``k`` (<= 16) cell columns on the handle's mesh: after it a batch
         allocates nothing."""
-        self._frames_bound = self._deltas_bound = self._gradp_bound = False
+        self._frames_bound = self._deltas_bound = self._gradp_bound = False; self._rows_bound = 0
         self._chk(self.lib.psm_bind_frames(self.h, int(n_frames), int(k)))
         self._frames_bound = True
 
     def unbind_frames(self):
-        self._frames_bound = self._deltas_bound = self._gradp_bound = False
+        self._frames_bound = self._deltas_bound = self._gradp_bound = False; self._rows_bound = 0
         self._chk(self.lib.psm_unbind_frames(self.h))
 
     def frames_to_grid_device(self, d_cols: int, n_frames: int, k: int, outs, fill: bool = True, stream: int = 0):
@@ -994,6 +994,146 @@ class GridSurrogate:
                                             opt(gradp, C.c_float), opt(p, C.c_float), opt(truth, C.c_double), _p(raw, C.c_double)))
         return gradp, p, truth, raw
 
+    # -- a frame's dataset rows (float32, as stored) -> scalars + columns on the device, and the evaluators' steps behind that stage
+    _rows_bound = 0                 # the width bound with bind_rows (0: none)
+    ROWS_KINDS = {"deltas": (0, 3, 11), "poisson": (1, 8, 11), "gradp": (2, 5, 8)}    # kind -> (PSM_ROWS_*, columns, least width)
+    ROW_SCALARS = ("U", "dU", "c", "relevant", "U2", "out_scale", "reserved0", "reserved1")
+
+    def bind_rows(self, width: int):
+        """After ``bind_frames``: staging for the bound frame count x mesh cells x ``width`` (8..16) float32 rows, the partial maxima
+        and the scalar slots: after it a rows step allocates nothing.  Dropped with the frame binding."""
+        if not getattr(self, "_frames_bound", False):
+            raise RuntimeError("bind_frames has not been called")
+        if not 8 <= int(width) <= 16:
+            raise ValueError("rows are 8..16 float32 columns wide")
+        self._rows_bound = 0
+        self._chk(self.lib.psm_bind_rows(self.h, int(width)))
+        self._rows_bound = int(width)
+
+    def unbind_rows(self):
+        self._rows_bound = 0
+        self._chk(self.lib.psm_unbind_rows(self.h))
+
+    def _rows_live(self) -> bool:
+        return bool(self._rows_bound) and getattr(self, "_frames_bound", False)
+
+    def _rows_call(self, kind: str, n_frames, width, base=1.0):
+        """The argument checks the rows entries share -> (PSM_ROWS_* value, columns)."""
+        if kind not in self.ROWS_KINDS:
+            raise ValueError(f"kind must be one of {sorted(self.ROWS_KINDS)}")
+        code, k, least = self.ROWS_KINDS[kind]
+        if not self._rows_live():
+            raise RuntimeError("bind_rows has not been called (bind_frames and a new mesh drop the binding)")
+        if not least <= int(width) <= 16:
+            raise ValueError(f"{kind} rows are {least}..16 float32 columns wide")
+        if not 1 <= int(n_frames) <= self.max_cases:
+            raise ValueError("n_frames outside [1, max_cases]")
+        if kind != "gradp" and not (np.isfinite(base) and base != 0):
+            raise ValueError("base must be finite and non-zero")
+        return code, k
+
+    def _host_rows(self, kind: str, rows, base=1.0):
+        """A host entry's rows [n,n_cells,width] (or [n_cells,width]) -> (float32 C-contiguous array, n, width)."""
+        v = np.asarray(rows)
+        if v.ndim == 2:
+            v = v[None]
+        if v.ndim != 3:
+            raise ValueError("rows must be [n,n_cells,width]")
+        n, n_cells, width = v.shape
+        self._rows_call(kind, n, width, base)
+        if self.mesh_cells is None:
+            raise RuntimeError("the handle holds no mesh (set_mesh / computeOnlyOnce)")
+        if n_cells != self.mesh_cells:
+            raise ValueError(f"rows must be [n >= 1, {self.mesh_cells} cells, width]")
+        if width > self._rows_bound:
+            raise ValueError("wider rows than bind_rows reserved staging for")
+        return _f32(v), n, width
+
+    def rows_prepare_device(self, kind: str, d_rows: int, n_frames: int, n_cells: int, width: int, d_cols: int = 0, d_scalars: int = 0,
+                            base: float = 1.0, phi: float = 1.0, ex: float = 1.0, ey: float = 1.0, stream: int = 0):
+        """The stage alone on raw device pointers, two plain launches, asynchronous on ``stream``: ``d_rows`` [n,n_cells,width]
+        float32 (the dataset frame cut at ``indice``) -> ``d_cols`` [n,n_cells,k] float64 (0: the frame binding's buffer) and
+        ``d_scalars`` [n,8] float64 = ``ROW_SCALARS`` (0: the binding's slots), bit for bit the host statements at the head of the
+        ``kind`` evaluator's ``timeSteps`` ('deltas' k = 3, 'poisson' k = 8, 'gradp' k = 5).  ``base``: max_abs_p / max_abs_delta_p
+        of the out-scale; ``ex``, ``ey``: max_x - min_x, max_y - min_y of the gradP dataset."""
+        code, _ = self._rows_call(kind, n_frames, width, base)
+        if self.mesh_cells is None or not 1 <= int(n_cells) <= self.mesh_cells:
+            raise ValueError("n_cells outside [1, cells of the mesh]")
+        d_rows = self._dev_ptr(d_rows, 4, "d_rows")
+        d_cols, d_scalars = self._dev_ptr(d_cols, 8, "d_cols", True), self._dev_ptr(d_scalars, 8, "d_scalars", True)
+        params = _f64(np.array([base, phi, ex, ey], np.float64))
+        self._chk(self.lib.psm_rows_prepare_device(self.h, code, C.c_void_p(d_rows), int(n_frames), int(n_cells), int(width),
+                                                   _p(params, C.c_double), C.c_void_p(d_cols or None), C.c_void_p(d_scalars or None),
+                                                   C.c_void_p(stream)))
+
+    def deltas_rows(self, rows: np.ndarray, base: float, apply_filter: bool = False, want_result: bool = True, want_truth: bool = True,
+                    want_raw: bool = True):
+        """``deltas_frames`` on the dataset rows themselves: ``rows`` [n,n_cells,width >= 11] float32 -> (result, truth, raw,
+        scalars [n,8] = ``ROW_SCALARS``); columns, U^2 and the out-scale ``base`` * U^2 are made on the device at the head of the one
+        graph replay.  An irrelevant frame (``scalars[:, 3] == 0``) keeps its slot: its result and sums are unspecified."""
+        if not self._deltas_bound:
+            raise RuntimeError("bind_deltas_frames has not been called (bind_frames and a new mesh drop the binding)")
+        v, n, width = self._host_rows("deltas", rows, base)
+        if apply_filter and not getattr(self, "_post_bound", False):
+            raise RuntimeError("apply_filter needs bind_poststeps")
+        result = np.empty((n, self.ny, self.nx), np.float32) if want_result else None
+        truth = np.empty((n, self.ny, self.nx), np.float64) if want_truth else None
+        raw = np.empty((n, 2, len(self.RAW_SUMS)), np.float64) if want_raw else None
+        scalars = np.empty((n, len(self.ROW_SCALARS)), np.float64)
+        opt = lambda a, t: _p(a, t) if a is not None else None
+        self._chk(self.lib.psm_deltas_rows(self.h, _p(v, C.c_float), n, width, float(base), int(bool(apply_filter)), opt(result, C.c_float),
+                                           opt(truth, C.c_double), opt(raw, C.c_double), _p(scalars, C.c_double)))
+        return result, truth, raw, scalars
+
+    def poisson_rows(self, rows: np.ndarray, base: float, phi: float = 1.0, apply_filter: bool = False, weighting: bool = True,
+                     want_extra: bool = True):
+        """``poisson_frames`` on the dataset rows themselves: ``rows`` [n,n_cells,width >= 11] float32 -> (result, change, next,
+        extra, scalars [n,8]); the eight columns, (L, U) = (``phi``, U) and the out-scale ``base`` * U^2 are made on the device."""
+        v, n, width = self._host_rows("poisson", rows, base)
+        n_extra = 2 if weighting else 4
+        result = np.empty((n, self.ny, self.nx, self.model.c_out), np.float32)
+        change = nxt = None
+        if weighting:
+            change, nxt = np.empty((n, self.ny, self.nx), np.float32), np.empty((n, self.ny, self.nx), np.float32)
+        extra = np.empty((n, n_extra, self.ny, self.nx), np.float64) if want_extra else None
+        scalars = np.empty((n, len(self.ROW_SCALARS)), np.float64)
+        opt = lambda a, t: _p(a, t) if a is not None else None
+        self._chk(self.lib.psm_poisson_rows(self.h, _p(v, C.c_float), n, width, float(base), float(phi), int(bool(apply_filter)),
+                                            int(bool(weighting)), opt(extra, C.c_double), _p(result, C.c_float), opt(change, C.c_float),
+                                            opt(nxt, C.c_float), _p(scalars, C.c_double)))
+        return result, change, nxt, extra, scalars
+
+    def poisson_rows_errors(self, rows: np.ndarray, base: float, phi: float = 1.0, apply_filter: bool = False):
+        """``poisson_frames_errors`` on the dataset rows themselves -> (raw [n,3,8], scalars [n,8]): nothing else comes back."""
+        v, n, width = self._host_rows("poisson", rows, base)
+        raw = np.empty((n, 3, len(self.RAW_SUMS)), np.float64)
+        scalars = np.empty((n, len(self.ROW_SCALARS)), np.float64)
+        self._chk(self.lib.psm_poisson_rows_errors(self.h, _p(v, C.c_float), n, width, float(base), float(phi), int(bool(apply_filter)), 1,
+                                                   _p(raw, C.c_double), _p(scalars, C.c_double)))
+        return raw, scalars
+
+    def gradp_rows(self, rows: np.ndarray, ex: float, ey: float, apply_filter: bool = False, want_gradp: bool = True, want_p: bool = True,
+                   want_truth: bool = True):
+        """``gradp_frames`` on the dataset rows themselves: ``rows`` [n,n_cells,width >= 8] float32 -> (gradp, p, truth, raw,
+        scalars [n,8]); ``ex`` = max_x - min_x and ``ey`` = max_y - min_y are taken in float32, as ``EvaluationGradP`` holds them."""
+        if not self._gradp_bound:
+            raise RuntimeError("bind_gradp_frames has not been called (bind_frames and a new mesh drop the binding)")
+        v, n, width = self._host_rows("gradp", rows)
+        if not (np.isfinite(ex) and np.isfinite(ey)):
+            raise ValueError("ex and ey must be finite")
+        if apply_filter and not getattr(self, "_post_bound", False):
+            raise RuntimeError("apply_filter needs bind_poststeps")
+        gradp = np.empty((n, self.ny, self.nx, 2), np.float32) if want_gradp else None
+        p = np.empty((n, self.ny, self.nx), np.float32) if want_p else None
+        truth = np.empty((n, 3, self.ny, self.nx), np.float64) if want_truth else None
+        raw = np.empty((n, 4, len(self.RAW_SUMS)), np.float64)
+        scalars = np.empty((n, len(self.ROW_SCALARS)), np.float64)
+        opt = lambda a, t: _p(a, t) if a is not None else None
+        self._chk(self.lib.psm_gradp_rows(self.h, _p(v, C.c_float), n, width, float(ex), float(ey), int(bool(apply_filter)),
+                                          opt(gradp, C.c_float), opt(p, C.c_float), opt(truth, C.c_double), _p(raw, C.c_double),
+                                          _p(scalars, C.c_double)))
+        return gradp, p, truth, raw, scalars
+
     @classmethod
     def metrics_from_sums(cls, raw) -> dict:
         """One row of raw sums -> the dict of ``error_metrics`` (psm_error_metrics_from_sums: host arithmetic, no GPU).  ValueError
@@ -1224,7 +1364,7 @@ class Evaluation:
         sur._chk(sur.lib.psm_set_geometry(sur.h, int(self.indice), t.ny, t.nx, _p(v1, C.c_int32), _p(w1, C.c_double),
                                           _p(idx, C.c_int32), _p(sdf, C.c_double), None, None, _p(mx, C.c_double), 1, 1, 0.05))
         sur.mesh_cells = int(self.indice)
-        sur._frames_bound = sur._feat_bound = sur._post_bound = sur._deltas_bound = sur._gradp_bound = False      # the new plan dropped them
+        sur._frames_bound = sur._feat_bound = sur._post_bound = sur._deltas_bound = sur._gradp_bound = False; sur._rows_bound = 0      # the new plan dropped them
         self.tables = t
         self._bind_simulation_geometry(sur, t.sdfunct, float(mx[2]))
         return 0
@@ -1310,7 +1450,7 @@ class Evaluation:
         sur.bind_deltas_frames(self.sdfunct[..., 0], [float(v) for v in self.maxs[:4]])
         self._frames_tables = self.tables
 
-    def timeSteps(self, sim, times, apply_filter=False, fields=True):
+    def timeSteps(self, sim, times, apply_filter=False, fields=True, device_prep=False):
         """``timeStep`` for several frames of one simulation, the relevant ones sent ``max_frames`` at a time as ONE call each
         (``deltas_frames``: cell columns -> planes -> image -> solve -> filter -> both error blocks on the device).  The per-frame
         host scalars and the skip rule are those of ``timeStep``; ``pred_minus_true*``, ``pred_minus_true*_block`` and
@@ -1319,11 +1459,16 @@ class Evaluation:
         the weighting planes are not produced).  The block errors come from the device sums in either mode.
         ``fields=False``: a metrics-only sweep -- nothing but the sums comes back, the field's metrics are taken from them too, the
         return is one ``{'delta_p': metrics, 'blocks': metrics}`` dict per frame (0 for an irrelevant frame) and ``cfd_results`` is
-        None."""
+        None.
+        ``device_prep=True``: the loop over ``times`` only slices the float32 rows; ``deltas_rows`` derives U_max_norm, the skip rule,
+        the columns and the scales on the device (every frame keeps its slot in its call, an irrelevant one is read off the
+        returned scalars), and everything returned and recorded holds the bits of the default mode."""
         from . import formats
         if getattr(self, "tables", None) is None:
             raise RuntimeError("computeOnlyOnce has not been called")
         times = [int(t) for t in times]
+        if device_prep:
+            return self._time_steps_rows(sim, times, apply_filter, fields)
         out, cols, Us, slot = [0] * len(times), [], [], []
         for i, time in enumerate(times):
             data, _, _ = formats.read_dataset(self.dataset_path, sim, time)
@@ -1369,6 +1514,51 @@ class Evaluation:
                 else:
                     m = self._record_metrics(sur.metrics_from_sums(raw[j, 0]))
                     out[slot[c0 + j]] = {"delta_p": m, "blocks": mb}
+        if not fields:
+            self.cfd_results = None
+        return out
+
+    def _time_steps_rows(self, sim, times, apply_filter, fields):
+        """``timeSteps(device_prep=True)``: the dataset rows as stored go up, the device makes scalars and columns."""
+        from . import formats
+        out = [0] * len(times)
+        rows = [formats.read_dataset(self.dataset_path, sim, time)[0][0, 0, :self.indice] for time in times]
+        if not rows:
+            return out
+        sur = self._surrogate(self.grid_shape_y, self.grid_shape_x)
+        self._bind_frames(sur, apply_filter)
+        if sur._rows_bound < rows[0].shape[1]:
+            sur.bind_rows(rows[0].shape[1])
+        max_abs_dist, max_abs_p = float(self.maxs[2]), float(self.maxs[3])
+        calls = [sur.deltas_rows(np.stack(rows[c0:c0 + self.max_frames]), max_abs_p, apply_filter=apply_filter, want_result=fields,
+                                 want_truth=fields) for c0 in range(0, len(rows), self.max_frames)]
+        if not any(sc[:, 3].any() for _, _, _, sc in calls):
+            return out
+        self.max_abs_p = max_abs_p
+        sd = np.nan_to_num(np.asarray(self.sdfunct[..., 0], np.float64), nan=0.0) / max_abs_dist
+        self.no_flow_bool = sd == 0
+        if not isinstance(getattr(self, "last_metrics", None), dict):
+            self.last_metrics = {}
+        for name in ("pred_minus_true_block", "pred_minus_true_squared_block"):
+            if not hasattr(self, name):
+                setattr(self, name, [])
+        for c, (res, truth, raw, sc) in enumerate(calls):
+            for j in range(sc.shape[0]):
+                if sc[j, 3] == 0:                                                              # :413-421, decided on the device
+                    continue
+                self.U_max_norm = float(sc[j, 0])
+                mb = sur.metrics_from_sums(raw[j, 1])
+                mb.update(norm_pred=float(raw[j, 1, 6] - raw[j, 1, 5]), n=int(raw[j, 1, 0]))
+                self.pred_minus_true_block.append(mb["mean_err"])
+                self.pred_minus_true_squared_block.append(mb["mean_sq_err"])
+                self.last_metrics["blocks"] = mb
+                if fields:
+                    self.cfd_results = truth[j]
+                    m = self._record_errors(res[j], self.cfd_results, self.no_flow_bool)
+                    out[c * self.max_frames + j] = res[j]
+                else:
+                    m = self._record_metrics(sur.metrics_from_sums(raw[j, 0]))
+                    out[c * self.max_frames + j] = {"delta_p": m, "blocks": mb}
         if not fields:
             self.cfd_results = None
         return out
@@ -1447,16 +1637,17 @@ class Evaluation:
 def call_SM_main(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num_PC, dataset_path,
                  plot_intermediate_fields=False, standardization_method="std", save_plots=False, show_plots=False,
                  apply_filter=False, create_GIF=False, n_sims=1, n_ts=1, device: int = 0, artifact_dir: str = None,
-                 frames_per_call: int = 1, fields: bool = True):
+                 frames_per_call: int = 1, fields: bool = True, device_prep: bool = False):
     """``pressureSM_deltas.SM_call.call_SM_main`` (SM_call.py:778-900): evaluate ``n_ts`` frames of ``n_sims``
     simulations of the dataset and return the error summary the reference prints -- per simulation and overall
     BIAS / STDE / RMSE [%] of delta-p over the flow cells, and BIAS_block / RSME_block / STDE_block [%] of the decoded blocks
     before the assembly (SM_call.py:824-826, from ``utils.compute_in_block_error``); plots and GIFs are not produced.
     ``frames_per_call`` > 1: the frames of a simulation go through ``Evaluation.timeSteps``, that many per call, instead of one
     ``timeStep`` each.  ``fields=False``: the same summary from ``timeSteps(..., fields=False)``, whose error sums are taken on the
-    device: no field is copied back."""
+    device: no field is copied back.  ``device_prep=True`` (implies ``timeSteps``): the per-frame scalars and columns are made on the
+    device from the dataset rows (``timeSteps(..., device_prep=True)``)."""
     overlap = int(overlap_ratio * shape)
-    batched = frames_per_call > 1 or not fields
+    batched = frames_per_call > 1 or not fields or device_prep
     ev = Evaluation(delta, shape, overlap, var_p, var_in, dataset_path, model_name, max_num_PC, standardization_method,
                     device=device, artifact_dir=artifact_dir, max_frames=frames_per_call)
     ev.pred_minus_true, ev.pred_minus_true_squared = [], []
@@ -1468,7 +1659,7 @@ def call_SM_main(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num
         n0 = len(ev.pred_minus_true)
         ev.computeOnlyOnce(sim)
         if batched:
-            ev.timeSteps(sim, range(n_ts), apply_filter, fields=fields)
+            ev.timeSteps(sim, range(n_ts), apply_filter, fields=fields, device_prep=device_prep)
         for time in range(0 if batched else n_ts):
             ev.timeStep(sim, time, plot_intermediate_fields, save_plots, show_plots, apply_filter)
         if len(ev.pred_minus_true) > n0:
@@ -1489,14 +1680,15 @@ def call_SM_main(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num
 def call_SM_main_Poisson(delta, model_name, shape, overlap_ratio, var_p, var_in, max_num_PC, dataset_path,
                          plot_intermediate_fields, standardization_method, k, save_plots, show_plots, apply_filter, create_GIF,
                          n_sims, n_ts, phis_fn, device: int = 0, artifact_dir: str = None, sim_offset: int = 1, time_offset: int = 16,
-                         frames_per_call: int = 1, fields: bool = True):
+                         frames_per_call: int = 1, fields: bool = True, device_prep: bool = False):
     """``pressureSM_Poisson.SM_call.call_SM_main`` (pressureSM_Poisson/SM_call.py:1069-1170), same argument list: evaluates
     frames ``time_offset .. time_offset + n_ts`` of simulations ``sim_offset .. sim_offset + n_sims`` (the reference's
     ``sim += 1`` / ``time += 16``, :1095, :1104) with ``phi = phi_list[sim]`` from ``phis_fn`` and returns the three error
     summaries it prints -- delta-p with the deltaU-change weighting, delta-p without it, and p -- per simulation (last
     ``n_ts`` frames, :1110-1116) and overall.  Plots and GIFs are not produced.  ``frames_per_call`` > 1: the frames of a
     simulation go through ``EvaluationPoisson.timeSteps``, that many per call, instead of one ``timeStep`` each.  ``fields=False``:
-    the same summaries from ``timeSteps(..., fields=False)``, whose error sums are taken on the device: no field is copied back."""
+    the same summaries from ``timeSteps(..., fields=False)``, whose error sums are taken on the device: no field is copied back.
+    ``device_prep=True`` (implies ``timeSteps``): the per-frame scalars and columns are made on the device from the dataset rows."""
     overlap = int(overlap_ratio * shape)
     ev = EvaluationPoisson(delta, shape, overlap, var_p, var_in, dataset_path, model_name, max_num_PC, standardization_method,
                            k, phis_fn, device=device, artifact_dir=artifact_dir, max_frames=frames_per_call)
@@ -1510,9 +1702,9 @@ def call_SM_main_Poisson(delta, model_name, shape, overlap_ratio, var_p, var_in,
         ev.computeOnlyOnce(sim)
         phi = phi_list[sim]
         n0 = len(ev.pred_minus_true)
-        batched = frames_per_call > 1 or not fields
+        batched = frames_per_call > 1 or not fields or device_prep
         if batched:
-            ev.timeSteps(sim, [time + time_offset for time in range(n_ts)], apply_filter, phi, fields=fields)
+            ev.timeSteps(sim, [time + time_offset for time in range(n_ts)], apply_filter, phi, fields=fields, device_prep=device_prep)
         for time in range(0 if batched else n_ts):
             ev.timeStep(sim, time + time_offset, plot_intermediate_fields, save_plots, show_plots, apply_filter, phi)
         if len(ev.pred_minus_true) > n0:
@@ -1531,26 +1723,27 @@ def call_SM_main_Poisson(delta, model_name, shape, overlap_ratio, var_p, var_in,
 def main_gradP(delta=5e-3, model_directory="model_1.h5", shape=128, avance=None, var_p=0.95, var_in=0.95, max_number_PC=512,
                hdf5_path="dataset_gradP_cil.hdf5", plot_intermediate_fields=True, save_plots=True, show_plots=False,
                apply_filter=False, sims=(0,), n_ts=5, device: int = 0, artifact_dir: str = None, frames_per_call: int = 1,
-               fields: bool = True):
+               fields: bool = True, device_prep: bool = False):
     """``main`` of the U_to_gradP evaluator (Eval_dual_Dense_onlycil.py:692-744) with its hard-coded inputs as defaults
     (``avance = int(0.75 * shape)``, simulations ``[0]``, five time steps): computeOnlyOnce + timeStep per frame, then
     BIAS / RMSE / STDE [%] "for the sim" from the accumulated per-frame values (:735-742) -- printed like the reference and
     returned.  Plots are not produced.
     ``frames_per_call`` > 1: the frames of a simulation go through ``EvaluationGradP.timeSteps``, that many per call, instead of one
     ``timeStep`` each.  ``fields=False``: the same summary from ``timeSteps(..., fields=False)``, whose error sums are taken on the
-    device: no field is copied back.  With the defaults the loop is the per-frame one."""
+    device: no field is copied back.  ``device_prep=True`` (implies ``timeSteps``): the per-frame scalar and columns are made on the
+    device from the dataset rows.  With the defaults the loop is the per-frame one."""
     if avance is None:
         avance = int(0.75 * shape)
     ev = EvaluationGradP(delta, shape, avance, var_p, var_in, hdf5_path, model_directory, max_number_PC, device=device,
                          artifact_dir=artifact_dir, max_frames=frames_per_call)
     ev.pred_minus_true, ev.pred_minus_true_squared = [], []
     out = {"sims": [], "frames": []}
-    batched = frames_per_call > 1 or not fields
+    batched = frames_per_call > 1 or not fields or device_prep
     for sim in sims:
         ev.computeOnlyOnce(sim)
         for t0 in range(0, n_ts if batched else 0, frames_per_call):
             chunk = range(t0, min(t0 + frames_per_call, n_ts))
-            ev.timeSteps(sim, chunk, apply_filter, fields=fields)
+            ev.timeSteps(sim, chunk, apply_filter, fields=fields, device_prep=device_prep)
             for time, m in zip(chunk, ev.frame_metrics):
                 out["frames"].append(dict(sim=sim, time=time, **{k: dict(v) for k, v in m.items()}))
         for time in range(0 if batched else n_ts):
@@ -1654,7 +1847,7 @@ class EvaluationPoisson(Evaluation):
 
     ERROR_BLOCKS = (("", "Error in delta_p"), ("_deltap_crude", "Error in delta_p - no weighting"), ("_p", "Error in p"))
 
-    def timeSteps(self, sim, times, apply_filter=False, phi=1.0, fields=True):
+    def timeSteps(self, sim, times, apply_filter=False, phi=1.0, fields=True, device_prep=False):
         """``timeStep`` for several frames of one simulation, the relevant ones sent ``max_frames`` at a time as ONE call each
         (``poisson_frames``: cell columns -> planes -> features -> solve -> post-steps on the device).  The per-frame host scalars
         and the three error blocks are those of ``timeStep``, in frame order; returns the list of ``field_deltap`` with 0 for an
@@ -1664,11 +1857,16 @@ class EvaluationPoisson(Evaluation):
         three error blocks and no field; the six lists and ``last_metrics`` are filled as above, the return is one
         ``{suffix: metrics}`` dict per frame ('' / '_deltap_crude' / '_p'; 0 for an irrelevant frame), and ``deltap_res``,
         ``cfd_results``, ``p_pred`` and ``label_planes`` are None.  The device takes nan0(label plane) as the delta-p truth where the
-        host chain writes nan_to_num(x / U^2) / m * m * U^2: at most 4 ulp per element apart."""
+        host chain writes nan_to_num(x / U^2) / m * m * U^2: at most 4 ulp per element apart.
+        ``device_prep=True``: the loop over ``times`` only slices the float32 rows; ``poisson_rows`` / ``poisson_rows_errors`` derive
+        U_max_norm, the skip rule, the eight columns, (L, U) and the scale on the device (every frame keeps its slot in its call, an
+        irrelevant one is read off the returned scalars), and everything returned and recorded holds the bits of the default mode."""
         from . import formats
         if getattr(self, "tables", None) is None:
             raise RuntimeError("computeOnlyOnce has not been called")
         times = [int(t) for t in times]
+        if device_prep:
+            return self._time_steps_rows(sim, times, apply_filter, phi, fields)
         out, cols, Us, slot = [0] * len(times), [], [], []
         self.label_planes = [None] * len(times)
         for i, time in enumerate(times):
@@ -1717,6 +1915,54 @@ class EvaluationPoisson(Evaluation):
                 self._record_errors(self.deltap_res, self.cfd_results, self.no_flow_bool, "_deltap_crude", "Error in delta_p - no weighting")
                 self._record_errors(self.p_pred, p_grid, self.no_flow_bool, "_p", "Error in p")
                 out[slot[c0 + j]], self.label_planes[slot[c0 + j]] = field_deltap, extra[j]
+        if not fields:
+            self.no_flow_bool = sd == 0
+            self.deltap_res = self.cfd_results = self.p_pred = self.label_planes = None
+        return out
+
+    def _time_steps_rows(self, sim, times, apply_filter, phi, fields):
+        """``timeSteps(device_prep=True)``: the dataset rows as stored go up, the device makes scalars and columns."""
+        from . import formats
+        out = [0] * len(times)
+        self.label_planes = [None] * len(times)
+        rows = [formats.read_dataset(self.dataset_path, sim, time)[0][0, 0, :self.indice] for time in times]
+        if not rows:
+            return out
+        sur = self._surrogate(self.grid_shape_y, self.grid_shape_x)
+        self._bind_frames(sur)
+        if sur._rows_bound < rows[0].shape[1]:
+            sur.bind_rows(rows[0].shape[1])
+        chunks = [np.stack(rows[c0:c0 + self.max_frames]) for c0 in range(0, len(rows), self.max_frames)]
+        if fields:
+            calls = [sur.poisson_rows(chunk, self.max_abs_delta_p, phi, apply_filter=apply_filter, weighting=True, want_extra=True) for chunk in chunks]
+        else:
+            calls = [sur.poisson_rows_errors(chunk, self.max_abs_delta_p, phi, apply_filter=apply_filter) for chunk in chunks]
+        if not any(call[-1][:, 3].any() for call in calls):
+            return out
+        sd = np.nan_to_num(self.sdfunct[..., 0], nan=0.0) / self.max_abs_dist
+        for c, call in enumerate(calls):
+            sc = call[-1]
+            for j in range(sc.shape[0]):
+                if sc[j, 3] == 0:                                                              # :562-567, decided on the device
+                    continue
+                i, U = c * self.max_frames + j, float(sc[j, 0])
+                self.U_max_norm = U
+                if not fields:
+                    out[i] = {sfx: self._record_metrics(sur.metrics_from_sums(call[0][j, q]), sfx, title)
+                              for q, (sfx, title) in enumerate(self.ERROR_BLOCKS)}
+                    continue
+                res, _, nxt, extra, _ = call
+                field_deltap = nxt[j]
+                self.deltap_res = res[j, :, :, 0]
+                delta_p_grid = np.nan_to_num(extra[j, 0] / pow(U, 2.0), nan=0.0) / self.max_abs_delta_p
+                p_grid = np.nan_to_num(extra[j, 1], nan=0.0)
+                self.cfd_results = delta_p_grid * self.max_abs_delta_p * pow(U, 2.0)
+                self.no_flow_bool = sd == 0
+                self.p_pred = (p_grid - self.cfd_results) + field_deltap
+                self._record_errors(field_deltap, self.cfd_results, self.no_flow_bool, "", "Error in delta_p")
+                self._record_errors(self.deltap_res, self.cfd_results, self.no_flow_bool, "_deltap_crude", "Error in delta_p - no weighting")
+                self._record_errors(self.p_pred, p_grid, self.no_flow_bool, "_p", "Error in p")
+                out[i], self.label_planes[i] = field_deltap, extra[j]
         if not fields:
             self.no_flow_bool = sd == 0
             self.deltap_res = self.cfd_results = self.p_pred = self.label_planes = None
@@ -1787,7 +2033,7 @@ class EvaluationGradP(Evaluation):
         sur._chk(sur.lib.psm_set_geometry(sur.h, int(self.indice), t.ny, t.nx, _p(v1, C.c_int32), _p(w1, C.c_double),
                                           _p(idx, C.c_int32), _p(sdf, C.c_double), None, None, _p(mx, C.c_double), 1, 1, 0.05))
         sur.mesh_cells = int(self.indice)
-        sur._frames_bound = sur._feat_bound = sur._post_bound = sur._deltas_bound = sur._gradp_bound = False      # the new plan dropped them
+        sur._frames_bound = sur._feat_bound = sur._post_bound = sur._deltas_bound = sur._gradp_bound = False; sur._rows_bound = 0      # the new plan dropped them
         self.tables = t
         self._bind_simulation_geometry(sur, t.sdfunct, float(mx[2]))
         return 0
@@ -1870,7 +2116,7 @@ class EvaluationGradP(Evaluation):
 
     METRIC_ROWS = ("reference", "p", "dp_dx", "dp_dy")    # the rows of gradp_frames' raw sums
 
-    def timeSteps(self, sim, times, apply_filter=False, fields=True):
+    def timeSteps(self, sim, times, apply_filter=False, fields=True, device_prep=False):
         """``timeStep`` for several frames of one simulation, sent ``max_frames`` at a time as ONE call each (``gradp_frames``: cell
         columns -> planes -> image, labels -> solve -> filter -> integration -> four error blocks on the device).  The per-frame
         host scalars and columns are those of ``timeStep``; ``pred_minus_true``, ``pred_minus_true_squared`` (the reference's own
@@ -1881,7 +2127,9 @@ class EvaluationGradP(Evaluation):
         ``timeStep`` leaves on the last frame (``grid`` is not produced).
         ``fields=False``: a metrics-only sweep -- nothing but the sums comes back (4 x 8 doubles per frame), the return is one dict
         of the four metric blocks per frame.
-        Either way ``frame_metrics`` holds the call's four metric blocks per frame."""
+        Either way ``frame_metrics`` holds the call's four metric blocks per frame.
+        ``device_prep=True``: the loop over ``times`` only slices the float32 rows; ``gradp_rows`` derives U_max_norm and the five
+        columns on the device, and everything returned and recorded holds the bits of the default mode."""
         from . import formats
         if getattr(self, "tables", None) is None:
             raise RuntimeError("computeOnlyOnce has not been called")
@@ -1890,6 +2138,9 @@ class EvaluationGradP(Evaluation):
         for time in times:
             data, _, _ = formats.read_dataset(self.hdf5_path, sim, time)
             d = data[0, 0, :self.indice]                                  # float32, normalised in float32 like the reference
+            if device_prep:
+                cols.append(d)
+                continue
             Ux, Uy, p, dPdx, dPdy = d[:, 0:1], d[:, 1:2], d[:, 2:3], d[:, 6:7], d[:, 7:8]
             U_max_norm = np.max(np.sqrt(np.square(Ux) + np.square(Uy)))                       # :438
             cols.append(np.concatenate([Ux / U_max_norm, Uy / U_max_norm,                   # :443-444
@@ -1909,7 +2160,14 @@ class EvaluationGradP(Evaluation):
             self.last_metrics = {}
         for c0 in range(0, len(cols), self.max_frames):
             chunk, U_chunk = np.stack(cols[c0:c0 + self.max_frames]), Us[c0:c0 + self.max_frames]
-            gradp, p, truth, raw = sur.gradp_frames(chunk, apply_filter=apply_filter, want_gradp=fields, want_p=fields, want_truth=fields)
+            if device_prep:
+                if sur._rows_bound < chunk.shape[2]:
+                    sur.bind_rows(chunk.shape[2])
+                gradp, p, truth, raw, sc = sur.gradp_rows(chunk, float(self.max_x - self.min_x), float(self.max_y - self.min_y),
+                                                          apply_filter=apply_filter, want_gradp=fields, want_p=fields, want_truth=fields)
+                U_chunk = sc[:, 0]
+            else:
+                gradp, p, truth, raw = sur.gradp_frames(chunk, apply_filter=apply_filter, want_gradp=fields, want_p=fields, want_truth=fields)
             for j, U in enumerate(U_chunk):
                 self.U_max_norm = float(U)
                 m = {name: sur.metrics_from_sums(raw[j, r]) for r, name in enumerate(self.METRIC_ROWS)}
