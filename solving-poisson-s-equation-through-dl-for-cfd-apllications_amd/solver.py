@@ -1,0 +1,223 @@
+"""The Chapter-5 solver module on top of ``GridSurrogate``: ``SolverModule`` (one case: ``init_func`` / ``py_func`` with the
+reference's signatures, python_module.py:172, :249, and the grid-native body of ``py_func``, :299-473, as ``py_func_grid``) and
+``SolverEnsemble`` (K cases on one handle).  ``surrogate.py`` re-exports both."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .surrogate import GridSurrogate, _f64, _p
+from .synthetic import SurrogateModel
+
+
+class SolverModule:
+    """Chapter-5 ``python_module`` (python_module.py): ``init_func`` / ``py_func`` with the
+    reference's signatures on one rank (the serial solver, singleCore/test_Case/python_module.py:
+    139,199; in the parallel solver the mpi4py gather/scatter of python_module.py:179-185,258,511
+    stays around these calls).  ``maxs`` = (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p) of
+    the ``maxs`` file (python_module.py:106-109)."""
+
+    def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), device: int = 0, delta: float = 5e-3,
+                 geometry: str = "scipy"):
+        """``geometry``: who builds init_func's tables -- 'scipy' (default in this Python mirror: the routines the reference
+        itself calls, qhull Delaunay in both directions, so that the tables -- including qhull's arbitrary choice of diagonal
+        in every cocircular lattice square of the grid -> mesh step -- are the reference's) or 'native' (the library's C++
+        builder behind ``psm_init_geometry``, csrc/psm_geometry.cpp: what a C++ solver gets; no SciPy).  The two differ only
+        where the reference's own result is an accident of qhull (include/psm.h): fixed lattice diagonals -- a second-order
+        difference on smooth fields, O(1) per cell on the white-noise fields of randomly initialised test networks
+        (tests/measure/mesh_native_vs_scipy.py) -- and the simplex used for lattice points outside the hull."""
+        if geometry not in ("scipy", "native"):
+            raise ValueError("geometry must be 'scipy' or 'native'")
+        self.model, self.maxs, self.device, self.delta = model, tuple(float(v) for v in maxs), device, delta
+        self.geometry = geometry
+        self._sur = None
+        self.tables = None
+
+    # -- grid-native body (python_module.py:299-473)
+    def py_func_grid(self, grid: np.ndarray) -> np.ndarray:
+        if self._sur is None or (self._sur.ny, self._sur.nx) != grid.shape[:2]:
+            if self._sur is not None:
+                self._sur.close()
+            self._sur = GridSurrogate(self.model, grid.shape[0], grid.shape[1], 1, self.device)
+        return self._sur.solve(grid)[0, :, :, 0]
+
+    # -- the solver boundary
+    def init_func(self, array, top_boundary, obst_boundary, placeholder=0):
+        """python_module.py:172: one-time tables (host, SciPy qhull like the reference), handed
+        to the GPU library with psm_set_geometry.  Returns 0."""
+        from .geometry import build_geometry
+        if self.geometry == "native":
+            return self._init_func_native(array, top_boundary, obst_boundary)
+        t = build_geometry(np.asarray(array, np.float64), top_boundary, obst_boundary, self.delta)
+        if self._sur is not None:
+            self._sur.close()
+        self._sur = GridSurrogate(self.model, t.ny, t.nx, 1, self.device)
+        v1, w1 = np.ascontiguousarray(t.vtx_m2g, np.int32), _f64(t.wts_m2g)
+        v2, w2 = np.ascontiguousarray(t.vtx_g2m, np.int32), _f64(t.wts_g2m)
+        idx, sdf, mx = np.ascontiguousarray(t.indices, np.int32), _f64(t.sdfunct), _f64(self.maxs)
+        self._sur._chk(self._sur.lib.psm_set_geometry(
+            self._sur.h, int(np.asarray(array).shape[0]), t.ny, t.nx, _p(v1, C.c_int32), _p(w1, C.c_double),
+            _p(idx, C.c_int32), _p(sdf, C.c_double), _p(v2, C.c_int32), _p(w2, C.c_double), _p(mx, C.c_double),
+            0, 0, 0.05))
+        self.tables = t
+        return 0
+
+    def _init_func_native(self, array, top_boundary, obst_boundary):
+        """psm_set_case + psm_init_geometry: the tables are built inside the library (csrc/psm_geometry.cpp)."""
+        a, t, o = _f64(array), _f64(top_boundary), _f64(obst_boundary)
+        lib = _lib.load()
+        ny, nx = C.c_int32(), C.c_int32()
+        if lib.psm_geometry_shape(_p(a, C.c_double), a.shape[0], self.delta, C.byref(ny), C.byref(nx), None):
+            raise ValueError(lib.psm_geometry_last_error().decode())
+        if self._sur is not None:
+            self._sur.close()
+        self._sur = GridSurrogate(self.model, ny.value, nx.value, 1, self.device)
+        mx = _f64(self.maxs)
+        self._sur._chk(lib.psm_set_case(self._sur.h, _p(mx, C.c_double), self.delta, 10, 0.05))
+        self._sur._chk(lib.psm_init_geometry(self._sur.h, _p(a, C.c_double), a.shape[0], _p(t, C.c_double), t.shape[0],
+                                             _p(o, C.c_double), o.shape[0], 0))
+        self.tables = "native"
+        return 0
+
+    def pin(self, array: np.ndarray, out: np.ndarray = None):
+        """psm_pin_buffers: register the caller's persistent [N,5] float64 array (and optionally a persistent output
+        array) for direct DMA; later ``py_func(array, out=out)`` calls with exactly these arrays skip the staging copies.
+        The caller keeps both arrays alive until ``unpin()`` / a new ``init_func``."""
+        if array.dtype != np.float64 or not array.flags.c_contiguous or (out is not None and (out.dtype != np.float64 or not out.flags.c_contiguous)):
+            raise ValueError("contiguous float64 arrays expected")
+        self._sur._chk(self._sur.lib.psm_pin_buffers(self._sur.h, _p(array, C.c_double), _p(out, C.c_double) if out is not None else None))
+        self._pinned = (array, out)
+
+    def unpin(self):
+        self._sur._chk(self._sur.lib.psm_unpin_buffers(self._sur.h))
+        self._pinned = None
+
+    def py_func_begin(self, array_in, out: np.ndarray = None):
+        """First half of :meth:`py_func` (psm_solve_begin): enqueue the step and return; several SolverModules (cases)
+        can be advanced from one thread by calling begin on all of them, then :meth:`py_func_end` on each."""
+        if self.tables is None:
+            raise RuntimeError("init_func has not been called")
+        a = _f64(array_in)
+        if a.ndim != 2 or a.shape[1] != 5:
+            raise ValueError("array must be [N,5] = (Ux, Uy, Cx, Cy, p)")
+        if out is None:
+            out = np.empty(a.shape[0], np.float64)
+        self._sur._chk(self._sur.lib.psm_solve_begin(self._sur.h, _p(a, C.c_double), a.shape[0], 0, _p(out, C.c_double)))
+        self._inflight = (a, out)                       # keeps both arrays alive until the end call (set only once the step is in flight)
+
+    def py_func_end(self) -> np.ndarray:
+        self._sur._chk(self._sur.lib.psm_solve_end(self._sur.h))
+        a, out = self._inflight
+        self._inflight = None
+        return out
+
+    def py_func(self, array_in, placeholder=0, out: np.ndarray = None) -> np.ndarray:
+        """python_module.py:249: cells [N,5] float64 -> p [N] float64."""
+        if self.tables is None:
+            raise RuntimeError("init_func has not been called")
+        a = _f64(array_in)
+        if a.ndim != 2 or a.shape[1] != 5:
+            raise ValueError("array must be [N,5] = (Ux, Uy, Cx, Cy, p)")
+        if out is None:
+            out = np.empty(a.shape[0], np.float64)
+        self._sur._chk(self._sur.lib.psm_solve(self._sur.h, _p(a, C.c_double), a.shape[0], int(placeholder),
+                                                _p(out, C.c_double)))
+        return out
+
+
+class SolverEnsemble:
+    """``SolverModule`` for an ensemble of cases that share one grid shape: K meshes with their own obstacles on ONE handle,
+    all advanced by one call (``psm_set_geometry_cases`` / ``psm_solve_cases``: one launch chain per step instead of one per
+    case).  ``init_func`` takes one (array, top, obst) per case, ``py_func`` one ``[N_i,5]`` array per case and returns the
+    list of ``p_i``.  ``geometry``: 'native' (``psm_init_geometry_cases``, the library's C++ table builder) or 'scipy'
+    (``geometry.build_geometry`` per case, handed over with ``psm_set_geometry_cases``) -- see :class:`SolverModule`."""
+
+    def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), max_cases: int = 8, geometry: str = "native",
+                 device: int = 0, delta: float = 5e-3):
+        if geometry not in ("scipy", "native"):
+            raise ValueError("geometry must be 'scipy' or 'native'")
+        self.model, self.maxs, self.max_cases = model, tuple(float(v) for v in maxs), int(max_cases)
+        self.geometry, self.device, self.delta = geometry, device, delta
+        self._sur = None
+        self.tables = None
+        self.cell_off = None
+        self._inflight = None
+
+    @staticmethod
+    def _ptrs(arrays):
+        return (C.c_void_p * len(arrays))(*[a.ctypes.data for a in arrays])
+
+    def init_func(self, arrays, tops, obsts):
+        """One-time tables of every case; all cases must give the same grid shape.  Returns 0."""
+        if not (len(arrays) == len(tops) == len(obsts)) or not 1 <= len(arrays) <= self.max_cases:
+            raise ValueError("one (array, top, obst) per case, 1..max_cases cases")
+        lib = _lib.load()
+        K = len(arrays)
+        a, t, o = [_f64(x) for x in arrays], [_f64(x) for x in tops], [_f64(x) for x in obsts]
+        mx = _f64(self.maxs)
+        if self.geometry == "native":
+            ny, nx = C.c_int32(), C.c_int32()
+            if lib.psm_geometry_shape(_p(a[0], C.c_double), a[0].shape[0], self.delta, C.byref(ny), C.byref(nx), None):
+                raise ValueError(lib.psm_geometry_last_error().decode())
+            ny, nx, tables = ny.value, nx.value, "native"
+        else:
+            from .geometry import build_geometry
+            tables = [build_geometry(a[k], t[k], o[k], self.delta) for k in range(K)]
+            ny, nx = tables[0].ny, tables[0].nx
+            if any((g.ny, g.nx) != (ny, nx) for g in tables):
+                raise ValueError("the cases of an ensemble must share one grid shape")
+        if self._sur is not None:
+            self._sur.close()
+        self._sur = sur = GridSurrogate(self.model, ny, nx, self.max_cases, self.device)
+        n = (C.c_int64 * K)(*[x.shape[0] for x in a])
+        if self.geometry == "native":
+            sur._chk(lib.psm_set_case(sur.h, _p(mx, C.c_double), self.delta, 10, 0.05))
+            sur._chk(lib.psm_init_geometry_cases(sur.h, K, self._ptrs(a), n, self._ptrs(t), (C.c_int64 * K)(*[x.shape[0] for x in t]),
+                                                 self._ptrs(o), (C.c_int64 * K)(*[x.shape[0] for x in o])))
+        else:
+            keep = [[np.ascontiguousarray(getattr(g, f), dt) for g in tables]
+                    for f, dt in (("vtx_m2g", np.int32), ("wts_m2g", np.float64), ("indices", np.int32), ("sdfunct", np.float64),
+                                  ("vtx_g2m", np.int32), ("wts_g2m", np.float64))]
+            sur._chk(lib.psm_set_geometry_cases(sur.h, K, n, ny, nx, *[self._ptrs(col) for col in keep], _p(mx, C.c_double), 0, 0, 0.05))
+        off = (C.c_int64 * (K + 1))()
+        sur._chk(lib.psm_mesh_cases(sur.h, None, off))
+        self.cell_off = [int(v) for v in off]
+        self.tables = tables
+        return 0
+
+    def _pack(self, arrays):
+        if self.tables is None:
+            raise RuntimeError("init_func has not been called")
+        K = len(self.cell_off) - 1
+        if len(arrays) != K:
+            raise ValueError(f"{K} cases were initialised")
+        cells = np.empty((self.cell_off[-1], 5), np.float64)
+        for k, x in enumerate(arrays):
+            x = np.asarray(x)
+            if x.shape != (self.cell_off[k + 1] - self.cell_off[k], 5):
+                raise ValueError("array must be [N,5] = (Ux, Uy, Cx, Cy, p) with the cell count of init_func")
+            cells[self.cell_off[k]:self.cell_off[k + 1]] = x
+        return cells, np.empty(self.cell_off[-1], np.float64)
+
+    def _split(self, p):
+        return [p[self.cell_off[k]:self.cell_off[k + 1]] for k in range(len(self.cell_off) - 1)]
+
+    def py_func_begin(self, arrays):
+        """First half of :meth:`py_func` (psm_solve_cases_begin): enqueue the step of all cases and return."""
+        cells, p = self._pack(arrays)
+        self._sur._chk(self._sur.lib.psm_solve_cases_begin(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
+        self._inflight = (cells, p)                     # keeps both arrays alive until the end call
+
+    def py_func_end(self):
+        self._sur._chk(self._sur.lib.psm_solve_cases_end(self._sur.h))
+        cells, p = self._inflight
+        self._inflight = None
+        return self._split(p)
+
+    def py_func(self, arrays):
+        """One step of every case: list of cells [N_i,5] float64 -> list of p_i [N_i] float64."""
+        cells, p = self._pack(arrays)
+        self._sur._chk(self._sur.lib.psm_solve_cases(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
+        return self._split(p)

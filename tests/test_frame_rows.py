@@ -1,7 +1,7 @@
 """A frame's dataset rows in, per-frame scalars and columns on the device (csrc/psm_rows.hip, csrc/psm_api_rows.cpp).
 
-The stage alone is held to the host statements at the head of the three ``timeSteps`` of surrogate.py, quoted below and executed
-on the same float32 rows: columns and scalars bit for bit (uint64 views, NaN positions included).  Shapes are the smallest that
+The stage alone is held to the host statements of the three evaluators' ``_frame_prepare`` (evaluators.py: what ``timeStep`` and
+``timeSteps`` both run on a frame's rows) and of their ``_host_call`` (U^2, the out-scale), quoted below and executed on the same float32 rows: columns and scalars bit for bit (uint64 views, NaN positions included).  Shapes are the smallest that
 can go wrong.  The partial launch gives every workgroup 256 cells per pass and at most 256 workgroups per frame; the finish
 launch writes 256 cells per workgroup and folds the frame's partials with 256 threads (4 waves):
     1      one cell: 255 idle threads, one partial
@@ -47,7 +47,7 @@ _dp, _fp = C.POINTER(C.c_double), C.POINTER(C.c_float)
 
 # ------------------------------------------------------------------------------------------- the host statements (the specification)
 def host_deltas(d, base):
-    """Evaluation.timeSteps, the loop body: -> (cols [n,3] float64, scalars [8])."""
+    """Evaluation._frame_prepare(d, full=False) and the scalars of _host_call: -> (cols [n,3] float64, scalars [8])."""
     Ux, Uy = d[:, 0:1], d[:, 1:2]
     delta_U, delta_p = d[:, 5:7], d[:, 7:8]
     U_max_norm = np.max(np.sqrt(np.square(Ux) + np.square(Uy)))
@@ -61,7 +61,7 @@ def host_deltas(d, base):
 
 
 def host_poisson(d, base):
-    """EvaluationPoisson.timeSteps, the loop body: -> (cols [n,8] float64, scalars [8])."""
+    """EvaluationPoisson._frame_prepare and the scalars of _host_call: -> (cols [n,8] float64, scalars [8])."""
     Ux, Uy, p = d[:, 0:1], d[:, 1:2], d[:, 2:3]
     delta_U, delta_p = d[:, 5:7], d[:, 7:8]
     delta_U_prev, delta_p_prev = d[:, 8:10], d[:, 10:11]
@@ -78,7 +78,7 @@ def host_poisson(d, base):
 
 
 def host_gradp(d, ex, ey):
-    """EvaluationGradP.timeSteps, the loop body, with max_x - min_x = ex and max_y - min_y = ey as float32 scalars."""
+    """EvaluationGradP._frame_prepare, with max_x - min_x = ex and max_y - min_y = ey as float32 scalars."""
     assert isinstance(ex, np.float32) and isinstance(ey, np.float32)
     Ux, Uy, p, dPdx, dPdy = d[:, 0:1], d[:, 1:2], d[:, 2:3], d[:, 6:7], d[:, 7:8]
     U_max_norm = np.max(np.sqrt(np.square(Ux) + np.square(Uy)))

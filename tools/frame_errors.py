@@ -41,7 +41,7 @@ say = ps.say
 
 
 def host_metrics(res, nxt, extra, Us, no_flow, max_abs_delta_p):
-    """The three error blocks of every frame as timeSteps takes them from the fields (surrogate.py)."""
+    """The three error blocks of every frame as timeSteps takes them from the fields (EvaluationPoisson._record_fields, evaluators.py)."""
     out = []
     for j, U in enumerate(Us):
         field = nxt[j]
