@@ -632,6 +632,42 @@ int psm_gradp_frames_device(psm_handle* h, const double* d_cols, int32_t n_frame
 int psm_gradp_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, const float* out_scale, int32_t apply_filter,
                      float* gradp, float* p, double* truth, double* raw);
 
+/* The frame batch of the two Chapter-4 evaluators (Chapter4/MLP/M_u/Evaluation/Eval_dual_Dense_onlycil.py: (Ux, Uy, SDF) -> p;
+ * Chapter4/MLP/M_fU/Evaluation/Eval.py: (f(U), SDF) -> p) on the device: cell columns -> planes -> the solve's image and the truth
+ * plane -> solve -> the frame's error block, without an image, a label or a field leaving the device.  Columns of a frame: the
+ * c_in - 1 input channels (M_u: Ux / U, Uy / U; M_fU: f(U) / U^2), then the pressure label p / U^2; further columns are not stored.
+ * No dimensional scale and no block stage enter: the reference compares prediction and label in normalised units (M_u :457-476).
+ * psm_bind_chapter4_frames: after psm_bind_frames, on a PSM_VARIANT_CHAPTER5 handle with c_out == 1, c_in in {2, 3} and
+ * sdf_channel == c_in - 1 (PSM_ERR_STATE naming the rule otherwise, and without a frame binding).  sdfunct [ny*nx] float64 is the
+ * simulation's raw SDF image (0 in solids, NaNs allowed), max_abs [c_in + 1] the scales of the c_in - 1 input channels, of the
+ * distance and of p, each finite and non-zero (PSM_ERR_ARG).  Keeps nan0(sdfunct) / max_abs_dist in float64 on the device -- channel
+ * c_in - 1 of every image, and the mask of the field errors (flow cell iff != 0) -- and reserves planes, image, truth, field, raw
+ * sums and pinned slots for the frame count bound with psm_bind_frames: after it a step allocates nothing.  psm_bind_frames /
+ * psm_unbind_frames, a new mesh, psm_plan_grid or a model change drop the binding. */
+int psm_bind_chapter4_frames(psm_handle* h, const double* sdfunct, const double* max_abs);
+int psm_unbind_chapter4_frames(psm_handle* h);
+/* The image stage alone: psm_frames_to_grid_device (fill = 1) of columns 0 .. c_in - 1 into the binding's planes, then one pack launch:
+ *     d_grid  [n][ny][nx][c_in] float32 = (float)(nan0(v_c) / max_abs_c), c < c_in - 1; channel c_in - 1 = (float)(nan0(sdfunct) / max_abs_dist)
+ *     d_truth [n][ny*nx]        float64 = nan0(v_{c_in - 1}) / max_abs_p                                     (NULL: not stored)
+ * -- divisions in float64, the cast behind them: the bits of the reference's NumPy statements (M_u :215-225, M_fU :213-223).  Device
+ * pointers aligned to their element, asynchronous on `stream` (NULL: the handle's).  PSM_ERR_ARG and nothing enqueued: k outside
+ * [c_in, 16], n_frames outside [1, bound count], d_cols or d_grid NULL, a misaligned destination. */
+int psm_chapter4_image_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, float* d_grid, double* d_truth, void* stream);
+/* The whole step as ONE graph replay: planes -> image and truth -> solve.  Inside it the frames are solved one by one, each as the
+ * single case the evaluator's per-frame call solves -- with a geometry bound for ONE case (psm_bind_geometry) the 6-launch route --,
+ * so a frame's field holds the bits of psm_solve_grid on its image whatever the batch (psm_read_stage then shows the last frame's
+ * solve).  There is no filter: both reference files fail on their own filtered field (M_u :421, :457-458).  Then, with d_raw != NULL,
+ * the two launches of psm_field_errors_device on the same stream, over the cells with nan0(sdfunct) / max_abs_dist != 0, that leave
+ * d_raw [n_frames][1][8]: the field against the truth plane.  d_result [n][ny*nx] float32 and d_truth [n][ny*nx] float64 may be
+ * NULL: the binding's buffers are used.  PSM_ERR_ARG and nothing enqueued: k outside [c_in, 16], n_frames outside [1, bound count],
+ * d_cols NULL, a misaligned destination (4 bytes for d_result, 8 for d_truth and d_raw). */
+int psm_chapter4_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, float* d_result, double* d_truth,
+                               double* d_raw, void* stream);
+/* host buffers, synchronous: one H2D of cols (k at most the count bound with psm_bind_frames), D2H of what is non-NULL only --
+ * result [n][ny*nx] float32, truth [n][ny*nx] float64, raw [n][1][8] (at least one of them).  Solves again on the general path
+ * after a guard trip, like psm_deltas_frames. */
+int psm_chapter4_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, float* result, double* truth, double* raw);
+
 /* A frame's dataset rows in, the per-frame scalars and the columns of the frame entries above made on the device: the head of the
  * three evaluators' timeSteps (surrogate.py) without per-cell host arithmetic, at half the bytes of the float64 columns.
  * rows [n_frames][n_cells][width] float32, row-major: the dataset frame cut at `indice`, nothing else done to it (r0, r1 = Ux, Uy;

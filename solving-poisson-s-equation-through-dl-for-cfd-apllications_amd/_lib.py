@@ -156,6 +156,11 @@ SIGNATURES = {
     "psm_gradp_frames_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, _f32p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
     "psm_gradp_frames": (C.c_int, [_hp, _f64p, C.c_int32, C.c_int32, _f32p, C.c_int32, _f32p, _f32p, _f64p, _f64p]),
+    "psm_bind_chapter4_frames": (C.c_int, [_hp, _f64p, _f64p]),
+    "psm_unbind_chapter4_frames": (C.c_int, [_hp]),
+    "psm_chapter4_image_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_chapter4_frames_device": (C.c_int, [_hp, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_chapter4_frames": (C.c_int, [_hp, _f64p, C.c_int32, C.c_int32, _f32p, _f64p, _f64p]),
     "psm_bind_rows": (C.c_int, [_hp, C.c_int32]),
     "psm_unbind_rows": (C.c_int, [_hp]),
     "psm_rows_prepare_device": (C.c_int, [_hp, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, _f64p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -14,7 +14,8 @@ static void drop_frame_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphK
 void frames_free(psm_handle* h) {
   FrameSet& s = h->frames;
   deltas_free(h);                       // psm_bind_deltas_frames stands on this binding,
-  gradp_free(h);                        // psm_bind_gradp_frames
+  gradp_free(h);                        // psm_bind_gradp_frames,
+  chapter4_free(h);                     // psm_bind_chapter4_frames
   rows_free(h);                         // and psm_bind_rows
   drop_frame_graphs(h);
   dev_free(s.d_cols); dev_free(s.d_extra); dev_free(s.d_raw);

@@ -71,9 +71,9 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
   const bool rows = step.rows.rows;
   if (step.rows.scaled()) d_scale = h->ws0.d_row_scale;   // the finish launch of the rows stage writes it, inside the sequence
   else if ((rc = prepare_scale(h, h->ws0, out_scale, n_cases, st, &d_scale))) return rc;
-  const bool frames = step.frames.cols, feat = step.feat.vel, deltas = step.deltas.planes, gradp = step.gradp.planes, post = step.post.apply_filter >= 0;
-  h->last_cases = gradp ? 1 : n_cases;  // gradp: ws0 holds the last frame's single-case solve
-  // the two rows launches (rows), the mesh -> grid launch (frames), the two feature launches (feat) or the image pack (deltas, gradp), the solve, then the two integration launches (p) or the
+  const bool frames = step.frames.cols, feat = step.feat.vel, deltas = step.deltas.planes, gradp = step.gradp.planes, chapter4 = step.chapter4.planes, post = step.post.apply_filter >= 0;
+  h->last_cases = gradp || chapter4 ? 1 : n_cases;  // gradp, chapter4: ws0 holds the last frame's single-case solve
+  // the two rows launches (rows), the mesh -> grid launch (frames), the two feature launches (feat) or the image pack (deltas, gradp, chapter4), the solve, then the two integration launches (p) or the
   // post-steps' (at most four); gradp: the filter among the post-steps and BEHIND it the integration with the gradp binding's tables: one linear chain
   auto sequence = [&](hipStream_t on, hipEvent_t* ev) {
     int rs = rows ? rows_device(h, step.rows, n_cases, on) : PSM_OK;
@@ -81,8 +81,9 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
     if (!rs && feat) rs = features_device(h, step.feat.vel, n_cases, step.feat.grid, on);
     if (!rs && deltas) rs = deltas_pack_device(h, step.deltas, n_cases, on);
     if (!rs && gradp) rs = gradp_pack_device(h, step.gradp, n_cases, on);
-    if (!rs && (deltas || gradp)) {
-      // An evaluator's frames are solved ONE BY ONE, each as the single case Evaluation.timeStep / EvaluationGradP.timeStep solves on
+    if (!rs && chapter4) rs = chapter4_pack_device(h, step.chapter4, n_cases, on);
+    if (!rs && (deltas || gradp || chapter4)) {
+      // An evaluator's frames are solved ONE BY ONE, each as the single case Evaluation.timeStep / EvaluationGradP.timeStep / EvaluationChapter4.timeStep solves on
       // its image (with a geometry bound for one case: the 6-launch route with the folded encode), so that a frame's field holds the
       // bits of that call whatever the batch.  deltas: the network output rows of every frame are kept for the block stage, which
       // decodes them again.

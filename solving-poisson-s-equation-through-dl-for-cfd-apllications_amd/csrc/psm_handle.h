@@ -1,5 +1,5 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in sixteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in seventeen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, psm_solve_grid*
@@ -14,6 +14,7 @@
 //   psm_api_errors.cpp      the per-frame error blocks of assembled fields on the device: psm_field_errors_device and the metrics-only frame step psm_poisson_frames_errors* (host arithmetic: psm_errors.cpp)
 //   psm_api_deltas_frames.cpp  the deltas evaluator's frame batch on the device: psm_bind_deltas_frames, the image pack psm_deltas_image_device, the batched block errors psm_block_errors_device and the step psm_deltas_frames*
 //   psm_api_gradp_frames.cpp   the U_to_gradP evaluator's frame batch on the device: psm_bind_gradp_frames, the image / label pack psm_gradp_image_device and the step psm_gradp_frames* (columns -> p -> errors)
+//   psm_api_chapter4_frames.cpp  the Chapter-4 evaluators' frame batch on the device: psm_bind_chapter4_frames, the image / label pack psm_chapter4_image_device and the step psm_chapter4_frames* (columns -> p -> errors)
 //   psm_api_rows.cpp        a frame's dataset rows -> scalars + columns on the device: psm_bind_rows, the stage alone psm_rows_prepare_device and the evaluators' steps behind it, psm_deltas_rows* / psm_poisson_rows* / psm_gradp_rows*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
@@ -188,6 +189,16 @@ struct GradpCall {
   auto tie() const { return std::tie(planes, grid, truth, p); }
 };
 
+// The image / label pack between the mesh -> grid stage and the solve of the Chapter-4 evaluators' frame batch (psm_chapter4_frames*):
+// every pointer is part of the captured launch; the SDF plane and the scales are the binding's (Chapter4Set), which drops these
+// graphs when it goes.
+struct Chapter4Call {
+  const double* planes = nullptr;       // [n_frames][c_in][npix] what the frame stage wrote; nullptr: no pack stage
+  float* grid = nullptr;
+  double* truth = nullptr;
+  auto tie() const { return std::tie(planes, grid, truth); }
+};
+
 // What surrounds ONE solve (solve_device, psm_api_step.cpp), in launch order; every stage keeps its own "absent" value.  A new stage
 // is one member here and one entry in key(): the graph cache compares nothing else, so a stage in the sequence is in the cache key.
 struct StepCall {
@@ -196,17 +207,24 @@ struct StepCall {
   FeatCall feat{};                      // psm_poisson_step*: the two feature launches write the solve's image (vel == nullptr: none)
   DeltasCall deltas{};                  // psm_deltas_frames*: the image pack, the frames solved one by one (planes == nullptr: none)
   GradpCall gradp{};                    // psm_gradp_frames*: likewise, and BEHIND the post-steps the integration with the binding's own tables
+  Chapter4Call chapter4{};              // psm_chapter4_frames*: the image pack, the frames solved one by one; nothing behind the solve
   float* p = nullptr;                   // psm_solve_pressure*: where the bound integration (psm_bind_integration) behind the solve writes p
   PostCall post{};                      // psm_solve_poststeps*: the bound post-steps behind the solve (apply_filter == -1: none)
-  auto key() const { return std::make_tuple(rows.tie(), frames.key(), feat.tie(), deltas.tie(), gradp.tie(), p, post.tie()); }
+  auto key() const { return std::make_tuple(rows.tie(), frames.key(), feat.tie(), deltas.tie(), gradp.tie(), chapter4.tie(), p, post.tie()); }
   const char* fault() const {           // the combinations the sequence does not define (null: defined); no C entry builds one
-    const bool fr = frames.cols, ft = feat.vel, dl = deltas.planes, gp = gradp.planes;
+    const bool fr = frames.cols, ft = feat.vel, dl = deltas.planes, gp = gradp.planes, c4 = chapter4.planes;
     if (rows.rows && (!fr || rows.cols != frames.cols)) return "the rows stage writes the columns the mesh -> grid stage reads: it needs frames on its columns";
     if (dl && gp) return "the deltas and the gradP pack exclude each other";
+    if (c4 && dl) return "the Chapter-4 and the deltas pack exclude each other";
+    if (c4 && gp) return "the Chapter-4 and the gradP pack exclude each other";
+    if (c4 && !fr) return "the Chapter-4 pack reads the planes of the mesh -> grid stage: it needs frames";
+    if (c4 && ft) return "the features and the Chapter-4 pack both write the solve's image";
+    if (c4 && p) return "the Chapter-4 frames solve p itself: no bound integration behind them";
+    if (c4 && post.apply_filter >= 0) return "the Chapter-4 frames have no post-steps: the reference cannot process a filtered field";
     if ((dl || gp) && !fr) return "an image pack reads the planes of the mesh -> grid stage: it needs frames";
     if (ft && (dl || gp)) return "the features and an image pack both write the solve's image";
     if (p && gp) return "the gradP frames integrate with their own tables: not the bound integration as well";
-    if (fr && !ft && !dl && !gp) return "frames alone: nothing reads the planes (features or an image pack)";
+    if (fr && !ft && !dl && !gp && !c4) return "frames alone: nothing reads the planes (features or an image pack)";
     return nullptr;
   }
 };
@@ -372,6 +390,23 @@ struct GradpSet {
   float *h_gradp = nullptr, *h_p = nullptr;      // pinned [n][npix][2], [n][npix]
   double* h_truth = nullptr;            // pinned [n][3][npix]
 };
+
+// Binding of the Chapter-4 evaluators' frame batch (psm_bind_chapter4_frames, behind psm_bind_frames): the simulation's normalised SDF
+// plane, the scales and every buffer a step touches for the bound frame count, so that a step allocates nothing.  DeltasSet without
+// the block stage and the U^2 ring: prediction and label are compared in normalised units.  The columns go through the frame
+// binding's staging.
+struct Chapter4Set {
+  bool ready = false;
+  int n_frames = 0;
+  double max_abs[4] = {1, 1, 1, 1};     // [c_in + 1]: the c_in - 1 input channels, dist, p
+  double* d_sdn = nullptr;              // [npix] nan0(sdfunct) / max_abs_dist in float64: channel c_in - 1 of the image, and the field errors' mask
+  double* d_planes = nullptr;           // [n_frames][c_in][npix] float64 planes of columns 0 .. c_in - 1
+  float *d_grid = nullptr, *d_result = nullptr;   // image [n][npix][c_in], field [n][npix]
+  double* d_truth = nullptr;            // [n][npix]
+  double *d_raw = nullptr, *h_raw = nullptr;      // [n][1][8], device and pinned (host entry)
+  float* h_result = nullptr;            // pinned [n][npix]
+  double* h_truth = nullptr;            // pinned [n][npix]
+};
 }  // namespace psm_impl
 using namespace psm_impl;
 
@@ -415,6 +450,7 @@ struct psm_handle {
   RowsSet rows;                         // the rows stage's staging behind it (psm_bind_rows)
   DeltasSet deltas;                     // the deltas evaluator's frame batch behind it (psm_bind_deltas_frames)
   GradpSet gradp;                       // the U_to_gradP evaluator's frame batch behind it (psm_bind_gradp_frames)
+  Chapter4Set chapter4;                 // the Chapter-4 evaluators' frame batch behind it (psm_bind_chapter4_frames)
   double maxs[4] = {1, 1, 1, 1};
   int normalise_sdf = 0, fill_input = 0;
   double case_maxs[4] = {1, 1, 1, 1}, case_delta = 5e-3, case_wall = 0.05;   // psm_set_case (PM:106-109, 195, 494)
@@ -557,6 +593,7 @@ void feat_free(FeatureSet& s);
 void frames_free(psm_handle* h);
 void deltas_free(psm_handle* h);
 void gradp_free(psm_handle* h);
+void chapter4_free(psm_handle* h);
 void rows_free(psm_handle* h);
 int rows_device(psm_handle* h, const RowsCall& rc, int n_frames, hipStream_t st);
 int frames_state(psm_handle* h);
@@ -594,6 +631,7 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
                  hipStream_t st, hipEvent_t* prof, const StepCall& step = {});
 int deltas_pack_device(psm_handle* h, const DeltasCall& dc, int n_frames, hipStream_t st);
 int gradp_pack_device(psm_handle* h, const GradpCall& gc, int n_frames, hipStream_t st);
+int chapter4_pack_device(psm_handle* h, const Chapter4Call& cc, int n_frames, hipStream_t st);
 // the evaluators' frame steps and the error stages behind them (psm_api_deltas_frames.cpp, psm_api_gradp_frames.cpp); with `rows` the
 // rows stage heads the step, d_cols are its columns, and U2 / out_scale are not read: the finish launch leaves them on the device
 int deltas_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* out_scale, int apply_filter,

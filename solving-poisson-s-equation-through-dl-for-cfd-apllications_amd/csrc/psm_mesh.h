@@ -97,6 +97,21 @@ struct PsmGradpPackArgs {
 };
 hipError_t psm_launch_gradp_pack(const PsmGradpPackArgs& a, hipStream_t st);
 
+// ---- the image / label pack of the Chapter-4 evaluators' frame batch (psm_chapter4_image_device): the float64 planes of columns
+// 0 .. c_in - 1 (M_u: Ux / U, Uy / U, p / U^2; M_fU: f(U) / U^2, p / U^2; NaNs of interpolate_fill kept) -> the solve's c_in-channel
+// image and the float64 truth plane, the statements of Chapter4/MLP/M_u/Evaluation/Eval_dual_Dense_onlycil.py:215-225 (M_fU/Evaluation/
+// Eval.py:213-223) per pixel.  One launch, the frame is launch dimension y; (c_in + 1) * 8 bytes in and c_in * 4 + 8 out per pixel.
+struct PsmChapter4PackArgs {
+  const double* planes;         // [n_frames][c_in][npix]: the c_in - 1 input channels, then the pressure label
+  const double* sdn;            // [npix] nan0(sdfunct) / max_abs_dist of the simulation, shared by the frames (float64, made at bind)
+  float* grid;                  // [n_frames][npix][c_in] = ((float)(nan0(v_c) / m[c]) for c < c_in - 1, (float)sdn)
+  double* truth;                // [n_frames][npix] = nan0(v_label) / m_p; nullptr: not stored
+  int64_t npix;
+  double m[2], m_p;             // max_abs of the input channels (m[1] is not read at c_in == 2) and of the pressure
+  int c_in, n_frames;           // c_in: 2 or 3, the image width
+};
+hipError_t psm_launch_chapter4_pack(const PsmChapter4PackArgs& a, hipStream_t st);
+
 // ---- the mesh ends for a case batch (psm_set_geometry_cases): K meshes on one planned grid, the case is launch dimension y.
 // Cell-side arrays are the cases' concatenated ([sum n_i, ...], case i at rows cell_off[i] .. cell_off[i + 1]), grid-side tables
 // are [K][n_grid, ...]; vertex indices are case-local as the caller gave them (the kernels add the case's offset).

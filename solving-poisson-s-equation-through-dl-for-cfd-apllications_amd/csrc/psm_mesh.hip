@@ -462,6 +462,65 @@ hipError_t psm_launch_gradp_pack(const PsmGradpPackArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// The image / label pack of the Chapter-4 evaluators' frame batch (PsmChapter4PackArgs in psm_mesh.h): what the two timeStep bodies
+// do on the host between the interpolation and the solve, per pixel and in their order -- NaN -> 0, the division by the channel's
+// max_abs in float64, then the float32 cast of the solve's entry (M_u :215-225, M_fU :213-223); the pressure label stays float64.
+// One IEEE division per value and no addition: nothing to contract, the outputs hold the bits of the NumPy statements.  C_IN is the
+// image width (M_u 3, M_fU 2), a template parameter so that the 4 * C_IN image floats of a thread go out as C_IN 16-byte stores.
+// The access pattern is the deltas pack's: frame blockIdx.y, a thread takes 4 consecutive pixels of every plane, 16-byte accesses
+// where the frame's plane or image starts 16-byte aligned, one access per element otherwise and in the tail.
+template <int C_IN>
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmChapter4PackArgs a) {
+  const int64_t frame = blockIdx.y;
+  const int64_t pix = (int64_t)blockIdx.x * PSM_DELTAS_PACK_SPAN + threadIdx.x * 4;
+  if (pix >= a.npix) return;
+  const int n = (int)min((int64_t)4, a.npix - pix);
+  const double* pl = a.planes + frame * C_IN * a.npix;
+  float g[4 * C_IN];
+#pragma unroll
+  for (int c = 0; c < C_IN - 1; ++c) {
+    const double* src = pl + c * a.npix;
+    double v[4];
+    pack_load4(src, pix, n, n == 4 && pack_aligned(src), v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[C_IN * e + c] = (float)((v[e] != v[e] ? 0.0 : v[e]) / a.m[c]);
+  }
+  {
+    double sd[4];
+    pack_load4(a.sdn, pix, n, n == 4 && pack_aligned(a.sdn), sd);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[C_IN * e + C_IN - 1] = (float)sd[e];
+  }
+  float* go = a.grid + (frame * a.npix + pix) * C_IN;
+  if (n == 4 && pack_aligned(go)) {
+#pragma unroll
+    for (int q = 0; q < C_IN; ++q) reinterpret_cast<psm_pack_f4*>(go)[q] = psm_pack_f4{g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]};
+  } else {
+    for (int e = 0; e < C_IN * n; ++e) go[e] = g[e];
+  }
+  if (!a.truth) return;
+  const double* src = pl + (C_IN - 1) * a.npix;
+  double v[4], t[4];
+  pack_load4(src, pix, n, n == 4 && pack_aligned(src), v);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) t[e] = (v[e] != v[e] ? 0.0 : v[e]) / a.m_p;
+  double* to = a.truth + frame * a.npix + pix;
+  if (n == 4 && pack_aligned(to)) {
+    reinterpret_cast<psm_pack_d2*>(to)[0] = psm_pack_d2{t[0], t[1]};
+    reinterpret_cast<psm_pack_d2*>(to)[1] = psm_pack_d2{t[2], t[3]};
+  } else {
+    for (int e = 0; e < n; ++e) to[e] = t[e];
+  }
+}
+
+hipError_t psm_launch_chapter4_pack(const PsmChapter4PackArgs& a, hipStream_t st) {
+  if (a.n_frames < 1 || a.npix < 1 || !a.planes || !a.sdn || !a.grid || (a.c_in != 2 && a.c_in != 3)) return hipErrorInvalidValue;
+  const dim3 wgs((unsigned)((a.npix + PSM_DELTAS_PACK_SPAN - 1) / PSM_DELTAS_PACK_SPAN), (unsigned)a.n_frames);
+  if (a.c_in == 3) hipLaunchKernelGGL(static_cast<void (*)(PsmChapter4PackArgs)>(psm_to_grid_kernel<3>), wgs, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(static_cast<void (*)(PsmChapter4PackArgs)>(psm_to_grid_kernel<2>), wgs, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(psm_to_mesh_kernel, dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
   return hipGetLastError();

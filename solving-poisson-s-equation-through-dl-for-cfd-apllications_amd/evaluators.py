@@ -31,20 +31,24 @@ def _grid_from_blocks(x_array: np.ndarray, blocks: np.ndarray, ny: int, nx: int)
 
 
 def load_artifacts(variant, model_path, directory, var_p, var_in, max_num_PC, standardization_method, shape, overlap,
-                   c_in: int = 3, sdf_ch: int = 2):
+                   c_in: int = 3, sdf_ch: int = 2, pca_stems=("ipca_input", "ipca_p"), pc_rule=None):
     """What the reference's ``Evaluation.__init__`` loads (SM_call.py:70-87; Eval_dual_Dense_onlycil.py:51-66):
     ``maxs`` (+ ``maxs_PCA`` for 'max_abs'), the Keras network of ``model_path`` (Dense stack, HDF5), the two
     pickled PCA objects (``ipca_input``, ``ipca_p``: ``.pkl`` like the reference or the ``.npz`` export) with the
     component-count rule of :86-87, and the scaler file of the chosen standardisation (:507-519).
+    ``pca_stems``: the file stems of the input and the output PCA; ``pc_rule(explained_variance_ratio, var, side)`` with side 'in' /
+    'p': another component-count rule (the Chapter-4 evaluators: ``ipca_*_more``, ``formats.select_num_pc_chapter4``).
     -> (SurrogateModel, maxs)."""
     from . import formats
     maxs = formats.read_maxs(os.path.join(directory, "maxs"))
     convs, weights = formats.read_keras_conv1d_head(model_path)     # Dense stack, or the conv1D_PCA head (NNs.py:75-124)
     attention = formats.read_keras_attention(model_path)            # densePCA_attention (NNs.py:40-72), else None
-    pin = formats.load_pca(formats.find_pca(directory, "ipca_input"))
-    pout = formats.load_pca(formats.find_pca(directory, "ipca_p"))
-    pc_p = formats.select_num_pc(pout.explained_variance_ratio_, var_p, max_num_PC)
-    pc_in = formats.select_num_pc(pin.explained_variance_ratio_, var_in, max_num_PC)
+    pin = formats.load_pca(formats.find_pca(directory, pca_stems[0]))
+    pout = formats.load_pca(formats.find_pca(directory, pca_stems[1]))
+    if pc_rule is None:
+        pc_rule = lambda evr, var, side: formats.select_num_pc(evr, var, max_num_PC)
+    pc_p = pc_rule(pout.explained_variance_ratio_, var_p, "p")
+    pc_in = pc_rule(pin.explained_variance_ratio_, var_in, "in")
     c_out = 2 if variant == "gradp" else 1
     if pin.components_.shape[1] != shape * shape * c_in or pout.components_.shape[1] != shape * shape * c_out:
         raise ValueError("PCA artefacts do not match the block shape / channel count")
@@ -156,11 +160,15 @@ class Evaluation:
         self.grid_shape_y, self.grid_shape_x = t.ny, t.nx
         self.vert, self.weights, self.indices, self.sdfunct = t.vtx_m2g, t.wts_m2g, t.indices, t.sdfunct[:, :, None]
         sur = self._surrogate(t.ny, t.nx)
-        mx = np.asarray(self.maxs if self.maxs is not None else (1.0, 1.0, 1.0, 1.0), np.float64)[:4]
+        mx = self._mesh_maxs()
         sur.set_mesh(t.vtx_m2g, t.wts_m2g, t.indices, t.sdfunct, self.indice, mx)
         self.tables = t
         self._bind_simulation_geometry(sur, t.sdfunct, float(mx[2]))
         return 0
+
+    def _mesh_maxs(self) -> np.ndarray:
+        """The four scales the mesh takes: (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p)."""
+        return np.asarray(self.maxs if self.maxs is not None else (1.0, 1.0, 1.0, 1.0), np.float64)[:4]
 
     def _bind_simulation_geometry(self, sur, sdfunct: np.ndarray, max_abs_dist: float):
         """computeOnlyOnce fixes the obstacle for every timeStep of the simulation: bind its flow-cell pattern (the SDF
@@ -902,3 +910,204 @@ class EvaluationGradP(Evaluation):
         if apply_filter:                                          # Eval_dual_Dense_onlycil.py:366-367 (returns the 2-D array)
             return sur.gaussian_filter(res, (10, 10))
         return res[None, :, :, None]
+
+
+class EvaluationChapter4(Evaluation):
+    """The ``Evaluation`` of the two Chapter-4 thesis evaluators on the GPU path, chosen by ``inputs``:
+
+    * ``'M_u'``  -- Thesis_Work/Chapter4/MLP/M_u/Evaluation/Eval_dual_Dense_onlycil.py: (Ux, Uy, SDF) -> p; ``maxs`` = (max_abs_Ux,
+      max_abs_Uy, max_abs_dist, max_abs_p);
+    * ``'M_fU'`` -- Thesis_Work/Chapter4/MLP/M_fU/Evaluation/Eval.py: (f(U), SDF) -> p, f(U) = dataset column 5; ``maxs`` =
+      (max_abs_fU, max_abs_dist, max_abs_p).
+
+    Both read ``maxs``, ``maxs_PCA``, ``ipca_input_more.pkl`` and ``ipca_p_more.pkl`` from the working directory (``artifact_dir``),
+    scale the PCA coefficients by the two ``maxs_PCA`` values, and count components by ``formats.select_num_pc_chapter4``.
+    Prediction and label are compared in normalised units: no dimensional scale enters (M_u :457-476).
+
+    The M_u file assigns ``self.var_p = var_in`` and never sets ``self.var_in``, which it then reads (:38-39, :56): as written its
+    constructor raises.  ``var_in`` is taken here the way the M_fU file takes it.
+    ``apply_filter=True`` is rejected: both files replace ``result_array`` by a 2-D array in the filter branch (M_u :421) and then
+    index it with four subscripts (:457-458), so the reference itself cannot process that input."""
+    variant = "chapter5"
+
+    def __init__(self, delta, shape, avance, var_p, var_in, hdf5_path, model_directory, inputs: str = "M_u",
+                 model: SurrogateModel = None, device: int = 0, artifact_dir: str = None, max_frames: int = None):
+        if inputs not in ("M_u", "M_fU"):
+            raise ValueError("inputs is 'M_u' or 'M_fU'")
+        from . import formats
+        self.inputs = inputs
+        self.c_in_expected = 3 if inputs == "M_u" else 2
+        self.sdf_ch_expected = self.c_in_expected - 1
+        maxs = None
+        if model is None:
+            model, maxs = load_artifacts(self.variant, model_directory, artifact_dir or os.getcwd(), var_p, var_in, None, "max_abs",
+                                         shape, avance, self.c_in_expected, self.sdf_ch_expected,
+                                         pca_stems=("ipca_input_more", "ipca_p_more"),
+                                         pc_rule=lambda evr, var, side: formats.select_num_pc_chapter4(evr, var, inputs, side))
+        if model.variant != self.variant or model.c_in != self.c_in_expected or model.sdf_ch != self.sdf_ch_expected or model.c_out != 1:
+            raise ValueError(f"{inputs} takes a chapter5-variant model with {self.c_in_expected} input channels, the SDF last, and 1 output channel")
+        super().__init__(delta, shape, avance, var_p, var_in, hdf5_path, model_directory, None, "max_abs", model, device,
+                         artifact_dir, max_frames)
+        self.maxs = maxs
+        if maxs is not None and len(maxs) < self.c_in_expected + 1:
+            raise ValueError(f"maxs must hold {self.c_in_expected + 1} values for {inputs}")
+        self.avance = avance
+        self.hdf5_path = hdf5_path
+
+    def _max_abs(self) -> list:
+        """[c_in + 1]: the scales of the c_in - 1 input channels, of the distance and of p (M_u :45, M_fU :45)."""
+        n = self.c_in_expected + 1
+        return [float(v) for v in (self.maxs[:n] if self.maxs is not None else (1.0,) * n)]
+
+    def _mesh_maxs(self) -> np.ndarray:
+        mx = self._max_abs()
+        return np.asarray([mx[0], mx[1] if self.inputs == "M_u" else 1.0, mx[-2], mx[-1]], np.float64)
+
+    def computeOnlyOnce(self, sim):
+        """M_u :105-189 (M_fU likewise): 2-digit bounds (:115-119), every 2nd boundary point (:150-151), the pressure column
+        decides interpolability (:174-178), no IDW fallback.  Returns 0."""
+        from . import formats
+        from .geometry import build_geometry_evaluator
+        data, top_b, obst_b = formats.read_dataset(self.hdf5_path, sim, 0)
+        self.indice = formats.first_index(data[0, 0, :, 0], formats.PAD_VALUE)
+        cells = np.asarray(data[0, 0, :self.indice], np.float64)
+        top = np.asarray(top_b[0, 0, :formats.first_index(top_b[0, 0, :, 0], formats.PAD_VALUE)], np.float64)
+        obst = np.asarray(obst_b[0, 0, :formats.first_index(obst_b[0, 0, :, 0], formats.PAD_VALUE)], np.float64)
+        return self._set_tables(build_geometry_evaluator(cells[:, 3:5], cells[:, 2], top, obst, self.delta, every=2, round_digits=2,
+                                                         idw_fallback=False))
+
+    def _frame_rows(self, sim, time) -> np.ndarray:
+        from . import formats
+        return formats.read_dataset(self.hdf5_path, sim, time)[0][0, 0, :self.indice]
+
+    def _frame_prepare(self, d: np.ndarray, full: bool = True):
+        """-> (U_max_norm as the float32 the statements give, the c_in cell columns float64): every frame is relevant."""
+        Ux, Uy, p = d[:, 0:1], d[:, 1:2], d[:, 2:3]
+        U_max_norm = np.max(np.sqrt(np.square(Ux) + np.square(Uy)))                       # M_u :203
+        if self.inputs == "M_u":
+            cols = [Ux / U_max_norm, Uy / U_max_norm, p / pow(U_max_norm, 2.0)]           # M_u :205-207
+        else:
+            cols = [d[:, 5:6] / pow(U_max_norm, 2.0), p / pow(U_max_norm, 2.0)]           # M_fU :203-208
+        return U_max_norm, np.concatenate(cols, axis=1).astype(np.float64)
+
+    @staticmethod
+    def _no_filter(apply_filter):
+        if apply_filter:
+            raise ValueError("apply_filter=True: the reference replaces result_array by a 2-D array (M_u :421) and then indexes it "
+                             "with four subscripts (:457-458); it cannot process that input, and neither does this evaluator")
+
+    def timeStep(self, sim, time, save_plots=False, show_plots=False, apply_filter=False):
+        """M_u :193-479 (M_fU :193-477) without plots and prints: frame (sim, time) -> the assembled normalised pressure image
+        [Ny,Nx].  Kept: ``grid`` (c_in + 1 channels, normalised), ``cfd_results`` (its label channel), ``no_flow_bool``,
+        ``U_max_norm``, ``last_metrics['p']``; the frame's two values are appended to ``pred_minus_true`` /
+        ``pred_minus_true_squared``."""
+        self._no_filter(apply_filter)
+        if getattr(self, "tables", None) is None:
+            raise RuntimeError("computeOnlyOnce has not been called")
+        U_max_norm, cols = self._frame_prepare(self._frame_rows(sim, time))
+        g = self._mesh_to_grid(cols)                                                      # :209-218, NaNs kept
+        c, mx = self.c_in_expected, self._max_abs()
+        grid = np.zeros((self.grid_shape_y, self.grid_shape_x, c + 1))
+        grid[..., :c - 1] = g[..., :c - 1]
+        grid[..., c - 1] = self.sdfunct[..., 0]
+        grid[..., c] = g[..., c - 1]
+        grid[np.isnan(grid)] = 0                                                          # :220
+        for ch in range(c + 1):
+            grid[..., ch] /= mx[ch]                                                       # :222-225
+        self.grid = grid
+        self.U_max_norm = float(U_max_norm)
+        res = self._surrogate(*grid.shape[:2]).solve(grid[..., :c])[0, :, :, 0]           # :230-414
+        self.cfd_results = grid[..., c]
+        self.no_flow_bool = grid[..., c - 1] == 0
+        self._record_p(error_metrics(res, self.cfd_results, self.no_flow_bool))           # :457-477
+        return res
+
+    def _record_p(self, m: dict) -> dict:
+        self._record_metrics(m, "", "Error in p (normalised)")
+        self.last_metrics["p"] = self.last_metrics.pop("delta_p")
+        return m
+
+    @property
+    def FRAME_COLUMNS(self):        # the c_in - 1 input columns and the label column p / U^2
+        return self.c_in_expected
+
+    def _bind_frames(self, sur, apply_filter: bool):
+        """What timeSteps needs on the handle, once per computeOnlyOnce (whose new plan drops them): the frame staging and the
+        Chapter-4 binding with the simulation's SDF plane and scales."""
+        if getattr(self, "_frames_tables", None) is self.tables and sur._frames_bound and sur._chapter4_bound:
+            return
+        sur.bind_frames(self.max_frames, self.FRAME_COLUMNS)
+        sur.bind_chapter4_frames(self.sdfunct[..., 0], self._max_abs())
+        self._frames_tables = self.tables
+
+    def timeSteps(self, sim, times, apply_filter=False, fields=True, device_prep=False):
+        """``timeStep`` for several frames of one simulation, sent ``max_frames`` at a time as ONE call each (``chapter4_frames``:
+        cell columns -> planes -> image, truth -> solve -> the error sums on the device).  The per-frame host scalar and columns
+        are those of ``timeStep``; ``pred_minus_true``, ``pred_minus_true_squared`` and ``last_metrics['p']`` are filled in frame
+        order.  Returns the list of normalised p images; afterwards ``cfd_results``, ``no_flow_bool`` and ``U_max_norm`` hold what
+        ``timeStep`` leaves on the last frame (``grid`` is not produced).
+        ``fields=False``: a metrics-only sweep -- nothing but the sums comes back (8 doubles per frame), the metrics are taken
+        from them, the return is one ``{'p': metrics}`` dict per frame and ``cfd_results`` is None.
+        ``device_prep=True`` raises: the rows stage takes rows 8 to 16 wide, Chapter-4 rows are 6 wide."""
+        self._no_filter(apply_filter)
+        if device_prep:
+            raise ValueError("device_prep=True: the rows stage (bind_rows) takes rows 8 to 16 columns wide; Chapter-4 dataset rows are 6 wide")
+        return self._time_steps(sim, times, apply_filter, fields, device_prep)
+
+    def _frames_start(self):
+        sd = np.nan_to_num(np.asarray(self.sdfunct[..., 0], np.float64), nan=0.0) / self._max_abs()[-2]
+        self.no_flow_bool = sd == 0
+
+    def _frames_end(self, fields: bool):
+        if not fields:
+            self.cfd_results = None
+
+    def _host_call(self, sur, cols, Us, apply_filter, fields):
+        return sur.chapter4_frames(cols, want_result=fields, want_truth=fields)
+
+    def _record_frame(self, sur, outs, j, slot, U, fields):
+        """One frame of a call's (result, truth, raw) -> its p image, or its metric block for a metrics-only sweep."""
+        res, truth, raw = outs
+        if not fields:
+            return {"p": self._record_p(sur.metrics_from_sums(raw[j, 0]))}
+        self.cfd_results = truth[j]
+        self._record_p(error_metrics(res[j], truth[j], self.no_flow_bool))
+        return res[j]
+
+
+def main_chapter4(delta=5e-3, model_directory="model_first_.h5", shape=128, avance=None, var_p=0.95, var_in=0.95,
+                  hdf5_path="dataset_unsteadyCil_fu_bound.hdf5", inputs="M_u", sims=(0, 3, 6, 8), n_ts=10, apply_filter=False,
+                  device: int = 0, artifact_dir: str = None, frames_per_call: int = 1, fields: bool = True):
+    """``main`` of the two Chapter-4 evaluators (M_u :483-533, M_fU :481-531) with their hard-coded inputs as defaults
+    (``avance = int(0.75 * shape)``, simulations 0, 3, 6, 8, ten time steps; the M_u file passes ``var_in = 0.995``):
+    computeOnlyOnce + timeStep per frame, then BIAS / RMSE / STDE [%] from the accumulated per-frame values.  The reference
+    prints them once, after the last simulation (:526-533); here they are printed and returned after every simulation, over
+    everything accumulated so far, so that the last entry is the reference's.  Plots are not produced.
+    ``frames_per_call`` > 1: the frames of a simulation go through ``EvaluationChapter4.timeSteps``, that many per call, instead of
+    one ``timeStep`` each.  ``fields=False``: the same summary from ``timeSteps(..., fields=False)``, whose error sums are taken on
+    the device: no field is copied back.  With the defaults the loop is the per-frame one."""
+    EvaluationChapter4._no_filter(apply_filter)
+    if avance is None:
+        avance = int(0.75 * shape)
+    ev = EvaluationChapter4(delta, shape, avance, var_p, var_in, hdf5_path, model_directory, inputs=inputs, device=device,
+                            artifact_dir=artifact_dir, max_frames=frames_per_call)
+    ev.pred_minus_true, ev.pred_minus_true_squared = [], []
+    out = {"sims": [], "frames": []}
+    batched = frames_per_call > 1 or not fields
+    for sim in sims:
+        ev.computeOnlyOnce(sim)
+        for t0 in range(0, n_ts, frames_per_call if batched else 1):
+            chunk = range(t0, min(t0 + (frames_per_call if batched else 1), n_ts))
+            n0 = len(ev.pred_minus_true)
+            if batched:
+                ev.timeSteps(sim, chunk, apply_filter, fields=fields)
+            else:
+                ev.timeStep(sim, t0, False, False, apply_filter)
+            for time, b, s in zip(chunk, ev.pred_minus_true[n0:], ev.pred_minus_true_squared[n0:]):
+                out["frames"].append(dict(sim=sim, time=time, mean_err=b, mean_sq_err=s))
+        s = _summary(ev.pred_minus_true, ev.pred_minus_true_squared)
+        print("BIAS for the sim: " + str(s["BIAS"]))
+        print("RMSE for the sim: " + str(s["RMSE"]))
+        print("STDE for the sim: " + str(s["STDE"]))
+        out["sims"].append(s)
+    return out

@@ -385,6 +385,23 @@ def select_num_pc(explained_variance_ratio: np.ndarray, var: float, max_num_pc: 
     return k if (k > 1 and k <= max_num_pc) else int(max_num_pc)
 
 
+def select_num_pc_chapter4(explained_variance_ratio: np.ndarray, var: float, inputs: str, side: str) -> int:
+    """PC-count rules of the two Chapter-4 evaluators, as the files state them; ``side`` is 'p' (``ipca_p_more``) or 'in'
+    (``ipca_input_more``).  With k = first index whose cumulative ratio exceeds ``var``:
+    'M_u'  (Chapter4/MLP/M_u/Evaluation/Eval_dual_Dense_onlycil.py:55-56): k if k > 1 and the first index above a FIXED threshold
+           -- 0.95 on the p side, 0.995 on the input side -- is at most 64, else 64;
+    'M_fU' (Chapter4/MLP/M_fU/Evaluation/Eval.py:55-56): k if k > 1 and k <= 512, else 512."""
+    if inputs not in ("M_u", "M_fU") or side not in ("p", "in"):
+        raise ValueError("inputs is 'M_u' or 'M_fU', side is 'p' or 'in'")
+    cum = np.cumsum(explained_variance_ratio)
+    k = int(np.argmax(cum > var))
+    if inputs == "M_u":
+        second, cap = int(np.argmax(cum > (0.95 if side == "p" else 0.995))), 64
+    else:
+        second, cap = k, 512
+    return k if (k > 1 and second <= cap) else cap
+
+
 # --------------------------------------------------------------------------
 # padded simulation dataset (utils.read_dataset, utils.py:57-71)
 # --------------------------------------------------------------------------

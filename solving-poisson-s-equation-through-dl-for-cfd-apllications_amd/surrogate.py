@@ -590,8 +590,8 @@ class GridSurrogate:
 
     # The mirrors of the library's bindings (``_*_bound``) are written by the bind / unbind methods and by these two alone.
     def _drop_frame_bindings(self):
-        """What a new frame binding (or none) drops in the library: the frame staging and the three bindings made on top of it."""
-        self._frames_bound = self._deltas_bound = self._gradp_bound = False
+        """What a new frame binding (or none) drops in the library: the frame staging and the four bindings made on top of it."""
+        self._frames_bound = self._deltas_bound = self._gradp_bound = self._chapter4_bound = False
         self._rows_bound = 0
 
     def _drop_mesh_bindings(self):
@@ -688,6 +688,12 @@ class GridSurrogate:
                 np.empty((n, self.ny, self.nx), np.float32) if want_p else None,
                 np.empty((n, 3, self.ny, self.nx), np.float64) if want_truth else None,
                 np.empty((n, 4, len(self.RAW_SUMS)), np.float64))
+
+    def _chapter4_out(self, n: int, want_result: bool, want_truth: bool, want_raw: bool):
+        """-> (result [n,Ny,Nx] float32, truth [n,Ny,Nx] float64, raw [n,1,8] float64)."""
+        return (np.empty((n, self.ny, self.nx), np.float32) if want_result else None,
+                np.empty((n, self.ny, self.nx), np.float64) if want_truth else None,
+                np.empty((n, 1, len(self.RAW_SUMS)), np.float64) if want_raw else None)
 
     def _scalars(self, n: int):
         return np.empty((n, len(self.ROW_SCALARS)), np.float64)
@@ -987,6 +993,76 @@ class GridSurrogate:
                                             _opt(gradp), _opt(p), _opt(truth, C.c_double), _p(raw, C.c_double)))
         return gradp, p, truth, raw
 
+    # -- the frame batch of the two Chapter-4 evaluators on the device: columns -> image, truth -> solve -> one error block
+    _chapter4_bound = False
+
+    def bind_chapter4_frames(self, sdfunct, max_abs):
+        """After ``bind_frames``, on a chapter5-variant model with 2 or 3 input channels, the SDF last, and a one-channel field: the
+        simulation's raw SDF plane ``sdfunct`` [Ny,Nx] float64 (0 in solids, NaNs allowed) and ``max_abs`` [c_in + 1] = the scales of
+        the c_in - 1 input channels, of the distance and of p, each finite and non-zero (M_u: max_abs_Ux, max_abs_Uy, max_abs_dist,
+        max_abs_p; M_fU: max_abs_fU, max_abs_dist, max_abs_p).  Reserves everything a step touches for the frame count bound with
+        ``bind_frames``."""
+        m = self.model
+        if m.variant != "chapter5" or m.c_in not in (2, 3) or m.sdf_ch != m.c_in - 1 or m.c_out != 1:
+            raise ValueError("the Chapter-4 frames take a chapter5-variant model with 2 or 3 input channels, the SDF in the last one, and 1 output channel")
+        if not getattr(self, "_frames_bound", False):
+            raise RuntimeError("bind_frames has not been called")
+        sdf = _f64(sdfunct)
+        if sdf.size != self.ny * self.nx:
+            raise ValueError(f"sdfunct must be [{self.ny},{self.nx}]")
+        mx = _f64(np.asarray(max_abs, np.float64).reshape(-1))
+        if mx.size != m.c_in + 1 or not np.all(np.isfinite(mx)) or np.any(mx == 0):
+            raise ValueError("max_abs must hold c_in + 1 finite non-zero scales: the c_in - 1 input channels, dist, p")
+        self._chapter4_bound = False
+        self._chk(self.lib.psm_bind_chapter4_frames(self.h, _p(sdf, C.c_double), _p(mx, C.c_double)))
+        self._chapter4_bound = True
+
+    def unbind_chapter4_frames(self):
+        self._chapter4_bound = False
+        self._chk(self.lib.psm_unbind_chapter4_frames(self.h))
+
+    def _chapter4_call(self, n_frames, k):
+        """The argument checks the Chapter-4 frame entries share."""
+        if not self._chapter4_bound:
+            raise RuntimeError("bind_chapter4_frames has not been called (bind_frames and a new mesh drop the binding)")
+        if not self.model.c_in <= int(k) <= 16:
+            raise ValueError("frames take c_in..16 columns: the c_in - 1 input channels, then p / U^2; further columns are not stored")
+        if not 1 <= int(n_frames) <= self.max_cases:
+            raise ValueError("n_frames outside [1, max_cases]")
+
+    def chapter4_image_device(self, d_cols: int, n_frames: int, k: int, d_grid: int, d_truth: int = 0, stream: int = 0):
+        """The image stage alone on raw device pointers, asynchronous on ``stream``: ``d_cols`` [n,n_cells,k] float64 -> ``d_grid``
+        [n,Ny,Nx,c_in] float32 and ``d_truth`` [n,Ny*Nx] float64 (the normalised pressure label; 0: not stored), bit for bit the
+        host statements of ``EvaluationChapter4.timeStep``."""
+        self._chapter4_call(n_frames, k)
+        d_cols = self._dev_ptr(d_cols, 8, "d_cols")
+        d_grid, d_truth = self._dev_ptr(d_grid, 4, "d_grid"), self._dev_ptr(d_truth, 8, "d_truth", True)
+        self._chk(self.lib.psm_chapter4_image_device(self.h, C.c_void_p(d_cols), int(n_frames), int(k), C.c_void_p(d_grid),
+                                                     C.c_void_p(d_truth or None), C.c_void_p(stream)))
+
+    def chapter4_frames_device(self, d_cols: int, n_frames: int, k: int, d_result: int = 0, d_truth: int = 0, d_raw: int = 0,
+                               stream: int = 0):
+        """The Chapter-4 evaluators' frames as one graph replay on raw device pointers: ``d_cols`` [n,n_cells,k] float64 -> planes
+        -> image, truth -> one single-case solve per frame -> ``d_result`` [n,Ny*Nx] float32, ``d_truth`` [n,Ny*Nx] float64 (0: the
+        binding's buffers); with ``d_raw`` [n,1,8] float64 the error block behind it: the field against the truth, both normalised."""
+        self._chapter4_call(n_frames, k)
+        d_cols = self._dev_ptr(d_cols, 8, "d_cols")
+        d_result, d_truth = self._dev_ptr(d_result, 4, "d_result", True), self._dev_ptr(d_truth, 8, "d_truth", True)
+        d_raw = self._dev_ptr(d_raw, 8, "d_raw", True)
+        self._chk(self.lib.psm_chapter4_frames_device(self.h, C.c_void_p(d_cols), int(n_frames), int(k), C.c_void_p(d_result or None),
+                                                      C.c_void_p(d_truth or None), C.c_void_p(d_raw or None), C.c_void_p(stream)))
+
+    def chapter4_frames(self, cols: np.ndarray, want_result: bool = True, want_truth: bool = True, want_raw: bool = True):
+        """Host buffers, synchronous: ``cols`` [n,n_cells,k] (or [n_cells,k]) float64 -> (result [n,Ny,Nx] float32, truth [n,Ny,Nx]
+        float64, raw [n,1,8] float64); what is not wanted is None and is not copied back -- a metrics-only sweep
+        (``want_result = want_truth = False``) brings back 8 doubles per frame."""
+        v, n, k, _ = self._host_cols(cols, self._chapter4_call)
+        if not (want_result or want_truth or want_raw):
+            raise ValueError("nothing to return")
+        result, truth, raw = self._chapter4_out(n, want_result, want_truth, want_raw)
+        self._chk(self.lib.psm_chapter4_frames(self.h, _p(v, C.c_double), n, k, _opt(result), _opt(truth, C.c_double), _opt(raw, C.c_double)))
+        return result, truth, raw
+
     # -- a frame's dataset rows (float32, as stored) -> scalars + columns on the device, and the evaluators' steps behind that stage
     _rows_bound = 0                 # the width bound with bind_rows (0: none)
     ROWS_KINDS = {"deltas": (0, 3, 11), "poisson": (1, 8, 11), "gradp": (2, 5, 8)}    # kind -> (PSM_ROWS_*, columns, least width)
@@ -1189,6 +1265,6 @@ def debug_reassemble_host(variant: str, grid: np.ndarray, block_pred: np.ndarray
 
 
 # the reference-shaped operators, one module per seam; imported last: both modules take GridSurrogate and the helpers from here
-from .evaluators import (Evaluation, EvaluationGradP, EvaluationPoisson, _summary, call_SM_main, call_SM_main_Poisson,  # noqa: E402,F401
-                         error_metrics, load_artifacts, main_gradP)
+from .evaluators import (Evaluation, EvaluationChapter4, EvaluationGradP, EvaluationPoisson, _summary, call_SM_main,  # noqa: E402,F401
+                         call_SM_main_Poisson, error_metrics, load_artifacts, main_chapter4, main_gradP)
 from .solver import SolverEnsemble, SolverModule  # noqa: E402,F401
