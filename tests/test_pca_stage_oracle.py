@@ -398,7 +398,7 @@ OUT_OF_SCOPE = {
        for k in ("conv3x3", "conv_stem", "head1x1", "pair32", "pair_stem16", "pair_up16")},
     **{f"psm_{k}_kernel": "mesh <-> grid (test_mesh_path.py)"
        for k in ("interp_to_grid", "to_grid", "to_mesh", "umax", "umax_partial", "stage_cells")},
-    **{f"psm_{k}_kernel": "Poisson features, filter, gradP integration (test_poisson_features.py, test_host_logic.py)"
+    **{f"psm_{k}_kernel": "Poisson features, filter, gradP integration (test_grid_stage_oracle.py: elementwise float64 oracles)"
        for k in ("poisson_grid", "poisson_term", "gauss1d", "integ_rows", "integ_cols", "integ_write")},
     **{f"psm_{k}_kernel": "geometry bind (test_bound_geometry.py)" for k in ("bind_rows", "bind_fold", "bind_own", "bind_copy", "pair_fold")},
     "psm_split_basis_kernel": "x6 basis split, once per handle", "psm_stage_in_kernel": "ring stage-in (test_ring.py)",
