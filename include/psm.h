@@ -379,6 +379,51 @@ int psm_solve_cases_begin(psm_handle* h, const double* cells, double* p_out);
 int psm_solve_cases_end(psm_handle* h);
 /* The case set of the handle: *n_cases and cell_off [n_cases + 1] (either may be NULL).  PSM_ERR_STATE without one. */
 int psm_mesh_cases(const psm_handle* h, int32_t* n_cases, int64_t* cell_off);
+/* ---- the solver boundary in DELTA form: [U(t) - U(t-1)], SDF -> p(t) - p(t-1) ------------
+ * The deltas model (pressureSM_deltas) behind the per-timestep call.  The reference evaluates it offline only and leaves the
+ * dimensionalisation "when calling the SM in the CFD solver" (SM_call.py:548-551); these entries are that call.  A step takes
+ * the cells [n,5] = (Ux, Uy, Cx, Cy, p) of psm_solve, where column 4 is p(t-1), and gives p(t):
+ *   image     interpolate_fill((U(t) - U(t-1)) / U_max) / max_abs, the difference formed per cell in float64 (SM_call.py:389-391,
+ *             418-419, 422-423, 432-443).  U_max = max sqrt(Ux^2 + Uy^2) of the CURRENT cells (:404, :417-419), not of the
+ *             difference: the three ways psm_solve takes it.
+ *   p_out[n]  cells[n][4] + field * max_abs_dp * U_max^2, and cells[n][4] BIT FOR BIT where psm_solve keeps the previous p
+ *             (near-wall cell, negative weight, NaN: PM:494-496 applied to dp).
+ * U(t-1) lives on the device ([sum n_i][2] float64, allocated with the geometry: a step allocates nothing).  The last launch of
+ * a step stores the cells' (Ux, Uy) into it, so the state advances only when the whole step was enqueued, and a step makes
+ * exactly the launches of psm_solve / psm_solve_cases on the same handle and route (bound, general, many-block).
+ * Requirements, checks and error codes are those of psm_solve / psm_solve_cases (c_in == 3, c_out == 1, grid -> mesh tables,
+ * matching cell count, single mesh or case set; the wrong kind is PSM_ERR_STATE).  The variant is not enforced: the layout is
+ * the handle's.  `maxs` of the geometry call are read as (max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp); the deltas
+ * model's convention is normalise_sdf = 1, fill_input = 1 (SM_call.py:441-443), which is the CALLER's to pass to
+ * psm_set_geometry*: psm_init_geometry* keep passing 0, 0 -- a C++ host builds the tables with psm_geometry_build and hands them
+ * to psm_set_geometry with 1, 1.
+ * State: psm_delta_prime sets U(t-1) := cells[:,0:2] (no other column is read), psm_delta_reset forgets it and zeroes `steps`,
+ * psm_delta_state reports *primed (0 / 1) and *steps, the delta steps taken since the state was last empty (either may be NULL).
+ * A step on a state that is not primed is the PRIMING step: PSM_OK, p_out = cells[:,4] bit for bit, U(t-1) := cells[:,0:2],
+ * `steps` not incremented, and the network does not run (its output for a zero image is not zero -- PCA means, biases -- so
+ * "dU = 0" through the chain would move p): a solver's first call never aborts it.  Whatever drops the geometry or the case set
+ * drops the state (a new psm_set_geometry*, psm_plan_grid, a model setter): psm_delta_state then reports primed = 0.
+ * One step in flight per handle across both kinds: a delta begin while a psm_solve_begin is in flight, or the reverse, is
+ * PSM_ERR_STATE, and either end completes the step that is in flight.  psm_solve* on the same handle neither reads nor moves
+ * the state.  Registered buffers (psm_pin_buffers): the DMA-copy form, p stored straight into the registered output where
+ * psm_solve does that; the one-kernel PCIe staging route of psm_solve is NOT taken by the delta entries.
+ * NOT applied: the evaluator's "irrelevant time step" rule (SM_call.py:407-415) -- bookkeeping of its error metrics, no part of
+ * the model -- and the Gaussian filter / dU weighting of assemble_prediction (psm_bind_poststeps has them). */
+int psm_delta_prime(psm_handle* h, const double* cells, int64_t n);
+int psm_delta_reset(psm_handle* h);
+int psm_delta_state(const psm_handle* h, int32_t* primed, int64_t* steps);
+int psm_solve_delta(psm_handle* h, const double* cells, int64_t n, int32_t rank, double* p_out);
+int psm_solve_delta_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank, double* p_out);
+int psm_solve_delta_end(psm_handle* h);
+/* The same for the case set of psm_set_geometry_cases, cell-side arrays concatenated in case order as for psm_solve_cases:
+ * cells [sum n_i, 5] -> p [sum n_i]; one state for the set (all cases are primed and advance together).  _device: device
+ * pointers (8-byte aligned), asynchronous on `stream` (NULL: the handle's), copies nothing; its priming step is one launch.
+ * With n_cases == 1 every bit of p is psm_solve_delta's. */
+int psm_delta_prime_cases(psm_handle* h, const double* cells);
+int psm_solve_cases_delta_device(psm_handle* h, const double* d_cells, double* d_p, void* stream);
+int psm_solve_cases_delta(psm_handle* h, const double* cells, double* p_out);
+int psm_solve_cases_delta_begin(psm_handle* h, const double* cells, double* p_out);
+int psm_solve_cases_delta_end(psm_handle* h);
 /* Generic mesh -> grid step of the evaluators (interpolate_fill + scatter, SM_call.py:419-436,
  * pressureSM_Poisson/SM_call.py:580-600): values [n_cells, k] float64 row-major (k columns of cell
  * data) -> grid_out [ny*nx, k] float64 holding, per image cell, the interpolated value of the grid

@@ -116,6 +116,17 @@ SIGNATURES = {
     "psm_solve_cases_begin": (C.c_int, [_hp, _f64p, _f64p]),
     "psm_solve_cases_end": (C.c_int, [_hp]),
     "psm_mesh_cases": (C.c_int, [_hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "psm_delta_prime": (C.c_int, [_hp, _f64p, C.c_int64]),
+    "psm_delta_reset": (C.c_int, [_hp]),
+    "psm_delta_state": (C.c_int, [_hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "psm_solve_delta": (C.c_int, [_hp, _f64p, C.c_int64, C.c_int32, _f64p]),
+    "psm_solve_delta_begin": (C.c_int, [_hp, _f64p, C.c_int64, C.c_int32, _f64p]),
+    "psm_solve_delta_end": (C.c_int, [_hp]),
+    "psm_delta_prime_cases": (C.c_int, [_hp, _f64p]),
+    "psm_solve_cases_delta_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_solve_cases_delta": (C.c_int, [_hp, _f64p, _f64p]),
+    "psm_solve_cases_delta_begin": (C.c_int, [_hp, _f64p, _f64p]),
+    "psm_solve_cases_delta_end": (C.c_int, [_hp]),
     "psm_poisson_features": (C.c_int, [_hp, _f64p, _f64p, _f64p, _f64p, _f64p, C.c_int32, C.c_int32, _f64p, _f32p]),
     "psm_pin_buffers": (C.c_int, [_hp, _f64p, _f64p]),
     "psm_unpin_buffers": (C.c_int, [_hp]),

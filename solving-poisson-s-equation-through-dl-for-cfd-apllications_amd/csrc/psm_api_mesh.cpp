@@ -58,7 +58,7 @@ static int mesh_sequence(psm_handle* h, int64_t n, hipStream_t st) {
 
 // ---- the case set of psm_set_geometry_cases -----------------------------------------------------------------------
 // state checks shared by the step entries
-static int cases_check(psm_handle* h) {
+int cases_check(psm_handle* h) {
   if (h->have_geometry && !h->mcs.ready)
     return fail(h, PSM_ERR_STATE, "the handle holds the single mesh of psm_set_geometry: psm_solve_cases* needs a case set (psm_set_geometry_cases)");
   if (!h->mcs.ready || !h->planned)
@@ -67,18 +67,28 @@ static int cases_check(psm_handle* h) {
 }
 
 // One step of the case set, a linear chain on `st`: U_max partials, to_grid, the batched solve, to_mesh.  Plain launches (like
-// psm_solve; the solve inside replays its graph under PSM_GRAPH=1); copies nothing.
-static int cases_sequence(psm_handle* h, const double* d_cells, double* d_p, hipStream_t st) {
-  PsmMeshCasesArgs a = h->mcs.args;
+// psm_solve; the solve inside replays its graph under PSM_GRAPH=1); copies nothing.  `delta`: the two ends in their delta form on
+// U(t-1); a state that is not primed gets the priming step, the last launch alone.  The state's host flags move once all is enqueued.
+static int cases_sequence(psm_handle* h, const double* d_cells, double* d_p, hipStream_t st, bool delta) {
+  PsmDeltaCasesArgs d{h->mcs.args, h->delta.d_u_prev, delta && !h->delta.primed};
+  PsmMeshCasesArgs& a = d.c;
   a.cells = d_cells; a.p_out = d_p;
-  HIPCHK(h, psm_launch_umax_cases(a, st));
-  HIPCHK(h, psm_launch_to_grid_cases(a, st));
-  h->in_mesh_solve = true;
-  const int rc = solve_device(h, h->d_grid_stage, h->mcs.n_cases, nullptr, h->d_fields_stage, st, nullptr);
-  h->in_mesh_solve = false;
-  if (rc) return rc;
-  HIPCHK(h, psm_launch_to_mesh_cases(a, st));
+  if (!d.prime) {
+    HIPCHK(h, psm_launch_umax_cases(a, st));
+    HIPCHK(h, delta ? psm_launch_to_grid_cases_delta(d, st) : psm_launch_to_grid_cases(a, st));
+    h->in_mesh_solve = true;
+    const int rc = solve_device(h, h->d_grid_stage, h->mcs.n_cases, nullptr, h->d_fields_stage, st, nullptr);
+    h->in_mesh_solve = false;
+    if (rc) return rc;
+  }
+  HIPCHK(h, delta ? psm_launch_to_mesh_cases_delta(d, st) : psm_launch_to_mesh_cases(a, st));
+  if (delta) { h->delta.steps += h->delta.primed; h->delta.primed = true; }
   return PSM_OK;
+}
+
+void delta_drop(psm_handle* h) {
+  dev_free(h->delta.d_u_prev);
+  h->delta.primed = false; h->delta.steps = 0;
 }
 
 }  // namespace psm_impl
@@ -107,7 +117,8 @@ int psm_set_geometry(psm_handle* h, int64_t n_cells, int32_t ny, int32_t nx, con
   MeshSingle& m = h->mesh;
   // all-or-nothing from here on: a failure leaves no geometry
   if ((rc = mesh_tables_upload(h, m.t, t)) || (rc = dev_alloc(h, &m.d_cells, (size_t)n_cells * 5)) || (rc = dev_alloc(h, &m.d_p, (size_t)n_cells)) ||
-      (rc = dev_alloc(h, &m.d_umax, (size_t)1)) || (rc = dev_alloc(h, &m.d_umax_part, (size_t)256))) { free_geometry(h); return rc; }
+      (rc = dev_alloc(h, &m.d_umax, (size_t)1)) || (rc = dev_alloc(h, &m.d_umax_part, (size_t)256)) ||
+      (rc = dev_alloc(h, &h->delta.d_u_prev, (size_t)n_cells * 2))) { free_geometry(h); return rc; }
   hipError_t e = hipSuccess;
   if ((e = hipHostMalloc((void**)&m.h_cells, (size_t)n_cells * 5 * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
       (e = hipHostMalloc((void**)&m.h_p, (size_t)n_cells * sizeof(double), hipHostMallocDefault)) != hipSuccess) {
@@ -165,7 +176,12 @@ int psm_init_geometry(psm_handle* h, const double* cells, int64_t n, const doubl
 
 int psm_solve_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank, double* p_out) {
   (void)rank;
-  if (!h) return PSM_ERR_ARG;
+  return h ? mesh_step_begin(h, cells, n, p_out, false) : PSM_ERR_ARG;
+}
+
+}  // extern "C"
+
+int psm_impl::mesh_step_begin(psm_handle* h, const double* cells, int64_t n, double* p_out, bool delta) {
   if (h->mesh.inflight) return fail(h, PSM_ERR_STATE, "a psm_solve_begin is already in flight on this handle: call psm_solve_end first");
   if (h->mcs.ready) return fail(h, PSM_ERR_STATE, "the handle holds the case set of psm_set_geometry_cases: psm_solve needs the single mesh of psm_set_geometry (use psm_solve_cases*)");
   if (!h->have_geometry || !h->planned)
@@ -186,7 +202,7 @@ int psm_solve_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank,
   // plain launches (measured default)
   static const int mesh_mode = getenv("PSM_MESH_GRAPH") ? atoi(getenv("PSM_MESH_GRAPH")) : 2;
   static const int64_t stage_max = getenv("PSM_MESH_STAGE_MAX") ? atoll(getenv("PSM_MESH_STAGE_MAX")) : PSM_MESH_STAGE_MAX_DEFAULT;
-  if (mesh_mode != 0 && h->timed_kernel < 0 && n <= stage_max && cells == m.pinned_cells && m.pinned_cells_dev && p_out == m.pinned_p && m.pinned_p_dev) {
+  if (!delta && mesh_mode != 0 && h->timed_kernel < 0 && n <= stage_max && cells == m.pinned_cells && m.pinned_cells_dev && p_out == m.pinned_p && m.pinned_p_dev) {
     h->last_cases = 1;
     if (mesh_mode == 2) {
       int rc = mesh_sequence(h, n, st);
@@ -217,11 +233,14 @@ int psm_solve_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank,
   // Large meshes (the host pass would take longer than the copy it hides under): parallel device reduction, whose
   // per-workgroup maxima every psm_to_grid workgroup folds itself.
   static const bool dev_umax_env = getenv("PSM_DEVICE_UMAX") != nullptr;
-  const bool big = n > 32768;
-  const bool dev_umax = dev_umax_env && !big;
+  const bool prime = delta && !h->delta.primed;           // the priming step: the last launch alone, p = cells[:,4]
+  const bool big = n > 32768 && !prime;
+  const bool dev_umax = dev_umax_env && !big && !prime;
   double umax_val = 0.0;
   int n_partials = 0;
-  if (big) {
+  if (prime) {
+    // nothing is scaled: no U_max
+  } else if (big) {
     HIPCHK(h, psm_launch_umax_partial(m.d_cells, n, m.d_umax_part, &n_partials, st));
   } else if (dev_umax) {
     HIPCHK(h, psm_launch_umax(m.d_cells, n, m.d_umax, st));
@@ -237,14 +256,19 @@ int psm_solve_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank,
   }
   // to_grid must not take the scalar in the `big` case: it folds the partials itself and only then leaves U_max in d_umax, for to_mesh
   const double* d_umax = (dev_umax || big) ? m.d_umax : nullptr;
-  HIPCHK(h, psm_launch_to_grid(to_grid_args(h, dev_umax ? m.d_umax : nullptr, umax_val, n_partials), st));
-  h->in_mesh_solve = true;
-  int rc = solve_device(h, h->d_grid_stage, 1, nullptr, h->d_fields_stage, st, nullptr);
-  h->in_mesh_solve = false;
-  if (rc) return rc;
+  if (!prime) {
+    const PsmToGridArgs ga = to_grid_args(h, dev_umax ? m.d_umax : nullptr, umax_val, n_partials);
+    HIPCHK(h, delta ? psm_launch_to_grid_delta(PsmDeltaGridArgs{ga, h->delta.d_u_prev}, st) : psm_launch_to_grid(ga, st));
+    h->in_mesh_solve = true;
+    int rc = solve_device(h, h->d_grid_stage, 1, nullptr, h->d_fields_stage, st, nullptr);
+    h->in_mesh_solve = false;
+    if (rc) return rc;
+  }
   const bool direct = p_out == m.pinned_p && m.pinned_p_dev != nullptr;
   // direct: 8 bytes per cell over PCIe from the kernel itself, no D2H copy
-  HIPCHK(h, psm_launch_to_mesh(to_mesh_args(h, d_umax, umax_val, direct ? m.pinned_p_dev : m.d_p), st));
+  const PsmToMeshArgs ma = to_mesh_args(h, d_umax, umax_val, direct ? m.pinned_p_dev : m.d_p);
+  HIPCHK(h, delta ? psm_launch_to_mesh_delta(PsmDeltaMeshArgs{ma, h->delta.d_u_prev, prime}, st) : psm_launch_to_mesh(ma, st));
+  if (delta) { h->delta.steps += h->delta.primed; h->delta.primed = true; }   // the whole chain is enqueued: the state has advanced
   if (p_out == m.pinned_p) {
     if (!direct) HIPCHK(h, hipMemcpyAsync(p_out, m.d_p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
     m.copy_out = nullptr;
@@ -256,6 +280,7 @@ int psm_solve_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank,
   return PSM_OK;
 }
 
+extern "C" {
 
 int psm_solve_end(psm_handle* h) {
   if (!h) return PSM_ERR_ARG;
@@ -300,7 +325,8 @@ int psm_set_geometry_cases(psm_handle* h, int32_t n_cases, const int64_t* n_cell
   const size_t total = (size_t)t.total;
   hipError_t e = hipSuccess;
   if ((rc = mesh_tables_upload(h, m.t, t)) || (rc = dev_alloc(h, &m.d_cells, total * 5)) || (rc = dev_alloc(h, &m.d_p, total)) ||
-      (rc = dev_alloc(h, &m.d_umax, (size_t)n_cases)) || (rc = dev_alloc(h, &m.d_umax_part, (size_t)n_cases * n_parts))) { mesh_cases_free(h); return rc; }
+      (rc = dev_alloc(h, &m.d_umax, (size_t)n_cases)) || (rc = dev_alloc(h, &m.d_umax_part, (size_t)n_cases * n_parts)) ||
+      (rc = dev_alloc(h, &h->delta.d_u_prev, total * 2))) { mesh_cases_free(h); return rc; }
   if ((e = hipHostMalloc((void**)&m.h_cells, total * 5 * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
       (e = hipHostMalloc((void**)&m.h_p, total * sizeof(double), hipHostMallocDefault)) != hipSuccess) {
     mesh_cases_free(h);
@@ -373,19 +399,27 @@ int psm_mesh_cases(const psm_handle* h, int32_t* n_cases, int64_t* cell_off) {
 
 
 int psm_solve_cases_device(psm_handle* h, const double* d_cells, double* d_p, void* stream) {
-  if (!h) return PSM_ERR_ARG;
+  return h ? cases_step_device(h, d_cells, d_p, stream, false) : PSM_ERR_ARG;
+}
+
+int psm_solve_cases_begin(psm_handle* h, const double* cells, double* p_out) {
+  return h ? cases_step_begin(h, cells, p_out, false) : PSM_ERR_ARG;
+}
+
+}  // extern "C"
+
+int psm_impl::cases_step_device(psm_handle* h, const double* d_cells, double* d_p, void* stream, bool delta) {
   int rc = cases_check(h);
   if (rc) return rc;
   if (h->mcs.inflight) return fail(h, PSM_ERR_STATE, "a psm_solve_cases_begin is in flight on this handle: call psm_solve_cases_end first");
   if (!d_cells || !d_p) return fail(h, PSM_ERR_ARG, "null buffer");
   if ((reinterpret_cast<uintptr_t>(d_cells) | reinterpret_cast<uintptr_t>(d_p)) & 7) return fail(h, PSM_ERR_ARG, "device buffers must be 8-byte aligned");
   HIPCHK(h, hipSetDevice(h->cfg.device));
-  return cases_sequence(h, d_cells, d_p, stream ? (hipStream_t)stream : h->stream);
+  return cases_sequence(h, d_cells, d_p, stream ? (hipStream_t)stream : h->stream, delta);
 }
 
 
-int psm_solve_cases_begin(psm_handle* h, const double* cells, double* p_out) {
-  if (!h) return PSM_ERR_ARG;
+int psm_impl::cases_step_begin(psm_handle* h, const double* cells, double* p_out, bool delta) {
   if (h->mcs.inflight) return fail(h, PSM_ERR_STATE, "a psm_solve_cases_begin is already in flight on this handle: call psm_solve_cases_end first");
   int rc = cases_check(h);
   if (rc) return rc;
@@ -398,12 +432,14 @@ int psm_solve_cases_begin(psm_handle* h, const double* cells, double* p_out) {
   const bool reg_in = host_registered(h, cells, in_bytes), reg_out = host_registered(h, p_out, out_bytes);
   if (!reg_in) memcpy(m.h_cells, cells, in_bytes);
   HIPCHK(h, hipMemcpyAsync(m.d_cells, reg_in ? cells : m.h_cells, in_bytes, hipMemcpyHostToDevice, st));
-  if ((rc = cases_sequence(h, m.d_cells, m.d_p, st))) return rc;
+  if ((rc = cases_sequence(h, m.d_cells, m.d_p, st, delta))) return rc;
   HIPCHK(h, hipMemcpyAsync(reg_out ? p_out : m.h_p, m.d_p, out_bytes, hipMemcpyDeviceToHost, st));
   m.copy_out = reg_out ? nullptr : p_out;
   m.inflight = true;
   return PSM_OK;
 }
+
+extern "C" {
 
 
 int psm_solve_cases_end(psm_handle* h) {

@@ -184,6 +184,7 @@ void mesh_cases_free(psm_handle* h) {
   if (m.h_cells) { (void)hipHostFree(m.h_cells); m.h_cells = nullptr; }
   if (m.h_p) { (void)hipHostFree(m.h_p); m.h_p = nullptr; }
   m.ready = false; m.inflight = false; m.n_cases = 0; m.off.clear();
+  delta_drop(h);                        // U(t-1) of the delta step belongs to the cells that go here
 }
 
 

@@ -1,11 +1,12 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in seventeen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in eighteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, psm_solve_grid*
 //   psm_api_step.cpp        the step around a solve (solve_device: StepCall, step_check, row scale, graph capture and key) and the guarded host loop of every host entry
 //   psm_api_ring.cpp        the pinned submission ring (psm_ring_*, psm_submit_grid*, psm_wait_grid) and registered host memory (psm_host_*)
 //   psm_api_mesh.cpp        the solver boundary (psm_set_geometry / psm_solve*; the case batch psm_set_geometry_cases / psm_solve_cases*; host tables of both in psm_mesh_tables.cpp), psm_mesh_to_grid
+//   psm_api_delta.cpp       the delta step at the solver boundary (dU -> dp, U(t-1) on the device): psm_delta_prime* / _reset / _state, psm_solve_delta*, psm_solve_cases_delta*
 //   psm_api_eval.cpp        evaluator helpers on the planned grid: psm_reassemble, psm_label_blocks, psm_block_error
 //   psm_api_integ.cpp       the gradP integration: tables, host entry and the device-resident U -> p (psm_set_integration ... psm_solve_pressure)
 //   psm_api_filter.cpp      the Gaussian post-steps: psm_gaussian_filter (host entry), psm_bind_poststeps and the device-resident / case-batched entries
@@ -301,6 +302,15 @@ struct MeshCaseSet {
   double* copy_out = nullptr;           // where psm_solve_cases_end copies p to (null: it was DMA'd into the caller's registered array)
 };
 
+// The state of the delta step (psm_solve_delta*, psm_solve_cases_delta*; psm_api_delta.cpp): U(t-1) per cell of the single mesh or of
+// the case set, allocated with the geometry and gone with it (delta_drop), so that a step allocates nothing.  Written by the last
+// launch of a step (psm_to_mesh_kernel, delta form); the host flags follow once the whole chain is enqueued.
+struct DeltaState {
+  double* d_u_prev = nullptr;           // [sum n_i][2]
+  bool primed = false;                  // d_u_prev holds the velocities of a previous step (or of psm_delta_prime*)
+  int64_t steps = 0;                    // delta steps taken since the state was last empty (a priming step does not count)
+};
+
 // Binding of the Gaussian post-steps to the planned grid (psm_bind_poststeps): the four tap tables and per-case scratch for
 // max_cases cases, so that a step allocates nothing and copies nothing.
 struct PostSet {
@@ -441,6 +451,7 @@ struct psm_handle {
   int64_t n_cells = 0;
   MeshSingle mesh;
   MeshCaseSet mcs;                      // or a case set (psm_set_geometry_cases): setting one drops the other
+  DeltaState delta;                     // U(t-1) of psm_solve_delta* / psm_solve_cases_delta*, allocated with either of the two
   // U_to_gradP integration: the evaluator's single geometry of any size (psm_set_integration, host buffers) and the case
   // batch on the planned grid (psm_bind_integration, device buffers)
   IntegSet integ_host, integ_dev;
@@ -626,6 +637,14 @@ PsmPasteArgs paste_args(const psm_handle* h, const Workspace& w, float* d_fields
 // n_partials > 0 partial maxima itself and leaves the scalar in the mesh's d_umax
 PsmToGridArgs to_grid_args(const psm_handle* h, const double* d_umax, double umax_val, int n_partials);
 PsmToMeshArgs to_mesh_args(const psm_handle* h, const double* d_umax, double umax_val, double* p_out);
+// The step entries of the solver boundary, absolute (psm_solve*, psm_solve_cases*) and delta (psm_api_delta.cpp) alike: the same
+// checks, copies and launches; `delta` swaps the two mesh ends for their delta forms, keeps off the one-kernel staging route of
+// registered buffers and, on a state that is not primed, enqueues the priming step instead (no U_max, no network).
+int mesh_step_begin(psm_handle* h, const double* cells, int64_t n, double* p_out, bool delta);
+int cases_check(psm_handle* h);
+int cases_step_device(psm_handle* h, const double* d_cells, double* d_p, void* stream, bool delta);
+int cases_step_begin(psm_handle* h, const double* cells, double* p_out, bool delta);
+void delta_drop(psm_handle* h);       // the geometry or case set goes: so does U(t-1)
 // the stages of `step` and the solve between them on one stream / in one graph replay; the combinations of stages: step_check there
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,
                  hipStream_t st, hipEvent_t* prof, const StepCall& step = {});

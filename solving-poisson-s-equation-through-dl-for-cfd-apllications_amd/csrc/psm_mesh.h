@@ -46,6 +46,21 @@ hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st);
 hipError_t psm_launch_interp_to_grid(const double* values, int k, const int32_t* vtx, const double* wts, const int32_t* src_of_cell,
                                      int fill, double* out, int64_t n_grid, hipStream_t st);
 
+// ---- the delta form of the two ends (psm_solve_delta*: [U(t) - U(t-1)], SDF -> p(t) - p(t-1), pressureSM_deltas/SM_call.py:389-391):
+// the same launches on the same tables plus the state u_prev [N][2] = (Ux, Uy) of the previous step, 16-byte aligned.  to_grid
+// gathers U - u_prev per vertex; to_mesh stores p(t-1) + dp (p(t-1) where it falls back) and then cells[n][0:2] into u_prev[n].
+struct PsmDeltaGridArgs {
+  PsmToGridArgs g;
+  const double* u_prev;         // [N][2] read at the three vertices of every written image cell
+};
+struct PsmDeltaMeshArgs {
+  PsmToMeshArgs m;
+  double* u_prev;               // [N][2] written, one row per thread, after p_out
+  int prime;                    // 1: the priming step -- no field is read, p_out = cells[:,4], u_prev = cells[:,0:2]
+};
+hipError_t psm_launch_to_grid_delta(const PsmDeltaGridArgs& d, hipStream_t st);
+hipError_t psm_launch_to_mesh_delta(const PsmDeltaMeshArgs& d, hipStream_t st);
+
 // ---- frame-batched, plane-writing form of psm_launch_interp_to_grid (psm_frames_to_grid_device): n_frames arrays of cell columns on
 // the single mesh of psm_set_geometry, the frame is launch dimension y, every column goes to a plane of its own.
 constexpr int PSM_FRAME_MAX_COLS = 16;
@@ -145,3 +160,11 @@ struct PsmMeshCasesArgs {
 hipError_t psm_launch_umax_cases(const PsmMeshCasesArgs& a, hipStream_t st);
 hipError_t psm_launch_to_grid_cases(const PsmMeshCasesArgs& a, hipStream_t st);
 hipError_t psm_launch_to_mesh_cases(const PsmMeshCasesArgs& a, hipStream_t st);
+// the delta form of the case batch's two ends: u_prev [sum n_i][2], the cases' rows concatenated like the cells'
+struct PsmDeltaCasesArgs {
+  PsmMeshCasesArgs c;
+  double* u_prev;
+  int prime;                    // as in PsmDeltaMeshArgs; read by to_mesh only
+};
+hipError_t psm_launch_to_grid_cases_delta(const PsmDeltaCasesArgs& d, hipStream_t st);
+hipError_t psm_launch_to_mesh_cases_delta(const PsmDeltaCasesArgs& d, hipStream_t st);

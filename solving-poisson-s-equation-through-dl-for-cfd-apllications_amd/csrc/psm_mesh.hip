@@ -7,6 +7,7 @@
 //              SDF channel, NaN -> 0                                        [PM:272-297]
 //   to_mesh  : gather at `indices`, barycentric grid->mesh interpolation with fill,
 //              dimensionalise, near-wall / NaN fallback to the previous p   [PM:481-496]
+//   both ends also in DELTA form (psm_solve_delta*): U - U(t-1) in, p(t-1) + dp out, U(t-1) := U   [SMD:389-391]
 //
 // All of them are HBM-bound gathers; interpolation is done in float64 like the reference.
 #include "psm_mesh.h"
@@ -95,8 +96,18 @@ __device__ __forceinline__ double umax_of_partials(const double* partials, int n
   return sqrt_rn(nanmax2(nanmax2(um_s[0], um_s[1]), nanmax2(um_s[2], um_s[3])));
 }
 
-// image cell `cell` of the mesh whose tables `a` points at
-__device__ __forceinline__ void to_grid_cell(const PsmToGridArgs& a, double umax_v, int64_t cell) {
+// p(t-1) + dp as NumPy adds them: one rounding, never folded into the multiplications in front of it
+__device__ __forceinline__ double add_np(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+typedef double psm_uv2 __attribute__((ext_vector_type(2)));   // one row of u_prev [N][2]: 16 bytes, 16-byte aligned
+
+// image cell `cell` of the mesh whose tables `a` points at.  DELTA (psm_solve_delta*, the deltas model at the solver boundary):
+// the gathered value is U(t) - U(t-1), formed in float64 per vertex in front of the chain (SM_call.py:389-391), with U(t-1) from
+// u_prev [N][2]; U_max stays that of the current cells (:404, :418-419).
+template <bool DELTA>
+__device__ __forceinline__ void to_grid_cell(const PsmToGridArgs& a, const double* u_prev, double umax_v, int64_t cell) {
   const int src = a.src_of_cell[cell];     // grid point whose value lands in this cell (-1: never written -> 0)
   float ux = 0.f, uy = 0.f;
   if (src >= 0) {
@@ -108,8 +119,13 @@ __device__ __forceinline__ void to_grid_cell(const PsmToGridArgs& a, double umax
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const double* c = a.cells + (int64_t)v[j] * 5;
-      sx += (c[0] * inv) * w[j];           // interpolate(Ux / U_max)  (PM:272,280)
-      sy += (c[1] * inv) * w[j];
+      double cx = c[0], cy = c[1];
+      if (DELTA) {
+        const psm_uv2 q = *reinterpret_cast<const psm_uv2*>(u_prev + (int64_t)v[j] * 2);
+        cx -= q.x; cy -= q.y;
+      }
+      sx += (cx * inv) * w[j];             // interpolate(Ux / U_max)  (PM:272,280)
+      sy += (cy * inv) * w[j];
       neg = neg || (w[j] < 0.0);
     }
     if (a.fill && neg) { sx = NAN; sy = NAN; }   // interpolate_fill (SMD:421-423): NaN, then NaN -> 0
@@ -125,22 +141,29 @@ __device__ __forceinline__ void to_grid_cell(const PsmToGridArgs& a, double umax
   g[2] = (sd != sd) ? 0.f : (float)sd;
 }
 
-// mesh cell n of the mesh whose tables `a` points at
-__device__ __forceinline__ void to_mesh_cell(const PsmToMeshArgs& a, double um, int64_t n) {
+// mesh cell n of the mesh whose tables `a` points at.  DELTA: the field is dp, so p = p(t-1) + dp and p(t-1) itself where the body
+// falls back (PM:494-496 applied to dp); the thread then leaves its cell's (Ux, Uy) in u_prev[n] -- the state turns over in the
+// step's last launch, behind every reader of the old one in stream order.  `prime` (uniform): no field yet, p = p(t-1) everywhere.
+template <bool DELTA>
+__device__ __forceinline__ void to_mesh_cell(const PsmToMeshArgs& a, double* u_prev, int prime, double um, int64_t n) {
   const int32_t* v = a.vtx + n * 3;
   const double* w = a.wts + n * 3;
   double acc = 0.0;
   bool neg = false;
+  if (!(DELTA && prime)) {
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int cell = a.cell_of_point[v[j]];                         // p_adim_unif = result[indices]  (PM:481)
-    acc += (double)a.field[(int64_t)cell * a.c_out] * w[j];
-    neg = neg || (w[j] < 0.0);
+    for (int j = 0; j < 3; ++j) {
+      const int cell = a.cell_of_point[v[j]];                       // p_adim_unif = result[indices]  (PM:481)
+      acc += (double)a.field[(int64_t)cell * a.c_out] * w[j];
+      neg = neg || (w[j] < 0.0);
+    }
   }
   double p = acc * a.max_abs_p * (um * um);                         // PM:490
   const double prev = a.cells[n * 5 + 4];
-  if (a.near_wall[n] || neg || acc != acc) p = prev;                // PM:494, 496 (interpolate_fill -> NaN)
+  if (DELTA) p = add_np(prev, p);
+  if ((DELTA && prime) || a.near_wall[n] || neg || acc != acc) p = prev;   // PM:494, 496 (interpolate_fill -> NaN)
   a.p_out[n] = p;
+  if (DELTA) *reinterpret_cast<psm_uv2*>(u_prev + n * 2) = psm_uv2{a.cells[n * 5], a.cells[n * 5 + 1]};
 }
 
 __global__ __launch_bounds__(1024) void psm_umax_partial_kernel(const double* cells, int64_t n, double* partials) {
@@ -231,13 +254,34 @@ __global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmToGridArgs a) {
   }
   const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (cell >= a.n_grid) return;
-  to_grid_cell(a, umax_v, cell);
+  to_grid_cell<false>(a, nullptr, umax_v, cell);
 }
 
 __global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmToMeshArgs a) {
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= a.n_cells) return;
-  to_mesh_cell(a, a.umax ? *a.umax : a.umax_val, n);
+  to_mesh_cell<false>(a, nullptr, 0, a.umax ? *a.umax : a.umax_val, n);
+}
+
+// The delta forms of the two kernels above (PsmDeltaGridArgs / PsmDeltaMeshArgs in psm_mesh.h): the same launch shapes and the same
+// three sources of U_max, the DELTA bodies.
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmDeltaGridArgs d) {
+  const PsmToGridArgs& a = d.g;
+  double umax_v = a.umax ? *a.umax : a.umax_val;
+  if (a.umax_partials) {
+    umax_v = umax_of_partials(a.umax_partials, a.n_partials);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.umax_out = umax_v;
+  }
+  const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (cell >= a.n_grid) return;
+  to_grid_cell<true>(a, d.u_prev, umax_v, cell);
+}
+
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmDeltaMeshArgs d) {
+  const PsmToMeshArgs& a = d.m;
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n >= a.n_cells) return;
+  to_mesh_cell<true>(a, d.u_prev, d.prime, d.prime ? 0.0 : (a.umax ? *a.umax : a.umax_val), n);
 }
 
 hipError_t psm_launch_umax_partial(const double* cells, int64_t n, double* partials, int* n_partials, hipStream_t st) {
@@ -252,7 +296,12 @@ hipError_t psm_launch_umax(const double* cells, int64_t n, double* umax, hipStre
   return hipGetLastError();
 }
 hipError_t psm_launch_to_grid(const PsmToGridArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(psm_to_grid_kernel, dim3((unsigned)((a.n_grid + 255) / 256)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(static_cast<void (*)(PsmToGridArgs)>(psm_to_grid_kernel), dim3((unsigned)((a.n_grid + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_to_grid_delta(const PsmDeltaGridArgs& d, hipStream_t st) {
+  if (!d.u_prev || d.g.n_grid < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmDeltaGridArgs)>(psm_to_grid_kernel), dim3((unsigned)((d.g.n_grid + 255) / 256)), dim3(256), 0, st, d);
   return hipGetLastError();
 }
 // One column of one image cell, the statements the two kernels below share: np.einsum('nj,nj->n', take(values, vtx), wts) over the
@@ -522,7 +571,12 @@ hipError_t psm_launch_chapter4_pack(const PsmChapter4PackArgs& a, hipStream_t st
 }
 
 hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(psm_to_mesh_kernel, dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(static_cast<void (*)(PsmToMeshArgs)>(psm_to_mesh_kernel), dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_to_mesh_delta(const PsmDeltaMeshArgs& d, hipStream_t st) {
+  if (!d.u_prev || d.m.n_cells < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmDeltaMeshArgs)>(psm_to_mesh_kernel), dim3((unsigned)((d.m.n_cells + 255) / 256)), dim3(256), 0, st, d);
   return hipGetLastError();
 }
 
@@ -554,7 +608,7 @@ __global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmMeshCasesArgs a) {
   g.vtx = a.vtx_m2g + g0 * 3; g.wts = a.wts_m2g + g0 * 3; g.src_of_cell = a.src_of_cell + g0;
   g.sdf = a.sdf + g0; g.grid = a.grid + g0 * a.c_in;
   g.max_abs_ux = a.max_abs_ux; g.max_abs_uy = a.max_abs_uy; g.sdf_scale = a.sdf_scale; g.c_in = a.c_in; g.fill = a.fill;
-  to_grid_cell(g, umax_v, cell);
+  to_grid_cell<false>(g, nullptr, umax_v, cell);
 }
 
 // grid -> mesh for all sum n_i cells in one launch.  The case is launch dimension y (x covers the largest case) and not a
@@ -571,7 +625,38 @@ __global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmMeshCasesArgs a) {
   m.vtx = a.vtx_g2m + c0 * 3; m.wts = a.wts_g2m + c0 * 3; m.cell_of_point = a.cell_of_point + g0;
   m.field = a.field + g0 * a.c_out; m.near_wall = a.near_wall + c0; m.p_out = a.p_out + c0;
   m.max_abs_p = a.max_abs_p; m.c_out = a.c_out;
-  to_mesh_cell(m, a.umax[cs], local);
+  to_mesh_cell<false>(m, nullptr, 0, a.umax[cs], local);
+}
+
+// The delta forms of the two case-batch kernels (PsmDeltaCasesArgs): the same slices, u_prev [sum n_i][2] sliced like the cells.
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmDeltaCasesArgs d) {
+  const PsmMeshCasesArgs& a = d.c;
+  const int cs = blockIdx.y;
+  const double umax_v = umax_of_partials(a.umax_part + (int64_t)cs * a.n_parts, a.n_parts);
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.umax[cs] = umax_v;
+  const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (cell >= a.n_grid) return;
+  const int64_t g0 = (int64_t)cs * a.n_grid, c0 = a.cell_off[cs];
+  PsmToGridArgs g{};
+  g.cells = a.cells + c0 * 5;
+  g.vtx = a.vtx_m2g + g0 * 3; g.wts = a.wts_m2g + g0 * 3; g.src_of_cell = a.src_of_cell + g0;
+  g.sdf = a.sdf + g0; g.grid = a.grid + g0 * a.c_in;
+  g.max_abs_ux = a.max_abs_ux; g.max_abs_uy = a.max_abs_uy; g.sdf_scale = a.sdf_scale; g.c_in = a.c_in; g.fill = a.fill;
+  to_grid_cell<true>(g, d.u_prev + c0 * 2, umax_v, cell);
+}
+
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmDeltaCasesArgs d) {
+  const PsmMeshCasesArgs& a = d.c;
+  const int cs = blockIdx.y;
+  const int64_t c0 = a.cell_off[cs], local = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (local >= a.cell_off[cs + 1] - c0) return;
+  const int64_t g0 = (int64_t)cs * a.n_grid;
+  PsmToMeshArgs m{};
+  m.cells = a.cells + c0 * 5;
+  m.vtx = a.vtx_g2m + c0 * 3; m.wts = a.wts_g2m + c0 * 3; m.cell_of_point = a.cell_of_point + g0;
+  m.field = a.field + g0 * a.c_out; m.near_wall = a.near_wall + c0; m.p_out = a.p_out + c0;
+  m.max_abs_p = a.max_abs_p; m.c_out = a.c_out;
+  to_mesh_cell<true>(m, d.u_prev + c0 * 2, d.prime, d.prime ? 0.0 : a.umax[cs], local);
 }
 
 typedef void (*PsmCasesKernel)(PsmMeshCasesArgs);
@@ -585,5 +670,16 @@ hipError_t psm_launch_to_grid_cases(const PsmMeshCasesArgs& a, hipStream_t st) {
 }
 hipError_t psm_launch_to_mesh_cases(const PsmMeshCasesArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(static_cast<PsmCasesKernel>(psm_to_mesh_kernel), dim3((unsigned)((a.max_cells + 255) / 256), a.n_cases), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+typedef void (*PsmDeltaCasesKernel)(PsmDeltaCasesArgs);
+hipError_t psm_launch_to_grid_cases_delta(const PsmDeltaCasesArgs& d, hipStream_t st) {
+  if (!d.u_prev || d.c.n_cases < 1 || d.c.n_grid < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<PsmDeltaCasesKernel>(psm_to_grid_kernel), dim3((unsigned)((d.c.n_grid + 255) / 256), d.c.n_cases), dim3(256), 0, st, d);
+  return hipGetLastError();
+}
+hipError_t psm_launch_to_mesh_cases_delta(const PsmDeltaCasesArgs& d, hipStream_t st) {
+  if (!d.u_prev || d.c.n_cases < 1 || d.c.max_cells < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<PsmDeltaCasesKernel>(psm_to_mesh_kernel), dim3((unsigned)((d.c.max_cells + 255) / 256), d.c.n_cases), dim3(256), 0, st, d);
   return hipGetLastError();
 }

@@ -11,6 +11,32 @@ from . import _lib
 from .surrogate import GridSurrogate, _f64, _p
 from .synthetic import SurrogateModel
 
+STEPS = ("absolute", "delta")
+
+
+def _check_step(step):
+    if step not in STEPS:
+        raise ValueError("step must be 'absolute' or 'delta'")
+    return step
+
+
+def _check_cells(array_in, out):
+    """The [N,5] float64 view of a step's input and its output array, refused before any library call."""
+    a = _f64(array_in)
+    if a.ndim != 2 or a.shape[1] != 5:
+        raise ValueError("array must be [N,5] = (Ux, Uy, Cx, Cy, p)")
+    if out is None:
+        out = np.empty(a.shape[0], np.float64)
+    elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
+        raise ValueError("out must be a contiguous float64 array [N]")
+    return a, out
+
+
+def _delta_state(sur):
+    primed, steps = C.c_int32(), C.c_int64()
+    sur._chk(sur.lib.psm_delta_state(sur.h, C.byref(primed), C.byref(steps)))
+    return bool(primed.value), int(steps.value)
+
 
 class SolverModule:
     """Chapter-5 ``python_module`` (python_module.py): ``init_func`` / ``py_func`` with the
@@ -20,8 +46,13 @@ class SolverModule:
     the ``maxs`` file (python_module.py:106-109)."""
 
     def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), device: int = 0, delta: float = 5e-3,
-                 geometry: str = "scipy"):
-        """``geometry``: who builds init_func's tables -- 'scipy' (default in this Python mirror: the routines the reference
+                 geometry: str = "scipy", step: str = "absolute"):
+        """``step``: 'absolute' (U -> p, the Chapter-5 module) or 'delta' (the deltas model behind the same two calls:
+        [U(t) - U(t-1)], SDF -> p(t) - p(t-1), psm_solve_delta* of include/psm.h).  With 'delta', ``maxs`` are
+        (max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp), ``init_func`` installs the tables with the deltas model's
+        convention (SDF divided by max_abs_dist, interpolate_fill) and primes U(t-1) with its own ``array`` -- the fields of
+        the start time -- and ``py_func`` returns ``array[:,4] + dp``.
+        ``geometry``: who builds init_func's tables -- 'scipy' (default in this Python mirror: the routines the reference
         itself calls, qhull Delaunay in both directions, so that the tables -- including qhull's arbitrary choice of diagonal
         in every cocircular lattice square of the grid -> mesh step -- are the reference's) or 'native' (the library's C++
         builder behind ``psm_init_geometry``, csrc/psm_geometry.cpp: what a C++ solver gets; no SciPy).  The two differ only
@@ -30,6 +61,7 @@ class SolverModule:
         (tests/measure/mesh_native_vs_scipy.py) -- and the simplex used for lattice points outside the hull."""
         if geometry not in ("scipy", "native"):
             raise ValueError("geometry must be 'scipy' or 'native'")
+        self.step = _check_step(step)
         self.model, self.maxs, self.device, self.delta = model, tuple(float(v) for v in maxs), device, delta
         self.geometry = geometry
         self._sur = None
@@ -57,15 +89,19 @@ class SolverModule:
         v1, w1 = np.ascontiguousarray(t.vtx_m2g, np.int32), _f64(t.wts_m2g)
         v2, w2 = np.ascontiguousarray(t.vtx_g2m, np.int32), _f64(t.wts_g2m)
         idx, sdf, mx = np.ascontiguousarray(t.indices, np.int32), _f64(t.sdfunct), _f64(self.maxs)
+        smd = int(self.step == "delta")          # the deltas model's convention: normalise_sdf = fill_input = 1 (SM_call.py:441-443)
         self._sur._chk(self._sur.lib.psm_set_geometry(
             self._sur.h, int(np.asarray(array).shape[0]), t.ny, t.nx, _p(v1, C.c_int32), _p(w1, C.c_double),
             _p(idx, C.c_int32), _p(sdf, C.c_double), _p(v2, C.c_int32), _p(w2, C.c_double), _p(mx, C.c_double),
-            0, 0, 0.05))
+            smd, smd, 0.05))
         self.tables = t
+        if smd:
+            self.prime(array)
         return 0
 
     def _init_func_native(self, array, top_boundary, obst_boundary):
-        """psm_set_case + psm_init_geometry: the tables are built inside the library (csrc/psm_geometry.cpp)."""
+        """psm_set_case + psm_init_geometry: the tables are built inside the library (csrc/psm_geometry.cpp).  step='delta':
+        psm_geometry_build + psm_set_geometry, which takes the deltas model's two flags (psm_init_geometry passes 0, 0)."""
         a, t, o = _f64(array), _f64(top_boundary), _f64(obst_boundary)
         lib = _lib.load()
         ny, nx = C.c_int32(), C.c_int32()
@@ -75,11 +111,51 @@ class SolverModule:
             self._sur.close()
         self._sur = GridSurrogate(self.model, ny.value, nx.value, 1, self.device)
         mx = _f64(self.maxs)
+        if self.step == "delta":
+            n, ng = a.shape[0], ny.value * nx.value
+            v1, w1, idx, sdf = np.empty((ng, 3), np.int32), np.empty((ng, 3)), np.empty((ng, 2), np.int32), np.empty(ng)
+            v2, w2 = np.empty((n, 3), np.int32), np.empty((n, 3))
+            if lib.psm_geometry_build(_p(a, C.c_double), n, _p(t, C.c_double), t.shape[0], _p(o, C.c_double), o.shape[0], self.delta, 10,
+                                      _p(v1, C.c_int32), _p(w1, C.c_double), _p(idx, C.c_int32), _p(sdf, C.c_double),
+                                      _p(v2, C.c_int32), _p(w2, C.c_double)):
+                raise ValueError(lib.psm_geometry_last_error().decode())
+            self._sur._chk(lib.psm_set_geometry(self._sur.h, n, ny.value, nx.value, _p(v1, C.c_int32), _p(w1, C.c_double),
+                                                _p(idx, C.c_int32), _p(sdf, C.c_double), _p(v2, C.c_int32), _p(w2, C.c_double),
+                                                _p(mx, C.c_double), 1, 1, 0.05))
+            self.tables = "native"
+            self.prime(a)
+            return 0
         self._sur._chk(lib.psm_set_case(self._sur.h, _p(mx, C.c_double), self.delta, 10, 0.05))
         self._sur._chk(lib.psm_init_geometry(self._sur.h, _p(a, C.c_double), a.shape[0], _p(t, C.c_double), t.shape[0],
                                              _p(o, C.c_double), o.shape[0], 0))
         self.tables = "native"
         return 0
+
+    # -- the state of step='delta' (psm_delta_prime / _reset / _state)
+    def _need_delta(self):
+        if self.step != "delta":
+            raise RuntimeError("this module was built with step='absolute': the state belongs to step='delta'")
+        if self.tables is None:
+            raise RuntimeError("init_func has not been called")
+
+    def prime(self, array):
+        """U(t-1) := array[:,0:2].  ``init_func`` does this with the start fields; a restart primes again."""
+        self._need_delta()
+        a = _f64(array)
+        if a.ndim != 2 or a.shape[1] != 5:
+            raise ValueError("array must be [N,5] = (Ux, Uy, Cx, Cy, p)")
+        self._sur._chk(self._sur.lib.psm_delta_prime(self._sur.h, _p(a, C.c_double), a.shape[0]))
+
+    def reset_state(self):
+        """Forget U(t-1): the next ``py_func`` is the priming step and returns ``array[:,4]``."""
+        self._need_delta()
+        self._sur._chk(self._sur.lib.psm_delta_reset(self._sur.h))
+
+    @property
+    def state(self):
+        """(primed, steps) of psm_delta_state."""
+        self._need_delta()
+        return _delta_state(self._sur)
 
     def pin(self, array: np.ndarray, out: np.ndarray = None):
         """psm_pin_buffers: register the caller's persistent [N,5] float64 array (and optionally a persistent output
@@ -99,6 +175,11 @@ class SolverModule:
         can be advanced from one thread by calling begin on all of them, then :meth:`py_func_end` on each."""
         if self.tables is None:
             raise RuntimeError("init_func has not been called")
+        if self.step == "delta":
+            a, out = _check_cells(array_in, out)
+            self._sur._chk(self._sur.lib.psm_solve_delta_begin(self._sur.h, _p(a, C.c_double), a.shape[0], 0, _p(out, C.c_double)))
+            self._inflight = (a, out)
+            return
         a = _f64(array_in)
         if a.ndim != 2 or a.shape[1] != 5:
             raise ValueError("array must be [N,5] = (Ux, Uy, Cx, Cy, p)")
@@ -108,15 +189,20 @@ class SolverModule:
         self._inflight = (a, out)                       # keeps both arrays alive until the end call (set only once the step is in flight)
 
     def py_func_end(self) -> np.ndarray:
-        self._sur._chk(self._sur.lib.psm_solve_end(self._sur.h))
+        end = self._sur.lib.psm_solve_delta_end if self.step == "delta" else self._sur.lib.psm_solve_end
+        self._sur._chk(end(self._sur.h))
         a, out = self._inflight
         self._inflight = None
         return out
 
     def py_func(self, array_in, placeholder=0, out: np.ndarray = None) -> np.ndarray:
-        """python_module.py:249: cells [N,5] float64 -> p [N] float64."""
+        """python_module.py:249: cells [N,5] float64 -> p [N] float64.  step='delta': p = array[:,4] + dp (psm_solve_delta)."""
         if self.tables is None:
             raise RuntimeError("init_func has not been called")
+        if self.step == "delta":
+            a, out = _check_cells(array_in, out)
+            self._sur._chk(self._sur.lib.psm_solve_delta(self._sur.h, _p(a, C.c_double), a.shape[0], int(placeholder), _p(out, C.c_double)))
+            return out
         a = _f64(array_in)
         if a.ndim != 2 or a.shape[1] != 5:
             raise ValueError("array must be [N,5] = (Ux, Uy, Cx, Cy, p)")
@@ -132,12 +218,14 @@ class SolverEnsemble:
     all advanced by one call (``psm_set_geometry_cases`` / ``psm_solve_cases``: one launch chain per step instead of one per
     case).  ``init_func`` takes one (array, top, obst) per case, ``py_func`` one ``[N_i,5]`` array per case and returns the
     list of ``p_i``.  ``geometry``: 'native' (``psm_init_geometry_cases``, the library's C++ table builder) or 'scipy'
-    (``geometry.build_geometry`` per case, handed over with ``psm_set_geometry_cases``) -- see :class:`SolverModule`."""
+    (``geometry.build_geometry`` per case, handed over with ``psm_set_geometry_cases``) -- see :class:`SolverModule`.
+    ``step``: 'absolute' or 'delta' as for :class:`SolverModule`, on ``psm_solve_cases_delta*``: one state for the set."""
 
     def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), max_cases: int = 8, geometry: str = "native",
-                 device: int = 0, delta: float = 5e-3):
+                 device: int = 0, delta: float = 5e-3, step: str = "absolute"):
         if geometry not in ("scipy", "native"):
             raise ValueError("geometry must be 'scipy' or 'native'")
+        self.step = _check_step(step)
         self.model, self.maxs, self.max_cases = model, tuple(float(v) for v in maxs), int(max_cases)
         self.geometry, self.device, self.delta = geometry, device, delta
         self._sur = None
@@ -172,7 +260,20 @@ class SolverEnsemble:
             self._sur.close()
         self._sur = sur = GridSurrogate(self.model, ny, nx, self.max_cases, self.device)
         n = (C.c_int64 * K)(*[x.shape[0] for x in a])
-        if self.geometry == "native":
+        smd = int(self.step == "delta")          # the deltas model's convention: normalise_sdf = fill_input = 1 (SM_call.py:441-443)
+        if self.geometry == "native" and smd:    # psm_init_geometry_cases passes 0, 0: build the tables, hand them over with 1, 1
+            ng = ny * nx
+            keep = [[np.empty((rows or x.shape[0]) * width, dt) for x in a]      # vtx_m2g, wts_m2g, indices, sdfunct, vtx_g2m, wts_g2m
+                    for rows, width, dt in ((ng, 3, np.int32), (ng, 3, np.float64), (ng, 2, np.int32), (ng, 1, np.float64),
+                                            (0, 3, np.int32), (0, 3, np.float64))]
+            for k in range(K):
+                v1, w1, idx, sdf, v2, w2 = (col[k] for col in keep)
+                if lib.psm_geometry_build(_p(a[k], C.c_double), a[k].shape[0], _p(t[k], C.c_double), t[k].shape[0], _p(o[k], C.c_double),
+                                          o[k].shape[0], self.delta, 10, _p(v1, C.c_int32), _p(w1, C.c_double), _p(idx, C.c_int32),
+                                          _p(sdf, C.c_double), _p(v2, C.c_int32), _p(w2, C.c_double)):
+                    raise ValueError(f"case {k}: " + lib.psm_geometry_last_error().decode())
+            sur._chk(lib.psm_set_geometry_cases(sur.h, K, n, ny, nx, *[self._ptrs(col) for col in keep], _p(mx, C.c_double), 1, 1, 0.05))
+        elif self.geometry == "native":
             sur._chk(lib.psm_set_case(sur.h, _p(mx, C.c_double), self.delta, 10, 0.05))
             sur._chk(lib.psm_init_geometry_cases(sur.h, K, self._ptrs(a), n, self._ptrs(t), (C.c_int64 * K)(*[x.shape[0] for x in t]),
                                                  self._ptrs(o), (C.c_int64 * K)(*[x.shape[0] for x in o])))
@@ -180,12 +281,42 @@ class SolverEnsemble:
             keep = [[np.ascontiguousarray(getattr(g, f), dt) for g in tables]
                     for f, dt in (("vtx_m2g", np.int32), ("wts_m2g", np.float64), ("indices", np.int32), ("sdfunct", np.float64),
                                   ("vtx_g2m", np.int32), ("wts_g2m", np.float64))]
-            sur._chk(lib.psm_set_geometry_cases(sur.h, K, n, ny, nx, *[self._ptrs(col) for col in keep], _p(mx, C.c_double), 0, 0, 0.05))
+            sur._chk(lib.psm_set_geometry_cases(sur.h, K, n, ny, nx, *[self._ptrs(col) for col in keep], _p(mx, C.c_double), smd, smd, 0.05))
         off = (C.c_int64 * (K + 1))()
         sur._chk(lib.psm_mesh_cases(sur.h, None, off))
         self.cell_off = [int(v) for v in off]
         self.tables = tables
+        if smd:
+            self.prime(a)
         return 0
+
+    # -- the state of step='delta' (psm_delta_prime_cases / psm_delta_reset / psm_delta_state)
+    def _need_delta(self):
+        if self.step != "delta":
+            raise RuntimeError("this ensemble was built with step='absolute': the state belongs to step='delta'")
+
+    def prime(self, arrays):
+        """U(t-1) := arrays[k][:,0:2] for every case.  ``init_func`` does this with the start fields."""
+        self._need_delta()
+        cells, _ = self._pack(arrays)
+        self._sur._chk(self._sur.lib.psm_delta_prime_cases(self._sur.h, _p(cells, C.c_double)))
+
+    def reset_state(self):
+        self._need_delta()
+        if self.tables is None:
+            raise RuntimeError("init_func has not been called")
+        self._sur._chk(self._sur.lib.psm_delta_reset(self._sur.h))
+
+    @property
+    def state(self):
+        """(primed, steps) of psm_delta_state."""
+        self._need_delta()
+        if self.tables is None:
+            raise RuntimeError("init_func has not been called")
+        return _delta_state(self._sur)
+
+    def _entry(self, name):
+        return getattr(self._sur.lib, name.replace("psm_solve_cases", "psm_solve_cases_delta") if self.step == "delta" else name)
 
     def _pack(self, arrays):
         if self.tables is None:
@@ -207,11 +338,11 @@ class SolverEnsemble:
     def py_func_begin(self, arrays):
         """First half of :meth:`py_func` (psm_solve_cases_begin): enqueue the step of all cases and return."""
         cells, p = self._pack(arrays)
-        self._sur._chk(self._sur.lib.psm_solve_cases_begin(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
+        self._sur._chk(self._entry("psm_solve_cases_begin")(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
         self._inflight = (cells, p)                     # keeps both arrays alive until the end call
 
     def py_func_end(self):
-        self._sur._chk(self._sur.lib.psm_solve_cases_end(self._sur.h))
+        self._sur._chk(self._entry("psm_solve_cases_end")(self._sur.h))
         cells, p = self._inflight
         self._inflight = None
         return self._split(p)
@@ -219,5 +350,5 @@ class SolverEnsemble:
     def py_func(self, arrays):
         """One step of every case: list of cells [N_i,5] float64 -> list of p_i [N_i] float64."""
         cells, p = self._pack(arrays)
-        self._sur._chk(self._sur.lib.psm_solve_cases(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
+        self._sur._chk(self._entry("psm_solve_cases")(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
         return self._split(p)
