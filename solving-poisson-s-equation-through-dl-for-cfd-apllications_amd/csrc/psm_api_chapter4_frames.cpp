@@ -1,7 +1,7 @@
 // psm_api_chapter4_frames.cpp -- C-ABI of libpsm_hip.so (include/psm.h): the frame batch of the two Chapter-4 evaluators
 // (Chapter4/MLP/M_u/Evaluation/Eval_dual_Dense_onlycil.py: (Ux, Uy, SDF) -> p; Chapter4/MLP/M_fU/Evaluation/Eval.py: (f(U), SDF) -> p)
 // on the device.  psm_bind_chapter4_frames stands on psm_bind_frames; psm_chapter4_image_device is the image stage alone (the mesh ->
-// grid launch of psm_api_frames.cpp, then the pack: the PsmChapter4PackArgs overload of psm_to_grid_kernel, psm_mesh.hip);
+// grid launch of psm_api_frames.cpp, then the pack: the PsmChapter4PackArgs overload of psm_to_grid_kernel, psm_pack.hip);
 // psm_chapter4_frames* put planes -> image, label -> one solve per frame into one graph replay (solve_device, psm_api_step.cpp) and
 // the field-error launches of psm_api_errors.cpp with one pair behind it, so that a metrics-only sweep returns 8 doubles per frame.
 // No block stage and no dimensional scale: the reference compares prediction and label in normalised units (M_u :457-476).

@@ -26,13 +26,8 @@ extern "C" {
 
 int psm_delta_prime(psm_handle* h, const double* cells, int64_t n) {
   if (!h) return PSM_ERR_ARG;
-  if (h->mesh.inflight) return fail(h, PSM_ERR_STATE, "a step is in flight on this handle: call psm_solve_end first");
-  if (h->mcs.ready) return fail(h, PSM_ERR_STATE, "the handle holds the case set of psm_set_geometry_cases: use psm_delta_prime_cases");
-  if (!h->have_geometry || !h->planned)
-    return fail(h, PSM_ERR_STATE, "psm_set_geometry has not been called (or the plan it belonged to was dropped by a later psm_set_* / psm_plan_grid)");
-  if (!cells) return fail(h, PSM_ERR_ARG, "null buffer");
-  if (n != h->n_cells) return fail(h, PSM_ERR_ARG, "cell count differs from the geometry");
-  return prime_from_host(h, cells, n, h->mesh.h_cells);
+  const int rc = mesh_step_check(h, cells, n, nullptr, true);
+  return rc ? rc : prime_from_host(h, cells, n, h->mesh.h_cells);
 }
 
 

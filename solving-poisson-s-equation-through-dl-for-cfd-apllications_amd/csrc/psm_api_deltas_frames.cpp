@@ -1,6 +1,6 @@
 // psm_api_deltas_frames.cpp -- C-ABI of libpsm_hip.so (include/psm.h): the frame batch of the pressureSM_deltas evaluator on the
 // device.  psm_bind_deltas_frames stands on psm_bind_frames; psm_deltas_image_device is the image stage alone (the mesh -> grid launch
-// of psm_api_frames.cpp, then the pack: the PsmDeltasPackArgs overload of psm_to_grid_kernel, psm_mesh.hip); psm_block_errors_device
+// of psm_api_frames.cpp, then the pack: the PsmDeltasPackArgs overload of psm_to_grid_kernel, psm_pack.hip); psm_block_errors_device
 // is compute_in_block_error for a batch of frames (decode again, then the PsmBlockErrorBatchArgs / PsmBlockErrorFoldArgs overloads of
 // psm_block_error_kernel, psm_eval.hip); psm_deltas_frames* put planes -> image -> one solve per frame (-> filter) into one graph replay and the
 // two error stages behind it, so that a metrics-only sweep returns 16 doubles per frame.  See psm_handle.h for the map of the files.

@@ -1,7 +1,7 @@
 // psm_api_gradp_frames.cpp -- C-ABI of libpsm_hip.so (include/psm.h): the frame batch of the U_to_gradP evaluator on the device.
 // psm_bind_gradp_frames stands on psm_bind_frames and holds integration tables of its own (integ_bind of psm_api_integ.cpp, the
 // simulation's one geometry for every frame slot); psm_gradp_image_device is the image stage alone (the mesh -> grid launch of
-// psm_api_frames.cpp, then the pack: the PsmGradpPackArgs overload of psm_to_grid_kernel, psm_mesh.hip); psm_gradp_frames* put
+// psm_api_frames.cpp, then the pack: the PsmGradpPackArgs overload of psm_to_grid_kernel, psm_pack.hip); psm_gradp_frames* put
 // planes -> image, labels -> one solve per frame (-> filter) -> integration into one graph replay (solve_device, psm_api_solve.cpp)
 // and the field-error launches of psm_api_errors.cpp with four pairs behind it, so that a metrics-only sweep returns 32 doubles per
 // frame.  See psm_handle.h for the map of the files.

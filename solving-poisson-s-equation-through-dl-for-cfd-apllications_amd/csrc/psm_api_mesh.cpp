@@ -42,6 +42,24 @@ void mesh_tables_free(MeshTablesDev& t) {
   dev_free(t.wts_m2g); dev_free(t.sdf); dev_free(t.wts_g2m); dev_free(t.near_wall);
 }
 
+int mesh_buffers_alloc(psm_handle* h, MeshBuffers& b, size_t total_cells, size_t n_umax, size_t n_partials, int host_alloc_err, const char* what) {
+  int rc;
+  if ((rc = dev_alloc(h, &b.d_cells, total_cells * 5)) || (rc = dev_alloc(h, &b.d_p, total_cells)) || (rc = dev_alloc(h, &b.d_umax, n_umax)) ||
+      (rc = dev_alloc(h, &b.d_umax_part, n_partials)) || (rc = dev_alloc(h, &h->delta.d_u_prev, total_cells * 2))) return rc;
+  hipError_t e = hipSuccess;
+  if ((e = hipHostMalloc((void**)&b.h_cells, total_cells * 5 * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
+      (e = hipHostMalloc((void**)&b.h_p, total_cells * sizeof(double), hipHostMallocDefault)) != hipSuccess)
+    return fail(h, host_alloc_err, std::string("hipHostMalloc(") + what + "): " + hipGetErrorString(e));
+  return PSM_OK;
+}
+
+void mesh_buffers_free(MeshBuffers& b) {
+  mesh_tables_free(b.t);
+  dev_free(b.d_cells); dev_free(b.d_p); dev_free(b.d_umax); dev_free(b.d_umax_part);
+  if (b.h_cells) { (void)hipHostFree(b.h_cells); b.h_cells = nullptr; }
+  if (b.h_p) { (void)hipHostFree(b.h_p); b.h_p = nullptr; }
+}
+
 // psm_solve on registered, mapped caller buffers: every device-side step of the call, in stream order (captured once)
 static int mesh_sequence(psm_handle* h, int64_t n, hipStream_t st) {
   MeshSingle& m = h->mesh;
@@ -66,6 +84,9 @@ int cases_check(psm_handle* h) {
   return PSM_OK;
 }
 
+// the whole chain of a delta step is enqueued: the state has advanced (a priming step does not count)
+static void delta_advance(psm_handle* h) { h->delta.steps += h->delta.primed; h->delta.primed = true; }
+
 // One step of the case set, a linear chain on `st`: U_max partials, to_grid, the batched solve, to_mesh.  Plain launches (like
 // psm_solve; the solve inside replays its graph under PSM_GRAPH=1); copies nothing.  `delta`: the two ends in their delta form on
 // U(t-1); a state that is not primed gets the priming step, the last launch alone.  The state's host flags move once all is enqueued.
@@ -82,8 +103,23 @@ static int cases_sequence(psm_handle* h, const double* d_cells, double* d_p, hip
     if (rc) return rc;
   }
   HIPCHK(h, delta ? psm_launch_to_mesh_cases_delta(d, st) : psm_launch_to_mesh_cases(a, st));
-  if (delta) { h->delta.steps += h->delta.primed; h->delta.primed = true; }
+  if (delta) delta_advance(h);
   return PSM_OK;
+}
+
+// The six tables of psm_set_geometry for one case on its ny x nx grid (psm_geometry_build), behind psm_init_geometry (the K = 1
+// use, no prefix to its messages) and psm_init_geometry_cases ("case k: ")
+struct GeometryTables {
+  std::vector<int32_t> v1, idx, v2;
+  std::vector<double> w1, sdf, w2;
+};
+static int geometry_tables_build(psm_handle* h, const std::string& prefix, const double* cells, int64_t n, const double* top, int64_t n_top,
+                                 const double* obst, int64_t n_obst, int32_t ny, int32_t nx, GeometryTables& t) {
+  const size_t ng = (size_t)ny * nx;
+  t.v1.resize(ng * 3); t.w1.resize(ng * 3); t.idx.resize(ng * 2); t.sdf.resize(ng); t.v2.resize((size_t)n * 3); t.w2.resize((size_t)n * 3);
+  const int rc = psm_geometry_build(cells, n, top, n_top, obst, n_obst, h->case_delta, h->case_every, t.v1.data(), t.w1.data(), t.idx.data(),
+                                    t.sdf.data(), t.v2.data(), t.w2.data());
+  return rc ? fail(h, rc, prefix + psm_geometry_last_error()) : PSM_OK;
 }
 
 void delta_drop(psm_handle* h) {
@@ -116,15 +152,7 @@ int psm_set_geometry(psm_handle* h, int64_t n_cells, int32_t ny, int32_t nx, con
   free_geometry(h);
   MeshSingle& m = h->mesh;
   // all-or-nothing from here on: a failure leaves no geometry
-  if ((rc = mesh_tables_upload(h, m.t, t)) || (rc = dev_alloc(h, &m.d_cells, (size_t)n_cells * 5)) || (rc = dev_alloc(h, &m.d_p, (size_t)n_cells)) ||
-      (rc = dev_alloc(h, &m.d_umax, (size_t)1)) || (rc = dev_alloc(h, &m.d_umax_part, (size_t)256)) ||
-      (rc = dev_alloc(h, &h->delta.d_u_prev, (size_t)n_cells * 2))) { free_geometry(h); return rc; }
-  hipError_t e = hipSuccess;
-  if ((e = hipHostMalloc((void**)&m.h_cells, (size_t)n_cells * 5 * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
-      (e = hipHostMalloc((void**)&m.h_p, (size_t)n_cells * sizeof(double), hipHostMallocDefault)) != hipSuccess) {
-    free_geometry(h);
-    return fail(h, PSM_ERR_HIP, std::string("hipHostMalloc(mesh staging): ") + hipGetErrorString(e));
-  }
+  if ((rc = mesh_tables_upload(h, m.t, t)) || (rc = mesh_buffers_alloc(h, m, (size_t)n_cells, 1, 256, PSM_ERR_HIP, "mesh staging"))) { free_geometry(h); return rc; }
   h->n_cells = n_cells;
   for (int k = 0; k < 4; ++k) h->maxs[k] = maxs[k];
   h->normalise_sdf = normalise_sdf; h->fill_input = fill_input;
@@ -164,13 +192,9 @@ int psm_init_geometry(psm_handle* h, const double* cells, int64_t n, const doubl
   if (!cells || !top || !obst) return fail(h, PSM_ERR_ARG, "null buffer");
   int32_t ny = 0, nx = 0;
   if (psm_geometry_shape(cells, n, h->case_delta, &ny, &nx, nullptr) != PSM_OK) return fail(h, PSM_ERR_ARG, psm_geometry_last_error());
-  const size_t ng = (size_t)ny * nx;
-  std::vector<int32_t> v1(ng * 3), idx(ng * 2), v2((size_t)n * 3);
-  std::vector<double> w1(ng * 3), sdf(ng), w2((size_t)n * 3);
-  int rc = psm_geometry_build(cells, n, top, n_top, obst, n_obst, h->case_delta, h->case_every, v1.data(), w1.data(), idx.data(),
-                              sdf.data(), v2.data(), w2.data());
-  if (rc) return fail(h, rc, psm_geometry_last_error());
-  return psm_set_geometry(h, n, ny, nx, v1.data(), w1.data(), idx.data(), sdf.data(), v2.data(), w2.data(), h->case_maxs, 0, 0, h->case_wall);
+  GeometryTables t;
+  const int rc = geometry_tables_build(h, "", cells, n, top, n_top, obst, n_obst, ny, nx, t);
+  return rc ? rc : psm_set_geometry(h, n, ny, nx, t.v1.data(), t.w1.data(), t.idx.data(), t.sdf.data(), t.v2.data(), t.w2.data(), h->case_maxs, 0, 0, h->case_wall);
 }
 
 
@@ -181,116 +205,144 @@ int psm_solve_begin(psm_handle* h, const double* cells, int64_t n, int32_t rank,
 
 }  // extern "C"
 
-int psm_impl::mesh_step_begin(psm_handle* h, const double* cells, int64_t n, double* p_out, bool delta) {
-  if (h->mesh.inflight) return fail(h, PSM_ERR_STATE, "a psm_solve_begin is already in flight on this handle: call psm_solve_end first");
-  if (h->mcs.ready) return fail(h, PSM_ERR_STATE, "the handle holds the case set of psm_set_geometry_cases: psm_solve needs the single mesh of psm_set_geometry (use psm_solve_cases*)");
+namespace psm_impl {
+
+int mesh_step_check(psm_handle* h, const double* cells, int64_t n, const double* p_out, bool prime) {
+  if (h->mesh.inflight)
+    return fail(h, PSM_ERR_STATE, prime ? "a step is in flight on this handle: call psm_solve_end first"
+                                        : "a psm_solve_begin is already in flight on this handle: call psm_solve_end first");
+  if (h->mcs.ready)
+    return fail(h, PSM_ERR_STATE, prime ? "the handle holds the case set of psm_set_geometry_cases: use psm_delta_prime_cases"
+                                        : "the handle holds the case set of psm_set_geometry_cases: psm_solve needs the single mesh of psm_set_geometry (use psm_solve_cases*)");
   if (!h->have_geometry || !h->planned)
     return fail(h, PSM_ERR_STATE, "psm_set_geometry has not been called (or the plan it belonged to was dropped by a later psm_set_* / psm_plan_grid)");
-  if (h->cfg.c_in != 3 || h->cfg.c_out != 1) return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292)");
-  if (!h->have_g2m) return fail(h, PSM_ERR_STATE, "psm_set_geometry was called without the grid->mesh tables");
-  if (!cells || !p_out) return fail(h, PSM_ERR_ARG, "null buffer");
+  if (!prime) {
+    if (h->cfg.c_in != 3 || h->cfg.c_out != 1) return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292)");
+    if (!h->have_g2m) return fail(h, PSM_ERR_STATE, "psm_set_geometry was called without the grid->mesh tables");
+  }
+  if (!cells || (!prime && !p_out)) return fail(h, PSM_ERR_ARG, "null buffer");
   if (n != h->n_cells) return fail(h, PSM_ERR_ARG, "cell count differs from the geometry");
+  return PSM_OK;
+}
+
+int step_end(psm_handle* h, MeshBuffers& b, int64_t total_cells, const char* begin_name) {
+  if (!b.inflight) return fail(h, PSM_ERR_STATE, std::string("no ") + begin_name + " in flight");
   HIPCHK(h, hipSetDevice(h->cfg.device));
+  b.inflight = false;
+  HIPCHK(h, wait_stream(h->stream));
+  if (b.copy_out) memcpy(b.copy_out, b.h_p, (size_t)total_cells * sizeof(double));
+  return PSM_OK;
+}
+
+// ---- the route of a step on the single mesh, chosen once (like choose_route of a solve, psm_api_solve.cpp) --------------------------
+// Its environment switches, read here and nowhere else.  Once per process, at the first step: PSM_MESH_GRAPH (registered + mapped
+// buffers: 0 = the staged route, 1 = one graph replay, 2 = the same sequence as plain launches, the measured default, DESIGN.md
+// section 5), PSM_MESH_STAGE_MAX (largest mesh psm_stage_cells_kernel reads over PCIe), PSM_DEVICE_UMAX (set: small meshes reduce
+// U_max by psm_umax_kernel, not on the host).  At every psm_pin_buffers: PSM_NO_DIRECT_IN / _OUT (set: no mapped address, DMA only).
+struct MeshEnv { int graph_mode; int64_t stage_max; bool device_umax; };
+static const MeshEnv& mesh_env() {
+  static const MeshEnv env{getenv("PSM_MESH_GRAPH") ? atoi(getenv("PSM_MESH_GRAPH")) : 2,
+                           getenv("PSM_MESH_STAGE_MAX") ? atoll(getenv("PSM_MESH_STAGE_MAX")) : PSM_MESH_STAGE_MAX_DEFAULT, getenv("PSM_DEVICE_UMAX") != nullptr};
+  return env;
+}
+static bool mesh_env_direct(bool out) { return getenv(out ? "PSM_NO_DIRECT_OUT" : "PSM_NO_DIRECT_IN") == nullptr; }
+
+// mapped_*: both arrays registered (psm_pin_buffers) and mapped -- psm_stage_cells_kernel reads the cells over PCIe and takes the
+// partial maxima of U_max on the way (no DMA-engine copy, no host pass, U_max never leaves the device: to_grid reduces the partials
+// and hands the scalar to to_mesh through d_umax), to_grid, the kernels of the solve, to_mesh storing p straight into the caller's
+// array; as ONE hipGraph replay or as plain launches.  A delta step stays off it.
+// staged: a DMA copy in; U_max on the host while that copy is in flight (one launch less), by psm_umax_kernel, or for large meshes
+// (the host pass would take longer than the copy it hides under) by the parallel reduction whose partials every to_grid workgroup
+// folds itself; none for the priming step of a delta state, which is the last launch alone, p = cells[:,4].
+enum class MeshRouteKind { mapped_graph, mapped_plain, staged };
+enum class UmaxFrom { none, host, device_scalar, partials };
+struct MeshRoute { MeshRouteKind kind; UmaxFrom umax; bool direct_p; };   // direct_p: to_mesh stores p over PCIe into the registered output, no D2H copy
+static MeshRoute choose_mesh_route(const psm_handle* h, const double* cells, int64_t n, const double* p_out, bool delta) {
+  const MeshEnv& env = mesh_env();
+  const MeshSingle& m = h->mesh;
+  if (!delta && env.graph_mode != 0 && h->timed_kernel < 0 && n <= env.stage_max && cells == m.pinned_cells && m.pinned_cells_dev && p_out == m.pinned_p && m.pinned_p_dev)
+    return MeshRoute{env.graph_mode == 2 ? MeshRouteKind::mapped_plain : MeshRouteKind::mapped_graph, UmaxFrom::partials, true};
+  const UmaxFrom umax = delta && !h->delta.primed ? UmaxFrom::none : n > 32768 ? UmaxFrom::partials : env.device_umax ? UmaxFrom::device_scalar : UmaxFrom::host;
+  return MeshRoute{MeshRouteKind::staged, umax, p_out == m.pinned_p && m.pinned_p_dev != nullptr};
+}
+
+// U_max = max sqrt(Ux^2 + Uy^2) (PM:270) on the host: sqrt is monotonic and correctly rounded on both sides, so
+// sqrt(max(Ux^2 + Uy^2)) is the kernel's value bit for bit (NaN propagates like np.max).
+static double host_umax(const double* cells, int64_t n) {
+  double m2 = 0.0; bool nan = false;
+  for (int64_t i = 0; i < n; ++i) {
+    const double ux = cells[i * 5], uy = cells[i * 5 + 1];
+    const double v = ux * ux + uy * uy;
+    nan = nan || (v != v);
+    m2 = v > m2 ? v : m2;
+  }
+  return nan ? std::nan("") : std::sqrt(m2);
+}
+
+static int mesh_step_mapped(psm_handle* h, int64_t n, bool graph) {
   MeshSingle& m = h->mesh;
   hipStream_t st = h->stream;
-  { int rc0 = ensure_encode_aux(h, 1); if (rc0) return rc0; }   // many-block cases (the shipped 104-block shape): the M-tiled encode's split basis, once, outside any capture
-  // Both arrays registered (psm_pin_buffers) and mapped: the whole call is ONE hipGraph replay -- psm_stage_cells_kernel reads
-  // the cells over PCIe and takes the partial maxima of U_max on the way (no DMA-engine copy, no host pass, U_max never leaves
-  // the device: to_grid reduces the partials and hands the scalar to to_mesh through d_umax), to_grid, the kernels of the
-  // solve, to_mesh storing p straight into the caller's array.
-  // PSM_MESH_GRAPH: 0 = the separate submissions below (DMA copy, host U_max), 1 = one graph replay, 2 = the same sequence as
-  // plain launches (measured default)
-  static const int mesh_mode = getenv("PSM_MESH_GRAPH") ? atoi(getenv("PSM_MESH_GRAPH")) : 2;
-  static const int64_t stage_max = getenv("PSM_MESH_STAGE_MAX") ? atoll(getenv("PSM_MESH_STAGE_MAX")) : PSM_MESH_STAGE_MAX_DEFAULT;
-  if (!delta && mesh_mode != 0 && h->timed_kernel < 0 && n <= stage_max && cells == m.pinned_cells && m.pinned_cells_dev && p_out == m.pinned_p && m.pinned_p_dev) {
-    h->last_cases = 1;
-    if (mesh_mode == 2) {
-      int rc = mesh_sequence(h, n, st);
-      if (rc) return rc;
-    } else {
-      if (!m.graph) {
-        int rc = capture_graph(h, st, "psm_solve", [&] { return mesh_sequence(h, n, st); }, &m.graph);
-        if (rc) return rc;
-        m.graph_left = h->last;
-      } else {
-        h->last = m.graph_left;
-      }
-      HIPCHK(h, hipGraphLaunch(m.graph, st));
-    }
-    m.copy_out = nullptr;
-    m.inflight = true;
-    return PSM_OK;
-  }
-  if (cells == m.pinned_cells) {            // registered by the caller: DMA straight from its buffer
-    HIPCHK(h, hipMemcpyAsync(m.d_cells, cells, (size_t)n * 5 * sizeof(double), hipMemcpyHostToDevice, st));
+  h->last_cases = 1;
+  m.copy_out = nullptr;
+  if (!graph) return mesh_sequence(h, n, st);
+  if (!m.graph) {
+    int rc = capture_graph(h, st, "psm_solve", [&] { return mesh_sequence(h, n, st); }, &m.graph);
+    if (rc) return rc;
+    m.graph_left = h->last;
   } else {
-    memcpy(m.h_cells, cells, (size_t)n * 5 * sizeof(double));
-    HIPCHK(h, hipMemcpyAsync(m.d_cells, m.h_cells, (size_t)n * 5 * sizeof(double), hipMemcpyHostToDevice, st));
+    h->last = m.graph_left;
   }
-  // U_max = max sqrt(Ux^2 + Uy^2) (PM:270) on the host while the copy above is in flight: sqrt is monotonic and
-  // correctly rounded on both sides, so sqrt(max(Ux^2 + Uy^2)) is the kernel's value bit for bit (NaN propagates
-  // like np.max); one launch less.  PSM_DEVICE_UMAX=1 keeps the device reduction.
-  // Large meshes (the host pass would take longer than the copy it hides under): parallel device reduction, whose
-  // per-workgroup maxima every psm_to_grid workgroup folds itself.
-  static const bool dev_umax_env = getenv("PSM_DEVICE_UMAX") != nullptr;
-  const bool prime = delta && !h->delta.primed;           // the priming step: the last launch alone, p = cells[:,4]
-  const bool big = n > 32768 && !prime;
-  const bool dev_umax = dev_umax_env && !big && !prime;
+  HIPCHK(h, hipGraphLaunch(m.graph, st));
+  return PSM_OK;
+}
+
+static int mesh_step_staged(psm_handle* h, const double* cells, int64_t n, double* p_out, bool delta, const MeshRoute& r) {
+  MeshSingle& m = h->mesh;
+  hipStream_t st = h->stream;
+  const bool reg_in = cells == m.pinned_cells, reg_out = p_out == m.pinned_p;   // registered by the caller: DMA straight from / into its buffer
+  if (!reg_in) memcpy(m.h_cells, cells, (size_t)n * 5 * sizeof(double));
+  HIPCHK(h, hipMemcpyAsync(m.d_cells, reg_in ? cells : m.h_cells, (size_t)n * 5 * sizeof(double), hipMemcpyHostToDevice, st));
+  const bool prime = r.umax == UmaxFrom::none;
   double umax_val = 0.0;
   int n_partials = 0;
-  if (prime) {
-    // nothing is scaled: no U_max
-  } else if (big) {
-    HIPCHK(h, psm_launch_umax_partial(m.d_cells, n, m.d_umax_part, &n_partials, st));
-  } else if (dev_umax) {
-    HIPCHK(h, psm_launch_umax(m.d_cells, n, m.d_umax, st));
-  } else {
-    double m2 = 0.0; bool nan = false;
-    for (int64_t i = 0; i < n; ++i) {
-      const double ux = cells[i * 5], uy = cells[i * 5 + 1];
-      const double v = ux * ux + uy * uy;
-      nan = nan || (v != v);
-      m2 = v > m2 ? v : m2;
-    }
-    umax_val = nan ? std::nan("") : std::sqrt(m2);
-  }
-  // to_grid must not take the scalar in the `big` case: it folds the partials itself and only then leaves U_max in d_umax, for to_mesh
-  const double* d_umax = (dev_umax || big) ? m.d_umax : nullptr;
+  if (r.umax == UmaxFrom::partials) HIPCHK(h, psm_launch_umax_partial(m.d_cells, n, m.d_umax_part, &n_partials, st));
+  else if (r.umax == UmaxFrom::device_scalar) HIPCHK(h, psm_launch_umax(m.d_cells, n, m.d_umax, st));
+  else if (r.umax == UmaxFrom::host) umax_val = host_umax(cells, n);   // while the copy above is in flight
   if (!prime) {
-    const PsmToGridArgs ga = to_grid_args(h, dev_umax ? m.d_umax : nullptr, umax_val, n_partials);
+    // to_grid must not take the scalar with partials: it folds them itself and only then leaves U_max in d_umax, for to_mesh
+    const PsmToGridArgs ga = to_grid_args(h, r.umax == UmaxFrom::device_scalar ? m.d_umax : nullptr, umax_val, n_partials);
     HIPCHK(h, delta ? psm_launch_to_grid_delta(PsmDeltaGridArgs{ga, h->delta.d_u_prev}, st) : psm_launch_to_grid(ga, st));
     h->in_mesh_solve = true;
     int rc = solve_device(h, h->d_grid_stage, 1, nullptr, h->d_fields_stage, st, nullptr);
     h->in_mesh_solve = false;
     if (rc) return rc;
   }
-  const bool direct = p_out == m.pinned_p && m.pinned_p_dev != nullptr;
-  // direct: 8 bytes per cell over PCIe from the kernel itself, no D2H copy
-  const PsmToMeshArgs ma = to_mesh_args(h, d_umax, umax_val, direct ? m.pinned_p_dev : m.d_p);
+  const double* d_umax = (r.umax == UmaxFrom::device_scalar || r.umax == UmaxFrom::partials) ? m.d_umax : nullptr;
+  const PsmToMeshArgs ma = to_mesh_args(h, d_umax, umax_val, r.direct_p ? m.pinned_p_dev : m.d_p);
   HIPCHK(h, delta ? psm_launch_to_mesh_delta(PsmDeltaMeshArgs{ma, h->delta.d_u_prev, prime}, st) : psm_launch_to_mesh(ma, st));
-  if (delta) { h->delta.steps += h->delta.primed; h->delta.primed = true; }   // the whole chain is enqueued: the state has advanced
-  if (p_out == m.pinned_p) {
-    if (!direct) HIPCHK(h, hipMemcpyAsync(p_out, m.d_p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    m.copy_out = nullptr;
-  } else {
-    HIPCHK(h, hipMemcpyAsync(m.h_p, m.d_p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
-    m.copy_out = p_out;
-  }
-  m.inflight = true;
+  if (delta) delta_advance(h);
+  if (!r.direct_p) HIPCHK(h, hipMemcpyAsync(reg_out ? p_out : m.h_p, m.d_p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+  m.copy_out = reg_out ? nullptr : p_out;
   return PSM_OK;
 }
+
+int mesh_step_begin(psm_handle* h, const double* cells, int64_t n, double* p_out, bool delta) {
+  int rc = mesh_step_check(h, cells, n, p_out, false);
+  if (rc) return rc;
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  if ((rc = ensure_encode_aux(h, 1))) return rc;   // many-block cases (the shipped 104-block shape): the M-tiled encode's split basis, once, outside any capture
+  const MeshRoute r = choose_mesh_route(h, cells, n, p_out, delta);
+  rc = r.kind == MeshRouteKind::staged ? mesh_step_staged(h, cells, n, p_out, delta, r) : mesh_step_mapped(h, n, r.kind == MeshRouteKind::mapped_graph);
+  if (rc) return rc;
+  h->mesh.inflight = true;
+  return PSM_OK;
+}
+
+}  // namespace psm_impl
 
 extern "C" {
 
-int psm_solve_end(psm_handle* h) {
-  if (!h) return PSM_ERR_ARG;
-  if (!h->mesh.inflight) return fail(h, PSM_ERR_STATE, "no psm_solve_begin in flight");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->mesh.inflight = false;
-  HIPCHK(h, wait_stream(h->stream));
-  if (h->mesh.copy_out) memcpy(h->mesh.copy_out, h->mesh.h_p, (size_t)h->n_cells * sizeof(double));
-  return PSM_OK;
-}
+int psm_solve_end(psm_handle* h) { return h ? step_end(h, h->mesh, h->n_cells, "psm_solve_begin") : PSM_ERR_ARG; }
 
 
 int psm_solve(psm_handle* h, const double* cells, int64_t n, int32_t rank, double* p_out) {
@@ -322,16 +374,8 @@ int psm_set_geometry_cases(psm_handle* h, int32_t n_cases, const int64_t* n_cell
   for (int k = 0; k < 4; ++k) h->maxs[k] = maxs[k];
   h->normalise_sdf = normalise_sdf; h->fill_input = fill_input;
   const int n_parts = (int)std::min<int64_t>(PSM_MESH_CASE_PARTS, (t.max_cells + 4095) / 4096);
-  const size_t total = (size_t)t.total;
-  hipError_t e = hipSuccess;
-  if ((rc = mesh_tables_upload(h, m.t, t)) || (rc = dev_alloc(h, &m.d_cells, total * 5)) || (rc = dev_alloc(h, &m.d_p, total)) ||
-      (rc = dev_alloc(h, &m.d_umax, (size_t)n_cases)) || (rc = dev_alloc(h, &m.d_umax_part, (size_t)n_cases * n_parts)) ||
-      (rc = dev_alloc(h, &h->delta.d_u_prev, total * 2))) { mesh_cases_free(h); return rc; }
-  if ((e = hipHostMalloc((void**)&m.h_cells, total * 5 * sizeof(double), hipHostMallocDefault)) != hipSuccess ||
-      (e = hipHostMalloc((void**)&m.h_p, total * sizeof(double), hipHostMallocDefault)) != hipSuccess) {
-    mesh_cases_free(h);
-    return fail(h, PSM_ERR_NOMEM, std::string("hipHostMalloc(case set staging): ") + hipGetErrorString(e));
-  }
+  if ((rc = mesh_tables_upload(h, m.t, t)) ||
+      (rc = mesh_buffers_alloc(h, m, (size_t)t.total, (size_t)n_cases, (size_t)n_cases * n_parts, PSM_ERR_NOMEM, "case set staging"))) { mesh_cases_free(h); return rc; }
   PsmMeshCasesArgs& a = m.args;
   a = PsmMeshCasesArgs{};
   a.cell_off = m.t.off; a.umax_part = m.d_umax_part; a.umax = m.d_umax; a.n_parts = n_parts; a.n_cases = n_cases;
@@ -372,17 +416,13 @@ int psm_init_geometry_cases(psm_handle* h, int32_t n_cases, const double* const*
       return fail(h, PSM_ERR_ARG, "case " + std::to_string(k) + ": grid shape " + std::to_string(nyk) + " x " + std::to_string(nxk) + " differs from case 0's " +
                                       std::to_string(ny) + " x " + std::to_string(nx));
   }
-  const size_t ng = (size_t)ny * nx;
-  std::vector<std::vector<int32_t>> v1(n_cases), idx(n_cases), v2(n_cases);
-  std::vector<std::vector<double>> w1(n_cases), sdf(n_cases), w2(n_cases);
+  std::vector<GeometryTables> t(n_cases);
   std::vector<const int32_t*> pv1(n_cases), pidx(n_cases), pv2(n_cases);
   std::vector<const double*> pw1(n_cases), psdf(n_cases), pw2(n_cases);
   for (int k = 0; k < n_cases; ++k) {
-    v1[k].resize(ng * 3); w1[k].resize(ng * 3); idx[k].resize(ng * 2); sdf[k].resize(ng); v2[k].resize((size_t)n[k] * 3); w2[k].resize((size_t)n[k] * 3);
-    const int rc = psm_geometry_build(cells[k], n[k], top[k], n_top[k], obst[k], n_obst[k], h->case_delta, h->case_every, v1[k].data(), w1[k].data(),
-                                      idx[k].data(), sdf[k].data(), v2[k].data(), w2[k].data());
-    if (rc) return fail(h, rc, "case " + std::to_string(k) + ": " + psm_geometry_last_error());
-    pv1[k] = v1[k].data(); pw1[k] = w1[k].data(); pidx[k] = idx[k].data(); psdf[k] = sdf[k].data(); pv2[k] = v2[k].data(); pw2[k] = w2[k].data();
+    const int rc = geometry_tables_build(h, "case " + std::to_string(k) + ": ", cells[k], n[k], top[k], n_top[k], obst[k], n_obst[k], ny, nx, t[k]);
+    if (rc) return rc;
+    pv1[k] = t[k].v1.data(); pw1[k] = t[k].w1.data(); pidx[k] = t[k].idx.data(); psdf[k] = t[k].sdf.data(); pv2[k] = t[k].v2.data(); pw2[k] = t[k].w2.data();
   }
   return psm_set_geometry_cases(h, n_cases, n, ny, nx, pv1.data(), pw1.data(), pidx.data(), psdf.data(), pv2.data(), pw2.data(), h->case_maxs, 0, 0,
                                 h->case_wall);
@@ -444,12 +484,7 @@ extern "C" {
 
 int psm_solve_cases_end(psm_handle* h) {
   if (!h) return PSM_ERR_ARG;
-  if (!h->mcs.inflight) return fail(h, PSM_ERR_STATE, "no psm_solve_cases_begin in flight");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  h->mcs.inflight = false;
-  HIPCHK(h, wait_stream(h->stream));
-  if (h->mcs.copy_out) memcpy(h->mcs.copy_out, h->mcs.h_p, (size_t)h->mcs.off[h->mcs.n_cases] * sizeof(double));
-  return PSM_OK;
+  return step_end(h, h->mcs, h->mcs.inflight ? h->mcs.off[h->mcs.n_cases] : 0, "psm_solve_cases_begin");
 }
 
 
@@ -471,7 +506,7 @@ int psm_pin_buffers(psm_handle* h, const double* cells, double* p_out) {
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, PSM_ERR_HIP, std::string("hipHostRegister(cells): ") + hipGetErrorString(e)); }
     h->mesh.pinned_cells = cells;
     void* dc = nullptr;                                   // mapped address: lets psm_stage_cells_kernel read the cells from the host array
-    if (hipHostGetDevicePointer(&dc, (void*)cells, 0) == hipSuccess && getenv("PSM_NO_DIRECT_IN") == nullptr) h->mesh.pinned_cells_dev = (const double*)dc;
+    if (hipHostGetDevicePointer(&dc, (void*)cells, 0) == hipSuccess && mesh_env_direct(false)) h->mesh.pinned_cells_dev = (const double*)dc;
     else (void)hipGetLastError();
   }
   if (p_out) {
@@ -479,7 +514,7 @@ int psm_pin_buffers(psm_handle* h, const double* cells, double* p_out) {
     if (e != hipSuccess) { (void)hipGetLastError(); unpin_buffers(h); return fail(h, PSM_ERR_HIP, std::string("hipHostRegister(p_out): ") + hipGetErrorString(e)); }
     h->mesh.pinned_p = p_out;
     void* dp = nullptr;                                   // mapped address: lets psm_to_mesh_kernel store p into the host array
-    if (hipHostGetDevicePointer(&dp, (void*)p_out, 0) == hipSuccess && getenv("PSM_NO_DIRECT_OUT") == nullptr) h->mesh.pinned_p_dev = (double*)dp;
+    if (hipHostGetDevicePointer(&dp, (void*)p_out, 0) == hipSuccess && mesh_env_direct(true)) h->mesh.pinned_p_dev = (double*)dp;
     else (void)hipGetLastError();
   }
   return PSM_OK;

@@ -179,10 +179,7 @@ void unpin_buffers(psm_handle* h) {
 
 void mesh_cases_free(psm_handle* h) {
   MeshCaseSet& m = h->mcs;
-  mesh_tables_free(m.t);
-  dev_free(m.d_cells); dev_free(m.d_p); dev_free(m.d_umax); dev_free(m.d_umax_part);
-  if (m.h_cells) { (void)hipHostFree(m.h_cells); m.h_cells = nullptr; }
-  if (m.h_p) { (void)hipHostFree(m.h_p); m.h_p = nullptr; }
+  mesh_buffers_free(m);
   m.ready = false; m.inflight = false; m.n_cases = 0; m.off.clear();
   delta_drop(h);                        // U(t-1) of the delta step belongs to the cells that go here
 }
@@ -192,12 +189,8 @@ void free_geometry(psm_handle* h) {
   unpin_buffers(h);
   mesh_cases_free(h);
   frames_free(h);                       // the frame batch reads this mesh's tables
-  MeshSingle& m = h->mesh;
-  mesh_tables_free(m.t);
-  dev_free(m.d_cells); dev_free(m.d_p); dev_free(m.d_umax); dev_free(m.d_umax_part);
+  mesh_buffers_free(h->mesh);
   integ_free(h->integ_host); integ_free(h->integ_dev);
-  if (m.h_cells) { (void)hipHostFree(m.h_cells); m.h_cells = nullptr; }
-  if (m.h_p) { (void)hipHostFree(m.h_p); m.h_p = nullptr; }
   h->have_geometry = false;
 }
 

@@ -13,7 +13,7 @@
 //   psm_api_features.cpp    the pressureSM_Poisson input features: the host entry psm_poisson_features; on the device psm_bind_features, psm_features_device and the whole step psm_poisson_step*
 //   psm_api_frames.cpp      frames of cell columns -> planes on the device: psm_bind_frames, psm_frames_to_grid_device and the evaluator's step psm_poisson_frames*
 //   psm_api_errors.cpp      the per-frame error blocks of assembled fields on the device: psm_field_errors_device and the metrics-only frame step psm_poisson_frames_errors* (host arithmetic: psm_errors.cpp)
-//   psm_api_deltas_frames.cpp  the deltas evaluator's frame batch on the device: psm_bind_deltas_frames, the image pack psm_deltas_image_device, the batched block errors psm_block_errors_device and the step psm_deltas_frames*
+//   psm_api_deltas_frames.cpp  the deltas evaluator's frame batch on the device: psm_bind_deltas_frames, the image pack psm_deltas_image_device (kernels of the three packs: psm_pack.hip), the batched block errors psm_block_errors_device and the step psm_deltas_frames*
 //   psm_api_gradp_frames.cpp   the U_to_gradP evaluator's frame batch on the device: psm_bind_gradp_frames, the image / label pack psm_gradp_image_device and the step psm_gradp_frames* (columns -> p -> errors)
 //   psm_api_chapter4_frames.cpp  the Chapter-4 evaluators' frame batch on the device: psm_bind_chapter4_frames, the image / label pack psm_chapter4_image_device and the step psm_chapter4_frames* (columns -> p -> errors)
 //   psm_api_rows.cpp        a frame's dataset rows -> scalars + columns on the device: psm_bind_rows, the stage alone psm_rows_prepare_device and the evaluators' steps behind it, psm_deltas_rows* / psm_poisson_rows* / psm_gradp_rows*
@@ -42,6 +42,7 @@
 #include "../../include/psm.h"
 #include "psm_kernels.h"
 #include "psm_mesh.h"
+#include "psm_pack.h"
 #include "psm_rows.h"
 #include "psm_eval.h"
 #include "psm_filter.h"
@@ -273,33 +274,33 @@ struct MeshTablesDev {
   uint8_t* near_wall = nullptr;
 };
 
-// The single mesh of psm_set_geometry: its tables and every buffer a psm_solve touches, so that a step allocates nothing.
-struct MeshSingle {
+// What the single mesh and the case set hold alike: the tables and every buffer a step touches, so that a step allocates nothing.
+// Allocated by mesh_buffers_alloc (with U(t-1) of the delta step, DeltaState below), released by mesh_buffers_free (psm_api_mesh.cpp).
+struct MeshBuffers {
   MeshTablesDev t;
-  double *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;   // staged cells, p, U_max, <= 256 partials
-  double *h_cells = nullptr, *h_p = nullptr;   // pinned staging
+  double *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;   // staged cells, p, U_max (one per case), partial maxima
+  double *h_cells = nullptr, *h_p = nullptr;   // pinned staging of the host entries
+  bool inflight = false;                // a *_begin is enqueued, its *_end not yet called
+  double* copy_out = nullptr;           // where *_end copies p to (null: it was DMA'd / stored into the caller's registered array)
+};
+
+// The single mesh of psm_set_geometry.  d_umax is one scalar, d_umax_part holds <= 256 partials.
+struct MeshSingle : MeshBuffers {
   const double* pinned_cells = nullptr;   // caller buffers registered with psm_pin_buffers (DMA without staging copies)
   double* pinned_p = nullptr;
   double* pinned_p_dev = nullptr;       // device-side address of the registered output (the last kernel writes p straight into it)
   const double* pinned_cells_dev = nullptr;   // device-side address of the registered input (psm_stage_cells_kernel reads it over PCIe)
   hipGraphExec_t graph = nullptr;       // psm_solve on registered buffers: stage + to_grid + the solve + to_mesh as ONE graph replay
   Ws0Solve graph_left;                  // what `graph` leaves on ws0
-  bool inflight = false;                // psm_solve_begin enqueued, psm_solve_end not yet called
-  double* copy_out = nullptr;           // where psm_solve_end copies p to (null: it was DMA'd / stored into the caller's registered array)
 };
 
-// The case set of psm_set_geometry_cases: K meshes on the planned grid, their tables in the layout of PsmMeshCasesArgs and every
-// buffer a step touches, so that a step allocates nothing.  A handle holds this or the single mesh of psm_set_geometry.
-struct MeshCaseSet {
+// The case set of psm_set_geometry_cases: K meshes on the planned grid, their tables in the layout of PsmMeshCasesArgs (d_umax [K],
+// d_umax_part [K][n_parts]).  A handle holds this or the single mesh of psm_set_geometry.
+struct MeshCaseSet : MeshBuffers {
   bool ready = false;
   int n_cases = 0;
   std::vector<int64_t> off;             // [n_cases + 1] host copy of t.off
-  MeshTablesDev t;
-  double *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;   // staged cells, p, U_max[K], partials [K][n_parts]
-  double *h_cells = nullptr, *h_p = nullptr;   // pinned staging of the host entries
   PsmMeshCasesArgs args{};              // everything but cells / p_out, which are the call's
-  bool inflight = false;                // psm_solve_cases_begin enqueued, psm_solve_cases_end not yet called
-  double* copy_out = nullptr;           // where psm_solve_cases_end copies p to (null: it was DMA'd into the caller's registered array)
 };
 
 // The state of the delta step (psm_solve_delta*, psm_solve_cases_delta*; psm_api_delta.cpp): U(t-1) per cell of the single mesh or of
@@ -592,6 +593,10 @@ void free_geometry(psm_handle* h);
 void mesh_cases_free(psm_handle* h);
 int mesh_tables_upload(psm_handle* h, MeshTablesDev& dev, const PsmMeshCaseTables& t);
 void mesh_tables_free(MeshTablesDev& dev);
+// every device and pinned buffer of `b` for total_cells cells, and U(t-1) of the delta step; the tables are the caller's upload.  A
+// failure leaves what was allocated to the caller's free function; a failed pinned allocation is host_alloc_err, "hipHostMalloc(<what>): ..."
+int mesh_buffers_alloc(psm_handle* h, MeshBuffers& b, size_t total_cells, size_t n_umax, size_t n_partials, int host_alloc_err, const char* what);
+void mesh_buffers_free(MeshBuffers& b);   // tables and buffers; U(t-1) goes with delta_drop
 void integ_free(IntegSet& s);
 int integ_bind(psm_handle* h, IntegSet& s, int ny, int nx, const double* sdfunct, int n_cases, const int32_t* cy, const int32_t* cx,
                double dx, double dy, bool one_geometry = false);
@@ -641,6 +646,9 @@ PsmToMeshArgs to_mesh_args(const psm_handle* h, const double* d_umax, double uma
 // checks, copies and launches; `delta` swaps the two mesh ends for their delta forms, keeps off the one-kernel staging route of
 // registered buffers and, on a state that is not primed, enqueues the priming step instead (no U_max, no network).
 int mesh_step_begin(psm_handle* h, const double* cells, int64_t n, double* p_out, bool delta);
+// the state and argument checks of a step on the single mesh, in the step's order; `prime`: those of psm_delta_prime (no p_out, no solve)
+int mesh_step_check(psm_handle* h, const double* cells, int64_t n, const double* p_out, bool prime);
+int step_end(psm_handle* h, MeshBuffers& b, int64_t total_cells, const char* begin_name);   // behind psm_solve_end and psm_solve_cases_end
 int cases_check(psm_handle* h);
 int cases_step_device(psm_handle* h, const double* d_cells, double* d_p, void* stream, bool delta);
 int cases_step_begin(psm_handle* h, const double* cells, double* p_out, bool delta);

@@ -46,18 +46,14 @@ __global__ __launch_bounds__(1024) void psm_umax_kernel(const double* cells, int
   double m = 0.0;
   for (int64_t i = tid; i < n; i += 1024) {
     const double ux = cells[i * 5], uy = cells[i * 5 + 1];
-    const double v = speed2_np(ux, uy);
-    m = (v > m || v != v) ? v : m;          // np.max propagates NaN
+    m = nanmax2(m, speed2_np(ux, uy));
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    const double other = __shfl_down(m, o, 64);
-    m = (other > m || other != other) ? other : m;
-  }
+  for (int o = 32; o > 0; o >>= 1) m = nanmax2(m, __shfl_down(m, o, 64));
   if (lane == 0) red[wave] = m;
   __syncthreads();
   if (tid == 0) {
     double r = red[0];
-    for (int w = 1; w < 16; ++w) r = (red[w] > r || red[w] != red[w]) ? red[w] : r;
+    for (int w = 1; w < 16; ++w) r = nanmax2(r, red[w]);
     *umax = sqrt_rn(r);
   }
 }
@@ -246,7 +242,11 @@ hipError_t psm_launch_stage_cells(const double* host_cells, double* cells, int64
   return hipGetLastError();
 }
 
-__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmToGridArgs a) {
+// ---------------------------------------------------------------------------
+// One wrapper per end and batch form: where U_max comes from, the bounds check, the cell body.  The kernels below are a call of
+// one of them each.  The argument structs go BY VALUE: behind a reference the uniform load of *a.umax becomes a load per lane.
+template <bool DELTA>
+__device__ __forceinline__ void to_grid_single(PsmToGridArgs a, const double* u_prev) {
   double umax_v = a.umax ? *a.umax : a.umax_val;
   if (a.umax_partials) {                      // uniform: every workgroup reduces the <= 256 partial maxima itself
     umax_v = umax_of_partials(a.umax_partials, a.n_partials);
@@ -254,35 +254,23 @@ __global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmToGridArgs a) {
   }
   const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (cell >= a.n_grid) return;
-  to_grid_cell<false>(a, nullptr, umax_v, cell);
+  to_grid_cell<DELTA>(a, u_prev, umax_v, cell);
 }
 
-__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmToMeshArgs a) {
+// `prime` (delta only): nothing is scaled, U_max is not read
+template <bool DELTA>
+__device__ __forceinline__ void to_mesh_single(PsmToMeshArgs a, double* u_prev, int prime) {
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (n >= a.n_cells) return;
-  to_mesh_cell<false>(a, nullptr, 0, a.umax ? *a.umax : a.umax_val, n);
+  to_mesh_cell<DELTA>(a, u_prev, prime, prime ? 0.0 : (a.umax ? *a.umax : a.umax_val), n);
 }
 
-// The delta forms of the two kernels above (PsmDeltaGridArgs / PsmDeltaMeshArgs in psm_mesh.h): the same launch shapes and the same
-// three sources of U_max, the DELTA bodies.
-__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmDeltaGridArgs d) {
-  const PsmToGridArgs& a = d.g;
-  double umax_v = a.umax ? *a.umax : a.umax_val;
-  if (a.umax_partials) {
-    umax_v = umax_of_partials(a.umax_partials, a.n_partials);
-    if (blockIdx.x == 0 && threadIdx.x == 0) *a.umax_out = umax_v;
-  }
-  const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (cell >= a.n_grid) return;
-  to_grid_cell<true>(a, d.u_prev, umax_v, cell);
-}
-
-__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmDeltaMeshArgs d) {
-  const PsmToMeshArgs& a = d.m;
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= a.n_cells) return;
-  to_mesh_cell<true>(a, d.u_prev, d.prime, d.prime ? 0.0 : (a.umax ? *a.umax : a.umax_val), n);
-}
+// The single mesh, absolute and delta (PsmDeltaGridArgs / PsmDeltaMeshArgs in psm_mesh.h): the same launch shapes and the same
+// three sources of U_max.
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmToGridArgs a) { to_grid_single<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmToMeshArgs a) { to_mesh_single<false>(a, nullptr, 0); }
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmDeltaGridArgs d) { to_grid_single<true>(d.g, d.u_prev); }
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmDeltaMeshArgs d) { to_mesh_single<true>(d.m, d.u_prev, d.prime); }
 
 hipError_t psm_launch_umax_partial(const double* cells, int64_t n, double* partials, int* n_partials, hipStream_t st) {
   const int nwg = (int)std::min<int64_t>(256, (n + 4095) / 4096);
@@ -376,200 +364,6 @@ hipError_t psm_launch_frames_to_grid(const PsmFrameArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-// The image pack of the deltas evaluator's frame batch (PsmDeltasPackArgs in psm_mesh.h): what Evaluation.timeStep does on the host
-// between psm_mesh_to_grid and the solve, per pixel and in its order -- NaN -> 0, the division by max_abs in float64, then the float32
-// cast of the solve's entry (SM_call.py:439-445) -- and the frame's truth image (:580).  Two float64 multiplications in a row and no
-// addition: nothing for the compiler to contract, and IEEE division, so the three outputs hold the bits of the NumPy statements.
-// HBM-bound stream: frame blockIdx.y, a thread takes 4 consecutive pixels -- two 16-byte loads per float64 plane, three 16-byte
-// stores of the 12 image floats, one of the labels, two of the truths where the frame's plane starts 16-byte aligned; else (odd
-// plane sizes, shifted destinations, the tail) one access per element.  The values do not depend on the path.
-typedef float psm_pack_f4 __attribute__((ext_vector_type(4)));
-typedef double psm_pack_d2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void pack_load4(const double* p, int64_t pix, int n, bool vec, double (&v)[4]) {
-  if (vec) {
-    const psm_pack_d2 q0 = *reinterpret_cast<const psm_pack_d2*>(p + pix), q1 = *reinterpret_cast<const psm_pack_d2*>(p + pix + 2);
-    v[0] = q0.x; v[1] = q0.y; v[2] = q1.x; v[3] = q1.y;
-    return;
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = e < n ? p[pix + e] : 0.0;
-}
-
-__device__ __forceinline__ bool pack_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmDeltasPackArgs a) {
-  const int64_t frame = blockIdx.y;
-  const int64_t pix = (int64_t)blockIdx.x * PSM_DELTAS_PACK_SPAN + threadIdx.x * 4;
-  if (pix >= a.npix) return;
-  const int n = (int)min((int64_t)4, a.npix - pix);
-  const double* pl = a.planes + frame * 3 * a.npix;
-  double v0[4], v1[4], v2[4], sd[4];
-  pack_load4(pl, pix, n, n == 4 && pack_aligned(pl), v0);
-  pack_load4(pl + a.npix, pix, n, n == 4 && pack_aligned(pl + a.npix), v1);
-  pack_load4(pl + 2 * a.npix, pix, n, n == 4 && pack_aligned(pl + 2 * a.npix), v2);
-  pack_load4(a.sdn, pix, n, n == 4 && pack_aligned(a.sdn), sd);
-  float g[12], lb[4];
-  double tr[4];
-  const double u2 = a.truth ? a.u2[frame] : 0.0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const double x = (v0[e] != v0[e] ? 0.0 : v0[e]) / a.max_abs_ux;
-    const double y = (v1[e] != v1[e] ? 0.0 : v1[e]) / a.max_abs_uy;
-    const double p = (v2[e] != v2[e] ? 0.0 : v2[e]) / a.max_abs_p;
-    g[3 * e] = (float)x; g[3 * e + 1] = (float)y; g[3 * e + 2] = (float)sd[e];
-    lb[e] = (float)p;
-    const double pm = p * a.max_abs_p;
-    tr[e] = pm * u2;
-  }
-  float* go = a.grid + (frame * a.npix + pix) * 3;
-  if (n == 4 && pack_aligned(go)) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) reinterpret_cast<psm_pack_f4*>(go)[q] = psm_pack_f4{g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]};
-  } else {
-    for (int e = 0; e < 3 * n; ++e) go[e] = g[e];
-  }
-  if (a.label) {
-    float* lo = a.label + frame * a.npix + pix;
-    if (n == 4 && pack_aligned(lo)) *reinterpret_cast<psm_pack_f4*>(lo) = psm_pack_f4{lb[0], lb[1], lb[2], lb[3]};
-    else for (int e = 0; e < n; ++e) lo[e] = lb[e];
-  }
-  if (a.truth) {
-    double* to = a.truth + frame * a.npix + pix;
-    if (n == 4 && pack_aligned(to)) {
-      reinterpret_cast<psm_pack_d2*>(to)[0] = psm_pack_d2{tr[0], tr[1]};
-      reinterpret_cast<psm_pack_d2*>(to)[1] = psm_pack_d2{tr[2], tr[3]};
-    } else {
-      for (int e = 0; e < n; ++e) to[e] = tr[e];
-    }
-  }
-}
-
-hipError_t psm_launch_deltas_pack(const PsmDeltasPackArgs& a, hipStream_t st) {
-  if (a.n_frames < 1 || a.npix < 1 || !a.planes || !a.sdn || !a.grid || (a.truth && !a.u2)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(static_cast<void (*)(PsmDeltasPackArgs)>(psm_to_grid_kernel),
-                     dim3((unsigned)((a.npix + PSM_DELTAS_PACK_SPAN - 1) / PSM_DELTAS_PACK_SPAN), (unsigned)a.n_frames), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-// The image / label pack of the U_to_gradP evaluator's frame batch (PsmGradpPackArgs in psm_mesh.h): what EvaluationGradP.timeStep
-// does on the host between psm_mesh_to_grid and the solve, per pixel and in its order -- NaN -> 0, the division by the channel's
-// max_abs in float64, then the float32 cast of the solve's entry (Eval_dual_Dense_onlycil.py:461-467); the label channels 3-5 stay
-// float64, the pressure label undivided.  One IEEE division per value and no addition: nothing to contract, the outputs hold the
-// bits of the NumPy statements.  The access pattern is the deltas pack's: frame blockIdx.y, a thread takes 4 consecutive pixels of
-// every plane, 16-byte accesses where the frame's plane starts 16-byte aligned, one access per element otherwise and in the tail.
-__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmGradpPackArgs a) {
-  const int64_t frame = blockIdx.y;
-  const int64_t pix = (int64_t)blockIdx.x * PSM_DELTAS_PACK_SPAN + threadIdx.x * 4;
-  if (pix >= a.npix) return;
-  const int n = (int)min((int64_t)4, a.npix - pix);
-  const double* pl = a.planes + frame * 5 * a.npix;
-  double v0[4], v1[4], sd[4];
-  pack_load4(pl, pix, n, n == 4 && pack_aligned(pl), v0);
-  pack_load4(pl + a.npix, pix, n, n == 4 && pack_aligned(pl + a.npix), v1);
-  pack_load4(a.sdn, pix, n, n == 4 && pack_aligned(a.sdn), sd);
-  float g[12];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const double x = (v0[e] != v0[e] ? 0.0 : v0[e]) / a.m0;
-    const double y = (v1[e] != v1[e] ? 0.0 : v1[e]) / a.m1;
-    g[3 * e] = (float)x; g[3 * e + 1] = (float)y; g[3 * e + 2] = (float)sd[e];
-  }
-  float* go = a.grid + (frame * a.npix + pix) * 3;
-  if (n == 4 && pack_aligned(go)) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) reinterpret_cast<psm_pack_f4*>(go)[q] = psm_pack_f4{g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]};
-  } else {
-    for (int e = 0; e < 3 * n; ++e) go[e] = g[e];
-  }
-  if (!a.truth) return;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const double* src = pl + (2 + c) * a.npix;
-    const double m = c == 0 ? a.m3 : c == 1 ? a.m4 : 1.0;
-    double v[4], t[4];
-    pack_load4(src, pix, n, n == 4 && pack_aligned(src), v);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const double z = v[e] != v[e] ? 0.0 : v[e];
-      t[e] = c < 2 ? z / m : z;
-    }
-    double* to = a.truth + (frame * 3 + c) * a.npix + pix;
-    if (n == 4 && pack_aligned(to)) {
-      reinterpret_cast<psm_pack_d2*>(to)[0] = psm_pack_d2{t[0], t[1]};
-      reinterpret_cast<psm_pack_d2*>(to)[1] = psm_pack_d2{t[2], t[3]};
-    } else {
-      for (int e = 0; e < n; ++e) to[e] = t[e];
-    }
-  }
-}
-
-hipError_t psm_launch_gradp_pack(const PsmGradpPackArgs& a, hipStream_t st) {
-  if (a.n_frames < 1 || a.npix < 1 || !a.planes || !a.sdn || !a.grid) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(static_cast<void (*)(PsmGradpPackArgs)>(psm_to_grid_kernel),
-                     dim3((unsigned)((a.npix + PSM_DELTAS_PACK_SPAN - 1) / PSM_DELTAS_PACK_SPAN), (unsigned)a.n_frames), dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
-// The image / label pack of the Chapter-4 evaluators' frame batch (PsmChapter4PackArgs in psm_mesh.h): what the two timeStep bodies
-// do on the host between the interpolation and the solve, per pixel and in their order -- NaN -> 0, the division by the channel's
-// max_abs in float64, then the float32 cast of the solve's entry (M_u :215-225, M_fU :213-223); the pressure label stays float64.
-// One IEEE division per value and no addition: nothing to contract, the outputs hold the bits of the NumPy statements.  C_IN is the
-// image width (M_u 3, M_fU 2), a template parameter so that the 4 * C_IN image floats of a thread go out as C_IN 16-byte stores.
-// The access pattern is the deltas pack's: frame blockIdx.y, a thread takes 4 consecutive pixels of every plane, 16-byte accesses
-// where the frame's plane or image starts 16-byte aligned, one access per element otherwise and in the tail.
-template <int C_IN>
-__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmChapter4PackArgs a) {
-  const int64_t frame = blockIdx.y;
-  const int64_t pix = (int64_t)blockIdx.x * PSM_DELTAS_PACK_SPAN + threadIdx.x * 4;
-  if (pix >= a.npix) return;
-  const int n = (int)min((int64_t)4, a.npix - pix);
-  const double* pl = a.planes + frame * C_IN * a.npix;
-  float g[4 * C_IN];
-#pragma unroll
-  for (int c = 0; c < C_IN - 1; ++c) {
-    const double* src = pl + c * a.npix;
-    double v[4];
-    pack_load4(src, pix, n, n == 4 && pack_aligned(src), v);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) g[C_IN * e + c] = (float)((v[e] != v[e] ? 0.0 : v[e]) / a.m[c]);
-  }
-  {
-    double sd[4];
-    pack_load4(a.sdn, pix, n, n == 4 && pack_aligned(a.sdn), sd);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) g[C_IN * e + C_IN - 1] = (float)sd[e];
-  }
-  float* go = a.grid + (frame * a.npix + pix) * C_IN;
-  if (n == 4 && pack_aligned(go)) {
-#pragma unroll
-    for (int q = 0; q < C_IN; ++q) reinterpret_cast<psm_pack_f4*>(go)[q] = psm_pack_f4{g[4 * q], g[4 * q + 1], g[4 * q + 2], g[4 * q + 3]};
-  } else {
-    for (int e = 0; e < C_IN * n; ++e) go[e] = g[e];
-  }
-  if (!a.truth) return;
-  const double* src = pl + (C_IN - 1) * a.npix;
-  double v[4], t[4];
-  pack_load4(src, pix, n, n == 4 && pack_aligned(src), v);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) t[e] = (v[e] != v[e] ? 0.0 : v[e]) / a.m_p;
-  double* to = a.truth + frame * a.npix + pix;
-  if (n == 4 && pack_aligned(to)) {
-    reinterpret_cast<psm_pack_d2*>(to)[0] = psm_pack_d2{t[0], t[1]};
-    reinterpret_cast<psm_pack_d2*>(to)[1] = psm_pack_d2{t[2], t[3]};
-  } else {
-    for (int e = 0; e < n; ++e) to[e] = t[e];
-  }
-}
-
-hipError_t psm_launch_chapter4_pack(const PsmChapter4PackArgs& a, hipStream_t st) {
-  if (a.n_frames < 1 || a.npix < 1 || !a.planes || !a.sdn || !a.grid || (a.c_in != 2 && a.c_in != 3)) return hipErrorInvalidValue;
-  const dim3 wgs((unsigned)((a.npix + PSM_DELTAS_PACK_SPAN - 1) / PSM_DELTAS_PACK_SPAN), (unsigned)a.n_frames);
-  if (a.c_in == 3) hipLaunchKernelGGL(static_cast<void (*)(PsmChapter4PackArgs)>(psm_to_grid_kernel<3>), wgs, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(static_cast<void (*)(PsmChapter4PackArgs)>(psm_to_grid_kernel<2>), wgs, dim3(256), 0, st, a);
-  return hipGetLastError();
-}
-
 hipError_t psm_launch_to_mesh(const PsmToMeshArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(static_cast<void (*)(PsmToMeshArgs)>(psm_to_mesh_kernel), dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
   return hipGetLastError();
@@ -594,70 +388,55 @@ __global__ __launch_bounds__(1024) void psm_umax_partial_kernel(PsmMeshCasesArgs
   umax2_partial(a.cells + c0 * 5, a.cell_off[cs + 1] - c0, a.umax_part + (int64_t)cs * a.n_parts + blockIdx.x);
 }
 
-// Level two + mesh -> grid: every workgroup folds its case's row of partials, workgroup 0 of the case leaves U_max[case] for the
-// batched psm_to_mesh_kernel; then the cell body on the case's tables, into image `case` of the staging grid.
-__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmMeshCasesArgs a) {
-  const int cs = blockIdx.y;
-  const double umax_v = umax_of_partials(a.umax_part + (int64_t)cs * a.n_parts, a.n_parts);
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.umax[cs] = umax_v;
-  const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (cell >= a.n_grid) return;
+// A case's slices of the concatenated tables, as the single-mesh bodies take them (U_max is the wrapper's)
+__device__ __forceinline__ PsmToGridArgs case_grid_slice(const PsmMeshCasesArgs& a, int cs) {
   const int64_t g0 = (int64_t)cs * a.n_grid;
   PsmToGridArgs g{};
   g.cells = a.cells + a.cell_off[cs] * 5;
   g.vtx = a.vtx_m2g + g0 * 3; g.wts = a.wts_m2g + g0 * 3; g.src_of_cell = a.src_of_cell + g0;
   g.sdf = a.sdf + g0; g.grid = a.grid + g0 * a.c_in;
   g.max_abs_ux = a.max_abs_ux; g.max_abs_uy = a.max_abs_uy; g.sdf_scale = a.sdf_scale; g.c_in = a.c_in; g.fill = a.fill;
-  to_grid_cell<false>(g, nullptr, umax_v, cell);
+  return g;
+}
+__device__ __forceinline__ PsmToMeshArgs case_mesh_slice(const PsmMeshCasesArgs& a, int cs, int64_t c0) {
+  const int64_t g0 = (int64_t)cs * a.n_grid;
+  PsmToMeshArgs m{};
+  m.cells = a.cells + c0 * 5;
+  m.vtx = a.vtx_g2m + c0 * 3; m.wts = a.wts_g2m + c0 * 3; m.cell_of_point = a.cell_of_point + g0;
+  m.field = a.field + g0 * a.c_out; m.near_wall = a.near_wall + c0; m.p_out = a.p_out + c0;
+  m.max_abs_p = a.max_abs_p; m.c_out = a.c_out;
+  return m;
+}
+
+// Level two + mesh -> grid: every workgroup folds its case's row of partials, workgroup 0 of the case leaves U_max[case] for the
+// batched psm_to_mesh_kernel; then the cell body on the case's tables, into image `case` of the staging grid.  DELTA: u_prev
+// [sum n_i][2] is sliced like the cells.
+template <bool DELTA>
+__device__ __forceinline__ void to_grid_case(PsmMeshCasesArgs a, const double* u_prev) {
+  const int cs = blockIdx.y;
+  const double umax_v = umax_of_partials(a.umax_part + (int64_t)cs * a.n_parts, a.n_parts);
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.umax[cs] = umax_v;
+  const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (cell >= a.n_grid) return;
+  to_grid_cell<DELTA>(case_grid_slice(a, cs), DELTA ? u_prev + a.cell_off[cs] * 2 : nullptr, umax_v, cell);
 }
 
 // grid -> mesh for all sum n_i cells in one launch.  The case is launch dimension y (x covers the largest case) and not a
 // search of cell_off per thread: a workgroup then reads its range with two uniform loads and gathers from one case's image
 // only, and what it costs is the workgroups beyond a shorter case's end, which return at once -- the cases of an ensemble
 // are meshes of one channel with different obstacles, a few per cent apart in size.
-__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmMeshCasesArgs a) {
+template <bool DELTA>
+__device__ __forceinline__ void to_mesh_case(PsmMeshCasesArgs a, double* u_prev, int prime) {
   const int cs = blockIdx.y;
   const int64_t c0 = a.cell_off[cs], local = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (local >= a.cell_off[cs + 1] - c0) return;
-  const int64_t g0 = (int64_t)cs * a.n_grid;
-  PsmToMeshArgs m{};
-  m.cells = a.cells + c0 * 5;
-  m.vtx = a.vtx_g2m + c0 * 3; m.wts = a.wts_g2m + c0 * 3; m.cell_of_point = a.cell_of_point + g0;
-  m.field = a.field + g0 * a.c_out; m.near_wall = a.near_wall + c0; m.p_out = a.p_out + c0;
-  m.max_abs_p = a.max_abs_p; m.c_out = a.c_out;
-  to_mesh_cell<false>(m, nullptr, 0, a.umax[cs], local);
+  to_mesh_cell<DELTA>(case_mesh_slice(a, cs, c0), DELTA ? u_prev + c0 * 2 : nullptr, prime, prime ? 0.0 : a.umax[cs], local);
 }
 
-// The delta forms of the two case-batch kernels (PsmDeltaCasesArgs): the same slices, u_prev [sum n_i][2] sliced like the cells.
-__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmDeltaCasesArgs d) {
-  const PsmMeshCasesArgs& a = d.c;
-  const int cs = blockIdx.y;
-  const double umax_v = umax_of_partials(a.umax_part + (int64_t)cs * a.n_parts, a.n_parts);
-  if (blockIdx.x == 0 && threadIdx.x == 0) a.umax[cs] = umax_v;
-  const int64_t cell = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (cell >= a.n_grid) return;
-  const int64_t g0 = (int64_t)cs * a.n_grid, c0 = a.cell_off[cs];
-  PsmToGridArgs g{};
-  g.cells = a.cells + c0 * 5;
-  g.vtx = a.vtx_m2g + g0 * 3; g.wts = a.wts_m2g + g0 * 3; g.src_of_cell = a.src_of_cell + g0;
-  g.sdf = a.sdf + g0; g.grid = a.grid + g0 * a.c_in;
-  g.max_abs_ux = a.max_abs_ux; g.max_abs_uy = a.max_abs_uy; g.sdf_scale = a.sdf_scale; g.c_in = a.c_in; g.fill = a.fill;
-  to_grid_cell<true>(g, d.u_prev + c0 * 2, umax_v, cell);
-}
-
-__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmDeltaCasesArgs d) {
-  const PsmMeshCasesArgs& a = d.c;
-  const int cs = blockIdx.y;
-  const int64_t c0 = a.cell_off[cs], local = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (local >= a.cell_off[cs + 1] - c0) return;
-  const int64_t g0 = (int64_t)cs * a.n_grid;
-  PsmToMeshArgs m{};
-  m.cells = a.cells + c0 * 5;
-  m.vtx = a.vtx_g2m + c0 * 3; m.wts = a.wts_g2m + c0 * 3; m.cell_of_point = a.cell_of_point + g0;
-  m.field = a.field + g0 * a.c_out; m.near_wall = a.near_wall + c0; m.p_out = a.p_out + c0;
-  m.max_abs_p = a.max_abs_p; m.c_out = a.c_out;
-  to_mesh_cell<true>(m, d.u_prev + c0 * 2, d.prime, d.prime ? 0.0 : a.umax[cs], local);
-}
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmMeshCasesArgs a) { to_grid_case<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmMeshCasesArgs a) { to_mesh_case<false>(a, nullptr, 0); }
+__global__ __launch_bounds__(256) void psm_to_grid_kernel(PsmDeltaCasesArgs d) { to_grid_case<true>(d.c, d.u_prev); }
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmDeltaCasesArgs d) { to_mesh_case<true>(d.c, d.u_prev, d.prime); }
 
 typedef void (*PsmCasesKernel)(PsmMeshCasesArgs);
 hipError_t psm_launch_umax_cases(const PsmMeshCasesArgs& a, hipStream_t st) {

@@ -63,6 +63,9 @@ BOUNDARY = {
     "solve_registered_graph2": {"PSM_MESH_GRAPH": "2"},      # the same as plain launches
     "solve_nan": {},                                         # one NaN velocity: U_max and with it every pressure
     "cases_k1": {}, "cases_k3": {},                          # psm_solve_cases: 16021 / 16165 / 15838 cells, none a multiple of 256
+    "delta_host_umax": {},                                   # psm_solve_delta from an unprimed state: the priming step, then two delta steps
+    "delta_partials": {},                                    # the same three steps on the 32769 + 37 cells of solve_partials
+    "cases_delta_k3": {},                                    # psm_solve_cases_delta on the three meshes of cases_k3, three steps from unprimed
     "mesh_to_grid": {},                                      # psm_mesh_to_grid k = 1 and 3, fill 0 / 1, on hand-made tables (130 x 131)
     "frames_to_grid": {},                                    # psm_frames_to_grid_device: 2 frames, a float64 plane, a float32 plane, a skipped column
     "block_error": {},                                       # psm_block_error behind a solve: label blocks + the per-block sums
@@ -71,8 +74,9 @@ BOUNDARY = {
 # name: (entry, frames per call; 0: the host entry, bound and tripping).  Frame entries on hand-made tables of 200 cells: 138 x 300, the
 # evaluator's grid (161 workgroups + 184 pixels); the gradP frames on 320 x 300.  k: 7 = the velocities, one extra plane, the
 # weighting pair (the error blocks need the two label planes: 8); 4 / 6 = one column more than the deltas / gradP pack stores.
+# chapter4_frames_<inputs>: both image widths (M_u 3, M_fU 2), c_in + 1 columns; the entry takes no scale and no filter.
 STEPS = {"pressure": None, "poststeps": None, "poisson_step": ("poisson_step", 2)}
-for _e in ("poisson_frames", "poisson_frames_errors", "deltas_frames", "gradp_frames"):
+for _e in ("poisson_frames", "poisson_frames_errors", "deltas_frames", "gradp_frames", "chapter4_frames_M_u", "chapter4_frames_M_fU"):
     STEPS.update({f"{_e}_n1": (_e, 1), f"{_e}_n3": (_e, 3), f"{_e}_host": (_e, 0)})
 OTHER = ["attention_ln_deferred", "attention_ln_launched", "conv1d_head", "mesh", "ring", "pressure", "poststeps"]
 _lines = []
@@ -255,7 +259,7 @@ def boundary_config(name):
             line(f"p solve{k + 1}", sm.py_func(cells, out=out).copy())
         if "registered" in name:
             sm.unpin()
-    elif name == "solve_partials":
+    elif name in ("solve_partials", "delta_partials"):
         _, _, _, model, maxs = cases.build_mesh_case()
         ny, nx, n = 138, 300, 32769 + 37
         ng, rng = ny * nx, np.random.default_rng(1501)
@@ -279,19 +283,36 @@ def boundary_config(name):
         cells = np.ascontiguousarray(rng.standard_normal((n, 5)))
         out = np.empty(n, np.float64)
         with GridSurrogate(model, ny, nx, 1) as sur:
+            smd = int(name == "delta_partials")                # the deltas model's convention: normalise_sdf = fill_input = 1
             sur._chk(sur.lib.psm_set_geometry(sur.h, n, ny, nx, _p(v1, C.c_int32), _p(w1, C.c_double), _p(idx, C.c_int32), _p(sdf, C.c_double),
-                                              _p(v2, C.c_int32), _p(w2, C.c_double), _p(mx, C.c_double), 0, 0, 0.05))
-            for k in range(2):
-                sur._chk(sur.lib.psm_solve(sur.h, _p(cells, C.c_double), n, 0, _p(out, C.c_double)))
+                                              _p(v2, C.c_int32), _p(w2, C.c_double), _p(mx, C.c_double), smd, smd, 0.05))
+            for k in range(3 if smd else 2):
+                solve = sur.lib.psm_solve_delta if smd else sur.lib.psm_solve
+                sur._chk(solve(sur.h, _p(cells, C.c_double), n, 0, _p(out, C.c_double)))
                 line(f"p solve{k + 1}", out.copy())
+                if smd:                                      # the next time step: other velocities, the pressure just returned
+                    cells[:, :2] += 0.1 * rng.standard_normal((n, 2))
+                    cells[:, 4] = out
+    elif name == "delta_host_umax":
+        _, _, _, model, maxs = cases.build_mesh_case()
+        sm = SolverModule(model, maxs, geometry="native", step="delta")
+        sm.init_func(*synthetic.channel_mesh())
+        sm.reset_state()                                     # init_func primes: forget it, the first step below is the priming step
+        for step in range(3):
+            line(f"p step{step + 1}", sm.py_func(synthetic.channel_mesh(step=step)[0]))
+        sm._sur.close()
     elif name.startswith("cases_"):
         _, _, _, model, maxs = cases.build_mesh_case()
+        delta = name.startswith("cases_delta")
         obstacles = (dict(), dict(cx=0.55, cy=0.05, R=0.06), dict(cx=0.9, cy=-0.08, R=0.1, step=2))[:int(name[-1])]
         mesh = [synthetic.channel_mesh(**kw) for kw in obstacles]
-        se = SolverEnsemble(model, maxs, 4, geometry="native")
+        se = SolverEnsemble(model, maxs, 4, geometry="native", step="delta" if delta else "absolute")
         se.init_func(*zip(*mesh))
-        for step in range(2):
-            for k, p in enumerate(se.py_func([m[0] for m in mesh])):
+        if delta:
+            se.reset_state()                                 # as in delta_host_umax
+        for step in range(3 if delta else 2):                # delta: the fields move from step to step
+            arrays = [synthetic.channel_mesh(**dict(kw, step=kw.get("step", 0) + step))[0] if delta else m[0] for kw, m in zip(obstacles, mesh)]
+            for k, p in enumerate(se.py_func(arrays)):
                 line(f"p step{step + 1} case{k}", p)
         se._sur.close()
     elif name == "mesh_to_grid":
@@ -369,8 +390,11 @@ def steps_config(name):
     from test_poisson_step_device import K, MAX_ABS, P_SCALE, S_FIELD, S_WEIGHT, model4
     entry, n = STEPS[name]
     poisson, NF, CELLS = entry.startswith("poisson"), 3, 200
+    chapter4 = entry.startswith("chapter4_frames")
+    c4_in = 3 if entry.endswith("M_u") else 2
+    c4_maxs = cases.DATASET_MAXS if c4_in == 3 else (cases.DATASET_MAXS[0],) + tuple(cases.DATASET_MAXS[2:])
     ny, nx = (320, 300) if entry == "gradp_frames" else (138, 300)
-    k = {"poisson_step": 0, "poisson_frames": 7, "poisson_frames_errors": 8, "deltas_frames": 4, "gradp_frames": 6}[entry]
+    k = c4_in + 1 if chapter4 else {"poisson_step": 0, "poisson_frames": 7, "poisson_frames_errors": 8, "deltas_frames": 4, "gradp_frames": 6}[entry]
     npix, rng = ny * nx, np.random.default_rng(1901)
     vtx = rng.integers(0, CELLS, (npix, 3)).astype(np.int32)                    # the tables of tests/test_field_errors.py:flow_tables on this grid
     w = rng.random((npix, 2)) * 0.5
@@ -394,6 +418,9 @@ def steps_config(name):
         model, c_in, sdf_scale = model4(), 4, MAX_ABS[3]
     elif entry == "deltas_frames":
         model, c_in, sdf_scale = synthetic.make_model("deltas", p_in=48, p_out=40, c_in=3, seed_pca=778, seed_w=6), 3, cases.DATASET_MAXS[2]
+    elif chapter4:
+        model, c_in, sdf_scale = synthetic.make_model("chapter5", p_in=32, p_out=32, c_in=c4_in), c4_in, c4_maxs[-2]
+        model.ov = 96
     else:
         model, c_in, sdf_scale = synthetic.make_model("gradp", p_in=32, p_out=32), 3, cases.GRADP_MAXS[2]
     model.sdf_ch = c_in - 1
@@ -411,6 +438,8 @@ def steps_config(name):
             sur.bind_deltas_frames(sdf, cases.DATASET_MAXS)
         if entry == "gradp_frames":
             assert sur.bind_gradp_frames(sdf, cases.GRADP_MAXS, 57, 50, 1.0 / nx, 1.0 / ny)
+        if chapter4:
+            sur.bind_chapter4_frames(sdf, c4_maxs)
         return sur
 
     def bind(sur, frames, other):                            # the frames' own geometry, or one whose flow-cell pattern is another
@@ -427,6 +456,8 @@ def steps_config(name):
             return {"raw": sur.poisson_frames_errors(c, lu[:frames], out_scale=s, apply_filter=af)}
         if entry == "deltas_frames":
             return dict(zip(("result", "truth", "raw"), sur.deltas_frames(c, u2[:frames], out_scale=s, apply_filter=af)))
+        if chapter4:
+            return dict(zip(("result", "truth", "raw"), sur.chapter4_frames(c)))
         return dict(zip(("gradp", "p", "truth", "raw"), sur.gradp_frames(c, out_scale=s, apply_filter=af)))
 
     def device_call(sur, b, sc, af):
@@ -439,6 +470,8 @@ def steps_config(name):
             sur.poisson_frames_errors_device(b["cols"].ptr, n, k, lu[:n], b["extra"].ptr, b["result"].ptr, b["next"].ptr, b["raw"].ptr, af, b["change"].ptr, out_scale=s)
         elif entry == "deltas_frames":
             sur.deltas_frames_device(b["cols"].ptr, n, k, u2[:n], b["result"].ptr, b["truth"].ptr, b["raw"].ptr, af, out_scale=s)
+        elif chapter4:
+            sur.chapter4_frames_device(b["cols"].ptr, n, k, b["result"].ptr, b["truth"].ptr, b["raw"].ptr)
         else:
             sur.gradp_frames_device(b["cols"].ptr, n, k, b["gradp"].ptr, b["p"].ptr, b["truth"].ptr, b["raw"].ptr, af, out_scale=s)
         sur.synchronize()
@@ -447,7 +480,7 @@ def steps_config(name):
     f32, f64 = np.float32, np.float64
     outputs = {"poisson_step": ("result", "change", "next"), "poisson_frames": ("result", "change", "next", "extra"),
                "poisson_frames_errors": ("result", "change", "next", "extra", "raw"), "deltas_frames": ("result", "truth", "raw"),
-               "gradp_frames": ("gradp", "p", "truth", "raw")}[entry]
+               "gradp_frames": ("gradp", "p", "truth", "raw")}.get(entry, ("result", "truth", "raw"))
     shapes = {"result": ((NF, npix), f32), "change": ((NF, npix), f32), "next": ((NF, npix), f32), "extra": ((NF, max(k - 6, 1), npix), f64),
               "raw": ((NF, 4, 8), f64), "truth": ((NF, 3, npix), f64), "gradp": ((NF, npix, 2), f32), "p": ((NF, npix), f32)}
     line = lambda what, outs: [say(f"{name:28s} {what:34s} {key:7s} {sha(a)}") for key, a in outs.items() if a is not None]
@@ -464,8 +497,8 @@ def steps_config(name):
                 continue
             b = {key: DeviceArray(np.zeros(*shapes[key])) for key in outputs}
             b.update(vel=DeviceArray(vel), dU=DeviceArray(dU), prev=DeviceArray(prev), cols=DeviceArray(cols))
-            for sc in (False, True):
-                for af in (False, True):
+            for sc in (False,) if chapter4 else (False, True):      # the Chapter-4 entry takes neither
+                for af in (False,) if chapter4 else (False, True):
                     for rep in range(3 if graph else 1):     # graph: the capture and two replays
                         what = ("plain" if not graph else ("capture", "replay1", "replay2")[rep]) + f" scale={int(sc)} af={int(af)}"
                         line(what, device_call(sur, b, sc, af))
