@@ -13,12 +13,19 @@ namespace psm_impl {
 // captured step graphs (StepCall::chapter4) hold the addresses of the binding's planes and SDF plane
 static void drop_chapter4_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.step.chapter4.planes != nullptr; }); }
 
+// columns 0 .. c_in - 1 are stored; c_in + 1 scales, the SDF plane by max_abs[c_in - 1] (the statements of M_u :215-225 on the SDF channel)
+static const EvalKind CHAPTER4{
+    "psm_bind_chapter4_frames", 0, 0, -1, 1, 1,
+    "k outside [c_in, 16]: the c_in - 1 input channels (Ux / U, Uy / U or f(U) / U^2), then p / U^2; further columns are not stored",
+    "a destination is misaligned (4 bytes for the image, 8 for the truth plane)",
+    "psm_bind_chapter4_frames has not been called (psm_bind_frames, a new mesh, plan or model drop the binding)"};
+
 void chapter4_free(psm_handle* h) {
   Chapter4Set& s = h->chapter4;
   drop_chapter4_graphs(h);
-  dev_free(s.d_sdn); dev_free(s.d_planes); dev_free(s.d_grid); dev_free(s.d_result); dev_free(s.d_truth); dev_free(s.d_raw);
-  pin_free(s.h_raw); pin_free(s.h_result); pin_free(s.h_truth);
-  s.ready = false; s.n_frames = 0;
+  dev_free(s.d_result);
+  pin_free(s.h_result);
+  eval_free(s);
 }
 
 // The pack launch on `st`: the binding's SDF plane and scales, the call's planes and destinations.
@@ -35,32 +42,6 @@ int chapter4_pack_device(psm_handle* h, const Chapter4Call& cc, int n_frames, hi
   return PSM_OK;
 }
 
-// the mesh, the frame binding and this binding
-static int chapter4_state(psm_handle* h) {
-  int rc = frames_state(h);
-  if (rc) return rc;
-  if (!h->chapter4.ready) return fail(h, PSM_ERR_STATE, "psm_bind_chapter4_frames has not been called (psm_bind_frames, a new mesh, plan or model drop the binding)");
-  return PSM_OK;
-}
-
-// state and arguments of the image stage; the frame stage's descriptors: columns 0 .. c_in - 1 into the binding's planes, the rest not stored
-static int image_call(psm_handle* h, const double* d_cols, int n_frames, int k, const float* d_grid, const double* d_truth, FrameCall& fc) {
-  int rc = chapter4_state(h);
-  if (rc) return rc;
-  const int c_in = h->cfg.c_in;
-  if (k < c_in || k > PSM_FRAME_MAX_COLS)
-    return fail(h, PSM_ERR_ARG, "k outside [c_in, 16]: the c_in - 1 input channels (Ux / U, Uy / U or f(U) / U^2), then p / U^2; further columns are not stored");
-  if ((rc = frames_count_check(h, n_frames))) return rc;
-  if (!d_cols || !d_grid) return fail(h, PSM_ERR_ARG, "null buffer");
-  if ((reinterpret_cast<uintptr_t>(d_grid) & 3) || (reinterpret_cast<uintptr_t>(d_truth) & 7))
-    return fail(h, PSM_ERR_ARG, "a destination is misaligned (4 bytes for the image, 8 for the truth plane)");
-  const int64_t npix = (int64_t)h->Ny * h->Nx;
-  fc = FrameCall{};
-  fc.cols = d_cols; fc.k = k; fc.fill = 1;
-  for (int c = 0; c < c_in; ++c) fc.out[c] = PsmFramePlane{h->chapter4.d_planes + c * npix, c_in * npix, 0};
-  return PSM_OK;
-}
-
 // The error block behind a step: the two field-error launches, one pair over the binding's SDF plane.
 static int chapter4_step_errors_device(psm_handle* h, int n_frames, const float* d_result, const double* d_truth, double* d_raw, hipStream_t st) {
   const int64_t npix = (int64_t)h->Ny * h->Nx;
@@ -72,17 +53,22 @@ static int chapter4_step_errors_device(psm_handle* h, int n_frames, const float*
   return field_errors_device(h, a, d_raw, st);
 }
 
-// every check of one step, then the one graph replay: frames -> planes -> image, label -> one solve per frame
-static int chapter4_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, float* d_result, double* d_truth, const double* d_raw,
+// a device or a host entry's step: null destinations become the binding's; every check of the step; the one graph replay: frames ->
+// planes -> image, label -> one solve per frame; the error block when d_raw is given
+static int chapter4_frames_step(psm_handle* h, const double* d_cols, int n_frames, int k, float* d_result, double* d_truth, double* d_raw,
                                 hipStream_t st) {
   Chapter4Set& S = h->chapter4;
+  if (!d_result) d_result = S.d_result;
+  if (!d_truth) d_truth = S.d_truth;
   StepCall step;
-  int rc = image_call(h, d_cols, n_frames, k, S.d_grid, d_truth, step.frames);
+  int rc = eval_image_call(h, h->chapter4, CHAPTER4, d_cols, n_frames, k, S.d_grid, d_truth, step.frames);
   if (rc) return rc;
   if ((reinterpret_cast<uintptr_t>(d_result) & 3) || (reinterpret_cast<uintptr_t>(d_raw) & 7))
     return fail(h, PSM_ERR_ARG, "a destination is misaligned (4 bytes for d_result, 8 for d_raw)");
   step.chapter4 = Chapter4Call{S.d_planes, S.d_grid, d_truth};
-  return solve_device(h, S.d_grid, n_frames, nullptr, d_result, st, nullptr, step);
+  rc = solve_device(h, S.d_grid, n_frames, nullptr, d_result, st, nullptr, step);
+  if (rc || !d_raw) return rc;
+  return chapter4_step_errors_device(h, n_frames, d_result, d_truth, d_raw, st);
 }
 
 }  // namespace psm_impl
@@ -98,24 +84,11 @@ int psm_bind_chapter4_frames(psm_handle* h, const double* sdfunct, const double*
   const int c_in = h->cfg.c_in;
   if (h->cfg.variant != PSM_VARIANT_CHAPTER5 || h->cfg.c_out != 1 || (c_in != 2 && c_in != 3) || h->cfg.sdf_channel != c_in - 1)
     return fail(h, PSM_ERR_STATE, "the Chapter-4 frames are a two- or three-channel image with the SDF last and a one-channel field on a chapter5-variant handle: variant == PSM_VARIANT_CHAPTER5, c_out == 1, c_in in {2, 3}, sdf_channel == c_in - 1");
-  if (!sdfunct || !max_abs) return fail(h, PSM_ERR_ARG, "null argument");
-  for (int q = 0; q < c_in + 1; ++q)
-    if (!(max_abs[q] != 0.0) || !std::isfinite(max_abs[q])) return fail(h, PSM_ERR_ARG, "max_abs scales must be finite and non-zero");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));           // a step in flight reads the buffers that are replaced
-  chapter4_free(h);
   Chapter4Set& s = h->chapter4;
-  const size_t npix = (size_t)h->Ny * h->Nx, n = (size_t)h->frames.n_frames;
-  if ((rc = dev_alloc(h, &s.d_sdn, npix)) || (rc = dev_alloc(h, &s.d_planes, n * c_in * npix)) || (rc = dev_alloc(h, &s.d_grid, n * npix * c_in)) ||
-      (rc = dev_alloc(h, &s.d_result, n * npix)) || (rc = dev_alloc(h, &s.d_truth, n * npix)) || (rc = dev_alloc(h, &s.d_raw, n * PSM_ERR_RAW))) { chapter4_free(h); return rc; }
-  if ((rc = pin_alloc(h, &s.h_raw, n * PSM_ERR_RAW, "psm_bind_chapter4_frames")) || (rc = pin_alloc(h, &s.h_result, n * npix, "psm_bind_chapter4_frames")) ||
-      (rc = pin_alloc(h, &s.h_truth, n * npix, "psm_bind_chapter4_frames"))) { chapter4_free(h); return rc; }
-  const hipError_t e = upload_sdf_plane(h, sdfunct, max_abs[c_in - 1], s.d_sdn);   // the statements of M_u :215-225 on the SDF channel
-  if (e != hipSuccess) { chapter4_free(h); return fail(h, PSM_ERR_NOMEM, std::string("psm_bind_chapter4_frames: ") + hipGetErrorString(e)); }
-  s.n_frames = h->frames.n_frames;
-  for (int q = 0; q < c_in + 1; ++q) s.max_abs[q] = max_abs[q];
-  s.ready = true;
-  return PSM_OK;
+  return eval_bind(h, s, CHAPTER4, sdfunct, max_abs, chapter4_free, [&](size_t n, size_t npix) {
+    const int ro = dev_alloc(h, &s.d_result, n * npix);
+    return ro ? ro : pin_alloc(h, &s.h_result, n * npix, CHAPTER4.bind_name);
+  });
 }
 
 
@@ -127,7 +100,7 @@ int psm_unbind_chapter4_frames(psm_handle* h) {
 int psm_chapter4_image_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, float* d_grid, double* d_truth, void* stream) {
   if (!h) return PSM_ERR_ARG;
   FrameCall fc;
-  int rc = image_call(h, d_cols, n_frames, k, d_grid, d_truth, fc);
+  int rc = eval_image_call(h, h->chapter4, CHAPTER4, d_cols, n_frames, k, d_grid, d_truth, fc);
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device));
   hipStream_t st = stream_of(h, stream);
@@ -139,41 +112,25 @@ int psm_chapter4_image_device(psm_handle* h, const double* d_cols, int32_t n_fra
 int psm_chapter4_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, float* d_result, double* d_truth,
                                double* d_raw, void* stream) {
   if (!h) return PSM_ERR_ARG;
-  hipStream_t st = stream_of(h, stream);
-  if (!d_result) d_result = h->chapter4.d_result;
-  if (!d_truth) d_truth = h->chapter4.d_truth;
-  int rc = chapter4_step_device(h, d_cols, n_frames, k, d_result, d_truth, d_raw, st);
-  if (rc || !d_raw) return rc;
-  return chapter4_step_errors_device(h, n_frames, d_result, d_truth, d_raw, st);
+  return chapter4_frames_step(h, d_cols, n_frames, k, d_result, d_truth, d_raw, stream_of(h, stream));
 }
 
 
 int psm_chapter4_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_t k, float* result, double* truth, double* raw) {
   if (!h) return PSM_ERR_ARG;
   if (!cols || !(result || truth || raw)) return fail(h, PSM_ERR_ARG, "null buffer");
-  FrameSet& F = h->frames;
+  const double* d_cols = h->frames.d_cols;
   Chapter4Set& S = h->chapter4;
   hipStream_t st = h->stream;
   // every check of the step before the first copy: the step itself repeats them
   FrameCall fc;
-  int rc = image_call(h, F.d_cols, n_frames, k, S.d_grid, S.d_truth, fc);
-  if (rc) return rc;
-  if ((rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
-  const size_t npix = (size_t)h->Ny * h->Nx;
-  const size_t fb = (size_t)n_frames * npix * sizeof(float), tb = 2 * fb, rb = (size_t)n_frames * PSM_ERR_RAW * sizeof(double);
-  rc = guarded_host_step(h, st, "psm_chapter4_frames", [&](int pass) {
-    int rs = chapter4_step_device(h, F.d_cols, n_frames, k, S.d_result, S.d_truth, S.d_raw, st);
-    if (rs || (raw && (rs = chapter4_step_errors_device(h, n_frames, S.d_result, S.d_truth, S.d_raw, st)))) return rs;
-    if (result) HIPCHK(h, hipMemcpyAsync(S.h_result, S.d_result, fb, hipMemcpyDeviceToHost, st));
-    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(S.h_truth, S.d_truth, tb, hipMemcpyDeviceToHost, st));   // the labels do not depend on the route
-    if (raw) HIPCHK(h, hipMemcpyAsync(S.h_raw, S.d_raw, rb, hipMemcpyDeviceToHost, st));
-    return PSM_OK;
-  });
-  if (rc) return rc;
-  if (result) memcpy(result, S.h_result, fb);
-  if (truth) memcpy(truth, S.h_truth, tb);
-  if (raw) memcpy(raw, S.h_raw, rb);
-  return PSM_OK;
+  int rc = eval_image_call(h, h->chapter4, CHAPTER4, d_cols, n_frames, k, S.d_grid, S.d_truth, fc);
+  if (rc || (rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
+  const size_t fb = (size_t)n_frames * h->Ny * h->Nx * sizeof(float);
+  const HostOut out[3] = {{result, S.h_result, S.d_result, fb, false},
+                          {truth, S.h_truth, S.d_truth, 2 * fb, true},            // the labels do not depend on the route
+                          {raw, S.h_raw, S.d_raw, (size_t)n_frames * PSM_ERR_RAW * sizeof(double), false}};
+  return host_step(h, st, "psm_chapter4_frames", out, [&] { return chapter4_frames_step(h, d_cols, n_frames, k, nullptr, nullptr, raw ? S.d_raw : nullptr, st); });
 }
 
 }  // extern "C"

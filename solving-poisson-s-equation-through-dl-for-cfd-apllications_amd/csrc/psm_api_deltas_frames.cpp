@@ -11,14 +11,21 @@ namespace psm_impl {
 // captured step graphs (StepCall::deltas) hold the addresses of the binding's planes, SDF plane and U^2 array
 static void drop_deltas_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.step.deltas.planes != nullptr; }); }
 
+// columns 0-2 are stored; four scales, the SDF plane by max_abs_dist (the statements of SM_call.py:439-444 on the SDF channel)
+static const EvalKind DELTAS{
+    "psm_bind_deltas_frames", 3, 4, 2, 1, 2,
+    "k outside [3, 16]: (dUx / U, dUy / U, dp / U^2), further columns are not stored",
+    "a destination is misaligned (4 bytes for the image and the label plane, 8 for the truth plane)",
+    "psm_bind_deltas_frames has not been called (psm_bind_frames, a new mesh, plan or model drop the binding)"};
+
 void deltas_free(psm_handle* h) {
   DeltasSet& s = h->deltas;
   drop_deltas_graphs(h);
-  dev_free(s.d_sdn); dev_free(s.d_planes); dev_free(s.d_grid); dev_free(s.d_label); dev_free(s.d_result); dev_free(s.d_truth);
-  dev_free(s.d_res); dev_free(s.d_part); dev_free(s.d_fraw); dev_free(s.d_raw); dev_free(s.d_u2);
-  pin_free(s.h_raw); pin_free(s.h_result); pin_free(s.h_truth); pin_free(s.h_u2);
+  dev_free(s.d_label); dev_free(s.d_result); dev_free(s.d_res); dev_free(s.d_part); dev_free(s.d_fraw); dev_free(s.d_u2);
+  pin_free(s.h_result); pin_free(s.h_u2);
   for (auto& e : s.u2_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  s.ready = false; s.n_frames = 0; s.u2_pos = 0;
+  s.u2_pos = 0;
+  eval_free(s);
 }
 
 // The pack launch on `st`: the binding's SDF plane, scales and U^2 array, the call's planes and destinations.
@@ -34,31 +41,15 @@ int deltas_pack_device(psm_handle* h, const DeltasCall& dc, int n_frames, hipStr
   return PSM_OK;
 }
 
-// the mesh, the frame binding and this binding
-static int deltas_state(psm_handle* h) {
-  int rc = frames_state(h);
-  if (rc) return rc;
-  if (!h->deltas.ready) return fail(h, PSM_ERR_STATE, "psm_bind_deltas_frames has not been called (psm_bind_frames, a new mesh, plan or model drop the binding)");
-  return PSM_OK;
-}
-
-// state and arguments of the image stage; the frame stage's descriptors: columns 0-2 into the binding's planes, the rest not stored
+// the shared image call, then what only this kind has: the label plane (one misalignment message for the three destinations) and U^2
 static int image_call(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* d_grid, const float* d_label,
                       const double* d_truth, FrameCall& fc) {
-  int rc = deltas_state(h);
+  int rc = eval_image_call(h, h->deltas, DELTAS, d_cols, n_frames, k, d_grid, d_truth, fc);
   if (rc) return rc;
-  if (k < 3 || k > PSM_FRAME_MAX_COLS) return fail(h, PSM_ERR_ARG, "k outside [3, 16]: (dUx / U, dUy / U, dp / U^2), further columns are not stored");
-  if ((rc = frames_count_check(h, n_frames))) return rc;
-  if (!d_cols || !d_grid) return fail(h, PSM_ERR_ARG, "null buffer");
-  if ((reinterpret_cast<uintptr_t>(d_grid) & 3) || (reinterpret_cast<uintptr_t>(d_label) & 3) || (reinterpret_cast<uintptr_t>(d_truth) & 7))
-    return fail(h, PSM_ERR_ARG, "a destination is misaligned (4 bytes for the image and the label plane, 8 for the truth plane)");
+  if (reinterpret_cast<uintptr_t>(d_label) & 3) return fail(h, PSM_ERR_ARG, DELTAS.align_msg);
   if (d_truth && !U2) return fail(h, PSM_ERR_ARG, "the truth plane needs U2");
   for (int f = 0; U2 && f < n_frames; ++f)
     if (!std::isfinite(U2[f])) return fail(h, PSM_ERR_ARG, "U2 must be finite for every frame");
-  const int64_t npix = (int64_t)h->Ny * h->Nx;
-  fc = FrameCall{};
-  fc.cols = d_cols; fc.k = k; fc.fill = 1;
-  for (int c = 0; c < 3; ++c) fc.out[c] = PsmFramePlane{h->deltas.d_planes + c * npix, 3 * npix, 0};
   return PSM_OK;
 }
 
@@ -104,7 +95,7 @@ static int block_errors_device(psm_handle* h, const float* d_grid, const float* 
 
 // The two error stages behind a step: the field's sums (the existing field-error launches, one pair) into the binding's scratch
 // row, then the block stage, whose fold leaves both rows in d_raw [n][2][8].
-int deltas_step_errors_device(psm_handle* h, int n_frames, const float* d_result, const double* d_truth, double* d_raw, hipStream_t st) {
+static int deltas_step_errors_device(psm_handle* h, int n_frames, const float* d_result, const double* d_truth, double* d_raw, hipStream_t st) {
   const DeltasSet& D = h->deltas;
   const int64_t npix = (int64_t)h->Ny * h->Nx;
   const PsmErrPlane none{nullptr, 0, 0, 0};
@@ -117,24 +108,52 @@ int deltas_step_errors_device(psm_handle* h, int n_frames, const float* d_result
   return block_errors_device(h, D.d_grid, D.d_label, n_frames, D.d_fraw, d_raw, st);
 }
 
-// every check of one step, then its scalars and the one graph replay: frames -> planes -> image (label, truth) -> solve (-> filter)
-int deltas_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* out_scale, int apply_filter,
-                       float* d_result, double* d_truth, const double* d_raw, hipStream_t st, const RowsCall* rows) {
-  DeltasSet& D = h->deltas;
-  StepCall step;
-  int rc = image_call(h, d_cols, n_frames, k, U2, D.d_grid, D.d_label, rows ? nullptr : d_truth, step.frames);   // rows: U^2 is made on the device
+// every check of one step; nothing is enqueued before they pass
+static int deltas_step_check(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, int apply_filter, const float* d_result,
+                             const double* d_truth, const double* d_raw, const RowsCall* rows, FrameCall& fc) {
+  const DeltasSet& D = h->deltas;
+  int rc = image_call(h, d_cols, n_frames, k, U2, D.d_grid, D.d_label, rows ? nullptr : d_truth, fc);   // rows: U^2 is made on the device
   if (rc) return rc;
   if (rows && (reinterpret_cast<uintptr_t>(d_truth) & 7)) return fail(h, PSM_ERR_ARG, "a destination is misaligned (8 bytes for the truth plane)");
   if (!rows && !U2) return fail(h, PSM_ERR_ARG, "null argument");
   if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_deltas_frames");
   if ((reinterpret_cast<uintptr_t>(d_result) & 3) || (reinterpret_cast<uintptr_t>(d_raw) & 7))
     return fail(h, PSM_ERR_ARG, "a destination is misaligned (4 bytes for d_result, 8 for d_raw)");
+  return PSM_OK;
+}
+
+int deltas_host_check(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, int apply_filter, const RowsCall* rows) {
+  const DeltasSet& D = h->deltas;
+  FrameCall fc;
+  return deltas_step_check(h, d_cols, n_frames, k, U2, apply_filter, D.d_result, D.d_truth, D.d_raw, rows, fc);
+}
+
+// null destinations become the binding's; the checks; the step's scalars and the one graph replay: frames -> planes -> image (label,
+// truth) -> solve (-> filter); the two error stages when d_raw is given
+int deltas_frames_step(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* out_scale, int apply_filter,
+                       float* d_result, double* d_truth, double* d_raw, hipStream_t st, const RowsCall* rows) {
+  DeltasSet& D = h->deltas;
+  if (!d_result) d_result = D.d_result;
+  if (!d_truth) d_truth = D.d_truth;
+  StepCall step;
+  int rc = deltas_step_check(h, d_cols, n_frames, k, U2, apply_filter, d_result, d_truth, d_raw, rows, step.frames);
+  if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (rows) step.rows = *rows;
   else if ((rc = upload_u2(h, U2, n_frames, st))) return rc;
   step.deltas = DeltasCall{D.d_planes, D.d_grid, D.d_label, d_truth, D.d_res};
   if (apply_filter) { step.post.apply_filter = 1; step.post.result = d_result; }
-  return solve_device(h, D.d_grid, n_frames, out_scale, apply_filter ? h->post.d_fields : d_result, st, nullptr, step);
+  rc = solve_device(h, D.d_grid, n_frames, out_scale, apply_filter ? h->post.d_fields : d_result, st, nullptr, step);
+  if (rc || !d_raw) return rc;
+  return deltas_step_errors_device(h, n_frames, d_result, d_truth, d_raw, st);
+}
+
+void deltas_host_outs(psm_handle* h, int n_frames, float* result, double* truth, double* raw, HostOut* out) {
+  const DeltasSet& D = h->deltas;
+  const size_t fb = (size_t)n_frames * h->Ny * h->Nx * sizeof(float);
+  out[0] = HostOut{result, D.h_result, D.d_result, fb, false};
+  out[1] = HostOut{truth, D.h_truth, D.d_truth, 2 * fb, true};            // the labels do not depend on the route
+  out[2] = HostOut{raw, D.h_raw, D.d_raw, (size_t)n_frames * 2 * PSM_ERR_RAW * sizeof(double), false};
 }
 
 }  // namespace psm_impl
@@ -149,31 +168,20 @@ int psm_bind_deltas_frames(psm_handle* h, const double* sdfunct, const double* m
   if (rc) return rc;
   if (h->cfg.c_in != 3 || h->cfg.sdf_channel != 2 || h->cfg.c_out != 1)
     return fail(h, PSM_ERR_STATE, "the deltas frames are a three-channel image with the SDF last and a one-channel field: c_in == 3, sdf_channel == 2, c_out == 1");
-  if (!sdfunct || !max_abs) return fail(h, PSM_ERR_ARG, "null argument");
-  for (int q = 0; q < 4; ++q)
-    if (!(max_abs[q] != 0.0) || !std::isfinite(max_abs[q])) return fail(h, PSM_ERR_ARG, "max_abs scales must be finite and non-zero");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));           // a step in flight reads the buffers that are replaced
-  deltas_free(h);
   DeltasSet& s = h->deltas;
-  const size_t npix = (size_t)h->Ny * h->Nx, n = (size_t)h->frames.n_frames;
-  if ((rc = dev_alloc(h, &s.d_sdn, npix)) || (rc = dev_alloc(h, &s.d_planes, n * 3 * npix)) || (rc = dev_alloc(h, &s.d_grid, n * npix * 3)) ||
-      (rc = dev_alloc(h, &s.d_label, n * npix)) || (rc = dev_alloc(h, &s.d_result, n * npix)) || (rc = dev_alloc(h, &s.d_truth, n * npix)) ||
-      (rc = dev_alloc(h, &s.d_res, (size_t)round_up((int)n * h->B, 32) * h->ld_out)) || (rc = dev_alloc(h, &s.d_part, n * h->B * PSM_ERR_RAW)) || (rc = dev_alloc(h, &s.d_fraw, n * PSM_ERR_RAW)) ||
-      (rc = dev_alloc(h, &s.d_raw, n * 2 * PSM_ERR_RAW)) || (rc = dev_alloc(h, &s.d_u2, n))) { deltas_free(h); return rc; }
-  if ((rc = pin_alloc(h, &s.h_raw, n * 2 * PSM_ERR_RAW, "psm_bind_deltas_frames")) || (rc = pin_alloc(h, &s.h_result, n * npix, "psm_bind_deltas_frames")) ||
-      (rc = pin_alloc(h, &s.h_truth, n * npix, "psm_bind_deltas_frames")) || (rc = pin_alloc(h, &s.h_u2, DeltasSet::RING * n, "psm_bind_deltas_frames"))) { deltas_free(h); return rc; }
-  hipError_t e = hipSuccess;
-  for (auto& ev : s.u2_ev) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-  if (e == hipSuccess) e = upload_sdf_plane(h, sdfunct, max_abs[2], s.d_sdn);     // the statements of SM_call.py:439-444 on the SDF channel
-  if (e == hipSuccess) e = hipMemset(s.d_res, 0, (size_t)round_up((int)n * h->B, 32) * h->ld_out * sizeof(float));   // the rows the decode pads to
-  const std::vector<double> ones(n, 1.0);
-  if (e == hipSuccess) e = psm_copy_h2d(s.d_u2, ones.data(), n * sizeof(double));
-  if (e != hipSuccess) { deltas_free(h); return fail(h, PSM_ERR_NOMEM, std::string("psm_bind_deltas_frames: ") + hipGetErrorString(e)); }
-  s.n_frames = h->frames.n_frames;
-  for (int q = 0; q < 4; ++q) s.max_abs[q] = max_abs[q];
-  s.ready = true;
-  return PSM_OK;
+  return eval_bind(h, s, DELTAS, sdfunct, max_abs, deltas_free, [&](size_t n, size_t npix) {
+    const size_t n_res = (size_t)round_up((int)n * h->B, 32) * h->ld_out;
+    int ro;
+    if ((ro = dev_alloc(h, &s.d_label, n * npix)) || (ro = dev_alloc(h, &s.d_result, n * npix)) || (ro = dev_alloc(h, &s.d_res, n_res)) ||
+        (ro = dev_alloc(h, &s.d_part, n * h->B * PSM_ERR_RAW)) || (ro = dev_alloc(h, &s.d_fraw, n * PSM_ERR_RAW)) || (ro = dev_alloc(h, &s.d_u2, n)) ||
+        (ro = pin_alloc(h, &s.h_result, n * npix, DELTAS.bind_name)) || (ro = pin_alloc(h, &s.h_u2, DeltasSet::RING * n, DELTAS.bind_name))) return ro;
+    hipError_t e = hipSuccess;
+    for (auto& ev : s.u2_ev) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMemset(s.d_res, 0, n_res * sizeof(float));   // the rows the decode pads to
+    const std::vector<double> ones(n, 1.0);
+    if (e == hipSuccess) e = psm_copy_h2d(s.d_u2, ones.data(), n * sizeof(double));
+    return e == hipSuccess ? PSM_OK : fail(h, PSM_ERR_NOMEM, std::string(DELTAS.bind_name) + ": " + hipGetErrorString(e));
+  });
 }
 
 
@@ -198,7 +206,7 @@ int psm_deltas_image_device(psm_handle* h, const double* d_cols, int32_t n_frame
 
 int psm_block_errors_device(psm_handle* h, const float* d_grid, const float* d_label, int32_t n_frames, double* d_raw, void* stream) {
   if (!h) return PSM_ERR_ARG;
-  int rc = deltas_state(h);
+  int rc = eval_state(h, h->deltas, DELTAS);
   if (rc) return rc;
   if ((rc = frames_count_check(h, n_frames))) return rc;
   if (!d_grid || !d_label || !d_raw) return fail(h, PSM_ERR_ARG, "null buffer");
@@ -213,12 +221,7 @@ int psm_block_errors_device(psm_handle* h, const float* d_grid, const float* d_l
 int psm_deltas_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const double* U2, const float* out_scale,
                              int32_t apply_filter, float* d_result, double* d_truth, double* d_raw, void* stream) {
   if (!h) return PSM_ERR_ARG;
-  hipStream_t st = stream_of(h, stream);
-  if (!d_result) d_result = h->deltas.d_result;
-  if (!d_truth) d_truth = h->deltas.d_truth;
-  int rc = deltas_step_device(h, d_cols, n_frames, k, U2, out_scale, apply_filter, d_result, d_truth, d_raw, st);
-  if (rc || !d_raw) return rc;
-  return deltas_step_errors_device(h, n_frames, d_result, d_truth, d_raw, st);
+  return deltas_frames_step(h, d_cols, n_frames, k, U2, out_scale, apply_filter, d_result, d_truth, d_raw, stream_of(h, stream));
 }
 
 
@@ -226,31 +229,16 @@ int psm_deltas_frames(psm_handle* h, const double* cols, int32_t n_frames, int32
                       int32_t apply_filter, float* result, double* truth, double* raw) {
   if (!h) return PSM_ERR_ARG;
   if (!cols || !(result || truth || raw)) return fail(h, PSM_ERR_ARG, "null buffer");
-  FrameSet& F = h->frames;
-  DeltasSet& D = h->deltas;
+  const double* d_cols = h->frames.d_cols;
   hipStream_t st = h->stream;
   // every check of the step before the first copy: the step itself repeats them
-  FrameCall fc;
-  int rc = image_call(h, F.d_cols, n_frames, k, U2, D.d_grid, D.d_label, D.d_truth, fc);
-  if (rc) return rc;
-  if (!U2) return fail(h, PSM_ERR_ARG, "null argument");
-  if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_deltas_frames");
-  if ((rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
-  const size_t npix = (size_t)h->Ny * h->Nx;
-  const size_t fb = (size_t)n_frames * npix * sizeof(float), tb = 2 * fb, rb = (size_t)n_frames * 2 * PSM_ERR_RAW * sizeof(double);
-  rc = guarded_host_step(h, st, "psm_deltas_frames", [&](int pass) {
-    int rs = deltas_step_device(h, F.d_cols, n_frames, k, U2, out_scale, apply_filter, D.d_result, D.d_truth, D.d_raw, st);
-    if (rs || (raw && (rs = deltas_step_errors_device(h, n_frames, D.d_result, D.d_truth, D.d_raw, st)))) return rs;
-    if (result) HIPCHK(h, hipMemcpyAsync(D.h_result, D.d_result, fb, hipMemcpyDeviceToHost, st));
-    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(D.h_truth, D.d_truth, tb, hipMemcpyDeviceToHost, st));   // the labels do not depend on the route
-    if (raw) HIPCHK(h, hipMemcpyAsync(D.h_raw, D.d_raw, rb, hipMemcpyDeviceToHost, st));
-    return PSM_OK;
+  int rc = deltas_host_check(h, d_cols, n_frames, k, U2, apply_filter);
+  if (rc || (rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
+  HostOut out[3];
+  deltas_host_outs(h, n_frames, result, truth, raw, out);
+  return host_step(h, st, "psm_deltas_frames", out, [&] {
+    return deltas_frames_step(h, d_cols, n_frames, k, U2, out_scale, apply_filter, nullptr, nullptr, raw ? h->deltas.d_raw : nullptr, st);
   });
-  if (rc) return rc;
-  if (result) memcpy(result, D.h_result, fb);
-  if (truth) memcpy(truth, D.h_truth, tb);
-  if (raw) memcpy(raw, D.h_raw, rb);
-  return PSM_OK;
 }
 
 }  // extern "C"

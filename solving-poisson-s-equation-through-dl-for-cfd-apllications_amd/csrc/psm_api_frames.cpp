@@ -64,6 +64,61 @@ hipError_t upload_sdf_plane(psm_handle* h, const double* sdfunct, double max_abs
   return psm_copy_h2d(d_sdn, sdn.data(), npix * sizeof(double));
 }
 
+// ---- what the three evaluator frame bindings share (EvalSet, EvalKind: psm_handle.h) ----
+void eval_free(EvalSet& s) {
+  dev_free(s.d_sdn); dev_free(s.d_planes); dev_free(s.d_grid); dev_free(s.d_truth); dev_free(s.d_raw);
+  pin_free(s.h_raw); pin_free(s.h_truth);
+  s.ready = false; s.n_frames = 0;
+}
+
+int eval_state(psm_handle* h, const EvalSet& s, const EvalKind& kind) {
+  int rc = frames_state(h);
+  if (rc) return rc;
+  if (!s.ready) return fail(h, PSM_ERR_STATE, kind.unbound_msg);
+  return PSM_OK;
+}
+
+int eval_image_call(psm_handle* h, const EvalSet& s, const EvalKind& kind, const double* d_cols, int n_frames, int k, const float* d_grid,
+                    const double* d_truth, FrameCall& fc) {
+  int rc = eval_state(h, s, kind);
+  if (rc) return rc;
+  const int cols = kind.n_cols(h->cfg);
+  if (k < cols || k > PSM_FRAME_MAX_COLS) return fail(h, PSM_ERR_ARG, kind.k_msg);
+  if ((rc = frames_count_check(h, n_frames))) return rc;
+  if (!d_cols || !d_grid) return fail(h, PSM_ERR_ARG, "null buffer");
+  if ((reinterpret_cast<uintptr_t>(d_grid) & 3) || (reinterpret_cast<uintptr_t>(d_truth) & 7)) return fail(h, PSM_ERR_ARG, kind.align_msg);
+  const int64_t npix = (int64_t)h->Ny * h->Nx;
+  fc = FrameCall{};
+  fc.cols = d_cols; fc.k = k; fc.fill = 1;
+  for (int c = 0; c < cols; ++c) fc.out[c] = PsmFramePlane{s.d_planes + c * npix, cols * npix, 0};
+  return PSM_OK;
+}
+
+int eval_bind(psm_handle* h, EvalSet& s, const EvalKind& kind, const double* sdfunct, const double* max_abs, void (*free_fn)(psm_handle*),
+              const std::function<int(size_t n, size_t npix)>& own) {
+  if (!sdfunct || !max_abs) return fail(h, PSM_ERR_ARG, "null argument");
+  const int scales = kind.n_scales(h->cfg);
+  for (int q = 0; q < scales; ++q)
+    if (!(max_abs[q] != 0.0) || !std::isfinite(max_abs[q])) return fail(h, PSM_ERR_ARG, "max_abs scales must be finite and non-zero");
+  HIPCHK(h, hipSetDevice(h->cfg.device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));           // a step in flight reads the buffers that are replaced
+  free_fn(h);
+  const size_t npix = (size_t)h->Ny * h->Nx, n = (size_t)h->frames.n_frames;
+  const size_t n_truth = n * kind.truth_planes * npix, n_raw = n * kind.raw_rows * PSM_ERR_RAW;
+  int rc = own(n, npix);
+  if (!rc && !(rc = dev_alloc(h, &s.d_sdn, npix)) && !(rc = dev_alloc(h, &s.d_planes, n * kind.n_cols(h->cfg) * npix)) &&
+      !(rc = dev_alloc(h, &s.d_grid, n * npix * h->cfg.c_in)) && !(rc = dev_alloc(h, &s.d_truth, n_truth)) && !(rc = dev_alloc(h, &s.d_raw, n_raw)) &&
+      !(rc = pin_alloc(h, &s.h_raw, n_raw, kind.bind_name)) && !(rc = pin_alloc(h, &s.h_truth, n_truth, kind.bind_name))) {
+    const hipError_t e = upload_sdf_plane(h, sdfunct, max_abs[kind.dist_at(h->cfg)], s.d_sdn);   // the reference's statements on the SDF channel
+    if (e != hipSuccess) rc = fail(h, PSM_ERR_NOMEM, std::string(kind.bind_name) + ": " + hipGetErrorString(e));
+  }
+  if (rc) { free_fn(h); return rc; }
+  s.n_frames = h->frames.n_frames;
+  for (int q = 0; q < scales; ++q) s.max_abs[q] = max_abs[q];
+  s.ready = true;
+  return PSM_OK;
+}
+
 // The evaluator's column convention as plane descriptors: 0-3 -> the feature binding's velocity planes, the last two (weighting) ->
 // the post-steps' dU / prev as float32, the columns between -> d_extra (nullptr: not stored).
 int poisson_frame_call(psm_handle* h, const double* d_cols, int n_frames, int k, int weighting, double* d_extra, FrameCall& fc) {

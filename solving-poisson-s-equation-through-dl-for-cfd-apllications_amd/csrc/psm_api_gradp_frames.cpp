@@ -15,13 +15,19 @@ static_assert(GRADP_PAIRS <= PSM_FIELD_ERR_MAX_PAIRS, "the step's error blocks a
 // captured step graphs (StepCall::gradp) hold the addresses of the binding's planes, SDF plane and integration tables
 static void drop_gradp_graphs(psm_handle* h) { drop_graphs_if(h, [](const GraphKey& k) { return k.step.gradp.planes != nullptr; }); }
 
+// columns 0-4 are stored; five scales, the SDF plane by max_abs[2] (the statements of Eval_dual_Dense_onlycil.py:461-465 on the SDF channel)
+static const EvalKind GRADP{
+    "psm_bind_gradp_frames", 5, 5, 2, 3, GRADP_PAIRS,
+    "k outside [5, 16]: (Ux / U, Uy / U, dPdx / U^2, dPdy / U^2, p / U^2), further columns are not stored",
+    "a destination is misaligned (4 bytes for the image, 8 for the label planes)",
+    "psm_bind_gradp_frames has not been called (psm_bind_frames, a new mesh, plan or model drop the binding)"};
+
 void gradp_free(psm_handle* h) {
   GradpSet& s = h->gradp;
   drop_gradp_graphs(h);
-  dev_free(s.d_sdn); dev_free(s.d_planes); dev_free(s.d_grid); dev_free(s.d_truth); dev_free(s.d_raw);
   integ_free(s.integ);
-  pin_free(s.h_raw); pin_free(s.h_gradp); pin_free(s.h_p); pin_free(s.h_truth);
-  s.ready = false; s.n_frames = 0;
+  pin_free(s.h_gradp); pin_free(s.h_p);
+  eval_free(s);
 }
 
 // The pack launch on `st`: the binding's SDF plane and scales, the call's planes and destinations.
@@ -37,32 +43,8 @@ int gradp_pack_device(psm_handle* h, const GradpCall& gc, int n_frames, hipStrea
   return PSM_OK;
 }
 
-// the mesh, the frame binding and this binding
-static int gradp_state(psm_handle* h) {
-  int rc = frames_state(h);
-  if (rc) return rc;
-  if (!h->gradp.ready) return fail(h, PSM_ERR_STATE, "psm_bind_gradp_frames has not been called (psm_bind_frames, a new mesh, plan or model drop the binding)");
-  return PSM_OK;
-}
-
-// state and arguments of the image stage; the frame stage's descriptors: columns 0-4 into the binding's planes, the rest not stored
-static int image_call(psm_handle* h, const double* d_cols, int n_frames, int k, const float* d_grid, const double* d_truth, FrameCall& fc) {
-  int rc = gradp_state(h);
-  if (rc) return rc;
-  if (k < 5 || k > PSM_FRAME_MAX_COLS) return fail(h, PSM_ERR_ARG, "k outside [5, 16]: (Ux / U, Uy / U, dPdx / U^2, dPdy / U^2, p / U^2), further columns are not stored");
-  if ((rc = frames_count_check(h, n_frames))) return rc;
-  if (!d_cols || !d_grid) return fail(h, PSM_ERR_ARG, "null buffer");
-  if ((reinterpret_cast<uintptr_t>(d_grid) & 3) || (reinterpret_cast<uintptr_t>(d_truth) & 7))
-    return fail(h, PSM_ERR_ARG, "a destination is misaligned (4 bytes for the image, 8 for the label planes)");
-  const int64_t npix = (int64_t)h->Ny * h->Nx;
-  fc = FrameCall{};
-  fc.cols = d_cols; fc.k = k; fc.fill = 1;
-  for (int c = 0; c < 5; ++c) fc.out[c] = PsmFramePlane{h->gradp.d_planes + c * npix, 5 * npix, 0};
-  return PSM_OK;
-}
-
 // The error blocks behind a step: the two field-error launches, four pairs over the binding's SDF plane.
-int gradp_step_errors_device(psm_handle* h, int n_frames, const float* d_gradp, const float* d_p, const double* d_truth, double* d_raw,
+static int gradp_step_errors_device(psm_handle* h, int n_frames, const float* d_gradp, const float* d_p, const double* d_truth, double* d_raw,
                               hipStream_t st) {
   const int64_t npix = (int64_t)h->Ny * h->Nx;
   const PsmErrPlane none{nullptr, 0, 0, 0};
@@ -78,20 +60,49 @@ int gradp_step_errors_device(psm_handle* h, int n_frames, const float* d_gradp, 
   return field_errors_device(h, a, d_raw, st);
 }
 
-// every check of one step, then the one graph replay: frames -> planes -> image, labels -> solve (-> filter) -> integration
-int gradp_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const float* out_scale, int apply_filter, float* d_gradp,
-                      float* d_p, double* d_truth, const double* d_raw, hipStream_t st, const RowsCall* rows) {
-  GradpSet& G = h->gradp;
-  StepCall step;
-  int rc = image_call(h, d_cols, n_frames, k, G.d_grid, d_truth, step.frames);
+// every check of one step; nothing is enqueued before they pass
+static int gradp_step_check(psm_handle* h, const double* d_cols, int n_frames, int k, int apply_filter, const float* d_gradp, const float* d_p,
+                            const double* d_truth, const double* d_raw, FrameCall& fc) {
+  int rc = eval_image_call(h, h->gradp, GRADP, d_cols, n_frames, k, h->gradp.d_grid, d_truth, fc);
   if (rc) return rc;
   if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_gradp_frames");
   if ((reinterpret_cast<uintptr_t>(d_gradp) & 7) || (reinterpret_cast<uintptr_t>(d_p) & 3) || (reinterpret_cast<uintptr_t>(d_raw) & 7))
     return fail(h, PSM_ERR_ARG, "a destination is misaligned (8 bytes for d_gradp and d_raw, 4 for d_p)");
+  return PSM_OK;
+}
+
+int gradp_host_check(psm_handle* h, const double* d_cols, int n_frames, int k, int apply_filter) {
+  const GradpSet& G = h->gradp;
+  FrameCall fc;
+  return gradp_step_check(h, d_cols, n_frames, k, apply_filter, G.integ.d_gradp, G.integ.d_p, G.d_truth, G.d_raw, fc);
+}
+
+// null destinations become the binding's; the checks; the one graph replay: frames -> planes -> image, labels -> solve (-> filter) ->
+// integration; the error blocks when d_raw is given
+int gradp_frames_step(psm_handle* h, const double* d_cols, int n_frames, int k, const float* out_scale, int apply_filter, float* d_gradp,
+                      float* d_p, double* d_truth, double* d_raw, hipStream_t st, const RowsCall* rows) {
+  GradpSet& G = h->gradp;
+  if (!d_gradp) d_gradp = G.integ.d_gradp;
+  if (!d_p) d_p = G.integ.d_p;
+  if (!d_truth) d_truth = G.d_truth;
+  StepCall step;
+  int rc = gradp_step_check(h, d_cols, n_frames, k, apply_filter, d_gradp, d_p, d_truth, d_raw, step.frames);
+  if (rc) return rc;
   if (rows) step.rows = *rows;
   step.gradp = GradpCall{G.d_planes, G.d_grid, d_truth, d_p};
   if (apply_filter) { step.post.apply_filter = 1; step.post.result = d_gradp; }
-  return solve_device(h, G.d_grid, n_frames, out_scale, apply_filter ? h->post.d_fields : d_gradp, st, nullptr, step);
+  rc = solve_device(h, G.d_grid, n_frames, out_scale, apply_filter ? h->post.d_fields : d_gradp, st, nullptr, step);
+  if (rc || !d_raw) return rc;
+  return gradp_step_errors_device(h, n_frames, d_gradp, d_p, d_truth, d_raw, st);
+}
+
+void gradp_host_outs(psm_handle* h, int n_frames, float* gradp, float* p, double* truth, double* raw, HostOut* out) {
+  const GradpSet& G = h->gradp;
+  const size_t npix = (size_t)h->Ny * h->Nx, pb = (size_t)n_frames * npix * sizeof(float);
+  out[0] = HostOut{gradp, G.h_gradp, G.integ.d_gradp, 2 * pb, false};
+  out[1] = HostOut{p, G.h_p, G.integ.d_p, pb, false};
+  out[2] = HostOut{truth, G.h_truth, G.d_truth, (size_t)n_frames * 3 * npix * sizeof(double), true};   // the labels do not depend on the route
+  out[3] = HostOut{raw, G.h_raw, G.d_raw, (size_t)n_frames * GRADP_PAIRS * PSM_ERR_RAW * sizeof(double), false};
 }
 
 }  // namespace psm_impl
@@ -107,26 +118,13 @@ int psm_bind_gradp_frames(psm_handle* h, const double* sdfunct, const double* ma
   if (rc) return rc;
   if (h->cfg.c_in != 3 || h->cfg.sdf_channel != 2 || h->cfg.c_out != 2)
     return fail(h, PSM_ERR_STATE, "the gradP frames are a three-channel image with the SDF last and a (dp/dx, dp/dy) field: c_in == 3, sdf_channel == 2, c_out == 2");
-  if (!sdfunct || !max_abs) return fail(h, PSM_ERR_ARG, "null argument");
-  for (int q = 0; q < 5; ++q)
-    if (!(max_abs[q] != 0.0) || !std::isfinite(max_abs[q])) return fail(h, PSM_ERR_ARG, "max_abs scales must be finite and non-zero");
-  HIPCHK(h, hipSetDevice(h->cfg.device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));           // a step in flight reads the buffers that are replaced
-  gradp_free(h);
   GradpSet& s = h->gradp;
-  const size_t npix = (size_t)h->Ny * h->Nx, n = (size_t)h->frames.n_frames;
-  // the tables first: a geometry the reference cannot process (PSM_ERR_UNSUPPORTED) or a cut outside the grid (PSM_ERR_ARG) binds nothing
-  if ((rc = integ_bind(h, s.integ, h->Ny, h->Nx, sdfunct, (int)n, &center_y, &center_x, dx, dy, true))) { gradp_free(h); return rc; }
-  if ((rc = dev_alloc(h, &s.d_sdn, npix)) || (rc = dev_alloc(h, &s.d_planes, n * 5 * npix)) || (rc = dev_alloc(h, &s.d_grid, n * npix * 3)) ||
-      (rc = dev_alloc(h, &s.d_truth, n * 3 * npix)) || (rc = dev_alloc(h, &s.d_raw, n * GRADP_PAIRS * PSM_ERR_RAW))) { gradp_free(h); return rc; }
-  if ((rc = pin_alloc(h, &s.h_raw, n * GRADP_PAIRS * PSM_ERR_RAW, "psm_bind_gradp_frames")) || (rc = pin_alloc(h, &s.h_gradp, n * npix * 2, "psm_bind_gradp_frames")) ||
-      (rc = pin_alloc(h, &s.h_p, n * npix, "psm_bind_gradp_frames")) || (rc = pin_alloc(h, &s.h_truth, n * 3 * npix, "psm_bind_gradp_frames"))) { gradp_free(h); return rc; }
-  const hipError_t e = upload_sdf_plane(h, sdfunct, max_abs[2], s.d_sdn);     // the statements of Eval_dual_Dense_onlycil.py:461-465 on the SDF channel
-  if (e != hipSuccess) { gradp_free(h); return fail(h, PSM_ERR_NOMEM, std::string("psm_bind_gradp_frames: ") + hipGetErrorString(e)); }
-  s.n_frames = h->frames.n_frames;
-  for (int q = 0; q < 5; ++q) s.max_abs[q] = max_abs[q];
-  s.ready = true;
-  return PSM_OK;
+  return eval_bind(h, s, GRADP, sdfunct, max_abs, gradp_free, [&](size_t n, size_t npix) {
+    // the tables first: a geometry the reference cannot process (PSM_ERR_UNSUPPORTED) or a cut outside the grid (PSM_ERR_ARG) binds nothing
+    int ro = integ_bind(h, s.integ, h->Ny, h->Nx, sdfunct, (int)n, &center_y, &center_x, dx, dy, true);
+    if (ro || (ro = pin_alloc(h, &s.h_gradp, n * npix * 2, GRADP.bind_name))) return ro;
+    return pin_alloc(h, &s.h_p, n * npix, GRADP.bind_name);
+  });
 }
 
 
@@ -138,7 +136,7 @@ int psm_unbind_gradp_frames(psm_handle* h) {
 int psm_gradp_image_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, float* d_grid, double* d_truth, void* stream) {
   if (!h) return PSM_ERR_ARG;
   FrameCall fc;
-  int rc = image_call(h, d_cols, n_frames, k, d_grid, d_truth, fc);
+  int rc = eval_image_call(h, h->gradp, GRADP, d_cols, n_frames, k, d_grid, d_truth, fc);
   if (rc) return rc;
   HIPCHK(h, hipSetDevice(h->cfg.device));
   hipStream_t st = stream_of(h, stream);
@@ -150,13 +148,7 @@ int psm_gradp_image_device(psm_handle* h, const double* d_cols, int32_t n_frames
 int psm_gradp_frames_device(psm_handle* h, const double* d_cols, int32_t n_frames, int32_t k, const float* out_scale,
                             int32_t apply_filter, float* d_gradp, float* d_p, double* d_truth, double* d_raw, void* stream) {
   if (!h) return PSM_ERR_ARG;
-  hipStream_t st = stream_of(h, stream);
-  if (!d_gradp) d_gradp = h->gradp.integ.d_gradp;
-  if (!d_p) d_p = h->gradp.integ.d_p;
-  if (!d_truth) d_truth = h->gradp.d_truth;
-  int rc = gradp_step_device(h, d_cols, n_frames, k, out_scale, apply_filter, d_gradp, d_p, d_truth, d_raw, st);
-  if (rc || !d_raw) return rc;
-  return gradp_step_errors_device(h, n_frames, d_gradp, d_p, d_truth, d_raw, st);
+  return gradp_frames_step(h, d_cols, n_frames, k, out_scale, apply_filter, d_gradp, d_p, d_truth, d_raw, stream_of(h, stream));
 }
 
 
@@ -164,33 +156,16 @@ int psm_gradp_frames(psm_handle* h, const double* cols, int32_t n_frames, int32_
                      float* gradp, float* p, double* truth, double* raw) {
   if (!h) return PSM_ERR_ARG;
   if (!cols || !(gradp || p || truth || raw)) return fail(h, PSM_ERR_ARG, "null buffer");
-  FrameSet& F = h->frames;
-  GradpSet& G = h->gradp;
+  const double* d_cols = h->frames.d_cols;
   hipStream_t st = h->stream;
   // every check of the step before the first copy: the step itself repeats them
-  FrameCall fc;
-  int rc = image_call(h, F.d_cols, n_frames, k, G.d_grid, G.d_truth, fc);
-  if (rc) return rc;
-  if (apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_gradp_frames");
-  if ((rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
-  const size_t npix = (size_t)h->Ny * h->Nx, pb = (size_t)n_frames * npix * sizeof(float), gb = 2 * pb;
-  const size_t tb = (size_t)n_frames * 3 * npix * sizeof(double), rb = (size_t)n_frames * GRADP_PAIRS * PSM_ERR_RAW * sizeof(double);
-  float *d_g = G.integ.d_gradp, *d_p = G.integ.d_p;
-  rc = guarded_host_step(h, st, "psm_gradp_frames", [&](int pass) {
-    int rs = gradp_step_device(h, F.d_cols, n_frames, k, out_scale, apply_filter, d_g, d_p, G.d_truth, G.d_raw, st);
-    if (rs || (raw && (rs = gradp_step_errors_device(h, n_frames, d_g, d_p, G.d_truth, G.d_raw, st)))) return rs;
-    if (gradp) HIPCHK(h, hipMemcpyAsync(G.h_gradp, d_g, gb, hipMemcpyDeviceToHost, st));
-    if (p) HIPCHK(h, hipMemcpyAsync(G.h_p, d_p, pb, hipMemcpyDeviceToHost, st));
-    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(G.h_truth, G.d_truth, tb, hipMemcpyDeviceToHost, st));   // the labels do not depend on the route
-    if (raw) HIPCHK(h, hipMemcpyAsync(G.h_raw, G.d_raw, rb, hipMemcpyDeviceToHost, st));
-    return PSM_OK;
+  int rc = gradp_host_check(h, d_cols, n_frames, k, apply_filter);
+  if (rc || (rc = frames_upload_cols(h, cols, n_frames, k))) return rc;
+  HostOut out[4];
+  gradp_host_outs(h, n_frames, gradp, p, truth, raw, out);
+  return host_step(h, st, "psm_gradp_frames", out, [&] {
+    return gradp_frames_step(h, d_cols, n_frames, k, out_scale, apply_filter, nullptr, nullptr, nullptr, raw ? h->gradp.d_raw : nullptr, st);
   });
-  if (rc) return rc;
-  if (gradp) memcpy(gradp, G.h_gradp, gb);
-  if (p) memcpy(p, G.h_p, pb);
-  if (truth) memcpy(truth, G.h_truth, tb);
-  if (raw) memcpy(raw, G.h_raw, rb);
-  return PSM_OK;
 }
 
 }  // extern "C"

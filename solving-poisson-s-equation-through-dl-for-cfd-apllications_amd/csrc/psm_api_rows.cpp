@@ -94,8 +94,9 @@ static int host_width_check(psm_handle* h, int width) {
   return PSM_OK;
 }
 
-static int filter_state(psm_handle* h, int apply_filter, const char* msg) {
-  return apply_filter && !h->post.ready ? fail(h, PSM_ERR_STATE, msg) : PSM_OK;
+// the scalars behind an evaluator's outputs: made by the rows stage, the same on every route
+static HostOut scalars_out(psm_handle* h, int n_frames, double* scalars) {
+  return HostOut{scalars, h->rows.h_scalars, h->rows.d_scalars, (size_t)n_frames * PSM_ROWS_SCALARS * sizeof(double), true};
 }
 
 // the Poisson step's post-step descriptor on caller pointers
@@ -154,12 +155,7 @@ int psm_deltas_rows_device(psm_handle* h, const float* d_rows, int32_t n_frames,
   RowsCall rc;
   int r = step_rows_call(h, PSM_ROWS_KIND_DELTAS, d_rows, n_frames, width, base, 1.0, 1.0, 1.0, d_scalars, rc);
   if (r) return r;
-  hipStream_t st = stream_of(h, stream);
-  if (!d_result) d_result = h->deltas.d_result;
-  if (!d_truth) d_truth = h->deltas.d_truth;
-  r = deltas_step_device(h, rc.cols, n_frames, 3, nullptr, nullptr, apply_filter, d_result, d_truth, d_raw, st, &rc);
-  if (r || !d_raw) return r;
-  return deltas_step_errors_device(h, n_frames, d_result, d_truth, d_raw, st);
+  return deltas_frames_step(h, rc.cols, n_frames, 3, nullptr, nullptr, apply_filter, d_result, d_truth, d_raw, stream_of(h, stream), &rc);
 }
 
 
@@ -168,33 +164,18 @@ int psm_deltas_rows(psm_handle* h, const float* rows, int32_t n_frames, int32_t 
   if (!h) return PSM_ERR_ARG;
   if (!rows || !(result || truth || raw || scalars)) return fail(h, PSM_ERR_ARG, "null buffer");
   RowsSet& R = h->rows;
-  DeltasSet& D = h->deltas;
   hipStream_t st = h->stream;
   // every check of the step before the first copy: the step itself repeats them
   RowsCall rc;
   int r = step_rows_call(h, PSM_ROWS_KIND_DELTAS, R.d_rows, n_frames, width, base, 1.0, 1.0, 1.0, R.d_scalars, rc);
-  if (r || (r = host_width_check(h, width))) return r;
-  if (!D.ready) return fail(h, PSM_ERR_STATE, "psm_bind_deltas_frames has not been called (psm_bind_frames, a new mesh, plan or model drop the binding)");
-  if ((r = filter_state(h, apply_filter, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_deltas_frames"))) return r;
+  if (r || (r = host_width_check(h, width)) || (r = deltas_host_check(h, rc.cols, n_frames, 3, nullptr, apply_filter, &rc))) return r;
   if ((r = upload_rows(h, rows, n_frames, width))) return r;
-  const size_t npix = (size_t)h->Ny * h->Nx;
-  const size_t fb = (size_t)n_frames * npix * sizeof(float), tb = 2 * fb, eb = (size_t)n_frames * 2 * PSM_ERR_RAW * sizeof(double);
-  const size_t sb = (size_t)n_frames * PSM_ROWS_SCALARS * sizeof(double);
-  r = guarded_host_step(h, st, "psm_deltas_rows", [&](int pass) {
-    int rs = deltas_step_device(h, rc.cols, n_frames, 3, nullptr, nullptr, apply_filter, D.d_result, D.d_truth, D.d_raw, st, &rc);
-    if (rs || (raw && (rs = deltas_step_errors_device(h, n_frames, D.d_result, D.d_truth, D.d_raw, st)))) return rs;
-    if (result) HIPCHK(h, hipMemcpyAsync(D.h_result, D.d_result, fb, hipMemcpyDeviceToHost, st));
-    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(D.h_truth, D.d_truth, tb, hipMemcpyDeviceToHost, st));   // the labels do not depend on the route
-    if (raw) HIPCHK(h, hipMemcpyAsync(D.h_raw, D.d_raw, eb, hipMemcpyDeviceToHost, st));
-    if (scalars && pass == 0) HIPCHK(h, hipMemcpyAsync(R.h_scalars, R.d_scalars, sb, hipMemcpyDeviceToHost, st));
-    return PSM_OK;
+  HostOut out[4];
+  deltas_host_outs(h, n_frames, result, truth, raw, out);
+  out[3] = scalars_out(h, n_frames, scalars);
+  return host_step(h, st, "psm_deltas_rows", out, [&] {
+    return deltas_frames_step(h, rc.cols, n_frames, 3, nullptr, nullptr, apply_filter, nullptr, nullptr, raw ? h->deltas.d_raw : nullptr, st, &rc);
   });
-  if (r) return r;
-  if (result) memcpy(result, D.h_result, fb);
-  if (truth) memcpy(truth, D.h_truth, tb);
-  if (raw) memcpy(raw, D.h_raw, eb);
-  if (scalars) memcpy(scalars, R.h_scalars, sb);
-  return PSM_OK;
 }
 
 
@@ -304,13 +285,7 @@ int psm_gradp_rows_device(psm_handle* h, const float* d_rows, int32_t n_frames, 
   RowsCall rc;
   int r = step_rows_call(h, PSM_ROWS_KIND_GRADP, d_rows, n_frames, width, 1.0, 1.0, ex, ey, d_scalars, rc);
   if (r) return r;
-  hipStream_t st = stream_of(h, stream);
-  if (!d_gradp) d_gradp = h->gradp.integ.d_gradp;
-  if (!d_p) d_p = h->gradp.integ.d_p;
-  if (!d_truth) d_truth = h->gradp.d_truth;
-  r = gradp_step_device(h, rc.cols, n_frames, 5, nullptr, apply_filter, d_gradp, d_p, d_truth, d_raw, st, &rc);
-  if (r || !d_raw) return r;
-  return gradp_step_errors_device(h, n_frames, d_gradp, d_p, d_truth, d_raw, st);
+  return gradp_frames_step(h, rc.cols, n_frames, 5, nullptr, apply_filter, d_gradp, d_p, d_truth, d_raw, stream_of(h, stream), &rc);
 }
 
 
@@ -319,36 +294,18 @@ int psm_gradp_rows(psm_handle* h, const float* rows, int32_t n_frames, int32_t w
   if (!h) return PSM_ERR_ARG;
   if (!rows || !(gradp || p || truth || raw || scalars)) return fail(h, PSM_ERR_ARG, "null buffer");
   RowsSet& R = h->rows;
-  GradpSet& G = h->gradp;
   hipStream_t st = h->stream;
   // every check of the step before the first copy: the step itself repeats them
   RowsCall rc;
   int r = step_rows_call(h, PSM_ROWS_KIND_GRADP, R.d_rows, n_frames, width, 1.0, 1.0, ex, ey, R.d_scalars, rc);
-  if (r || (r = host_width_check(h, width))) return r;
-  if (!G.ready) return fail(h, PSM_ERR_STATE, "psm_bind_gradp_frames has not been called (psm_bind_frames, a new mesh, plan or model drop the binding)");
-  if ((r = filter_state(h, apply_filter, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_gradp_frames"))) return r;
+  if (r || (r = host_width_check(h, width)) || (r = gradp_host_check(h, rc.cols, n_frames, 5, apply_filter))) return r;
   if ((r = upload_rows(h, rows, n_frames, width))) return r;
-  const size_t npix = (size_t)h->Ny * h->Nx, pb = (size_t)n_frames * npix * sizeof(float), gb = 2 * pb;
-  const size_t tb = (size_t)n_frames * 3 * npix * sizeof(double), eb = (size_t)n_frames * 4 * PSM_ERR_RAW * sizeof(double);
-  const size_t sb = (size_t)n_frames * PSM_ROWS_SCALARS * sizeof(double);
-  float *d_g = G.integ.d_gradp, *d_p = G.integ.d_p;
-  r = guarded_host_step(h, st, "psm_gradp_rows", [&](int pass) {
-    int rs = gradp_step_device(h, rc.cols, n_frames, 5, nullptr, apply_filter, d_g, d_p, G.d_truth, G.d_raw, st, &rc);
-    if (rs || (raw && (rs = gradp_step_errors_device(h, n_frames, d_g, d_p, G.d_truth, G.d_raw, st)))) return rs;
-    if (gradp) HIPCHK(h, hipMemcpyAsync(G.h_gradp, d_g, gb, hipMemcpyDeviceToHost, st));
-    if (p) HIPCHK(h, hipMemcpyAsync(G.h_p, d_p, pb, hipMemcpyDeviceToHost, st));
-    if (truth && pass == 0) HIPCHK(h, hipMemcpyAsync(G.h_truth, G.d_truth, tb, hipMemcpyDeviceToHost, st));   // the labels do not depend on the route
-    if (raw) HIPCHK(h, hipMemcpyAsync(G.h_raw, G.d_raw, eb, hipMemcpyDeviceToHost, st));
-    if (scalars && pass == 0) HIPCHK(h, hipMemcpyAsync(R.h_scalars, R.d_scalars, sb, hipMemcpyDeviceToHost, st));
-    return PSM_OK;
+  HostOut out[5];
+  gradp_host_outs(h, n_frames, gradp, p, truth, raw, out);
+  out[4] = scalars_out(h, n_frames, scalars);
+  return host_step(h, st, "psm_gradp_rows", out, [&] {
+    return gradp_frames_step(h, rc.cols, n_frames, 5, nullptr, apply_filter, nullptr, nullptr, nullptr, raw ? h->gradp.d_raw : nullptr, st, &rc);
   });
-  if (r) return r;
-  if (gradp) memcpy(gradp, G.h_gradp, gb);
-  if (p) memcpy(p, G.h_p, pb);
-  if (truth) memcpy(truth, G.h_truth, tb);
-  if (raw) memcpy(raw, G.h_raw, eb);
-  if (scalars) memcpy(scalars, R.h_scalars, sb);
-  return PSM_OK;
 }
 
 }  // extern "C"

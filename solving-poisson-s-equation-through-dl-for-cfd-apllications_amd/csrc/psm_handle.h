@@ -11,7 +11,7 @@
 //   psm_api_integ.cpp       the gradP integration: tables, host entry and the device-resident U -> p (psm_set_integration ... psm_solve_pressure)
 //   psm_api_filter.cpp      the Gaussian post-steps: psm_gaussian_filter (host entry), psm_bind_poststeps and the device-resident / case-batched entries
 //   psm_api_features.cpp    the pressureSM_Poisson input features: the host entry psm_poisson_features; on the device psm_bind_features, psm_features_device and the whole step psm_poisson_step*
-//   psm_api_frames.cpp      frames of cell columns -> planes on the device: psm_bind_frames, psm_frames_to_grid_device and the evaluator's step psm_poisson_frames*
+//   psm_api_frames.cpp      frames of cell columns -> planes on the device: psm_bind_frames, psm_frames_to_grid_device and the evaluator's step psm_poisson_frames*; what the three evaluator bindings below share (EvalSet / EvalKind: eval_free, eval_state, eval_image_call, eval_bind)
 //   psm_api_errors.cpp      the per-frame error blocks of assembled fields on the device: psm_field_errors_device and the metrics-only frame step psm_poisson_frames_errors* (host arithmetic: psm_errors.cpp)
 //   psm_api_deltas_frames.cpp  the deltas evaluator's frame batch on the device: psm_bind_deltas_frames, the image pack psm_deltas_image_device (kernels of the three packs: psm_pack.hip), the batched block errors psm_block_errors_device and the step psm_deltas_frames*
 //   psm_api_gradp_frames.cpp   the U_to_gradP evaluator's frame batch on the device: psm_bind_gradp_frames, the image / label pack psm_gradp_image_device and the step psm_gradp_frames* (columns -> p -> errors)
@@ -362,61 +362,63 @@ struct RowsSet {
   double *d_scalars = nullptr, *h_scalars = nullptr;   // [n_frames][8], device and pinned
 };
 
-// Binding of the deltas evaluator's frame batch (psm_bind_deltas_frames, behind psm_bind_frames): the simulation's normalised SDF
-// plane, the scales, and every buffer a step touches for the bound frame count, so that a step allocates nothing.  The columns go
-// through the frame binding's staging (FrameSet::d_cols / h_cols).
-struct DeltasSet {
-  static constexpr int RING = 8;
+// What the three evaluator frame bindings hold alike (psm_bind_deltas_frames, psm_bind_gradp_frames, psm_bind_chapter4_frames, each
+// behind psm_bind_frames): the simulation's normalised SDF plane, the scales and the buffers every one of them touches in a step for
+// the bound frame count, so that a step allocates nothing.  The columns go through the frame binding's staging (FrameSet::d_cols /
+// h_cols).  Allocated by eval_bind, released by eval_free (psm_api_frames.cpp); the sizes that differ are the kind's (EvalKind).
+struct EvalSet {
   bool ready = false;
   int n_frames = 0;
-  double max_abs[4] = {1, 1, 1, 1};     // max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p
-  double* d_sdn = nullptr;              // [npix] nan0(sdfunct) / max_abs_dist in float64: channel 2 of the image, and the field errors' mask
-  double* d_planes = nullptr;           // [n_frames][3][npix] float64 planes of columns 0-2
-  float *d_grid = nullptr, *d_label = nullptr, *d_result = nullptr;   // image [n][npix][3], label plane [n][npix], field [n][npix]
-  double* d_truth = nullptr;            // [n][npix]
+  double max_abs[5] = {1, 1, 1, 1, 1};  // the scales the kind checks, in the order of its image and label channels
+  double* d_sdn = nullptr;              // [npix] nan0(sdfunct) / max_abs_dist in float64: the SDF channel of the image, and the field errors' mask
+  double* d_planes = nullptr;           // [n_frames][cols][npix] float64 planes of the stored columns
+  float* d_grid = nullptr;              // image [n][npix][c_in]
+  double* d_truth = nullptr;            // [n][truth_planes][npix]
+  double *d_raw = nullptr, *h_raw = nullptr;     // [n][raw_rows][8], device and pinned (host entry)
+  double* h_truth = nullptr;            // pinned [n][truth_planes][npix]
+};
+
+// What differs between the three kinds and is not a buffer, as data: the shared bodies (eval_state, eval_image_call, eval_bind) take one
+// of these and never ask which evaluator called.  0 / -1 stand for the value the model's c_in gives.
+struct EvalKind {
+  const char* bind_name;                // the bind entry, in front of its allocation failures
+  int cols;                             // columns stored as planes (0: c_in)
+  int scales;                           // max_abs scales checked and kept (0: c_in + 1)
+  int dist;                             // index of the distance scale among them (-1: c_in - 1)
+  int truth_planes, raw_rows;           // label planes and error blocks per frame
+  const char *k_msg, *align_msg, *unbound_msg;
+  int n_cols(const psm_config& c) const { return cols ? cols : c.c_in; }
+  int n_scales(const psm_config& c) const { return scales ? scales : c.c_in + 1; }
+  int dist_at(const psm_config& c) const { return dist >= 0 ? dist : c.c_in - 1; }
+};
+
+// The deltas evaluator's frame batch: max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p; planes of columns 0-2; truth [n][npix];
+// raw [n][2][8].  On top of the common set the label plane, the field, the block stage's buffers and the U^2 ring.
+struct DeltasSet : EvalSet {
+  static constexpr int RING = 8;
+  float *d_label = nullptr, *d_result = nullptr;   // label plane [n][npix], field [n][npix]
   float* d_res = nullptr;               // [round_up(n * B, 32)][ld_out] network output rows of the step's frames, for the block stage
   double *d_part = nullptr, *d_fraw = nullptr;   // block partials [n][B][8]; the field's sums [n][8] in front of the fold
-  double *d_raw = nullptr, *h_raw = nullptr;     // [n][2][8], device and pinned (host entry)
   float* h_result = nullptr;            // pinned [n][npix]
-  double* h_truth = nullptr;            // pinned [n][npix]
   double *d_u2 = nullptr, *h_u2 = nullptr;       // U^2 of the step's frames [n]; pinned upload ring [RING][n]
   hipEvent_t u2_ev[RING] = {};
   int u2_pos = 0;
 };
 
-// Binding of the U_to_gradP evaluator's frame batch (psm_bind_gradp_frames, behind psm_bind_frames): the simulation's normalised SDF
-// plane, the scales, integration tables OF ITS OWN (the simulation's one geometry and cut, replicated per frame slot so that the
-// integration kernels index them by case as ever; h->integ_dev and h->integ_host are not touched) and every buffer a step touches
-// for the bound frame count, so that a step allocates nothing.  The columns go through the frame binding's staging.
-struct GradpSet {
-  bool ready = false;
-  int n_frames = 0;
-  double max_abs[5] = {1, 1, 1, 1, 1};  // of grid channels 0-4: Ux, Uy, SDF, dPdx label, dPdy label
-  double* d_sdn = nullptr;              // [npix] nan0(sdfunct) / max_abs[2] in float64: channel 2 of the image, and the field errors' mask
-  double* d_planes = nullptr;           // [n_frames][5][npix] float64 planes of columns 0-4
-  float* d_grid = nullptr;              // image [n][npix][3]
-  double* d_truth = nullptr;            // [n][3][npix]: grid channels 3-5
+// The U_to_gradP evaluator's frame batch: scales of grid channels 0-4 (Ux, Uy, SDF, dPdx label, dPdy label); planes of columns 0-4;
+// truth [n][3][npix] (grid channels 3-5); raw [n][4][8].  On top of the common set integration tables OF ITS OWN (the simulation's
+// one geometry and cut, replicated per frame slot so that the integration kernels index them by case as ever; h->integ_dev and
+// h->integ_host are not touched).
+struct GradpSet : EvalSet {
   IntegSet integ;                       // the tables; integ.d_gradp [n][npix][2] and integ.d_p [n][npix] are the step's gradient and p
-  double *d_raw = nullptr, *h_raw = nullptr;     // [n][4][8], device and pinned (host entry)
   float *h_gradp = nullptr, *h_p = nullptr;      // pinned [n][npix][2], [n][npix]
-  double* h_truth = nullptr;            // pinned [n][3][npix]
 };
 
-// Binding of the Chapter-4 evaluators' frame batch (psm_bind_chapter4_frames, behind psm_bind_frames): the simulation's normalised SDF
-// plane, the scales and every buffer a step touches for the bound frame count, so that a step allocates nothing.  DeltasSet without
-// the block stage and the U^2 ring: prediction and label are compared in normalised units.  The columns go through the frame
-// binding's staging.
-struct Chapter4Set {
-  bool ready = false;
-  int n_frames = 0;
-  double max_abs[4] = {1, 1, 1, 1};     // [c_in + 1]: the c_in - 1 input channels, dist, p
-  double* d_sdn = nullptr;              // [npix] nan0(sdfunct) / max_abs_dist in float64: channel c_in - 1 of the image, and the field errors' mask
-  double* d_planes = nullptr;           // [n_frames][c_in][npix] float64 planes of columns 0 .. c_in - 1
-  float *d_grid = nullptr, *d_result = nullptr;   // image [n][npix][c_in], field [n][npix]
-  double* d_truth = nullptr;            // [n][npix]
-  double *d_raw = nullptr, *h_raw = nullptr;      // [n][1][8], device and pinned (host entry)
+// The Chapter-4 evaluators' frame batch: scales [c_in + 1] (the c_in - 1 input channels, dist, p); planes of columns 0 .. c_in - 1;
+// truth [n][npix]; raw [n][1][8].  No block stage and no U^2 ring: prediction and label are compared in normalised units.
+struct Chapter4Set : EvalSet {
+  float* d_result = nullptr;            // field [n][npix]
   float* h_result = nullptr;            // pinned [n][npix]
-  double* h_truth = nullptr;            // pinned [n][npix]
 };
 }  // namespace psm_impl
 using namespace psm_impl;
@@ -659,15 +661,28 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
 int deltas_pack_device(psm_handle* h, const DeltasCall& dc, int n_frames, hipStream_t st);
 int gradp_pack_device(psm_handle* h, const GradpCall& gc, int n_frames, hipStream_t st);
 int chapter4_pack_device(psm_handle* h, const Chapter4Call& cc, int n_frames, hipStream_t st);
-// the evaluators' frame steps and the error stages behind them (psm_api_deltas_frames.cpp, psm_api_gradp_frames.cpp); with `rows` the
-// rows stage heads the step, d_cols are its columns, and U2 / out_scale are not read: the finish launch leaves them on the device
-int deltas_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* out_scale, int apply_filter,
-                       float* d_result, double* d_truth, const double* d_raw, hipStream_t st, const RowsCall* rows = nullptr);
-int deltas_step_errors_device(psm_handle* h, int n_frames, const float* d_result, const double* d_truth, double* d_raw, hipStream_t st);
-int gradp_step_device(psm_handle* h, const double* d_cols, int n_frames, int k, const float* out_scale, int apply_filter, float* d_gradp,
-                      float* d_p, double* d_truth, const double* d_raw, hipStream_t st, const RowsCall* rows = nullptr);
-int gradp_step_errors_device(psm_handle* h, int n_frames, const float* d_gradp, const float* d_p, const double* d_truth, double* d_raw,
-                             hipStream_t st);
+// what the three evaluator bindings share (psm_api_frames.cpp); the kind is data, none of these asks which evaluator called
+void eval_free(EvalSet& s);           // the common buffers and the flags; the kind's *_free drops its graphs and its own buffers first
+int eval_state(psm_handle* h, const EvalSet& s, const EvalKind& kind);   // the mesh, the frame binding and this binding
+// state and arguments of a kind's image stage; the frame stage's descriptors: the stored columns into the binding's planes, the rest not stored
+int eval_image_call(psm_handle* h, const EvalSet& s, const EvalKind& kind, const double* d_cols, int n_frames, int k, const float* d_grid,
+                    const double* d_truth, FrameCall& fc);
+// The body of a psm_bind_*_frames entry behind its model-shape check: argument checks, nothing in flight, free_fn, `own` (the kind's own
+// tables and buffers for n frames of npix pixels, first: what it refuses binds nothing), the common buffers, the SDF plane, the flags.
+// Any failure leaves the set freed and not ready.
+int eval_bind(psm_handle* h, EvalSet& s, const EvalKind& kind, const double* sdfunct, const double* max_abs, void (*free_fn)(psm_handle*),
+              const std::function<int(size_t n, size_t npix)>& own);
+// The deltas and the gradP evaluator's frame step behind a device or a host entry, of the _frames and the _rows form alike
+// (psm_api_deltas_frames.cpp, psm_api_gradp_frames.cpp): null destinations become the binding's, then the step's checks and its one
+// graph replay, then the error stage when d_raw is given.  With `rows` the rows stage heads the step, d_cols are its columns, and U2 /
+// out_scale are not read: the finish launch leaves them on the device.  *_host_check: every check of that step on the binding's own
+// buffers and nothing else, for a host entry to run before its first copy.
+int deltas_frames_step(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, const float* out_scale, int apply_filter,
+                       float* d_result, double* d_truth, double* d_raw, hipStream_t st, const RowsCall* rows = nullptr);
+int deltas_host_check(psm_handle* h, const double* d_cols, int n_frames, int k, const double* U2, int apply_filter, const RowsCall* rows = nullptr);
+int gradp_frames_step(psm_handle* h, const double* d_cols, int n_frames, int k, const float* out_scale, int apply_filter, float* d_gradp,
+                      float* d_p, double* d_truth, double* d_raw, hipStream_t st, const RowsCall* rows = nullptr);
+int gradp_host_check(psm_handle* h, const double* d_cols, int n_frames, int k, int apply_filter);
 PsmFieldErrorArgs poisson_error_pairs(const psm_handle* h, int n_frames, int n_extra, const double* d_extra, const float* d_result, const float* d_next);
 int poisson_errors_call_check(psm_handle* h, int k, int weighting, const void* d_raw);
 bool guard_take(psm_handle* h, Workspace& w);
@@ -760,6 +775,37 @@ struct PostOut {
   }
   void deliver() const { for (int q = 0; q < 3; ++q) if (host[q]) memcpy(host[q], pin[q], bytes[q]); }
 };
+
+
+// One output of an evaluator's host entry through pinned memory, companion of PostOut: a host entry describes what it returns as a
+// stack array of at most five of these (a step allocates nothing) and host_step runs the step, the copies and the delivery.
+struct HostOut {
+  void* host;                           // the caller's destination (null: not wanted)
+  void* pin;                            // the binding's pinned staging
+  const void* dev;                      // the device source
+  size_t bytes;
+  bool pass0_only;                      // does not depend on the route (labels, the rows' scalars): not copied again after a guard trip
+};
+// what the deltas / gradP host entries return, the same for the _frames and the _rows form (which adds the scalars behind them)
+void deltas_host_outs(psm_handle* h, int n_frames, float* result, double* truth, double* raw, HostOut* out);             // 3 outputs
+void gradp_host_outs(psm_handle* h, int n_frames, float* gradp, float* p, double* truth, double* raw, HostOut* out);     // 4 outputs
+
+// The tail of an evaluator's host entry: `step` (the step and its error stage) and one device -> host copy per wanted output on `st`
+// under guarded_host_step, then one memcpy per wanted output, in the order of `out`.
+template <size_t N, typename Step>
+int host_step(psm_handle* h, hipStream_t st, const char* where, const HostOut (&out)[N], const Step& step) {
+  static_assert(N <= 5, "a host entry returns at most five outputs");
+  const int rc = guarded_host_step(h, st, where, [&](int pass) {
+    const int rs = step();
+    if (rs) return rs;
+    for (const HostOut& o : out)
+      if (o.host && (pass == 0 || !o.pass0_only)) HIPCHK(h, hipMemcpyAsync(o.pin, o.dev, o.bytes, hipMemcpyDeviceToHost, st));
+    return PSM_OK;
+  });
+  if (rc) return rc;
+  for (const HostOut& o : out) if (o.host) memcpy(o.host, o.pin, o.bytes);
+  return PSM_OK;
+}
 
 
 inline uint16_t f2bf(double v) {             // round-to-nearest-even float -> bf16 (NaN stays NaN)

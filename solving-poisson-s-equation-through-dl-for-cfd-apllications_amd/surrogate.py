@@ -801,6 +801,36 @@ class GridSurrogate:
                                                      _p(raw, C.c_double)))
         return raw
 
+    # -- what the three evaluator frame batches below share: the checks of a bind and of a call, before any library call
+    _EVAL_COLUMNS = {   # kind -> (fewest columns (0: the model's c_in), the message of a k outside the range)
+        "deltas": (3, "frames take 3..16 columns: (dUx / U, dUy / U, dp / U^2), further columns are not stored"),
+        "gradp": (5, "frames take 5..16 columns: (Ux / U, Uy / U, dPdx / U^2, dPdy / U^2, p / U^2), further columns are not stored"),
+        "chapter4": (0, "frames take c_in..16 columns: the c_in - 1 input channels, then p / U^2; further columns are not stored")}
+
+    def _bind_eval_frames(self, model_ok: bool, model_msg: str, sdfunct, max_abs, n_scales: int, scales_msg: str):
+        """The argument checks the three ``bind_*_frames`` share -> (sdfunct, max_abs) as float64 arrays."""
+        if not model_ok:
+            raise ValueError(model_msg)
+        if not getattr(self, "_frames_bound", False):
+            raise RuntimeError("bind_frames has not been called")
+        sdf = _f64(sdfunct)
+        if sdf.size != self.ny * self.nx:
+            raise ValueError(f"sdfunct must be [{self.ny},{self.nx}]")
+        mx = _f64(np.asarray(max_abs, np.float64).reshape(-1))
+        if mx.size != n_scales or not np.all(np.isfinite(mx)) or np.any(mx == 0):
+            raise ValueError(f"max_abs must hold {scales_msg}")
+        return sdf, mx
+
+    def _eval_call(self, kind: str, n_frames, k):
+        """The argument checks the frame entries of the three evaluators share."""
+        k_min, k_msg = self._EVAL_COLUMNS[kind]
+        if not getattr(self, f"_{kind}_bound"):
+            raise RuntimeError(f"bind_{kind}_frames has not been called (bind_frames and a new mesh drop the binding)")
+        if not (k_min or self.model.c_in) <= int(k) <= 16:
+            raise ValueError(k_msg)
+        if not 1 <= int(n_frames) <= self.max_cases:
+            raise ValueError("n_frames outside [1, max_cases]")
+
     # -- the frame batch of the pressureSM_deltas evaluator on the device: columns -> image, label, truth -> solve -> two error blocks
     _deltas_bound = False
 
@@ -809,16 +839,9 @@ class GridSurrogate:
         ``sdfunct`` [Ny,Nx] float64 (NaNs allowed) and ``max_abs`` = (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p), each finite
         and non-zero.  Reserves everything a step touches for the frame count bound with ``bind_frames``."""
         m = self.model
-        if m.c_in != 3 or m.sdf_ch != 2 or m.c_out != 1:
-            raise ValueError("the deltas frames take a model with 3 input channels, the SDF in channel 2, and 1 output channel")
-        if not getattr(self, "_frames_bound", False):
-            raise RuntimeError("bind_frames has not been called")
-        sdf = _f64(sdfunct)
-        if sdf.size != self.ny * self.nx:
-            raise ValueError(f"sdfunct must be [{self.ny},{self.nx}]")
-        mx = _f64(np.asarray(max_abs, np.float64).reshape(-1))
-        if mx.size != 4 or not np.all(np.isfinite(mx)) or np.any(mx == 0):
-            raise ValueError("max_abs must hold four finite non-zero scales: (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p)")
+        sdf, mx = self._bind_eval_frames(
+            m.c_in == 3 and m.sdf_ch == 2 and m.c_out == 1, "the deltas frames take a model with 3 input channels, the SDF in channel 2, and 1 output channel",
+            sdfunct, max_abs, 4, "four finite non-zero scales: (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p)")
         self._deltas_bound = False
         self._chk(self.lib.psm_bind_deltas_frames(self.h, _p(sdf, C.c_double), _p(mx, C.c_double)))
         self._deltas_bound = True
@@ -829,12 +852,7 @@ class GridSurrogate:
 
     def _deltas_call(self, n_frames, k, U2, need_u2: bool = True):
         """The argument checks the deltas frame entries share -> U2 as a float64 array (None where it is optional and absent)."""
-        if not self._deltas_bound:
-            raise RuntimeError("bind_deltas_frames has not been called (bind_frames and a new mesh drop the binding)")
-        if not 3 <= int(k) <= 16:
-            raise ValueError("frames take 3..16 columns: (dUx / U, dUy / U, dp / U^2), further columns are not stored")
-        if not 1 <= int(n_frames) <= self.max_cases:
-            raise ValueError("n_frames outside [1, max_cases]")
+        self._eval_call("deltas", n_frames, k)
         if U2 is None:
             if need_u2:
                 raise ValueError("U2 must hold one value per frame")
@@ -919,16 +937,9 @@ class GridSurrogate:
         own (``bind_integration`` / ``set_integration`` are not touched).  Reserves everything a step touches for the frame count
         bound with ``bind_frames``.  Returns False -- nothing bound -- where the reference itself raises on the geometry."""
         m = self.model
-        if m.c_in != 3 or m.sdf_ch != 2 or m.c_out != 2:
-            raise ValueError("the gradP frames take a model with 3 input channels, the SDF in channel 2, and 2 output channels")
-        if not getattr(self, "_frames_bound", False):
-            raise RuntimeError("bind_frames has not been called")
-        sdf = _f64(sdfunct)
-        if sdf.size != self.ny * self.nx:
-            raise ValueError(f"sdfunct must be [{self.ny},{self.nx}]")
-        mx = _f64(np.asarray(max_abs, np.float64).reshape(-1))
-        if mx.size != 5 or not np.all(np.isfinite(mx)) or np.any(mx == 0):
-            raise ValueError("max_abs must hold five finite non-zero scales: those of grid channels 0-4")
+        sdf, mx = self._bind_eval_frames(
+            m.c_in == 3 and m.sdf_ch == 2 and m.c_out == 2, "the gradP frames take a model with 3 input channels, the SDF in channel 2, and 2 output channels",
+            sdfunct, max_abs, 5, "five finite non-zero scales: those of grid channels 0-4")
         if not (1 <= int(center_y) < self.ny and 1 <= int(center_x) < self.nx):
             raise ValueError("the cut (center_y, center_x) lies outside the grid")
         self._gradp_bound = False
@@ -943,20 +954,11 @@ class GridSurrogate:
         self._gradp_bound = False
         self._chk(self.lib.psm_unbind_gradp_frames(self.h))
 
-    def _gradp_call(self, n_frames, k):
-        """The argument checks the gradP frame entries share."""
-        if not self._gradp_bound:
-            raise RuntimeError("bind_gradp_frames has not been called (bind_frames and a new mesh drop the binding)")
-        if not 5 <= int(k) <= 16:
-            raise ValueError("frames take 5..16 columns: (Ux / U, Uy / U, dPdx / U^2, dPdy / U^2, p / U^2), further columns are not stored")
-        if not 1 <= int(n_frames) <= self.max_cases:
-            raise ValueError("n_frames outside [1, max_cases]")
-
     def gradp_image_device(self, d_cols: int, n_frames: int, k: int, d_grid: int, d_truth: int = 0, stream: int = 0):
         """The image stage alone on raw device pointers, asynchronous on ``stream``: ``d_cols`` [n,n_cells,k] float64 -> ``d_grid``
         [n,Ny,Nx,3] float32 and ``d_truth`` [n,3,Ny*Nx] float64 (grid channels 3-5; 0: not stored), bit for bit the host statements
         of ``EvaluationGradP.timeStep``."""
-        self._gradp_call(n_frames, k)
+        self._eval_call("gradp", n_frames, k)
         d_cols = self._dev_ptr(d_cols, 8, "d_cols")
         d_grid, d_truth = self._dev_ptr(d_grid, 4, "d_grid"), self._dev_ptr(d_truth, 8, "d_truth", True)
         self._chk(self.lib.psm_gradp_image_device(self.h, C.c_void_p(d_cols), int(n_frames), int(k), C.c_void_p(d_grid),
@@ -969,7 +971,7 @@ class GridSurrogate:
         ``apply_filter``) -> integration with the binding's tables -> ``d_gradp`` [n,Ny*Nx,2] float32, ``d_p`` [n,Ny*Nx] float32,
         ``d_truth`` [n,3,Ny*Nx] float64 (0: the binding's buffers); with ``d_raw`` [n,4,8] float64 the four error blocks behind it:
         p against label 0 (the reference's metric), p against the pressure label, the two gradient components against theirs."""
-        self._gradp_call(n_frames, k)
+        self._eval_call("gradp", n_frames, k)
         self._needs_post(apply_filter)
         d_cols = self._dev_ptr(d_cols, 8, "d_cols")
         d_gradp, d_p = self._dev_ptr(d_gradp, 8, "d_gradp", True), self._dev_ptr(d_p, 4, "d_p", True)
@@ -985,7 +987,7 @@ class GridSurrogate:
         """Host buffers, synchronous: ``cols`` [n,n_cells,k] (or [n_cells,k]) float64 -> (gradp [n,Ny,Nx,2] float32, p [n,Ny,Nx]
         float32, truth [n,3,Ny,Nx] float64, raw [n,4,8] float64); what is not wanted is None and is not copied back -- a
         metrics-only sweep (``want_gradp = want_p = want_truth = False``) brings back 32 doubles per frame."""
-        v, n, k, _ = self._host_cols(cols, self._gradp_call)
+        v, n, k, _ = self._host_cols(cols, lambda n, k: self._eval_call("gradp", n, k))
         self._needs_post(apply_filter)
         sc = self._frame_scale(out_scale, n)
         gradp, p, truth, raw = self._gradp_out(n, want_gradp, want_p, want_truth)
@@ -1003,16 +1005,10 @@ class GridSurrogate:
         max_abs_p; M_fU: max_abs_fU, max_abs_dist, max_abs_p).  Reserves everything a step touches for the frame count bound with
         ``bind_frames``."""
         m = self.model
-        if m.variant != "chapter5" or m.c_in not in (2, 3) or m.sdf_ch != m.c_in - 1 or m.c_out != 1:
-            raise ValueError("the Chapter-4 frames take a chapter5-variant model with 2 or 3 input channels, the SDF in the last one, and 1 output channel")
-        if not getattr(self, "_frames_bound", False):
-            raise RuntimeError("bind_frames has not been called")
-        sdf = _f64(sdfunct)
-        if sdf.size != self.ny * self.nx:
-            raise ValueError(f"sdfunct must be [{self.ny},{self.nx}]")
-        mx = _f64(np.asarray(max_abs, np.float64).reshape(-1))
-        if mx.size != m.c_in + 1 or not np.all(np.isfinite(mx)) or np.any(mx == 0):
-            raise ValueError("max_abs must hold c_in + 1 finite non-zero scales: the c_in - 1 input channels, dist, p")
+        sdf, mx = self._bind_eval_frames(
+            m.variant == "chapter5" and m.c_in in (2, 3) and m.sdf_ch == m.c_in - 1 and m.c_out == 1,
+            "the Chapter-4 frames take a chapter5-variant model with 2 or 3 input channels, the SDF in the last one, and 1 output channel",
+            sdfunct, max_abs, m.c_in + 1, "c_in + 1 finite non-zero scales: the c_in - 1 input channels, dist, p")
         self._chapter4_bound = False
         self._chk(self.lib.psm_bind_chapter4_frames(self.h, _p(sdf, C.c_double), _p(mx, C.c_double)))
         self._chapter4_bound = True
@@ -1021,20 +1017,11 @@ class GridSurrogate:
         self._chapter4_bound = False
         self._chk(self.lib.psm_unbind_chapter4_frames(self.h))
 
-    def _chapter4_call(self, n_frames, k):
-        """The argument checks the Chapter-4 frame entries share."""
-        if not self._chapter4_bound:
-            raise RuntimeError("bind_chapter4_frames has not been called (bind_frames and a new mesh drop the binding)")
-        if not self.model.c_in <= int(k) <= 16:
-            raise ValueError("frames take c_in..16 columns: the c_in - 1 input channels, then p / U^2; further columns are not stored")
-        if not 1 <= int(n_frames) <= self.max_cases:
-            raise ValueError("n_frames outside [1, max_cases]")
-
     def chapter4_image_device(self, d_cols: int, n_frames: int, k: int, d_grid: int, d_truth: int = 0, stream: int = 0):
         """The image stage alone on raw device pointers, asynchronous on ``stream``: ``d_cols`` [n,n_cells,k] float64 -> ``d_grid``
         [n,Ny,Nx,c_in] float32 and ``d_truth`` [n,Ny*Nx] float64 (the normalised pressure label; 0: not stored), bit for bit the
         host statements of ``EvaluationChapter4.timeStep``."""
-        self._chapter4_call(n_frames, k)
+        self._eval_call("chapter4", n_frames, k)
         d_cols = self._dev_ptr(d_cols, 8, "d_cols")
         d_grid, d_truth = self._dev_ptr(d_grid, 4, "d_grid"), self._dev_ptr(d_truth, 8, "d_truth", True)
         self._chk(self.lib.psm_chapter4_image_device(self.h, C.c_void_p(d_cols), int(n_frames), int(k), C.c_void_p(d_grid),
@@ -1045,7 +1032,7 @@ class GridSurrogate:
         """The Chapter-4 evaluators' frames as one graph replay on raw device pointers: ``d_cols`` [n,n_cells,k] float64 -> planes
         -> image, truth -> one single-case solve per frame -> ``d_result`` [n,Ny*Nx] float32, ``d_truth`` [n,Ny*Nx] float64 (0: the
         binding's buffers); with ``d_raw`` [n,1,8] float64 the error block behind it: the field against the truth, both normalised."""
-        self._chapter4_call(n_frames, k)
+        self._eval_call("chapter4", n_frames, k)
         d_cols = self._dev_ptr(d_cols, 8, "d_cols")
         d_result, d_truth = self._dev_ptr(d_result, 4, "d_result", True), self._dev_ptr(d_truth, 8, "d_truth", True)
         d_raw = self._dev_ptr(d_raw, 8, "d_raw", True)
@@ -1056,7 +1043,7 @@ class GridSurrogate:
         """Host buffers, synchronous: ``cols`` [n,n_cells,k] (or [n_cells,k]) float64 -> (result [n,Ny,Nx] float32, truth [n,Ny,Nx]
         float64, raw [n,1,8] float64); what is not wanted is None and is not copied back -- a metrics-only sweep
         (``want_result = want_truth = False``) brings back 8 doubles per frame."""
-        v, n, k, _ = self._host_cols(cols, self._chapter4_call)
+        v, n, k, _ = self._host_cols(cols, lambda n, k: self._eval_call("chapter4", n, k))
         if not (want_result or want_truth or want_raw):
             raise ValueError("nothing to return")
         result, truth, raw = self._chapter4_out(n, want_result, want_truth, want_raw)

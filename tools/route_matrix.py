@@ -16,7 +16,12 @@ The `steps` configurations (--only steps, or one of STEPS by name) hash the entr
 csrc/psm_api_step.cpp), each in a child process of its own: per variant (with / without out_scale, apply_filter 0 / 1) one call on a
 handle that launches plainly, then a capture and two replays on a PSM_GRAPH=1 handle, one SHA-256 per output; the `_host`
 configurations go through the host entry on a bound geometry and then, with one frame, on a geometry that is not the frames' (one
-guard trip, the re-run on the general path).
+guard trip, the re-run on the general path).  The `_rows` entries take the frames as float32 dataset rows (width 11, gradP 8): no
+out_scale (the rows stage makes it on the device), and the per-frame scalars are one more hashed output.
+
+The `refusals` configuration (--only refusals) is a fixed list of calls that the three evaluators' image, device, host and rows
+entries refuse from their argument checks, before anything is enqueued: one line per call with the return code and the text of
+psm_last_error, to be compared with diff between two builds.
 
 --lib: the library to load (default: the tree's libpsm_hip.so), e.g. the parent commit's build.  PSM_MESH_GRAPH is read once per
 process: the `mesh` configuration runs in the mode --mesh-graph sets (default 2), so the three modes take three runs.
@@ -76,8 +81,10 @@ BOUNDARY = {
 # weighting pair (the error blocks need the two label planes: 8); 4 / 6 = one column more than the deltas / gradP pack stores.
 # chapter4_frames_<inputs>: both image widths (M_u 3, M_fU 2), c_in + 1 columns; the entry takes no scale and no filter.
 STEPS = {"pressure": None, "poststeps": None, "poisson_step": ("poisson_step", 2)}
-for _e in ("poisson_frames", "poisson_frames_errors", "deltas_frames", "gradp_frames", "chapter4_frames_M_u", "chapter4_frames_M_fU"):
+for _e in ("poisson_frames", "poisson_frames_errors", "deltas_frames", "gradp_frames", "chapter4_frames_M_u", "chapter4_frames_M_fU",
+           "deltas_rows", "gradp_rows", "poisson_rows"):
     STEPS.update({f"{_e}_n1": (_e, 1), f"{_e}_n3": (_e, 3), f"{_e}_host": (_e, 0)})
+REFUSALS = {"refusals": {}}
 OTHER = ["attention_ln_deferred", "attention_ln_launched", "conv1d_head", "mesh", "ring", "pressure", "poststeps"]
 _lines = []
 
@@ -390,11 +397,13 @@ def steps_config(name):
     from test_poisson_step_device import K, MAX_ABS, P_SCALE, S_FIELD, S_WEIGHT, model4
     entry, n = STEPS[name]
     poisson, NF, CELLS = entry.startswith("poisson"), 3, 200
+    fam, by_rows = entry.split("_")[0], entry.endswith("_rows")             # poisson / deltas / gradp / chapter4; frames as dataset rows
     chapter4 = entry.startswith("chapter4_frames")
     c4_in = 3 if entry.endswith("M_u") else 2
     c4_maxs = cases.DATASET_MAXS if c4_in == 3 else (cases.DATASET_MAXS[0],) + tuple(cases.DATASET_MAXS[2:])
-    ny, nx = (320, 300) if entry == "gradp_frames" else (138, 300)
-    k = c4_in + 1 if chapter4 else {"poisson_step": 0, "poisson_frames": 7, "poisson_frames_errors": 8, "deltas_frames": 4, "gradp_frames": 6}[entry]
+    ny, nx = (320, 300) if fam == "gradp" else (138, 300)
+    k = c4_in + 1 if chapter4 else {"poisson_step": 0, "poisson_frames": 7, "poisson_frames_errors": 8, "deltas_frames": 4, "gradp_frames": 6,
+                                    "deltas_rows": 3, "gradp_rows": 5, "poisson_rows": 8}[entry]    # rows: the columns the stage writes
     npix, rng = ny * nx, np.random.default_rng(1901)
     vtx = rng.integers(0, CELLS, (npix, 3)).astype(np.int32)                    # the tables of tests/test_field_errors.py:flow_tables on this grid
     w = rng.random((npix, 2)) * 0.5
@@ -409,6 +418,11 @@ def steps_config(name):
         cols[..., k - 1] *= 0.1
         cols[0, 3:6, 4] = np.nan                                                # a label plane with NaN cells
     cols = np.ascontiguousarray(cols)
+    width = 8 if fam == "gradp" else 11                                         # dataset rows: the least width of the kind
+    rows = rng.standard_normal((NF, CELLS, width)).astype(np.float32) * (1.0 + 0.3 * np.arange(NF, dtype=np.float32))[:, None, None]
+    rows[..., 5:7] *= np.float32(0.05)
+    rows[..., 8:10] *= np.float32(0.05)
+    base, phi, ex, ey = (cases.POISSON_MAXS[4] if poisson else cases.DATASET_MAXS[3]), 0.16, 1.45, 0.63
     U = [float(np.sqrt(cols[f, :, 0] ** 2 + cols[f, :, 1] ** 2).max()) for f in range(NF)] if k else [1.3, 1.7, 2.1]
     lu, u2 = np.array([[0.16, u] for u in U]), [u * u for u in U]
     scale = [P_SCALE * u * u for u in U]
@@ -416,7 +430,7 @@ def steps_config(name):
     dU, prev = np.abs(rng.standard_normal((NF, ny, nx))).astype(np.float32), (0.1 * rng.standard_normal((NF, ny, nx))).astype(np.float32)
     if poisson:
         model, c_in, sdf_scale = model4(), 4, MAX_ABS[3]
-    elif entry == "deltas_frames":
+    elif fam == "deltas":
         model, c_in, sdf_scale = synthetic.make_model("deltas", p_in=48, p_out=40, c_in=3, seed_pca=778, seed_w=6), 3, cases.DATASET_MAXS[2]
     elif chapter4:
         model, c_in, sdf_scale = synthetic.make_model("chapter5", p_in=32, p_out=32, c_in=c4_in), c4_in, c4_maxs[-2]
@@ -434,10 +448,12 @@ def steps_config(name):
             sur.bind_features(np.repeat(sdf[None], NF, axis=0), K, MAX_ABS)
         if k:
             sur.bind_frames(NF, k)
-        if entry == "deltas_frames":
+        if fam == "deltas":
             sur.bind_deltas_frames(sdf, cases.DATASET_MAXS)
-        if entry == "gradp_frames":
+        if fam == "gradp":
             assert sur.bind_gradp_frames(sdf, cases.GRADP_MAXS, 57, 50, 1.0 / nx, 1.0 / ny)
+        if by_rows:
+            sur.bind_rows(width)
         if chapter4:
             sur.bind_chapter4_frames(sdf, c4_maxs)
         return sur
@@ -450,6 +466,12 @@ def steps_config(name):
 
     def host_call(sur, frames, sc, af):
         c, s = cols[:frames], (scale[:frames] if sc else None)
+        if entry == "deltas_rows":
+            return dict(zip(("result", "truth", "raw", "scalars"), sur.deltas_rows(rows[:frames], base, apply_filter=af)))
+        if entry == "gradp_rows":
+            return dict(zip(("gradp", "p", "truth", "raw", "scalars"), sur.gradp_rows(rows[:frames], ex, ey, apply_filter=af)))
+        if entry == "poisson_rows":
+            return dict(zip(("result", "change", "next", "extra", "scalars"), sur.poisson_rows(rows[:frames], base, phi, apply_filter=af)))
         if entry == "poisson_frames":
             return dict(zip(("result", "change", "next", "extra"), sur.poisson_frames(c, lu[:frames], out_scale=s, apply_filter=af)))
         if entry == "poisson_frames_errors":
@@ -462,7 +484,16 @@ def steps_config(name):
 
     def device_call(sur, b, sc, af):
         s = scale[:n] if sc else None
-        if entry == "poisson_step":
+        ptr = lambda key: C.c_void_p(b[key].ptr)
+        if entry == "deltas_rows":                           # the rows' device entries have no Python mirror: the C entries
+            sur._chk(sur.lib.psm_deltas_rows_device(sur.h, ptr("rows"), n, width, base, int(af), ptr("result"), ptr("truth"), ptr("raw"), ptr("scalars"), None))
+        elif entry == "gradp_rows":
+            sur._chk(sur.lib.psm_gradp_rows_device(sur.h, ptr("rows"), n, width, ex, ey, int(af), ptr("gradp"), ptr("p"), ptr("truth"), ptr("raw"),
+                                                   ptr("scalars"), None))
+        elif entry == "poisson_rows":
+            sur._chk(sur.lib.psm_poisson_rows_device(sur.h, ptr("rows"), n, width, base, phi, int(af), 1, ptr("extra"), ptr("result"), ptr("change"),
+                                                     ptr("next"), ptr("scalars"), None))
+        elif entry == "poisson_step":
             sur.poisson_step_device(b["vel"].ptr, n, lu[:n], b["result"].ptr, af, b["dU"].ptr, b["prev"].ptr, b["change"].ptr, b["next"].ptr, out_scale=s)
         elif entry == "poisson_frames":
             sur.poisson_frames_device(b["cols"].ptr, n, k, lu[:n], b["result"].ptr, af, True, b["extra"].ptr, b["change"].ptr, b["next"].ptr, out_scale=s)
@@ -480,30 +511,138 @@ def steps_config(name):
     f32, f64 = np.float32, np.float64
     outputs = {"poisson_step": ("result", "change", "next"), "poisson_frames": ("result", "change", "next", "extra"),
                "poisson_frames_errors": ("result", "change", "next", "extra", "raw"), "deltas_frames": ("result", "truth", "raw"),
-               "gradp_frames": ("gradp", "p", "truth", "raw")}.get(entry, ("result", "truth", "raw"))
+               "gradp_frames": ("gradp", "p", "truth", "raw"), "deltas_rows": ("result", "truth", "raw", "scalars"),
+               "gradp_rows": ("gradp", "p", "truth", "raw", "scalars"),
+               "poisson_rows": ("result", "change", "next", "extra", "scalars")}.get(entry, ("result", "truth", "raw"))
     shapes = {"result": ((NF, npix), f32), "change": ((NF, npix), f32), "next": ((NF, npix), f32), "extra": ((NF, max(k - 6, 1), npix), f64),
-              "raw": ((NF, 4, 8), f64), "truth": ((NF, 3, npix), f64), "gradp": ((NF, npix, 2), f32), "p": ((NF, npix), f32)}
+              "raw": ((NF, 4, 8), f64), "truth": ((NF, 3, npix), f64), "gradp": ((NF, npix, 2), f32), "p": ((NF, npix), f32), "scalars": ((NF, 8), f64)}
     line = lambda what, outs: [say(f"{name:28s} {what:34s} {key:7s} {sha(a)}") for key, a in outs.items() if a is not None]
     for graph in (False, True):
         with handle(graph) as sur:
             mode = "graph" if graph else "plain"
             if n == 0:                                       # host entry: bound (3 frames), then one frame on another geometry
                 bind(sur, NF, other=False)
-                line(f"{mode} host bound scale=1 af=1", host_call(sur, NF, True, True))
+                line(f"{mode} host bound scale={int(not by_rows)} af=1", host_call(sur, NF, not by_rows, True))
                 assert sur.guard_trips == 0 and sur.geometry_bound, "the frames' own geometry tripped the guard"
                 bind(sur, 1, other=True)
                 line(f"{mode} host trip scale=0 af=0", host_call(sur, 1, False, False))
                 say(f"{name:28s} {mode} host trip: guard trips {sur.guard_trips}, still bound {sur.geometry_bound}")
                 continue
             b = {key: DeviceArray(np.zeros(*shapes[key])) for key in outputs}
-            b.update(vel=DeviceArray(vel), dU=DeviceArray(dU), prev=DeviceArray(prev), cols=DeviceArray(cols))
-            for sc in (False,) if chapter4 else (False, True):      # the Chapter-4 entry takes neither
+            b.update(vel=DeviceArray(vel), dU=DeviceArray(dU), prev=DeviceArray(prev), cols=DeviceArray(cols), rows=DeviceArray(rows))
+            for sc in (False,) if chapter4 or by_rows else (False, True):      # the Chapter-4 entry takes neither, a rows entry no scale
                 for af in (False,) if chapter4 else (False, True):
                     for rep in range(3 if graph else 1):     # graph: the capture and two replays
                         what = ("plain" if not graph else ("capture", "replay1", "replay2")[rep]) + f" scale={int(sc)} af={int(af)}"
                         line(what, device_call(sur, b, sc, af))
             for d in b.values():
                 d.free()
+
+
+def refusals_config():
+    """Runs in the child process: one line per refused call, `<evaluator> <call> rc=<code> <psm_last_error>`.  The tables, frames and
+    SDF plane of tests/test_field_errors.py (130 x 131, 200 cells, 3 frames); no post-steps are bound, so apply_filter is refused too.
+    Every pointer that is not the one under test is a real buffer of the full size: a call that were NOT refused would stay in bounds."""
+    import numpy as np
+    import cases
+    from hipmem import DeviceArray
+    from psm_amd import GridSurrogate, _lib, synthetic
+    from test_field_errors import NF, flow_tables
+    os.environ["PSM_GRAPH"] = "0"
+    t = flow_tables()
+    npix, sdf = t.ny * t.nx, np.ascontiguousarray(t.sdfunct)
+    f64p, f32p = (lambda a: a.ctypes.data_as(C.POINTER(C.c_double))), (lambda a: a.ctypes.data_as(C.POINTER(C.c_float)))
+    chapter4 = synthetic.make_model("chapter5", p_in=32, p_out=32, c_in=3)
+    chapter4.ov, chapter4.sdf_ch = 96, 2
+    # evaluator: (model, scales, stored columns, rows width or 0, bind arguments behind the scales, float32 outputs per pixel)
+    kinds = {"deltas": (synthetic.make_model("deltas", p_in=32, p_out=32), cases.DATASET_MAXS, 3, 11, ()),
+             "gradp": (synthetic.make_model("gradp", p_in=32, p_out=32), cases.GRADP_MAXS, 5, 8, (57, 50, 1.0 / t.nx, 1.0 / t.ny)),
+             "chapter4": (chapter4, cases.DATASET_MAXS, 3, 0, ())}
+    for ev, (model, maxs, k0, width, bind_tail) in kinds.items():
+        with GridSurrogate(model, t.ny, t.nx, max_cases=NF) as sur:
+            lib, h = sur.lib, sur.h
+            sur.set_mesh(t.vtx, t.wts, t.indices, t.sdfunct, t.n_cells)
+            cols, rows = np.zeros((NF + 1, t.n_cells, 16)), np.zeros((NF + 1, t.n_cells, 16), np.float32)
+            u2, mx = np.ones(NF + 1), np.array(maxs, np.float64)
+            d = {key: DeviceArray(np.zeros((NF + 1) * 3 * npix + 2, dt)) for key, dt in
+                 dict(cols=np.float64, rows=np.float32, grid=np.float32, label=np.float32, a=np.float32, b=np.float32, truth=np.float64,
+                      raw=np.float64, scalars=np.float64).items()}
+            host = {key: np.zeros((NF + 1) * 3 * npix, dt) for key, dt in dict(a=np.float32, b=np.float32, truth=np.float64, raw=np.float64, scalars=np.float64).items()}
+
+            def call(what, n=NF, k=k0, af=0, off={}, null=()):
+                """One call of entry `what` with n frames, k columns; off: byte offsets added to device pointers; null: pointers passed as NULL."""
+                P = lambda key: None if key in null else C.c_void_p(d[key].ptr + off.get(key, 0))
+                H = lambda key: None if key in null else (f32p if host[key].dtype == np.float32 else f64p)(host[key])
+                U2 = None if "U2" in null else f64p(u2)
+                c_cols, c_rows = (None if "cols" in null else f64p(cols)), (None if "rows" in null else f32p(rows))
+                if what == "image":
+                    lead = (h, P("cols"), n, k) + ((U2, P("grid"), P("label")) if ev == "deltas" else (P("grid"),))
+                    return getattr(lib, f"psm_{ev}_image_device")(*lead, P("truth"), None)
+                if what == "device":
+                    args = {"deltas": (U2, None, af, P("a"), P("truth"), P("raw")), "gradp": (None, af, P("a"), P("b"), P("truth"), P("raw")),
+                            "chapter4": (P("a"), P("truth"), P("raw"))}[ev]
+                    return getattr(lib, f"psm_{ev}_frames_device")(h, P("cols"), n, k, *args, None)
+                if what == "host":
+                    args = {"deltas": (U2, None, af, H("a"), H("truth"), H("raw")), "gradp": (None, af, H("a"), H("b"), H("truth"), H("raw")),
+                            "chapter4": (H("a"), H("truth"), H("raw"))}[ev]
+                    return getattr(lib, f"psm_{ev}_frames")(h, c_cols, n, k, *args)
+                lead = (h, P("rows") if what == "rows_device" else c_rows, n, width) + ((1.0, af) if ev == "deltas" else (1.45, 0.63, af))
+                outs = (P if what == "rows_device" else H)
+                tail = (outs("a"), outs("truth"), outs("raw"), outs("scalars")) if ev == "deltas" else (outs("a"), outs("b"), outs("truth"), outs("raw"), outs("scalars"))
+                return getattr(lib, f"psm_{ev}_{what}")(*lead, *tail, *((None,) if what == "rows_device" else ()))
+
+            def bind(m=mx, tail=bind_tail):
+                return getattr(lib, f"psm_bind_{ev}_frames")(h, f64p(sdf), f64p(np.ascontiguousarray(m, np.float64)), *tail)
+
+            def note(label, rc):
+                msg = _lib.last_error(h) if rc else ""
+                say(f"{ev:9s} {label:44s} rc={rc} {msg}")
+            entries = ["image", "device", "host"] + (["rows_device", "rows"] if width else [])
+            note("bind, frames unbound", bind())
+            for e in entries:
+                note(f"{e}, frames unbound", call(e))
+            sur.bind_frames(NF, k0)
+            if width:
+                sur.bind_rows(width)
+            for e in entries:
+                note(f"{e}, evaluator binding unbound", call(e))
+            for q, bad in ((2, 0.0), (0, np.inf), (len(mx) - 1, np.nan)):
+                m = mx.copy()
+                m[q] = bad
+                note(f"bind, scale {q} = {bad}", bind(m))
+            if ev == "gradp":
+                note("bind, the cut the reference raises on", bind(tail=(57, 30) + bind_tail[2:]))
+                note("bind, a cut outside the grid", bind(tail=(t.ny, 50) + bind_tail[2:]))
+            for e in entries:
+                note(f"{e}, after the refused binds", call(e))
+            note("bind", bind())
+            for e in entries[:3]:                            # the rows entries take no k
+                for k in (k0 - 1, 17):
+                    note(f"{e}, k = {k}", call(e, k=k))
+            for e in entries:
+                for n in (0, NF + 1):
+                    note(f"{e}, n_frames = {n}", call(e, n=n))
+                note(f"{e}, input NULL", call(e, null=("rows" if e.startswith("rows") else "cols",)))
+            note("image, d_grid NULL", call("image", null=("grid",)))
+            note("image, d_grid 2 bytes off", call("image", off={"grid": 2}))
+            note("image, d_truth 4 bytes off", call("image", off={"truth": 4}))
+            if ev == "deltas":
+                note("image, d_label 2 bytes off", call("image", off={"label": 2}))
+                note("image, d_truth without U2", call("image", null=("U2",)))
+                note("device, U2 NULL", call("device", null=("U2",)))
+                note("host, U2 NULL", call("host", null=("U2",)))
+            for e in ("device", "rows_device")[:2 if width else 1]:
+                for key, half in (("a", 4 if ev == "gradp" else 2), ("b", 2), ("truth", 4), ("raw", 4), ("scalars", 4)):
+                    if (key == "b" and ev != "gradp") or (key == "scalars" and e == "device"):
+                        continue
+                    note(f"{e}, {key} {half} bytes off", call(e, off={key: half}))
+            if ev != "chapter4":
+                for e in entries[1:]:
+                    note(f"{e}, apply_filter without post-steps", call(e, af=1))
+            note("host, nothing wanted", call("host", null=("a", "b", "truth", "raw")))
+            sur.synchronize()
+            for a in d.values():
+                a.free()
 
 
 def children(names, lib, flag, envs):
@@ -565,6 +704,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--boundary-child", help=argparse.SUPPRESS)
     ap.add_argument("--steps-child", help=argparse.SUPPRESS)
+    ap.add_argument("--refusals-child", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.dispatches:
         return dispatches(args.dispatches)
@@ -576,12 +716,17 @@ def main():
         return boundary_config(args.boundary_child)
     if args.steps_child:
         return steps_config(args.steps_child)
+    if args.refusals_child:
+        return refusals_config()
     only = args.only.split(",") if args.only else []
-    group = next((g for g, names in (("boundary", BOUNDARY), ("steps", STEPS)) if only and all(n == g or n in names for n in only)), None)
+    group = next((g for g, names in (("boundary", BOUNDARY), ("steps", STEPS), ("refusals", REFUSALS)) if only and all(n == g or n in names for n in only)), None)
     if group:                                                            # the parent process never opens the GPU
         if group == "boundary":
             say(f"# tools/route_matrix.py boundary lib={args.lib or 'libpsm_hip.so of the tree'}")
             rc = boundary([b for n in only for b in (BOUNDARY if n == "boundary" else [n])], args.lib)
+        elif group == "refusals":
+            say("# tools/route_matrix.py refusals")
+            rc = children(["refusals"], args.lib, "--refusals-child", {})
         else:                                                            # no library path in the output: two libraries' runs are compared with cmp
             say("# tools/route_matrix.py steps")
             rc = children([b for n in only for b in (STEPS if n == "steps" else [n])], args.lib, "--steps-child", {})
