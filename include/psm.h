@@ -837,6 +837,48 @@ int psm_profile_solve(psm_handle* h, const float* d_grid, int32_t n_cases,
 int psm_enable_kernel_timing(psm_handle* h, int32_t kernel, int32_t on);
 int psm_get_kernel_timing(psm_handle* h, int32_t kernel, double* total_ms, int64_t* launches);
 
+/* ---- the Poisson-model step at the solver boundary: cells [n,5] -> p [n], two-frame state on the device ----------------------
+ * pressureSM_Poisson's timeStep behind the contract of psm_solve (pressureSM_Poisson/SM_call.py:815-818: "This only needs to be done
+ * when calling the SM in the CFD solver").  Call k passes cells_k = (Ux, Uy, Cx, Cy, p(t-1)); the handle keeps, per mesh cell,
+ * u_prev = U of the previous call, du_prev = its dU and p_prev = its column 4, and a count of held frames (0, 1 or 2).
+ * One step, all of it float64 per cell and rounded operation by operation:
+ *   head   U = max sqrt(Ux^2 + Uy^2) (SMP:556); dU = cells[:,0:2] - u_prev; c_cell = |dUx - du_prev_x| + |dUy - du_prev_y| (SMP:549),
+ *          c = max c_cell, weight = c_cell / c (0 where c == 0; SMP:550); dp_prev = cells[:,4] - p_prev.  No atomics: bit-reproducible.
+ *   mesh -> grid   interpolate_fill + last-writer scatter, the statements of psm_mesh_to_grid: (Ux, Uy, dUx, dUy) as float64 into the
+ *          feature binding's velocity planes (NaNs kept), weight and dp_prev as float32 into the post-steps' dU / prev planes with
+ *          NaN -> 0: a solver's tables carry negative weights (PM:210, no IDW fallback), and a NaN there would reach every pixel within
+ *          the sigma_weight filter's radius.
+ *   chain  psm_poisson_step_device's launches; (L, U) = (phi, U) and the decode's row scale max_abs_delta_p * U^2 are written on the
+ *          device by the head.  Nothing but `cells` is uploaded in front of a step.
+ *   tail   field = next = prev + change with the weighting, else result (SMP:842-847), already dimensional;
+ *          dp[n] = sum_j field[cell_of_point[vtx[n][j]]] * wts[n][j]; p_out[n] = cells[n][4] + dp[n], and cells[n][4] bit for bit where
+ *          psm_solve falls back (near-wall cell, negative weight, NaN: PM:494-496).  The same thread then turns the state over:
+ *          du_prev := cells[:,0:2] - u_prev, u_prev := cells[:,0:2], p_prev := cells[:,4].
+ * Head and tail are three launches in the chain's graph replay.  A step is SKIPPED when !(U > 0 and finite), or with the weighting
+ * when c is NaN: the chain runs on U = 1, out-scale 0 and all-zero columns, p_out = cells[:,4], the state still turns over.  The
+ * evaluator's "irrelevant time step" rule (SMP:562-567) is not applied, as in psm_solve_delta.  A step needs 1 + weighting held
+ * frames; with fewer it is a PRIMING step: PSM_OK, p_out = cells[:,4] bit for bit, the frame is pushed (one launch, no network),
+ * `steps` is not incremented.  A push at 0 frames sets du_prev := 0.
+ * psm_bind_poisson_solve: needs the single mesh of psm_set_geometry with its grid -> mesh tables (PSM_ERR_ARG without them; a case set:
+ * PSM_ERR_STATE), c_in == 4, c_out == 1, sdf_channel == 3 (PSM_ERR_UNSUPPORTED) and psm_bind_features, psm_bind_poststeps and
+ * psm_bind_frames (k >= 6) (PSM_ERR_STATE names the missing one); phi and max_abs_delta_p finite and non-zero (PSM_ERR_ARG).  It
+ * allocates the state, the partial maxima and the scalar slots: after it a step allocates nothing.  Whatever drops one of the three
+ * bindings or the mesh drops it; psm_poisson_solve_state then reports 0 frames.
+ * psm_poisson_solve_push: one frame from the host (a restart primes with two); _reset: frames = 0, steps = 0; _state: either may be NULL.
+ * psm_solve_poisson: host buffers, synchronous: one H2D copy of cells and one D2H copy of p through the handle's pinned staging, or
+ * straight from / into ranges registered with psm_host_register.  One step in flight per handle across all step kinds.
+ * psm_solve_poisson_device: device pointers, 8-byte aligned, asynchronous on `stream` (NULL: the handle's), copies nothing.
+ * d_fields [3][ny*nx] float32 receives (result, change, next) and may be NULL; change / next are written only with the weighting.
+ * d_scalars [8] float64 = U, c, U^2, out-scale, skip, frames held before the call, 0, 0; NULL: the binding's slots.
+ * Not provided: _begin / _end halves, the psm_pin_buffers direct routes, case sets. */
+int psm_bind_poisson_solve(psm_handle* h, double phi, double max_abs_delta_p, int32_t weighting, int32_t apply_filter);
+int psm_unbind_poisson_solve(psm_handle* h);
+int psm_poisson_solve_push(psm_handle* h, const double* cells, int64_t n);
+int psm_poisson_solve_reset(psm_handle* h);
+int psm_poisson_solve_state(const psm_handle* h, int32_t* frames, int64_t* steps);
+int psm_solve_poisson(psm_handle* h, const double* cells, int64_t n, int32_t rank, double* p_out);
+int psm_solve_poisson_device(psm_handle* h, const double* d_cells, double* d_p, float* d_fields, double* d_scalars, void* stream);
+
 /* Dispatch-level time of EVERY kernel of the solve path: `steps` solves of d_grid through the launch sequence of
  * psm_solve_grid_device on the handle's stream, each dispatch stamped with its own begin / end by
  * hipExtLaunchKernelGGL (the timestamps rocprofv3 --kernel-trace reads).  names [cap][64] receives the kernel

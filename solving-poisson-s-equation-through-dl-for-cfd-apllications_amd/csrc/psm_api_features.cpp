@@ -68,16 +68,18 @@ PostCall post_call(int apply_filter, const float* dU, const float* prev, float* 
 // every check of one whole step, then its scalars and the one graph replay: (frames -> planes,) features into the binding's image, solve,
 // post-steps
 int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const double* LU, const float* out_scale, const PostCall& pc, hipStream_t st,
-                        const FrameCall* frames, const RowsCall* rows) {
-  int rc = rows ? feat_check_state(h, n_cases) : feat_check(h, n_cases, LU);   // rows: (L, U) are made on the device, nothing to check or upload
+                        const FrameCall* frames, const RowsCall* rows, const PoissonSolveCall* psolve) {
+  const bool device_lu = rows || psolve;                   // (L, U) are made on the device, nothing to check or upload
+  int rc = device_lu ? feat_check_state(h, n_cases) : feat_check(h, n_cases, LU);
   if (rc) return rc;
   if (!h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: a Poisson step needs it as well as psm_bind_features");
   if ((rc = post_check(h, n_cases, pc))) return rc;
   if (!d_vel) return fail(h, PSM_ERR_ARG, "null buffer");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (!st) st = h->stream;
-  if (!rows && (rc = upload_lu(h, LU, n_cases, st))) return rc;
+  if (!device_lu && (rc = upload_lu(h, LU, n_cases, st))) return rc;
   StepCall step;
+  if (psolve) step.psolve = *psolve;
   if (rows) step.rows = *rows;
   if (frames) step.frames = *frames;
   step.feat = FeatCall{d_vel, h->feat.d_grid};
@@ -139,6 +141,7 @@ int psm_bind_features(psm_handle* h, const double* sdfunct, int32_t n_cases, dou
   HIPCHK(h, hipSetDevice(h->cfg.device));
   HIPCHK(h, hipStreamSynchronize(h->stream));           // features in flight read the planes that are replaced,
   drop_feature_graphs(h);                               // and the captured step graphs hold their addresses
+  poisson_solve_free(h);                                // psm_bind_poisson_solve stands on this binding
   FeatureSet& s = h->feat;
   feat_free(s);
   const size_t npix = (size_t)h->Ny * h->Nx, nwg = (npix + 255) / 256, n = (size_t)n_cases;
@@ -166,7 +169,7 @@ int psm_bind_features(psm_handle* h, const double* sdfunct, int32_t n_cases, dou
 
 
 int psm_unbind_features(psm_handle* h) {
-  return unbind(h, [h] { drop_feature_graphs(h); feat_free(h->feat); });
+  return unbind(h, [h] { drop_feature_graphs(h); poisson_solve_free(h); feat_free(h->feat); });
 }
 
 

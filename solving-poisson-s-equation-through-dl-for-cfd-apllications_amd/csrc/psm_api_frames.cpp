@@ -16,7 +16,8 @@ void frames_free(psm_handle* h) {
   deltas_free(h);                       // psm_bind_deltas_frames stands on this binding,
   gradp_free(h);                        // psm_bind_gradp_frames,
   chapter4_free(h);                     // psm_bind_chapter4_frames
-  rows_free(h);                         // and psm_bind_rows
+  rows_free(h);                         // psm_bind_rows
+  poisson_solve_free(h);                // and psm_bind_poisson_solve
   drop_frame_graphs(h);
   dev_free(s.d_cols); dev_free(s.d_extra); dev_free(s.d_raw);
   pin_free(s.h_cols); pin_free(s.h_extra); pin_free(s.h_out); pin_free(s.h_raw);

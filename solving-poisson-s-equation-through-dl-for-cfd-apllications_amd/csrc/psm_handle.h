@@ -1,5 +1,5 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in eighteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in nineteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, psm_solve_grid*
@@ -17,6 +17,7 @@
 //   psm_api_gradp_frames.cpp   the U_to_gradP evaluator's frame batch on the device: psm_bind_gradp_frames, the image / label pack psm_gradp_image_device and the step psm_gradp_frames* (columns -> p -> errors)
 //   psm_api_chapter4_frames.cpp  the Chapter-4 evaluators' frame batch on the device: psm_bind_chapter4_frames, the image / label pack psm_chapter4_image_device and the step psm_chapter4_frames* (columns -> p -> errors)
 //   psm_api_rows.cpp        a frame's dataset rows -> scalars + columns on the device: psm_bind_rows, the stage alone psm_rows_prepare_device and the evaluators' steps behind it, psm_deltas_rows* / psm_poisson_rows* / psm_gradp_rows*
+//   psm_api_poisson_solve.cpp  the Poisson-model step at the solver boundary (cells -> p, two-frame state on the device): psm_bind_poisson_solve, psm_poisson_solve_push / _reset / _state, psm_solve_poisson*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -201,6 +202,18 @@ struct Chapter4Call {
   auto tie() const { return std::tie(planes, grid, truth); }
 };
 
+// The mesh ends of the Poisson-model step at the solver boundary (psm_solve_poisson*): two launches in front of the features (partial
+// maxima; mesh -> grid of the six columns gathered from cells + state, the step's scalars into the device arrays the chain reads)
+// and one behind the post-steps (grid -> mesh, p(t-1) + dp, the state turned over).  Every member is held by the captured launches;
+// the state, the partials and the tables are the binding's (PoissonSolveSet) and the mesh's, which drop these graphs when they go.
+struct PoissonSolveCall {
+  const double* cells = nullptr;        // [N,5]; nullptr: no such stage
+  double* p = nullptr;                  // [N]
+  double* scalars = nullptr;            // [8]
+  int weighting = 0, prime = 0, frames = 0;   // prime: the push alone is a plain launch, never part of a sequence (always 0 in one); frames held before the call
+  auto tie() const { return std::tie(cells, p, scalars, weighting, prime, frames); }
+};
+
 // What surrounds ONE solve (solve_device, psm_api_step.cpp), in launch order; every stage keeps its own "absent" value.  A new stage
 // is one member here and one entry in key(): the graph cache compares nothing else, so a stage in the sequence is in the cache key.
 struct StepCall {
@@ -212,9 +225,13 @@ struct StepCall {
   Chapter4Call chapter4{};              // psm_chapter4_frames*: the image pack, the frames solved one by one; nothing behind the solve
   float* p = nullptr;                   // psm_solve_pressure*: where the bound integration (psm_bind_integration) behind the solve writes p
   PostCall post{};                      // psm_solve_poststeps*: the bound post-steps behind the solve (apply_filter == -1: none)
-  auto key() const { return std::make_tuple(rows.tie(), frames.key(), feat.tie(), deltas.tie(), gradp.tie(), chapter4.tie(), p, post.tie()); }
+  PoissonSolveCall psolve{};            // psm_solve_poisson*: the head in front of the features, the tail behind the post-steps (cells == nullptr: none)
+  auto key() const { return std::make_tuple(rows.tie(), frames.key(), feat.tie(), deltas.tie(), gradp.tie(), chapter4.tie(), p, post.tie(), psolve.tie()); }
   const char* fault() const {           // the combinations the sequence does not define (null: defined); no C entry builds one
     const bool fr = frames.cols, ft = feat.vel, dl = deltas.planes, gp = gradp.planes, c4 = chapter4.planes;
+    if (psolve.cells && (!ft || post.apply_filter < 0)) return "the Poisson solver step is the features, the solve and the post-steps between its mesh ends: it needs all three";
+    if (psolve.cells && (rows.rows || fr || dl || gp || c4 || p)) return "the Poisson solver step writes the feature planes itself: no rows, frames, pack or integration stage beside it";
+    if (psolve.cells && psolve.prime) return "a priming step of the Poisson solver step is one plain launch, not a sequence";
     if (rows.rows && (!fr || rows.cols != frames.cols)) return "the rows stage writes the columns the mesh -> grid stage reads: it needs frames on its columns";
     if (dl && gp) return "the deltas and the gradP pack exclude each other";
     if (c4 && dl) return "the Chapter-4 and the deltas pack exclude each other";
@@ -352,6 +369,20 @@ struct FrameSet {
   double *d_raw = nullptr, *h_raw = nullptr;   // psm_poisson_frames_errors: [n_frames][3][8] sums, device and pinned
 };
 
+// Binding of the Poisson-model step at the solver boundary (psm_bind_poisson_solve, behind psm_bind_features, psm_bind_poststeps and
+// psm_bind_frames on the single mesh): the step's constants, the two-frame state, the partial maxima and the scalar slots, so that a
+// step allocates nothing.  The state is written by the last launch of a step; the host counters follow once the whole step is enqueued.
+struct PoissonSolveSet {
+  bool ready = false;
+  double phi = 1.0, max_abs_dp = 1.0;
+  int weighting = 0, apply_filter = 0;
+  double* d_state = nullptr;            // [5 N]: u_prev [N][2] | du_prev [N][2] | p_prev [N], every piece 16-byte aligned
+  double* d_part = nullptr;             // [2][PSM_POISSON_PARTS]
+  double* d_scalars = nullptr;          // [PSM_POISSON_SCALARS]
+  int frames = 0;                       // frames held: 0, 1 or 2
+  int64_t steps = 0;                    // steps taken since the state was last empty (a priming step does not count)
+};
+
 // Binding of the rows stage (psm_bind_rows, behind psm_bind_frames): staging for the bound frame count x mesh cells x width float32
 // rows, the partial maxima and the scalar slots, so that a step allocates nothing.  The columns go to the frame binding's d_cols.
 struct RowsSet {
@@ -462,6 +493,7 @@ struct psm_handle {
   FeatureSet feat;                      // Poisson input features on the planned grid (psm_bind_features)
   FrameSet frames;                      // frame batch on the single mesh (psm_bind_frames)
   RowsSet rows;                         // the rows stage's staging behind it (psm_bind_rows)
+  PoissonSolveSet psolve;               // the Poisson-model step at the solver boundary behind features, post-steps and frames (psm_bind_poisson_solve)
   DeltasSet deltas;                     // the deltas evaluator's frame batch behind it (psm_bind_deltas_frames)
   GradpSet gradp;                       // the U_to_gradP evaluator's frame batch behind it (psm_bind_gradp_frames)
   Chapter4Set chapter4;                 // the Chapter-4 evaluators' frame batch behind it (psm_bind_chapter4_frames)
@@ -613,6 +645,10 @@ void deltas_free(psm_handle* h);
 void gradp_free(psm_handle* h);
 void chapter4_free(psm_handle* h);
 void rows_free(psm_handle* h);
+void poisson_solve_free(psm_handle* h);   // whatever drops the feature, post-step or frame binding or the mesh drops this one (psm_api_poisson_solve.cpp)
+// the two head launches / the tail launch of a Poisson solver step on `st` (the tail's field: next with the weighting, else result)
+int poisson_solve_head(psm_handle* h, const PoissonSolveCall& ps, hipStream_t st);
+int poisson_solve_tail(psm_handle* h, const PoissonSolveCall& ps, const PostCall& pc, hipStream_t st);
 int rows_device(psm_handle* h, const RowsCall& rc, int n_frames, hipStream_t st);
 int frames_state(psm_handle* h);
 int frames_count_check(psm_handle* h, int n_frames);
@@ -620,7 +656,7 @@ int frames_device(psm_handle* h, const FrameCall& fc, int n_frames, hipStream_t 
 int poisson_frame_call(psm_handle* h, const double* d_cols, int n_frames, int k, int weighting, double* d_extra, FrameCall& fc);
 int field_errors_device(psm_handle* h, const PsmFieldErrorArgs& stage, double* d_raw, hipStream_t st);
 int poisson_step_device(psm_handle* h, const double* d_vel, int n_cases, const double* LU, const float* out_scale, const PostCall& pc,
-                        hipStream_t st, const FrameCall* frames = nullptr, const RowsCall* rows = nullptr);
+                        hipStream_t st, const FrameCall* frames = nullptr, const RowsCall* rows = nullptr, const PoissonSolveCall* psolve = nullptr);
 PostCall post_call(int apply_filter, const float* dU, const float* prev, float* result, float* change, float* next);
 int features_device(psm_handle* h, const double* d_vel, int n_cases, float* d_grid, hipStream_t st);
 std::vector<uint16_t> pack_comp_in_bf16(const double* comp, int P, int K, int c_in, int S, int NT);

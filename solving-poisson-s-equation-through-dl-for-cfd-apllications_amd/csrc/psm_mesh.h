@@ -80,6 +80,51 @@ struct PsmFrameArgs {
 };
 hipError_t psm_launch_frames_to_grid(const PsmFrameArgs& a, hipStream_t st);
 
+// ---- the mesh ends of the Poisson-model step at the solver boundary (psm_solve_poisson*, pressureSM_Poisson/SM_call.py:549-556,
+// 815-818, 842-847): three launches around the chain of psm_poisson_step_device on the single mesh of psm_set_geometry.  The state
+// is two frames per mesh cell, every row 16-byte aligned: u_prev [N][2] = U of the previous call, du_prev [N][2] = its dU, and
+// p_prev [N] = its column 4.  The head (partial maxima, then mesh -> grid) gathers the six columns (Ux, Uy, dUx, dUy, dU-change
+// weight, dp_prev) per vertex straight from cells + state; the tail (grid -> mesh) stores p(t-1) + dp and turns the state over.
+constexpr int PSM_POISSON_PARTS = 256;     // capacity of one row of partial maxima (every mesh -> grid workgroup folds both rows)
+constexpr int PSM_POISSON_SCALARS = 8;     // U, c, U^2, out-scale, skip, frames held before the call, 0, 0
+struct PsmPoissonCellsArgs {
+  const double* cells;          // [N,5] Ux,Uy,Cx,Cy,p(t-1)
+  const double *u_prev, *du_prev, *p_prev;   // the state, read only
+  int64_t n_cells;
+  double* partials;             // [2][PSM_POISSON_PARTS] maxima of the SQUARED speed and of c_cell = |dUx - du_prev_x| + |dUy - du_prev_y|
+  int n_partials;
+  // mesh -> grid
+  const int32_t* vtx;           // [n_grid,3] mesh->grid simplices
+  const double* wts;            // [n_grid,3]
+  const int32_t* src_of_cell;   // [n_grid]
+  int64_t n_grid;
+  double* vel;                  // [4][n_grid] float64 planes (Ux, Uy, dUx, dUy): NaNs of interpolate_fill kept
+  float *w_plane, *prev_plane;  // [n_grid] float32 planes of the weight and of dp_prev, NaN -> 0; both nullptr without the weighting
+  double* scalars;              // [PSM_POISSON_SCALARS], stored by workgroup 0 ...
+  double* lu;                   // ... with (phi, U) for the feature kernels
+  float* row_scale;             // ... and the decode's row scale (float)(max_abs_dp * U^2), B rows
+  int B;
+  double phi, max_abs_dp;
+  int weighting, frames;
+};
+struct PsmPoissonMeshArgs {
+  const double* cells;          // [N,5]
+  const int32_t* vtx;           // [N,3] grid->mesh simplices
+  const double* wts;            // [N,3]
+  const int32_t* cell_of_point; // [n_grid]
+  const float* field;           // [n_grid] dp on the grid, dimensional (next with the weighting, else result); not read when prime
+  const uint8_t* near_wall;     // [N]
+  double* p_out;                // [N]
+  int64_t n_cells;
+  double *u_prev, *du_prev, *p_prev;   // the state, one row each per thread, written after p_out
+  double* scalars;              // a step reads [4] (skip) of what the head stored; the push stores all eight
+  int prime, frames;            // prime: the push alone, p_out = cells[:,4]; frames held before the call (0: du_prev := 0)
+};
+hipError_t psm_launch_poisson_partial(const PsmPoissonCellsArgs& a, hipStream_t st);   // a.n_partials: psm_poisson_parts(n_cells)
+hipError_t psm_launch_poisson_to_grid(const PsmPoissonCellsArgs& a, hipStream_t st);
+hipError_t psm_launch_poisson_to_mesh(const PsmPoissonMeshArgs& a, hipStream_t st);
+inline int psm_poisson_parts(int64_t n_cells) { return (int)(n_cells + 1023 < (int64_t)PSM_POISSON_PARTS * 1024 ? (n_cells + 1023) / 1024 : PSM_POISSON_PARTS); }
+
 // ---- the mesh ends for a case batch (psm_set_geometry_cases): K meshes on one planned grid, the case is launch dimension y.
 // Cell-side arrays are the cases' concatenated ([sum n_i, ...], case i at rows cell_off[i] .. cell_off[i + 1]), grid-side tables
 // are [K][n_grid, ...]; vertex indices are case-local as the caller gave them (the kernels add the case's offset).

@@ -8,6 +8,8 @@
 //   to_mesh  : gather at `indices`, barycentric grid->mesh interpolation with fill,
 //              dimensionalise, near-wall / NaN fallback to the previous p   [PM:481-496]
 //   both ends also in DELTA form (psm_solve_delta*): U - U(t-1) in, p(t-1) + dp out, U(t-1) := U   [SMD:389-391]
+//   and as the ends of the Poisson-model step (psm_solve_poisson*, at the end of this file): six columns from cells + a two-frame
+//   state in, p(t-1) + dp out, the state turned over                                                [SMP:549-556, 842-847]
 //
 // All of them are HBM-bound gathers; interpolation is done in float64 like the reference.
 #include "psm_mesh.h"
@@ -460,5 +462,173 @@ hipError_t psm_launch_to_grid_cases_delta(const PsmDeltaCasesArgs& d, hipStream_
 hipError_t psm_launch_to_mesh_cases_delta(const PsmDeltaCasesArgs& d, hipStream_t st) {
   if (!d.u_prev || d.c.n_cases < 1 || d.c.max_cells < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(static_cast<PsmDeltaCasesKernel>(psm_to_mesh_kernel), dim3((unsigned)((d.c.max_cells + 255) / 256), d.c.n_cases), dim3(256), 0, st, d);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The mesh ends of the Poisson-model step at the solver boundary (psm_solve_poisson*, PsmPoissonCellsArgs / PsmPoissonMeshArgs in
+// psm_mesh.h): three launches around the chain of psm_poisson_step_device, overloads of the kernels of the same purpose above.
+// What a cell's columns are made of is float64 and rounded operation by operation (`fp contract(off)`); the interpolation of a
+// column is the statement of interp_column, so that a plane holds the bits psm_poisson_frames leaves on host-made columns.
+
+// c_cell = np.abs(delta_U - delta_U_prev).sum(axis=-1)  (SMP:549)
+__device__ __forceinline__ double poisson_change(double dux, double duy, double dpx, double dpy) {
+#pragma clang fp contract(off)
+  const double d0 = dux - dpx, d1 = duy - dpy;
+  return fabs(d0) + fabs(d1);
+}
+
+// The six columns of mesh cell i: (Ux, Uy, dUx, dUy, c_cell / c, dp_prev); the last two only with the weighting.  A skipped step: zeros.
+struct PoissonCols { double v[6]; };
+__device__ __forceinline__ PoissonCols poisson_cols(const PsmPoissonCellsArgs& a, int64_t i, double c, bool skip) {
+#pragma clang fp contract(off)
+  PoissonCols o;
+#pragma unroll
+  for (int q = 0; q < 6; ++q) o.v[q] = 0.0;
+  if (skip) return o;
+  const double* r = a.cells + i * 5;
+  const psm_uv2 up = *reinterpret_cast<const psm_uv2*>(a.u_prev + i * 2);
+  const double ux = r[0], uy = r[1];
+  const double dux = ux - up.x, duy = uy - up.y;
+  o.v[0] = ux; o.v[1] = uy; o.v[2] = dux; o.v[3] = duy;
+  if (a.weighting) {
+    const psm_uv2 dq = *reinterpret_cast<const psm_uv2*>(a.du_prev + i * 2);
+    const double cc = poisson_change(dux, duy, dq.x, dq.y);
+    o.v[4] = (c == 0.0) ? 0.0 : cc / c;                    // deltaU_changed / deltaU_changed.max()  (SMP:550); 0 where nothing changed at all
+    o.v[5] = r[4] - a.p_prev[i];
+  }
+  return o;
+}
+
+// Head, level one: workgroup b leaves the maxima of the squared speed and of c_cell over its cells (b * 1024 + tid, + gridDim.x *
+// 1024, ...) in partials[b] and partials[PSM_POISSON_PARTS + b].  cells and the state are read once.
+__global__ __launch_bounds__(1024) void psm_umax_partial_kernel(PsmPoissonCellsArgs a) {
+  __shared__ double red[2][16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double m = 0.0, mc = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * 1024 + tid; i < a.n_cells; i += (int64_t)gridDim.x * 1024) {
+    const double ux = a.cells[i * 5], uy = a.cells[i * 5 + 1];
+    const psm_uv2 up = *reinterpret_cast<const psm_uv2*>(a.u_prev + i * 2);
+    const psm_uv2 dq = *reinterpret_cast<const psm_uv2*>(a.du_prev + i * 2);
+    m = nanmax2(m, speed2_np(ux, uy));
+    mc = nanmax2(mc, poisson_change(ux - up.x, uy - up.y, dq.x, dq.y));
+  }
+  for (int o = 32; o > 0; o >>= 1) { m = nanmax2(m, __shfl_down(m, o, 64)); mc = nanmax2(mc, __shfl_down(mc, o, 64)); }
+  if (lane == 0) { red[0][wave] = m; red[1][wave] = mc; }
+  __syncthreads();
+  if (tid < 2) {
+    double r = red[tid][0];
+    for (int w = 1; w < 16; ++w) r = nanmax2(r, red[tid][w]);
+    a.partials[tid * PSM_POISSON_PARTS + blockIdx.x] = r;
+  }
+}
+
+// Head, level two + mesh -> grid: every workgroup folds both rows of partials itself, workgroup 0 stores the step's scalars -- into
+// `scalars` and into the device arrays the chain reads, as psm_rows.hip's finish launch does --; then one thread per image cell
+// gathers the columns of the three vertices of its source point and writes the six planes: 0 where nobody writes, NaN for a negative
+// weight (interpolate_fill) in the four velocity planes, NaN -> 0 in the two float32 planes.
+__global__ __launch_bounds__(256) void psm_interp_to_grid_kernel(PsmPoissonCellsArgs a) {
+  __shared__ double fold_s[2][4];
+  const int tid = threadIdx.x;
+  const int p = min(tid, a.n_partials - 1);
+  double m = a.partials[p], mc = a.partials[PSM_POISSON_PARTS + p];
+  for (int o = 32; o > 0; o >>= 1) { m = nanmax2(m, __shfl_down(m, o, 64)); mc = nanmax2(mc, __shfl_down(mc, o, 64)); }
+  if ((tid & 63) == 0) { fold_s[0][tid >> 6] = m; fold_s[1][tid >> 6] = mc; }
+  __syncthreads();
+  double U = sqrt_rn(nanmax2(nanmax2(fold_s[0][0], fold_s[0][1]), nanmax2(fold_s[0][2], fold_s[0][3])));
+  const double c = nanmax2(nanmax2(fold_s[1][0], fold_s[1][1]), nanmax2(fold_s[1][2], fold_s[1][3]));
+  const bool skip = !(U > 0.0 && U < INFINITY) || (a.weighting && c != c);
+  if (skip) U = 1.0;
+  if (blockIdx.x == 0) {
+#pragma clang fp contract(off)
+    const double U2 = U * U;
+    const double scale = skip ? 0.0 : a.max_abs_dp * U2;
+    if (tid == 0) {
+      double* o = a.scalars;
+      o[0] = U; o[1] = c; o[2] = U2; o[3] = scale; o[4] = skip ? 1.0 : 0.0; o[5] = (double)a.frames; o[6] = 0.0; o[7] = 0.0;
+      a.lu[0] = a.phi; a.lu[1] = U;
+    }
+    for (int b = tid; b < a.B; b += 256) a.row_scale[b] = (float)scale;
+  }
+  const int64_t cell = (int64_t)blockIdx.x * 256 + tid;
+  if (cell >= a.n_grid) return;
+  const int src = a.src_of_cell[cell];
+  double r[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (src >= 0) {
+    const int32_t* v = a.vtx + (int64_t)src * 3;
+    const double* w = a.wts + (int64_t)src * 3;
+    const double w0 = w[0], w1 = w[1], w2 = w[2];
+    const bool neg = (w0 < 0.0) || (w1 < 0.0) || (w2 < 0.0);
+    const PoissonCols c0 = poisson_cols(a, v[0], c, skip), c1 = poisson_cols(a, v[1], c, skip), c2 = poisson_cols(a, v[2], c, skip);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {                          // (without the weighting columns 4 and 5 are zeros and are not stored)
+      double s = 0.0;                                      // the statements of interp_column, vertex by vertex
+      s += c0.v[q] * w0;
+      s += c1.v[q] * w1;
+      s += c2.v[q] * w2;
+      r[q] = neg ? NAN : s;                                // interpolate_fill
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) a.vel[q * a.n_grid + cell] = r[q];
+  if (a.weighting) {
+    a.w_plane[cell] = (r[4] != r[4]) ? 0.f : (float)r[4];  // a solver's tables carry negative weights (PM:210, no IDW fallback): a NaN here
+    a.prev_plane[cell] = (r[5] != r[5]) ? 0.f : (float)r[5];   // would spread through the sigma_weight filter over its whole radius
+  }
+}
+
+// Tail, grid -> mesh: dp[n] = sum_j field[cell_of_point[vtx[n][j]]] * wts[n][j] in float64, p = p(t-1) + dp, p(t-1) itself bit for
+// bit where psm_to_mesh_kernel falls back (near-wall cell, negative weight, NaN: PM:494-496) and everywhere on a skipped step; then
+// the same thread turns its cell's state over.  prime (uniform): the push alone -- no field, p = p(t-1), block 0 stores the scalars.
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmPoissonMeshArgs a) {
+#pragma clang fp contract(off)
+  const bool skip = a.prime ? true : (a.scalars[4] != 0.0);
+  if (a.prime && blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int q = 0; q < PSM_POISSON_SCALARS; ++q) a.scalars[q] = 0.0;
+    a.scalars[5] = (double)a.frames;
+  }
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n >= a.n_cells) return;
+  const double* r = a.cells + n * 5;
+  const double ux = r[0], uy = r[1], prev = r[4];
+  double p = prev;
+  if (!skip) {
+    const int32_t* v = a.vtx + n * 3;
+    const double* w = a.wts + n * 3;
+    double acc = 0.0;
+    bool neg = false;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double f = (double)a.field[a.cell_of_point[v[j]]];
+      const double t = f * w[j];
+      acc = acc + t;
+      neg = neg || (w[j] < 0.0);
+    }
+    if (!(a.near_wall[n] || neg || acc != acc)) p = prev + acc;
+  }
+  a.p_out[n] = p;
+  psm_uv2 du = psm_uv2{0.0, 0.0};
+  if (a.frames > 0) {
+    const psm_uv2 up = *reinterpret_cast<const psm_uv2*>(a.u_prev + n * 2);
+    du = psm_uv2{ux - up.x, uy - up.y};
+  }
+  *reinterpret_cast<psm_uv2*>(a.du_prev + n * 2) = du;
+  *reinterpret_cast<psm_uv2*>(a.u_prev + n * 2) = psm_uv2{ux, uy};
+  a.p_prev[n] = prev;
+}
+
+hipError_t psm_launch_poisson_partial(const PsmPoissonCellsArgs& a, hipStream_t st) {
+  if (a.n_cells < 1 || a.n_partials < 1 || a.n_partials > PSM_POISSON_PARTS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmPoissonCellsArgs)>(psm_umax_partial_kernel), dim3((unsigned)a.n_partials), dim3(1024), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_poisson_to_grid(const PsmPoissonCellsArgs& a, hipStream_t st) {
+  if (a.n_grid < 1 || a.n_partials < 1 || a.n_partials > PSM_POISSON_PARTS || (a.weighting && (!a.w_plane || !a.prev_plane))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmPoissonCellsArgs)>(psm_interp_to_grid_kernel), dim3((unsigned)((a.n_grid + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_poisson_to_mesh(const PsmPoissonMeshArgs& a, hipStream_t st) {
+  if (a.n_cells < 1 || !a.u_prev || !a.du_prev || !a.p_prev || !a.scalars || (!a.prime && !a.field)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmPoissonMeshArgs)>(psm_to_mesh_kernel), dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
   return hipGetLastError();
 }

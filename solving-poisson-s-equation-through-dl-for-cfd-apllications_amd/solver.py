@@ -12,11 +12,12 @@ from .surrogate import GridSurrogate, _f64, _p
 from .synthetic import SurrogateModel
 
 STEPS = ("absolute", "delta")
+MODULE_STEPS = STEPS + ("poisson",)      # SolverModule alone: the Poisson-model step has no case-batch form
 
 
-def _check_step(step):
-    if step not in STEPS:
-        raise ValueError("step must be 'absolute' or 'delta'")
+def _check_step(step, allowed=STEPS):
+    if step not in allowed:
+        raise ValueError("step must be 'absolute' or 'delta'" + (" or 'poisson'" if "poisson" in allowed else ""))
     return step
 
 
@@ -30,6 +31,12 @@ def _check_cells(array_in, out):
     elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
         raise ValueError("out must be a contiguous float64 array [N]")
     return a, out
+
+
+def _poisson_state(sur):
+    frames, steps = C.c_int32(), C.c_int64()
+    sur._chk(sur.lib.psm_poisson_solve_state(sur.h, C.byref(frames), C.byref(steps)))
+    return int(frames.value), int(steps.value)
 
 
 def _delta_state(sur):
@@ -46,12 +53,19 @@ class SolverModule:
     the ``maxs`` file (python_module.py:106-109)."""
 
     def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), device: int = 0, delta: float = 5e-3,
-                 geometry: str = "scipy", step: str = "absolute"):
+                 geometry: str = "scipy", step: str = "absolute", phi: float = None, k: float = None, weighting: bool = True,
+                 apply_filter: bool = True, sigma_field=(10, 10), sigma_weight=(50, 50)):
         """``step``: 'absolute' (U -> p, the Chapter-5 module) or 'delta' (the deltas model behind the same two calls:
         [U(t) - U(t-1)], SDF -> p(t) - p(t-1), psm_solve_delta* of include/psm.h).  With 'delta', ``maxs`` are
         (max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp), ``init_func`` installs the tables with the deltas model's
         convention (SDF divided by max_abs_dist, interpolate_fill) and primes U(t-1) with its own ``array`` -- the fields of
         the start time -- and ``py_func`` returns ``array[:,4] + dp``.
+        ``step='poisson'``: pressureSM_Poisson's time step behind the same two calls (psm_solve_poisson of include/psm.h): ``maxs`` =
+        (max_abs_Poisson_term_1, max_abs_delta_Ux, max_abs_delta_Uy, max_abs_dist, max_abs_delta_p), ``phi`` the length scale of
+        the features, ``k`` the arcsinh smoothing's constant, ``weighting`` / ``apply_filter`` and the two filter widths as in the
+        reference's ``timeStep``.  ``init_func`` installs the tables, binds features, post-steps, frames and the step, and pushes
+        its own ``array`` as the first frame; the state is U, dU and p of the previous call, on the device: with the weighting the
+        first ``py_func`` is a priming step too (it returns ``array[:,4]``), then every call returns ``array[:,4] + dp``.
         ``geometry``: who builds init_func's tables -- 'scipy' (default in this Python mirror: the routines the reference
         itself calls, qhull Delaunay in both directions, so that the tables -- including qhull's arbitrary choice of diagonal
         in every cocircular lattice square of the grid -> mesh step -- are the reference's) or 'native' (the library's C++
@@ -61,9 +75,16 @@ class SolverModule:
         (tests/measure/mesh_native_vs_scipy.py) -- and the simplex used for lattice points outside the hull."""
         if geometry not in ("scipy", "native"):
             raise ValueError("geometry must be 'scipy' or 'native'")
-        self.step = _check_step(step)
+        self.step = _check_step(step, MODULE_STEPS)
         self.model, self.maxs, self.device, self.delta = model, tuple(float(v) for v in maxs), device, delta
         self.geometry = geometry
+        if self.step == "poisson":
+            if len(self.maxs) != 5:
+                raise ValueError("step='poisson' takes five maxs: (max_abs_Poisson_term_1, max_abs_delta_Ux, max_abs_delta_Uy, max_abs_dist, max_abs_delta_p)")
+            if phi is None or k is None:
+                raise ValueError("step='poisson' needs phi and k")
+            self.phi, self.k, self.weighting, self.apply_filter = float(phi), float(k), bool(weighting), bool(apply_filter)
+            self.sigma_field, self.sigma_weight = tuple(sigma_field), tuple(sigma_weight)
         self._sur = None
         self.tables = None
 
@@ -88,16 +109,26 @@ class SolverModule:
         self._sur = GridSurrogate(self.model, t.ny, t.nx, 1, self.device)
         v1, w1 = np.ascontiguousarray(t.vtx_m2g, np.int32), _f64(t.wts_m2g)
         v2, w2 = np.ascontiguousarray(t.vtx_g2m, np.int32), _f64(t.wts_g2m)
-        idx, sdf, mx = np.ascontiguousarray(t.indices, np.int32), _f64(t.sdfunct), _f64(self.maxs)
-        smd = int(self.step == "delta")          # the deltas model's convention: normalise_sdf = fill_input = 1 (SM_call.py:441-443)
+        idx, sdf, mx = np.ascontiguousarray(t.indices, np.int32), _f64(t.sdfunct), _f64(self.maxs[-4:])
+        smd = int(self.step != "absolute")       # the deltas model's convention: normalise_sdf = fill_input = 1 (SM_call.py:441-443)
         self._sur._chk(self._sur.lib.psm_set_geometry(
             self._sur.h, int(np.asarray(array).shape[0]), t.ny, t.nx, _p(v1, C.c_int32), _p(w1, C.c_double),
             _p(idx, C.c_int32), _p(sdf, C.c_double), _p(v2, C.c_int32), _p(w2, C.c_double), _p(mx, C.c_double),
             smd, smd, 0.05))
         self.tables = t
+        if self.step == "poisson":
+            self._bind_poisson(sdf.reshape(t.ny, t.nx))
         if smd:
             self.prime(array)
         return 0
+
+    def _bind_poisson(self, sdfunct):
+        """Everything a Poisson-model step stands on, in the order the library asks for it; after it a step allocates nothing."""
+        sur = self._sur
+        sur.bind_features(sdfunct, self.k, self.maxs[:4])
+        sur.bind_poststeps(self.sigma_field, self.sigma_weight)
+        sur.bind_frames(1, 6)
+        sur.bind_poisson_solve(self.phi, self.maxs[4], self.weighting, self.apply_filter)
 
     def _init_func_native(self, array, top_boundary, obst_boundary):
         """psm_set_case + psm_init_geometry: the tables are built inside the library (csrc/psm_geometry.cpp).  step='delta':
@@ -110,8 +141,8 @@ class SolverModule:
         if self._sur is not None:
             self._sur.close()
         self._sur = GridSurrogate(self.model, ny.value, nx.value, 1, self.device)
-        mx = _f64(self.maxs)
-        if self.step == "delta":
+        mx = _f64(self.maxs[-4:])
+        if self.step != "absolute":
             n, ng = a.shape[0], ny.value * nx.value
             v1, w1, idx, sdf = np.empty((ng, 3), np.int32), np.empty((ng, 3)), np.empty((ng, 2), np.int32), np.empty(ng)
             v2, w2 = np.empty((n, 3), np.int32), np.empty((n, 3))
@@ -123,6 +154,8 @@ class SolverModule:
                                                 _p(idx, C.c_int32), _p(sdf, C.c_double), _p(v2, C.c_int32), _p(w2, C.c_double),
                                                 _p(mx, C.c_double), 1, 1, 0.05))
             self.tables = "native"
+            if self.step == "poisson":
+                self._bind_poisson(sdf.reshape(ny.value, nx.value))
             self.prime(a)
             return 0
         self._sur._chk(lib.psm_set_case(self._sur.h, _p(mx, C.c_double), self.delta, 10, 0.05))
@@ -131,31 +164,38 @@ class SolverModule:
         self.tables = "native"
         return 0
 
-    # -- the state of step='delta' (psm_delta_prime / _reset / _state)
+    # -- the state of step='delta' (psm_delta_prime / _reset / _state) and of step='poisson' (psm_poisson_solve_push / _reset / _state)
     def _need_delta(self):
-        if self.step != "delta":
+        if self.step == "absolute":
             raise RuntimeError("this module was built with step='absolute': the state belongs to step='delta'")
         if self.tables is None:
             raise RuntimeError("init_func has not been called")
 
     def prime(self, array):
-        """U(t-1) := array[:,0:2].  ``init_func`` does this with the start fields; a restart primes again."""
+        """U(t-1) := array[:,0:2].  ``init_func`` does this with the start fields; a restart primes again.  step='poisson': one
+        frame (U and p) is pushed into the two-frame state; a restart primes with two."""
         self._need_delta()
         a = _f64(array)
         if a.ndim != 2 or a.shape[1] != 5:
             raise ValueError("array must be [N,5] = (Ux, Uy, Cx, Cy, p)")
+        if self.step == "poisson":
+            self._sur._chk(self._sur.lib.psm_poisson_solve_push(self._sur.h, _p(a, C.c_double), a.shape[0]))
+            return
         self._sur._chk(self._sur.lib.psm_delta_prime(self._sur.h, _p(a, C.c_double), a.shape[0]))
 
     def reset_state(self):
         """Forget U(t-1): the next ``py_func`` is the priming step and returns ``array[:,4]``."""
         self._need_delta()
+        if self.step == "poisson":
+            self._sur._chk(self._sur.lib.psm_poisson_solve_reset(self._sur.h))
+            return
         self._sur._chk(self._sur.lib.psm_delta_reset(self._sur.h))
 
     @property
     def state(self):
-        """(primed, steps) of psm_delta_state."""
+        """(primed, steps) of psm_delta_state; step='poisson': (frames held, steps) of psm_poisson_solve_state."""
         self._need_delta()
-        return _delta_state(self._sur)
+        return _poisson_state(self._sur) if self.step == "poisson" else _delta_state(self._sur)
 
     def pin(self, array: np.ndarray, out: np.ndarray = None):
         """psm_pin_buffers: register the caller's persistent [N,5] float64 array (and optionally a persistent output
@@ -175,6 +215,8 @@ class SolverModule:
         can be advanced from one thread by calling begin on all of them, then :meth:`py_func_end` on each."""
         if self.tables is None:
             raise RuntimeError("init_func has not been called")
+        if self.step == "poisson":
+            raise RuntimeError("step='poisson' has no begin / end halves: use py_func")
         if self.step == "delta":
             a, out = _check_cells(array_in, out)
             self._sur._chk(self._sur.lib.psm_solve_delta_begin(self._sur.h, _p(a, C.c_double), a.shape[0], 0, _p(out, C.c_double)))
@@ -196,9 +238,14 @@ class SolverModule:
         return out
 
     def py_func(self, array_in, placeholder=0, out: np.ndarray = None) -> np.ndarray:
-        """python_module.py:249: cells [N,5] float64 -> p [N] float64.  step='delta': p = array[:,4] + dp (psm_solve_delta)."""
+        """python_module.py:249: cells [N,5] float64 -> p [N] float64.  step='delta': p = array[:,4] + dp (psm_solve_delta);
+        step='poisson': likewise through psm_solve_poisson."""
         if self.tables is None:
             raise RuntimeError("init_func has not been called")
+        if self.step == "poisson":
+            a, out = _check_cells(array_in, out)
+            self._sur._chk(self._sur.lib.psm_solve_poisson(self._sur.h, _p(a, C.c_double), a.shape[0], int(placeholder), _p(out, C.c_double)))
+            return out
         if self.step == "delta":
             a, out = _check_cells(array_in, out)
             self._sur._chk(self._sur.lib.psm_solve_delta(self._sur.h, _p(a, C.c_double), a.shape[0], int(placeholder), _p(out, C.c_double)))

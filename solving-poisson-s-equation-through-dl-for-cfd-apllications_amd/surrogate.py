@@ -724,6 +724,58 @@ class GridSurrogate:
                                               int(bool(weighting)), _opt(extra, C.c_double), _p(result, C.c_float), _opt(change), _opt(nxt)))
         return result, change, nxt, extra
 
+    # -- the Poisson-model step at the solver boundary (psm_solve_poisson*): cells [N,5] -> p [N], two-frame state on the device
+    POISSON_SOLVE_SCALARS = ("U", "c", "U2", "out_scale", "skip", "frames", "_6", "_7")
+
+    def bind_poisson_solve(self, phi: float, max_abs_delta_p: float, weighting: bool = True, apply_filter: bool = True):
+        """The state (U, dU and p of the previous call per mesh cell), the partial maxima and the scalar slots of the Poisson solver
+        step, behind ``bind_features``, ``bind_poststeps`` and ``bind_frames(n, k >= 6)`` on a mesh with both table sets: after it
+        a step allocates nothing.  ``phi`` is the length scale L of the features, ``max_abs_delta_p`` the label scale."""
+        self._chk(self.lib.psm_bind_poisson_solve(self.h, float(phi), float(max_abs_delta_p), int(bool(weighting)), int(bool(apply_filter))))
+
+    def unbind_poisson_solve(self):
+        self._chk(self.lib.psm_unbind_poisson_solve(self.h))
+
+    def poisson_solve_push(self, cells: np.ndarray):
+        """One frame [N,5] = (Ux, Uy, Cx, Cy, p) from the host into the state (a restart primes with two)."""
+        a = self._solver_cells(cells)
+        self._chk(self.lib.psm_poisson_solve_push(self.h, _p(a, C.c_double), a.shape[0]))
+
+    def poisson_solve_reset(self):
+        self._chk(self.lib.psm_poisson_solve_reset(self.h))
+
+    @property
+    def poisson_solve_state(self):
+        """(frames held, steps taken) of psm_poisson_solve_state."""
+        frames, steps = C.c_int32(), C.c_int64()
+        self._chk(self.lib.psm_poisson_solve_state(self.h, C.byref(frames), C.byref(steps)))
+        return int(frames.value), int(steps.value)
+
+    @staticmethod
+    def _solver_cells(cells):
+        a = _f64(cells)
+        if a.ndim != 2 or a.shape[1] != 5:
+            raise ValueError("cells must be [N,5] = (Ux, Uy, Cx, Cy, p)")
+        return a
+
+    def solve_poisson(self, cells: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Host buffers, synchronous: cells [N,5] float64 = (Ux, Uy, Cx, Cy, p(t-1)) -> p [N] float64 = p(t-1) + dp; p(t-1) itself
+        on a priming or skipped step and on the fallback cells."""
+        a = self._solver_cells(cells)
+        if out is None:
+            out = np.empty(a.shape[0], np.float64)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
+            raise ValueError("out must be a contiguous float64 array [N]")
+        self._chk(self.lib.psm_solve_poisson(self.h, _p(a, C.c_double), a.shape[0], 0, _p(out, C.c_double)))
+        return out
+
+    def solve_poisson_device(self, d_cells: int, d_p: int, d_fields: int = 0, d_scalars: int = 0, stream: int = 0):
+        """The same step on raw device pointers, asynchronous on ``stream``: ``d_cells`` [N,5] and ``d_p`` [N] float64;
+        ``d_fields`` [3,Ny*Nx] float32 receives (result, change, next) and ``d_scalars`` [8] float64 ``POISSON_SOLVE_SCALARS``
+        (0: the handle's own buffers)."""
+        self._chk(self.lib.psm_solve_poisson_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_fields or None),
+                                                    C.c_void_p(d_scalars or None), C.c_void_p(stream)))
+
     # -- the per-frame error blocks of assembled fields on the device: eight float64 sums per (frame, pair) instead of the fields
     RAW_SUMS = ("n", "s1", "s2", "tmin", "tmax", "pmin", "pmax", "tnan")
     METRICS = ("normVal", "biasNorm", "stdeNorm", "rmseNorm", "mean_err", "mean_sq_err")
