@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "psm_launch.h"
+#include "psm_unet_plan.h"   // tile shapes of the arrangements, PSM_PAIR_*, psm_pair_kernel_available: shared with the device-free planner
 
 enum { PSM_SRC_SAME = 0, PSM_SRC_UPSAMPLE = 1, PSM_SRC_MAXPOOL = 2 };
 
@@ -38,8 +39,8 @@ struct PsmConvArgs {
   int H0, W0;                  // resolution of in0
   int cout, relu;
   int64_t in0_case, in1_case, out_case;   // per-case strides (elements)
-  // row pitches in pixels (in0 at ITS resolution).  Finished bf16 activations live in zero-haloed tensors (psm_unet_api.cpp,
-  // act_layout): the pointers above address pixel (0, 0) of case 0, a row is P pixels apart, a case *_case elements.  Dense
+  // row pitches in pixels (in0 at ITS resolution).  Finished bf16 activations live in zero-haloed tensors (psm_unet_plan.h,
+  // ACT_PAD*; psm_unet_plan.cpp, act_layout): the pointers above address pixel (0, 0) of case 0, a row is P pixels apart, a case *_case elements.  Dense
   // tensors (the raw image, float32 activations, split-K slabs): P = the tensor's width.
   int P0, P1, PO;
 };
@@ -62,8 +63,7 @@ struct PsmHeadArgs {           // 1x1 convolution on a thin activation (c_in <= 
 //   2 = 16 rows x 4 channel tiles, each wave 4 rows x 4 channel tiles (64 px x 64 channels: 8 reads per 16 MFMAs)
 //   3 = 16 rows x 2 channel tiles, each wave 4 rows x 2 channel tiles (6 reads per 8 MFMAs)
 //   4 =  8 rows x 4 channel tiles, each wave 2 rows x 4 channel tiles (6 reads per 8 MFMAs; the input tile staged once for 64 channels)
-inline int psm_conv_tile_rows(int arrangement) { return arrangement == 0 ? 8 : arrangement == 1 ? 2 : arrangement == 2 ? 16 : arrangement == 3 ? 16 : arrangement == 4 ? 8 : 0; }
-inline int psm_conv_tile_nct(int arrangement, int nct) { return arrangement == 0 ? (nct == 2 ? 2 : 1) : arrangement == 3 ? 2 : 4; }
+// (psm_conv_tile_rows / psm_conv_tile_nct: psm_unet_plan.h)
 hipError_t psm_launch_conv3x3(const PsmConvArgs& a, int arrangement, int nct, int n_cases, hipStream_t st);
 hipError_t psm_launch_head1x1(const PsmHeadArgs& a, hipStream_t st);
 hipError_t psm_unet_read_stamps(unsigned long long* out);   // [64]; zeros unless built with -DPSM_STAMPS
@@ -71,9 +71,7 @@ hipError_t psm_unet_read_stamps(unsigned long long* out);   // [64]; zeros unles
 hipError_t psm_launch_conv_stem(const PsmConvArgs& a, int n_cases, hipStream_t st);
 
 // ---- fused level pairs (psm_unet_pair.hip): conv A + conv B of a level in one launch, bf16 mode ----------------------
-#define PSM_PAIR_TX 30          // output tile of a workgroup (the mid tile is 32 x 16: two MFMA pixel tiles wide)
-#define PSM_PAIR_TY 14
-enum { PSM_PAIR_STEM = 0, PSM_PAIR_UPCAT = 1, PSM_PAIR_POOL = 2 };
+// (PSM_PAIR_TX x PSM_PAIR_TY output tile of a workgroup, the PSM_PAIR_* kinds: psm_unet_plan.h)
 // One fused-pair tile, host-built (psm_unet_api.cpp, build_pair_tiles): the kernel reads it with ONE scalar load per tile instead of
 // two integer divisions and 64-bit address chains.  Offsets are BYTES from the tensors' (0, 0) pointers -- 32 bits: a case batch
 // of activations is < 4 GB (checked at plan time).
@@ -101,5 +99,4 @@ struct PsmPairArgs {
   const PsmPairTile* tiles;    // [n_cases * tiles_y * tiles_x], tile t = (cs * tiles_y + by) * tiles_x + bx
 };
 hipError_t psm_unet_pair_read_stamps(unsigned long long* out);   // [64]: 3 workgroups x 16 stamps; zeros unless built with -DPSM_STAMPS
-bool psm_pair_kernel_available(int kind, int cm, int c0, int c1, bool head);   // shared by the planner and the launcher
 hipError_t psm_launch_conv_pair(const PsmPairArgs& a, int kind, int cm, int n_cases, hipStream_t st);

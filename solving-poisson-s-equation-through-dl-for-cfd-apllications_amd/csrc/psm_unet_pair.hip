@@ -147,7 +147,7 @@ struct Stage {
 #endif
     const int M = NQ == 4 ? 2 : 1;                           // source pixels per tile pixel and direction
     const int64_t row_bytes = (int64_t)Ps * cpx * 2;         // one source row (Ps: the source tensor's pitch in ITS pixels)
-    // (round 6) the sources of the 32-channel pairs are ZERO-HALOED bf16 tensors (psm_unet_api.cpp, act_layout: 4 pixels left / top, 64 / 32
+    // (round 6) the sources of the 32-channel pairs are ZERO-HALOED bf16 tensors (psm_unet_plan.cpp, act_layout: 4 pixels left / top, 64 / 32
     // right / bottom): the 'same' padding, the last tile's overhang and a max-pool's doubled extent are read from memory like any other
     // pixel -- no clamps, no predicates, and write() below needs no selects (Hs, Ws stay in the signature for the callers)
     (void)Hs; (void)Ws;
@@ -649,7 +649,7 @@ __global__ __launch_bounds__(256, 2) void psm_pair_stem16_kernel(PsmPairArgs a) 
 // applied on the SOURCE side: a lane fetches the channel group that belongs in its slot) is cut into pieces of 1 KiB, piece i is
 // issued by wave i % 4.  A lane's source offset relative to the tile's first source pixel depends on (piece, lane) only, so it is
 // computed ONCE per kernel (one VGPR per piece) and a tile costs a wave PW instructions: no staging registers, no LDS stores, no
-// address arithmetic per tile.  The tensors are zero-haloed (psm_unet_api.cpp, act_layout), so there is nothing to clamp or to
+// address arithmetic per tile.  The tensors are zero-haloed (psm_unet_plan.cpp, act_layout), so there is nothing to clamp or to
 // zero: the 'same' padding and the overhang of the last tile are read from memory like any other pixel.
 //   PXB: bytes per LDS pixel;  PITCH x NROW: the LDS image;  NCOL: source columns that exist for the tile (columns beyond repeat
 //   the last one -- they are LDS padding no convolution reads)
@@ -963,17 +963,8 @@ __global__ __launch_bounds__(256, 2) void psm_pair32_kernel(PsmPairArgs a) {
 }  // namespace
 
 // grid: persistent workgroups, two per CU, a multiple of 8 (one share per XCD) when the tile count allows
-// Which (kind, channel counts, fused head) combinations the pair kernels below are instantiated for: the ONE predicate the
-// planner (psm_unet_api.cpp) and the launcher share.
-bool psm_pair_kernel_available(int kind, int cm, int c0, int c1, bool head) {
-  if (kind == PSM_PAIR_STEM) return cm == 16 && (c0 == 3 || c0 == 4) && !head;
-  if (kind == PSM_PAIR_POOL) return cm == 32 && c0 % 16 == 0 && c0 >= 16 && !head;
-  if (kind == PSM_PAIR_UPCAT) {
-    if (cm == 16) return c0 == 32 && c1 == 16;                                   // with or without the fused 1x1 head
-    if (cm == 32) return c0 % 32 == 0 && c0 >= 32 && c1 % 16 == 0 && c1 >= 16 && !head;
-  }
-  return false;
-}
+// Which (kind, channel counts, fused head) combinations the ladder below has a kernel for is psm_pair_kernel_available
+// (psm_unet_plan.cpp): the ONE predicate the planner and this launcher share.
 
 hipError_t psm_launch_conv_pair(const PsmPairArgs& a, int kind, int cm, int n_cases, hipStream_t st) {
   if (a.tiles_x != (a.W + TX - 1) / TX || a.tiles_y != (a.H + TY - 1) / TY || n_cases < 1 || a.n_cases != n_cases) return hipErrorInvalidValue;

@@ -19,6 +19,10 @@ configurations go through the host entry on a bound geometry and then, with one 
 guard trip, the re-run on the general path).  The `_rows` entries take the frames as float32 dataset rows (width 11, gradP 8): no
 out_scale (the rows stage makes it on the device), and the per-frame scalars are one more hashed output.
 
+The `conv` configurations (--only conv, or one of CONV by name) run the convolutional path, each in a child process with its planner
+switches in the environment: per precision one forward pass under the planner's own plan, one line with the SHA-256 of the field and the
+plan (psm_unet_plan_info per layer).
+
 The `refusals` configuration (--only refusals) is a fixed list of calls that the three evaluators' image, device, host and rows
 entries refuse from their argument checks, before anything is enqueued: one line per call with the return code and the text of
 psm_last_error, to be compared with diff between two builds.
@@ -85,6 +89,15 @@ for _e in ("poisson_frames", "poisson_frames_errors", "deltas_frames", "gradp_fr
            "deltas_rows", "gradp_rows", "poisson_rows"):
     STEPS.update({f"{_e}_n1": (_e, 1), f"{_e}_n3": (_e, 3), f"{_e}_host": (_e, 0)})
 REFUSALS = {"refusals": {}}
+# conv path, name: (widths, (ny, nx), n, c_in, environment of the child process): one forward pass per precision under the planner's own plan
+_M4 = ((16, 32, 64, 128), (56, 88), 2, 3)
+CONV = {
+    "conv_m4": _M4 + ({},),                                                              # stem, split-K slabs, x6, fused head
+    "conv_m4_pairs": _M4 + ({"PSM_UNET_PAIR_MIN": "1"},),                                # stem / pool / upsample pairs
+    "conv_m4_kw": _M4 + ({"PSM_UNET_KW": "-2", "PSM_UNET_NO_PAIR": "1"},),               # in-workgroup K split wherever eligible
+    "conv_pairs_44x52": ((16, 32, 64), (44, 52), 3, 4, {"PSM_UNET_PAIR_MIN": "1"}),      # every pair kernel, tiles that overhang on both axes
+    "conv_unet_s_256_n8": ((16, 32, 64, 128, 256), (256, 256), 8, 3, {}),                # the bench shape
+}
 OTHER = ["attention_ln_deferred", "attention_ln_launched", "conv1d_head", "mesh", "ring", "pressure", "poststeps"]
 _lines = []
 
@@ -539,6 +552,19 @@ def steps_config(name):
                 d.free()
 
 
+def conv_config(name):
+    """Runs in the child process: per precision the plan and the SHA-256 of the field of one forward pass."""
+    import numpy as np
+    from psm_amd import UNetSurrogate, synthetic
+    widths, (ny, nx), n, c_in, _ = CONV[name]
+    weights = synthetic.unet_he_weights(c_in, widths, 1, seed=23)
+    grids = np.random.default_rng(5).standard_normal((n, ny, nx, c_in)).astype(np.float32)
+    for precision in ("f32", "bf16"):
+        with UNetSurrogate(weights, ny, nx, c_in=c_in, widths=widths, max_cases=n, precision=precision) as net:
+            plan = " ".join("".join(str(v) for v in net.plan_info(i)) for i in range(len(weights)))
+            say(f"{name:28s} {precision:4s} field={sha(net.forward(grids))}  plan={plan}")
+
+
 def refusals_config():
     """Runs in the child process: one line per refused call, `<evaluator> <call> rc=<code> <psm_last_error>`.  The tables, frames and
     SDF plane of tests/test_field_errors.py (130 x 131, 200 cells, 3 frames); no post-steps are bound, so apply_filter is refused too.
@@ -705,6 +731,7 @@ def main():
     ap.add_argument("--boundary-child", help=argparse.SUPPRESS)
     ap.add_argument("--steps-child", help=argparse.SUPPRESS)
     ap.add_argument("--refusals-child", help=argparse.SUPPRESS)
+    ap.add_argument("--conv-child", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.dispatches:
         return dispatches(args.dispatches)
@@ -718,8 +745,10 @@ def main():
         return steps_config(args.steps_child)
     if args.refusals_child:
         return refusals_config()
+    if args.conv_child:
+        return conv_config(args.conv_child)
     only = args.only.split(",") if args.only else []
-    group = next((g for g, names in (("boundary", BOUNDARY), ("steps", STEPS), ("refusals", REFUSALS)) if only and all(n == g or n in names for n in only)), None)
+    group = next((g for g, names in (("boundary", BOUNDARY), ("steps", STEPS), ("refusals", REFUSALS), ("conv", CONV)) if only and all(n == g or n in names for n in only)), None)
     if group:                                                            # the parent process never opens the GPU
         if group == "boundary":
             say(f"# tools/route_matrix.py boundary lib={args.lib or 'libpsm_hip.so of the tree'}")
@@ -727,6 +756,9 @@ def main():
         elif group == "refusals":
             say("# tools/route_matrix.py refusals")
             rc = children(["refusals"], args.lib, "--refusals-child", {})
+        elif group == "conv":
+            say("# tools/route_matrix.py conv")
+            rc = children([b for n in only for b in (CONV if n == "conv" else [n])], args.lib, "--conv-child", {k: v[4] for k, v in CONV.items()})
         else:                                                            # no library path in the output: two libraries' runs are compared with cmp
             say("# tools/route_matrix.py steps")
             rc = children([b for n in only for b in (STEPS if n == "steps" else [n])], args.lib, "--steps-child", {})
