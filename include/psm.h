@@ -353,7 +353,10 @@ int psm_unpin_buffers(psm_handle* h);
  * All-or-nothing: every table is validated like psm_set_geometry's (the message names the case) before the handle is
  * touched; then the grid is planned, the per-case tables are uploaded and every per-step buffer is reserved (a step
  * allocates nothing).  Needs 1 <= n_cases <= max_cases (PSM_ERR_ARG), c_in == 3 and c_out == 1 (PSM_ERR_UNSUPPORTED) and
- * the grid -> mesh tables of every case (PSM_ERR_ARG).  The K geometries are bound for this entry only (the scope
+ * the grid -> mesh tables of every case (PSM_ERR_ARG).  Also accepted: the four-channel Poisson model (c_in == 4, c_out == 1,
+ * sdf_channel == 3), with maxs = (max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp) as psm_set_geometry reads them for that
+ * model; such a set binds no geometry and serves psm_bind_poisson_solve_cases / psm_solve_cases_poisson* alone:
+ * psm_solve_cases*, psm_solve_cases_delta* and psm_delta_prime_cases on it are PSM_ERR_UNSUPPORTED.  The K geometries are bound for this entry only (the scope
  * psm_set_geometry gives its one; a configuration outside the bound path solves on the general path; PSM_NO_BIND=1 keeps
  * the general path); with n_cases == 1 the route -- and every bit of p -- is that of psm_solve.
  * A handle holds EITHER the single mesh of psm_set_geometry OR a case set: setting one drops the other, psm_solve* on a case
@@ -870,7 +873,7 @@ int psm_get_kernel_timing(psm_handle* h, int32_t kernel, double* total_ms, int64
  * psm_solve_poisson_device: device pointers, 8-byte aligned, asynchronous on `stream` (NULL: the handle's), copies nothing.
  * d_fields [3][ny*nx] float32 receives (result, change, next) and may be NULL; change / next are written only with the weighting.
  * d_scalars [8] float64 = U, c, U^2, out-scale, skip, frames held before the call, 0, 0; NULL: the binding's slots.
- * Not provided: _begin / _end halves, the psm_pin_buffers direct routes, case sets. */
+ * Not provided: _begin / _end halves and the psm_pin_buffers direct routes; case sets: the `_cases` entries below. */
 int psm_bind_poisson_solve(psm_handle* h, double phi, double max_abs_delta_p, int32_t weighting, int32_t apply_filter);
 int psm_unbind_poisson_solve(psm_handle* h);
 int psm_poisson_solve_push(psm_handle* h, const double* cells, int64_t n);
@@ -878,6 +881,30 @@ int psm_poisson_solve_reset(psm_handle* h);
 int psm_poisson_solve_state(const psm_handle* h, int32_t* frames, int64_t* steps);
 int psm_solve_poisson(psm_handle* h, const double* cells, int64_t n, int32_t rank, double* p_out);
 int psm_solve_poisson_device(psm_handle* h, const double* d_cells, double* d_p, float* d_fields, double* d_scalars, void* stream);
+/* The same step for the case set of psm_set_geometry_cases under the four-channel model: K meshes on one grid advanced by ONE call,
+ * the chain run on K cases between the three mesh-end launches in their case-batched form (the case is launch dimension y), in one
+ * graph replay.  Cell-side arrays are the cases' concatenated in case order, as for psm_solve_cases: cells [sum n_i, 5], p [sum n_i].
+ * Per case the semantics are those above, bit for bit what psm_solve_poisson gives on a single mesh with the same tables: U, c, the
+ * weight, dp_prev, the fallback cells, the turn-over of the state.  Every case decides on its own whether its step is SKIPPED (its
+ * chain runs on U = 1, out-scale 0 and zero columns, it returns cells[:,4] and scalars[k][4] == 1; its neighbours are not
+ * affected).  The set has ONE frame counter and one step counter: all cases are pushed and advanced together; a priming step returns
+ * p = cells[:,4] for every case.  No atomics: a step is bit-reproducible.
+ * psm_bind_poisson_solve_cases: needs a case set (PSM_ERR_STATE; on a single mesh the message names psm_bind_poisson_solve), c_in == 4,
+ * c_out == 1, sdf_channel == 3 (PSM_ERR_UNSUPPORTED), psm_bind_features for at least the set's K cases, with the K sdfuncts in case
+ * order, and psm_bind_poststeps (PSM_ERR_STATE names the missing one, or says that the features are bound for fewer cases); phi and
+ * max_abs_delta_p finite and non-zero (PSM_ERR_ARG).  psm_bind_frames is not needed (it belongs to the single mesh).  It allocates the
+ * state (zeroed), the partial maxima and the scalar slots: after it a step allocates nothing.  Whatever drops the case set, the
+ * features or the post-steps drops it.  psm_poisson_solve_reset, psm_poisson_solve_state and psm_unbind_poisson_solve serve whichever
+ * of the two bindings the handle holds; psm_solve_poisson* and psm_poisson_solve_push on this binding, and the entries below on
+ * psm_bind_poisson_solve's, are PSM_ERR_STATE naming the other form.
+ * psm_solve_cases_poisson_device: d_fields [3][K][ny*nx] float32 receives (result, change, next) and may be NULL; d_scalars [K][8]
+ * float64, one row per case as above, NULL: the binding's slots; pointers aligned as for psm_solve_poisson_device, checked before
+ * anything is enqueued.
+ * Not provided either: _begin / _end halves and the psm_pin_buffers direct routes. */
+int psm_bind_poisson_solve_cases(psm_handle* h, double phi, double max_abs_delta_p, int32_t weighting, int32_t apply_filter);
+int psm_poisson_solve_push_cases(psm_handle* h, const double* cells);                 /* [sum n_i, 5] */
+int psm_solve_cases_poisson(psm_handle* h, const double* cells, double* p_out);       /* [sum n_i, 5] -> [sum n_i] */
+int psm_solve_cases_poisson_device(psm_handle* h, const double* d_cells, double* d_p, float* d_fields, double* d_scalars, void* stream);
 
 /* Dispatch-level time of EVERY kernel of the solve path: `steps` solves of d_grid through the launch sequence of
  * psm_solve_grid_device on the handle's stream, each dispatch stamped with its own begin / end by

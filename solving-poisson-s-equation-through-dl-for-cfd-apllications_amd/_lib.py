@@ -195,6 +195,10 @@ SIGNATURES = {
     "psm_poisson_solve_state": (C.c_int, [_hp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "psm_solve_poisson": (C.c_int, [_hp, _f64p, C.c_int64, C.c_int32, _f64p]),
     "psm_solve_poisson_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_bind_poisson_solve_cases": (C.c_int, [_hp, C.c_double, C.c_double, C.c_int32, C.c_int32]),
+    "psm_poisson_solve_push_cases": (C.c_int, [_hp, _f64p]),
+    "psm_solve_cases_poisson": (C.c_int, [_hp, _f64p, _f64p]),
+    "psm_solve_cases_poisson_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
     "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),

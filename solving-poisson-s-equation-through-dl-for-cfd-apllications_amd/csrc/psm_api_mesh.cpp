@@ -81,6 +81,8 @@ int cases_check(psm_handle* h) {
     return fail(h, PSM_ERR_STATE, "the handle holds the single mesh of psm_set_geometry: psm_solve_cases* needs a case set (psm_set_geometry_cases)");
   if (!h->mcs.ready || !h->planned)
     return fail(h, PSM_ERR_STATE, "psm_set_geometry_cases has not been called (or its case set was dropped by a later psm_set_* / psm_plan_grid)");
+  // a case set under the four-channel model serves psm_solve_cases_poisson* alone
+  if (h->cfg.c_in != 3 || h->cfg.c_out != 1) return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292)");
   return PSM_OK;
 }
 
@@ -358,7 +360,11 @@ int psm_set_geometry_cases(psm_handle* h, int32_t n_cases, const int64_t* n_cell
   if (!h) return PSM_ERR_ARG;
   if (!n_cells || !vtx_m2g || !wts_m2g || !indices || !sdfunct || !vtx_g2m || !wts_g2m || !maxs) return fail(h, PSM_ERR_ARG, "null geometry table");
   if (n_cases < 1 || n_cases > h->cfg.max_cases) return fail(h, PSM_ERR_ARG, "n_cases outside [1, max_cases]");
-  if (h->cfg.c_in != 3 || h->cfg.c_out != 1) return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292)");
+  // the three-channel models of psm_solve_cases*, or the four-channel Poisson model, whose set serves psm_solve_cases_poisson* alone
+  // (maxs: max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp, as the single mesh reads them for that model)
+  const bool poisson_model = h->cfg.c_in == 4 && h->cfg.c_out == 1 && h->cfg.sdf_channel == 3;
+  if (!poisson_model && (h->cfg.c_in != 3 || h->cfg.c_out != 1))
+    return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292), or the Poisson model's c_in == 4, c_out == 1, sdf_channel == 3");
   if (ny < 1 || nx < 1) return fail(h, PSM_ERR_ARG, "bad grid shape");
   // everything that needs no device first: a bad table leaves the handle as it was
   std::vector<PsmMeshCaseInput> in(n_cases);

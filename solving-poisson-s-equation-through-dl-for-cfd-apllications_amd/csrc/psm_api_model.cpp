@@ -179,6 +179,7 @@ void unpin_buffers(psm_handle* h) {
 
 void mesh_cases_free(psm_handle* h) {
   MeshCaseSet& m = h->mcs;
+  if (h->psolve.cases) poisson_solve_free(h);   // psm_bind_poisson_solve_cases stands on this set's tables and cell ranges
   mesh_buffers_free(m);
   m.ready = false; m.inflight = false; m.n_cases = 0; m.off.clear();
   delta_drop(h);                        // U(t-1) of the delta step belongs to the cells that go here

@@ -17,7 +17,7 @@
 //   psm_api_gradp_frames.cpp   the U_to_gradP evaluator's frame batch on the device: psm_bind_gradp_frames, the image / label pack psm_gradp_image_device and the step psm_gradp_frames* (columns -> p -> errors)
 //   psm_api_chapter4_frames.cpp  the Chapter-4 evaluators' frame batch on the device: psm_bind_chapter4_frames, the image / label pack psm_chapter4_image_device and the step psm_chapter4_frames* (columns -> p -> errors)
 //   psm_api_rows.cpp        a frame's dataset rows -> scalars + columns on the device: psm_bind_rows, the stage alone psm_rows_prepare_device and the evaluators' steps behind it, psm_deltas_rows* / psm_poisson_rows* / psm_gradp_rows*
-//   psm_api_poisson_solve.cpp  the Poisson-model step at the solver boundary (cells -> p, two-frame state on the device): psm_bind_poisson_solve, psm_poisson_solve_push / _reset / _state, psm_solve_poisson*
+//   psm_api_poisson_solve.cpp  the Poisson-model step at the solver boundary (cells -> p, two-frame state on the device): psm_bind_poisson_solve, psm_poisson_solve_push / _reset / _state, psm_solve_poisson*; for a case set psm_bind_poisson_solve_cases, psm_poisson_solve_push_cases, psm_solve_cases_poisson*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -211,7 +211,8 @@ struct PoissonSolveCall {
   double* p = nullptr;                  // [N]
   double* scalars = nullptr;            // [8]
   int weighting = 0, prime = 0, frames = 0;   // prime: the push alone is a plain launch, never part of a sequence (always 0 in one); frames held before the call
-  auto tie() const { return std::tie(cells, p, scalars, weighting, prime, frames); }
+  int cases = 0;                        // 0: the single mesh; K: the case set's form (psm_solve_cases_poisson*): cells [sum n_i, 5], p [sum n_i], scalars [K][8]
+  auto tie() const { return std::tie(cells, p, scalars, weighting, prime, frames, cases); }
 };
 
 // What surrounds ONE solve (solve_device, psm_api_step.cpp), in launch order; every stage keeps its own "absent" value.  A new stage
@@ -370,15 +371,18 @@ struct FrameSet {
 };
 
 // Binding of the Poisson-model step at the solver boundary (psm_bind_poisson_solve, behind psm_bind_features, psm_bind_poststeps and
-// psm_bind_frames on the single mesh): the step's constants, the two-frame state, the partial maxima and the scalar slots, so that a
-// step allocates nothing.  The state is written by the last launch of a step; the host counters follow once the whole step is enqueued.
+// psm_bind_frames on the single mesh; psm_bind_poisson_solve_cases, behind the first two on a case set): the step's constants, the
+// two-frame state, the partial maxima and the scalar slots, so that a step allocates nothing.  The state is written by the last launch
+// of a step; the host counters follow once the whole step is enqueued.  A case set has ONE frame counter and one step counter; its
+// arrays are the single mesh's with N = sum n_i and a row of partials and of scalars per case.
 struct PoissonSolveSet {
   bool ready = false;
+  int cases = 0;                        // 0: bound on the single mesh; K: bound on a case set of K cases
   double phi = 1.0, max_abs_dp = 1.0;
   int weighting = 0, apply_filter = 0;
   double* d_state = nullptr;            // [5 N]: u_prev [N][2] | du_prev [N][2] | p_prev [N], every piece 16-byte aligned
-  double* d_part = nullptr;             // [2][PSM_POISSON_PARTS]
-  double* d_scalars = nullptr;          // [PSM_POISSON_SCALARS]
+  double* d_part = nullptr;             // [2][PSM_POISSON_PARTS] ([K] of them for a case set)
+  double* d_scalars = nullptr;          // [PSM_POISSON_SCALARS] ([K] of them for a case set)
   int frames = 0;                       // frames held: 0, 1 or 2
   int64_t steps = 0;                    // steps taken since the state was last empty (a priming step does not count)
 };
@@ -493,7 +497,7 @@ struct psm_handle {
   FeatureSet feat;                      // Poisson input features on the planned grid (psm_bind_features)
   FrameSet frames;                      // frame batch on the single mesh (psm_bind_frames)
   RowsSet rows;                         // the rows stage's staging behind it (psm_bind_rows)
-  PoissonSolveSet psolve;               // the Poisson-model step at the solver boundary behind features, post-steps and frames (psm_bind_poisson_solve)
+  PoissonSolveSet psolve;               // the Poisson-model step at the solver boundary behind features, post-steps and frames (psm_bind_poisson_solve) or behind features and post-steps on a case set (psm_bind_poisson_solve_cases)
   DeltasSet deltas;                     // the deltas evaluator's frame batch behind it (psm_bind_deltas_frames)
   GradpSet gradp;                       // the U_to_gradP evaluator's frame batch behind it (psm_bind_gradp_frames)
   Chapter4Set chapter4;                 // the Chapter-4 evaluators' frame batch behind it (psm_bind_chapter4_frames)
@@ -645,7 +649,7 @@ void deltas_free(psm_handle* h);
 void gradp_free(psm_handle* h);
 void chapter4_free(psm_handle* h);
 void rows_free(psm_handle* h);
-void poisson_solve_free(psm_handle* h);   // whatever drops the feature, post-step or frame binding or the mesh drops this one (psm_api_poisson_solve.cpp)
+void poisson_solve_free(psm_handle* h);   // whatever drops the feature, post-step or frame binding, the mesh or the case set drops this one (psm_api_poisson_solve.cpp)
 // the two head launches / the tail launch of a Poisson solver step on `st` (the tail's field: next with the weighting, else result)
 int poisson_solve_head(psm_handle* h, const PoissonSolveCall& ps, hipStream_t st);
 int poisson_solve_tail(psm_handle* h, const PoissonSolveCall& ps, const PostCall& pc, hipStream_t st);

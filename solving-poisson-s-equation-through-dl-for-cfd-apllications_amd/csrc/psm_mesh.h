@@ -125,6 +125,43 @@ hipError_t psm_launch_poisson_to_grid(const PsmPoissonCellsArgs& a, hipStream_t 
 hipError_t psm_launch_poisson_to_mesh(const PsmPoissonMeshArgs& a, hipStream_t st);
 inline int psm_poisson_parts(int64_t n_cells) { return (int)(n_cells + 1023 < (int64_t)PSM_POISSON_PARTS * 1024 ? (n_cells + 1023) / 1024 : PSM_POISSON_PARTS); }
 
+// ---- the same three launches for a case set (psm_solve_cases_poisson*, psm_set_geometry_cases under a four-channel model): K meshes
+// on one planned grid, the case is launch dimension y.  Cell-side arrays -- the cells, the grid -> mesh tables, the state, p -- are the
+// cases' concatenated (case i at rows cell_off[i] .. cell_off[i + 1], vertex indices case-local); grid-side tables and planes are
+// [K][n_grid, ...] at the strides of the feature and post-step bindings.  A workgroup takes its case's slices and runs the single
+// mesh's body on them, so a case's result does not depend on what the other slots hold.
+struct PsmPoissonCasesArgs {
+  const double* cells;          // [sum n_i, 5]
+  const int64_t* cell_off;      // [K + 1]
+  int n_cases, n_parts;         // n_parts: psm_poisson_parts(largest n_i), launch dimension x of the partial launch
+  int64_t max_cells;            // largest n_i: sizes launch dimension x of the tail
+  double *u_prev, *du_prev, *p_prev;   // the state [sum n_i][2] | [sum n_i][2] | [sum n_i]: read by the head, turned over by the tail
+  double* partials;             // [K][2][PSM_POISSON_PARTS]; every (part, case) slot below n_parts is written at every step
+  // mesh -> grid
+  const int32_t* vtx_m2g;       // [K][n_grid, 3]
+  const double* wts_m2g;        // [K][n_grid, 3]
+  const int32_t* src_of_cell;   // [K][n_grid]
+  int64_t n_grid;
+  double* vel;                  // [K][4][n_grid]
+  float *w_plane, *prev_plane;  // [K][n_grid]; both nullptr without the weighting
+  double* scalars;              // [K][PSM_POISSON_SCALARS]
+  double* lu;                   // [K][2]
+  float* row_scale;             // [K][B]
+  int B;
+  double phi, max_abs_dp;
+  int weighting, frames, prime; // frames held before the call, the same for every case; prime: read by the tail only
+  // grid -> mesh
+  const int32_t* vtx_g2m;       // [sum n_i, 3]
+  const double* wts_g2m;        // [sum n_i, 3]
+  const int32_t* cell_of_point; // [K][n_grid]
+  const float* field;           // [K][n_grid]; not read when prime
+  const uint8_t* near_wall;     // [sum n_i]
+  double* p_out;                // [sum n_i]
+};
+hipError_t psm_launch_poisson_partial_cases(const PsmPoissonCasesArgs& a, hipStream_t st);
+hipError_t psm_launch_poisson_to_grid_cases(const PsmPoissonCasesArgs& a, hipStream_t st);
+hipError_t psm_launch_poisson_to_mesh_cases(const PsmPoissonCasesArgs& a, hipStream_t st);
+
 // ---- the mesh ends for a case batch (psm_set_geometry_cases): K meshes on one planned grid, the case is launch dimension y.
 // Cell-side arrays are the cases' concatenated ([sum n_i, ...], case i at rows cell_off[i] .. cell_off[i + 1]), grid-side tables
 // are [K][n_grid, ...]; vertex indices are case-local as the caller gave them (the kernels add the case's offset).

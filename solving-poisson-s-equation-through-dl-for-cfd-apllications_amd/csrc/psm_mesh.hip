@@ -9,7 +9,7 @@
 //              dimensionalise, near-wall / NaN fallback to the previous p   [PM:481-496]
 //   both ends also in DELTA form (psm_solve_delta*): U - U(t-1) in, p(t-1) + dp out, U(t-1) := U   [SMD:389-391]
 //   and as the ends of the Poisson-model step (psm_solve_poisson*, at the end of this file): six columns from cells + a two-frame
-//   state in, p(t-1) + dp out, the state turned over                                                [SMP:549-556, 842-847]
+//   state in, p(t-1) + dp out, the state turned over; for a case set too (psm_solve_cases_poisson*)  [SMP:549-556, 842-847]
 //
 // All of them are HBM-bound gathers; interpolation is done in float64 like the reference.
 #include "psm_mesh.h"
@@ -500,9 +500,13 @@ __device__ __forceinline__ PoissonCols poisson_cols(const PsmPoissonCellsArgs& a
   return o;
 }
 
+// One body per launch, called by the single-mesh kernel and by the case-set kernel (PsmPoissonCasesArgs) alike: a kernel is the
+// offsetting of its case's base pointers, then the body.  The argument structs go BY VALUE, as above.
+
 // Head, level one: workgroup b leaves the maxima of the squared speed and of c_cell over its cells (b * 1024 + tid, + gridDim.x *
-// 1024, ...) in partials[b] and partials[PSM_POISSON_PARTS + b].  cells and the state are read once.
-__global__ __launch_bounds__(1024) void psm_umax_partial_kernel(PsmPoissonCellsArgs a) {
+// 1024, ...) in partials[b] and partials[PSM_POISSON_PARTS + b].  cells and the state are read once.  A workgroup that owns no cell
+// (a shorter case of a set) stores 0.0, the start value of the fold.
+__device__ __forceinline__ void poisson_partial(PsmPoissonCellsArgs a) {
   __shared__ double red[2][16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   double m = 0.0, mc = 0.0;
@@ -527,7 +531,7 @@ __global__ __launch_bounds__(1024) void psm_umax_partial_kernel(PsmPoissonCellsA
 // `scalars` and into the device arrays the chain reads, as psm_rows.hip's finish launch does --; then one thread per image cell
 // gathers the columns of the three vertices of its source point and writes the six planes: 0 where nobody writes, NaN for a negative
 // weight (interpolate_fill) in the four velocity planes, NaN -> 0 in the two float32 planes.
-__global__ __launch_bounds__(256) void psm_interp_to_grid_kernel(PsmPoissonCellsArgs a) {
+__device__ __forceinline__ void poisson_to_grid(PsmPoissonCellsArgs a) {
   __shared__ double fold_s[2][4];
   const int tid = threadIdx.x;
   const int p = min(tid, a.n_partials - 1);
@@ -576,11 +580,13 @@ __global__ __launch_bounds__(256) void psm_interp_to_grid_kernel(PsmPoissonCells
     a.prev_plane[cell] = (r[5] != r[5]) ? 0.f : (float)r[5];   // would spread through the sigma_weight filter over its whole radius
   }
 }
+__global__ __launch_bounds__(1024) void psm_umax_partial_kernel(PsmPoissonCellsArgs a) { poisson_partial(a); }
+__global__ __launch_bounds__(256) void psm_interp_to_grid_kernel(PsmPoissonCellsArgs a) { poisson_to_grid(a); }
 
 // Tail, grid -> mesh: dp[n] = sum_j field[cell_of_point[vtx[n][j]]] * wts[n][j] in float64, p = p(t-1) + dp, p(t-1) itself bit for
 // bit where psm_to_mesh_kernel falls back (near-wall cell, negative weight, NaN: PM:494-496) and everywhere on a skipped step; then
 // the same thread turns its cell's state over.  prime (uniform): the push alone -- no field, p = p(t-1), block 0 stores the scalars.
-__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmPoissonMeshArgs a) {
+__device__ __forceinline__ void poisson_to_mesh(PsmPoissonMeshArgs a) {
 #pragma clang fp contract(off)
   const bool skip = a.prime ? true : (a.scalars[4] != 0.0);
   if (a.prime && blockIdx.x == 0 && threadIdx.x == 0) {
@@ -616,6 +622,40 @@ __global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmPoissonMeshArgs a) 
   *reinterpret_cast<psm_uv2*>(a.u_prev + n * 2) = psm_uv2{ux, uy};
   a.p_prev[n] = prev;
 }
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmPoissonMeshArgs a) { poisson_to_mesh(a); }
+
+// ---- the case set (psm_solve_cases_poisson*, PsmPoissonCasesArgs in psm_mesh.h): the case is launch dimension y of all three
+// launches; a workgroup reads its case's range from cell_off and runs the body above on the case's slices, so that a case of a set
+// holds the bits the single mesh gives on the same tables, decides on its own whether its step is skipped and stores its own
+// scalars, (phi, U) and row scales.  No atomics: a step is bit-reproducible.
+__device__ __forceinline__ PsmPoissonCellsArgs case_poisson_cells(const PsmPoissonCasesArgs& a, int cs) {
+  const int64_t c0 = a.cell_off[cs], g0 = (int64_t)cs * a.n_grid;
+  PsmPoissonCellsArgs s{};
+  s.cells = a.cells + c0 * 5; s.u_prev = a.u_prev + c0 * 2; s.du_prev = a.du_prev + c0 * 2; s.p_prev = a.p_prev + c0;
+  s.n_cells = a.cell_off[cs + 1] - c0;
+  s.partials = a.partials + (int64_t)cs * 2 * PSM_POISSON_PARTS; s.n_partials = a.n_parts;
+  s.vtx = a.vtx_m2g + g0 * 3; s.wts = a.wts_m2g + g0 * 3; s.src_of_cell = a.src_of_cell + g0; s.n_grid = a.n_grid;
+  s.vel = a.vel + g0 * 4;
+  if (a.weighting) { s.w_plane = a.w_plane + g0; s.prev_plane = a.prev_plane + g0; }
+  s.scalars = a.scalars + (int64_t)cs * PSM_POISSON_SCALARS; s.lu = a.lu + 2 * cs; s.row_scale = a.row_scale + (int64_t)cs * a.B; s.B = a.B;
+  s.phi = a.phi; s.max_abs_dp = a.max_abs_dp; s.weighting = a.weighting; s.frames = a.frames;
+  return s;
+}
+__device__ __forceinline__ PsmPoissonMeshArgs case_poisson_mesh(const PsmPoissonCasesArgs& a, int cs) {
+  const int64_t c0 = a.cell_off[cs], g0 = (int64_t)cs * a.n_grid;
+  PsmPoissonMeshArgs m{};
+  m.cells = a.cells + c0 * 5; m.vtx = a.vtx_g2m + c0 * 3; m.wts = a.wts_g2m + c0 * 3; m.cell_of_point = a.cell_of_point + g0;
+  m.field = a.prime ? nullptr : a.field + g0; m.near_wall = a.near_wall + c0; m.p_out = a.p_out + c0; m.n_cells = a.cell_off[cs + 1] - c0;
+  m.u_prev = a.u_prev + c0 * 2; m.du_prev = a.du_prev + c0 * 2; m.p_prev = a.p_prev + c0;
+  m.scalars = a.scalars + (int64_t)cs * PSM_POISSON_SCALARS; m.prime = a.prime; m.frames = a.frames;
+  return m;
+}
+// head, level one: part blockIdx.x of case blockIdx.y; every (part, case) slot is written, 0.0 where a shorter case has no cell there
+__global__ __launch_bounds__(1024) void psm_umax_partial_kernel(PsmPoissonCasesArgs a) { poisson_partial(case_poisson_cells(a, blockIdx.y)); }
+// head, level two + mesh -> grid: workgroup 0 of a case stores that case's scalars
+__global__ __launch_bounds__(256) void psm_interp_to_grid_kernel(PsmPoissonCasesArgs a) { poisson_to_grid(case_poisson_cells(a, blockIdx.y)); }
+// tail: x covers the largest case, the workgroups beyond a shorter case's end return at once (as to_mesh_case)
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmPoissonCasesArgs a) { poisson_to_mesh(case_poisson_mesh(a, blockIdx.y)); }
 
 hipError_t psm_launch_poisson_partial(const PsmPoissonCellsArgs& a, hipStream_t st) {
   if (a.n_cells < 1 || a.n_partials < 1 || a.n_partials > PSM_POISSON_PARTS) return hipErrorInvalidValue;
@@ -630,5 +670,26 @@ hipError_t psm_launch_poisson_to_grid(const PsmPoissonCellsArgs& a, hipStream_t 
 hipError_t psm_launch_poisson_to_mesh(const PsmPoissonMeshArgs& a, hipStream_t st) {
   if (a.n_cells < 1 || !a.u_prev || !a.du_prev || !a.p_prev || !a.scalars || (!a.prime && !a.field)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(static_cast<void (*)(PsmPoissonMeshArgs)>(psm_to_mesh_kernel), dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+typedef void (*PsmPoissonCasesKernel)(PsmPoissonCasesArgs);
+static bool poisson_cases_ok(const PsmPoissonCasesArgs& a) {
+  return a.n_cases >= 1 && a.cell_off && a.cells && a.u_prev && a.du_prev && a.p_prev && a.scalars;
+}
+hipError_t psm_launch_poisson_partial_cases(const PsmPoissonCasesArgs& a, hipStream_t st) {
+  if (!poisson_cases_ok(a) || a.n_parts < 1 || a.n_parts > PSM_POISSON_PARTS || !a.partials) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<PsmPoissonCasesKernel>(psm_umax_partial_kernel), dim3((unsigned)a.n_parts, (unsigned)a.n_cases), dim3(1024), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_poisson_to_grid_cases(const PsmPoissonCasesArgs& a, hipStream_t st) {
+  if (!poisson_cases_ok(a) || a.n_grid < 1 || a.n_parts < 1 || a.n_parts > PSM_POISSON_PARTS || !a.partials || !a.vel || !a.lu || !a.row_scale ||
+      (a.weighting && (!a.w_plane || !a.prev_plane))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<PsmPoissonCasesKernel>(psm_interp_to_grid_kernel), dim3((unsigned)((a.n_grid + 255) / 256), (unsigned)a.n_cases), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_poisson_to_mesh_cases(const PsmPoissonCasesArgs& a, hipStream_t st) {
+  if (!poisson_cases_ok(a) || a.max_cells < 1 || !a.p_out || (!a.prime && !a.field)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<PsmPoissonCasesKernel>(psm_to_mesh_kernel), dim3((unsigned)((a.max_cells + 255) / 256), (unsigned)a.n_cases), dim3(256), 0, st, a);
   return hipGetLastError();
 }

@@ -12,7 +12,7 @@ from .surrogate import GridSurrogate, _f64, _p
 from .synthetic import SurrogateModel
 
 STEPS = ("absolute", "delta")
-MODULE_STEPS = STEPS + ("poisson",)      # SolverModule alone: the Poisson-model step has no case-batch form
+MODULE_STEPS = STEPS + ("poisson",)      # the Poisson-model step: psm_solve_poisson (SolverModule), psm_solve_cases_poisson (SolverEnsemble)
 
 
 def _check_step(step, allowed=STEPS):
@@ -31,6 +31,14 @@ def _check_cells(array_in, out):
     elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
         raise ValueError("out must be a contiguous float64 array [N]")
     return a, out
+
+
+def _check_poisson(maxs, phi, k):
+    """The argument checks of step='poisson', of SolverModule and SolverEnsemble alike, before any library call."""
+    if len(maxs) != 5:
+        raise ValueError("step='poisson' takes five maxs: (max_abs_Poisson_term_1, max_abs_delta_Ux, max_abs_delta_Uy, max_abs_dist, max_abs_delta_p)")
+    if phi is None or k is None:
+        raise ValueError("step='poisson' needs phi and k")
 
 
 def _poisson_state(sur):
@@ -79,10 +87,7 @@ class SolverModule:
         self.model, self.maxs, self.device, self.delta = model, tuple(float(v) for v in maxs), device, delta
         self.geometry = geometry
         if self.step == "poisson":
-            if len(self.maxs) != 5:
-                raise ValueError("step='poisson' takes five maxs: (max_abs_Poisson_term_1, max_abs_delta_Ux, max_abs_delta_Uy, max_abs_dist, max_abs_delta_p)")
-            if phi is None or k is None:
-                raise ValueError("step='poisson' needs phi and k")
+            _check_poisson(self.maxs, phi, k)
             self.phi, self.k, self.weighting, self.apply_filter = float(phi), float(k), bool(weighting), bool(apply_filter)
             self.sigma_field, self.sigma_weight = tuple(sigma_field), tuple(sigma_weight)
         self._sur = None
@@ -266,15 +271,24 @@ class SolverEnsemble:
     case).  ``init_func`` takes one (array, top, obst) per case, ``py_func`` one ``[N_i,5]`` array per case and returns the
     list of ``p_i``.  ``geometry``: 'native' (``psm_init_geometry_cases``, the library's C++ table builder) or 'scipy'
     (``geometry.build_geometry`` per case, handed over with ``psm_set_geometry_cases``) -- see :class:`SolverModule`.
-    ``step``: 'absolute' or 'delta' as for :class:`SolverModule`, on ``psm_solve_cases_delta*``: one state for the set."""
+    ``step``: 'absolute' or 'delta' as for :class:`SolverModule`, on ``psm_solve_cases_delta*``: one state for the set; or
+    'poisson' with the further arguments of :class:`SolverModule` (five ``maxs``, ``phi``, ``k``, the weighting, the filter and its
+    widths), on ``psm_solve_cases_poisson``: ``init_func`` installs the K table sets, binds the features with the K SDF planes, the
+    post-steps and the step, and pushes its own ``arrays`` as the first frame; one two-frame state, one frame counter and one step
+    counter for the set; no begin / end halves."""
 
     def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), max_cases: int = 8, geometry: str = "native",
-                 device: int = 0, delta: float = 5e-3, step: str = "absolute"):
+                 device: int = 0, delta: float = 5e-3, step: str = "absolute", phi: float = None, k: float = None, weighting: bool = True,
+                 apply_filter: bool = True, sigma_field=(10, 10), sigma_weight=(50, 50)):
         if geometry not in ("scipy", "native"):
             raise ValueError("geometry must be 'scipy' or 'native'")
-        self.step = _check_step(step)
+        self.step = _check_step(step, MODULE_STEPS)
         self.model, self.maxs, self.max_cases = model, tuple(float(v) for v in maxs), int(max_cases)
         self.geometry, self.device, self.delta = geometry, device, delta
+        if self.step == "poisson":
+            _check_poisson(self.maxs, phi, k)
+            self.phi, self.k, self.weighting, self.apply_filter = float(phi), float(k), bool(weighting), bool(apply_filter)
+            self.sigma_field, self.sigma_weight = tuple(sigma_field), tuple(sigma_weight)
         self._sur = None
         self.tables = None
         self.cell_off = None
@@ -291,7 +305,7 @@ class SolverEnsemble:
         lib = _lib.load()
         K = len(arrays)
         a, t, o = [_f64(x) for x in arrays], [_f64(x) for x in tops], [_f64(x) for x in obsts]
-        mx = _f64(self.maxs)
+        mx = _f64(self.maxs[-4:])
         if self.geometry == "native":
             ny, nx = C.c_int32(), C.c_int32()
             if lib.psm_geometry_shape(_p(a[0], C.c_double), a[0].shape[0], self.delta, C.byref(ny), C.byref(nx), None):
@@ -307,7 +321,7 @@ class SolverEnsemble:
             self._sur.close()
         self._sur = sur = GridSurrogate(self.model, ny, nx, self.max_cases, self.device)
         n = (C.c_int64 * K)(*[x.shape[0] for x in a])
-        smd = int(self.step == "delta")          # the deltas model's convention: normalise_sdf = fill_input = 1 (SM_call.py:441-443)
+        smd = int(self.step != "absolute")       # the deltas model's convention: normalise_sdf = fill_input = 1 (SM_call.py:441-443)
         if self.geometry == "native" and smd:    # psm_init_geometry_cases passes 0, 0: build the tables, hand them over with 1, 1
             ng = ny * nx
             keep = [[np.empty((rows or x.shape[0]) * width, dt) for x in a]      # vtx_m2g, wts_m2g, indices, sdfunct, vtx_g2m, wts_g2m
@@ -333,34 +347,46 @@ class SolverEnsemble:
         sur._chk(lib.psm_mesh_cases(sur.h, None, off))
         self.cell_off = [int(v) for v in off]
         self.tables = tables
+        if self.step == "poisson":               # everything a step stands on, in the order the library asks for it (keep[3]: the K sdfuncts)
+            sur.bind_features(np.stack([np.asarray(sd, np.float64).reshape(ny, nx) for sd in keep[3]]), self.k, self.maxs[:4])
+            sur.bind_poststeps(self.sigma_field, self.sigma_weight)
+            sur.bind_poisson_solve_cases(self.phi, self.maxs[4], self.weighting, self.apply_filter)
         if smd:
             self.prime(a)
         return 0
 
-    # -- the state of step='delta' (psm_delta_prime_cases / psm_delta_reset / psm_delta_state)
+    # -- the state of step='delta' (psm_delta_prime_cases / psm_delta_reset / psm_delta_state) and of step='poisson'
+    # (psm_poisson_solve_push_cases / psm_poisson_solve_reset / psm_poisson_solve_state)
     def _need_delta(self):
-        if self.step != "delta":
+        if self.step == "absolute":
             raise RuntimeError("this ensemble was built with step='absolute': the state belongs to step='delta'")
 
     def prime(self, arrays):
-        """U(t-1) := arrays[k][:,0:2] for every case.  ``init_func`` does this with the start fields."""
+        """U(t-1) := arrays[k][:,0:2] for every case.  ``init_func`` does this with the start fields.  step='poisson': one frame
+        (U and p) of every case is pushed into the two-frame state; a restart primes with two."""
         self._need_delta()
         cells, _ = self._pack(arrays)
+        if self.step == "poisson":
+            self._sur._chk(self._sur.lib.psm_poisson_solve_push_cases(self._sur.h, _p(cells, C.c_double)))
+            return
         self._sur._chk(self._sur.lib.psm_delta_prime_cases(self._sur.h, _p(cells, C.c_double)))
 
     def reset_state(self):
         self._need_delta()
         if self.tables is None:
             raise RuntimeError("init_func has not been called")
+        if self.step == "poisson":
+            self._sur._chk(self._sur.lib.psm_poisson_solve_reset(self._sur.h))
+            return
         self._sur._chk(self._sur.lib.psm_delta_reset(self._sur.h))
 
     @property
     def state(self):
-        """(primed, steps) of psm_delta_state."""
+        """(primed, steps) of psm_delta_state; step='poisson': (frames held, steps) of psm_poisson_solve_state."""
         self._need_delta()
         if self.tables is None:
             raise RuntimeError("init_func has not been called")
-        return _delta_state(self._sur)
+        return _poisson_state(self._sur) if self.step == "poisson" else _delta_state(self._sur)
 
     def _entry(self, name):
         return getattr(self._sur.lib, name.replace("psm_solve_cases", "psm_solve_cases_delta") if self.step == "delta" else name)
@@ -384,6 +410,8 @@ class SolverEnsemble:
 
     def py_func_begin(self, arrays):
         """First half of :meth:`py_func` (psm_solve_cases_begin): enqueue the step of all cases and return."""
+        if self.step == "poisson":
+            raise RuntimeError("step='poisson' has no begin / end halves: use py_func")
         cells, p = self._pack(arrays)
         self._sur._chk(self._entry("psm_solve_cases_begin")(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
         self._inflight = (cells, p)                     # keeps both arrays alive until the end call
@@ -397,5 +425,8 @@ class SolverEnsemble:
     def py_func(self, arrays):
         """One step of every case: list of cells [N_i,5] float64 -> list of p_i [N_i] float64."""
         cells, p = self._pack(arrays)
+        if self.step == "poisson":
+            self._sur._chk(self._sur.lib.psm_solve_cases_poisson(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
+            return self._split(p)
         self._sur._chk(self._entry("psm_solve_cases")(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
         return self._split(p)

@@ -776,6 +776,52 @@ class GridSurrogate:
         self._chk(self.lib.psm_solve_poisson_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_fields or None),
                                                     C.c_void_p(d_scalars or None), C.c_void_p(stream)))
 
+    # -- the same step for the case set of psm_set_geometry_cases (psm_solve_cases_poisson*): cells [sum N_i,5] -> p [sum N_i]
+    def bind_poisson_solve_cases(self, phi: float, max_abs_delta_p: float, weighting: bool = True, apply_filter: bool = True):
+        """``bind_poisson_solve`` on a case set of K meshes under the four-channel model, behind ``bind_features`` (the K SDF planes
+        in case order) and ``bind_poststeps``; no ``bind_frames``.  One state, one frame counter and one step counter for the set."""
+        self._chk(self.lib.psm_bind_poisson_solve_cases(self.h, float(phi), float(max_abs_delta_p), int(bool(weighting)), int(bool(apply_filter))))
+
+    def poisson_solve_push_cases(self, cells: np.ndarray):
+        """One frame of every case, concatenated in case order [sum N_i,5], from the host into the state."""
+        a = self._solver_cells(cells)
+        self._cases_count(a)
+        self._chk(self.lib.psm_poisson_solve_push_cases(self.h, _p(a, C.c_double)))
+
+    def solve_cases_poisson(self, cells: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Host buffers, synchronous: the cases' cells concatenated in case order [sum N_i,5] float64 -> p [sum N_i] float64, per case
+        what ``solve_poisson`` returns for a single mesh."""
+        a = self._solver_cells(cells)
+        if out is None:
+            out = np.empty(a.shape[0], np.float64)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
+            raise ValueError("out must be a contiguous float64 array [sum N_i]")
+        self._cases_count(a)
+        self._chk(self.lib.psm_solve_cases_poisson(self.h, _p(a, C.c_double), _p(out, C.c_double)))
+        return out
+
+    def _cases_count(self, a):
+        """The entries of a case set take no cell count, so the mirror checks it; without a case set the entry itself refuses."""
+        total = self._cases_total()
+        if total is not None and a.shape[0] != total:
+            raise ValueError(f"cells must hold the {total} cells of the case set")
+
+    def _cases_total(self):
+        """sum N_i of the case set (psm_mesh_cases), None without one."""
+        n = C.c_int32()
+        if self.lib.psm_mesh_cases(self.h, C.byref(n), None):
+            return None
+        off = (C.c_int64 * (n.value + 1))()
+        self._chk(self.lib.psm_mesh_cases(self.h, None, off))
+        return int(off[n.value])
+
+    def solve_cases_poisson_device(self, d_cells: int, d_p: int, d_fields: int = 0, d_scalars: int = 0, stream: int = 0):
+        """The same step on raw device pointers, asynchronous on ``stream``: ``d_cells`` [sum N_i,5] and ``d_p`` [sum N_i] float64;
+        ``d_fields`` [3,K,Ny*Nx] float32 receives (result, change, next) and ``d_scalars`` [K,8] float64 ``POISSON_SOLVE_SCALARS`` per
+        case (0: the handle's own buffers)."""
+        self._chk(self.lib.psm_solve_cases_poisson_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_fields or None),
+                                                          C.c_void_p(d_scalars or None), C.c_void_p(stream)))
+
     # -- the per-frame error blocks of assembled fields on the device: eight float64 sums per (frame, pair) instead of the fields
     RAW_SUMS = ("n", "s1", "s2", "tmin", "tmax", "pmin", "pmax", "tnan")
     METRICS = ("normVal", "biasNorm", "stdeNorm", "rmseNorm", "mean_err", "mean_sq_err")
