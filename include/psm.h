@@ -356,7 +356,10 @@ int psm_unpin_buffers(psm_handle* h);
  * the grid -> mesh tables of every case (PSM_ERR_ARG).  Also accepted: the four-channel Poisson model (c_in == 4, c_out == 1,
  * sdf_channel == 3), with maxs = (max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp) as psm_set_geometry reads them for that
  * model; such a set binds no geometry and serves psm_bind_poisson_solve_cases / psm_solve_cases_poisson* alone:
- * psm_solve_cases*, psm_solve_cases_delta* and psm_delta_prime_cases on it are PSM_ERR_UNSUPPORTED.  The K geometries are bound for this entry only (the scope
+ * psm_solve_cases*, psm_solve_cases_delta* and psm_delta_prime_cases on it are PSM_ERR_UNSUPPORTED.  And the gradP model
+ * (c_in == 3, c_out == 2), with maxs = (max_abs_Ux, max_abs_Uy, max_abs_dist, unused): such a set binds its K geometries and serves
+ * psm_bind_gradp_solve_cases / psm_solve_cases_gradp* alone, the three entries above are PSM_ERR_UNSUPPORTED on it too.
+ * The K geometries are bound for this entry only (the scope
  * psm_set_geometry gives its one; a configuration outside the bound path solves on the general path; PSM_NO_BIND=1 keeps
  * the general path); with n_cases == 1 the route -- and every bit of p -- is that of psm_solve.
  * A handle holds EITHER the single mesh of psm_set_geometry OR a case set: setting one drops the other, psm_solve* on a case
@@ -905,6 +908,60 @@ int psm_bind_poisson_solve_cases(psm_handle* h, double phi, double max_abs_delta
 int psm_poisson_solve_push_cases(psm_handle* h, const double* cells);                 /* [sum n_i, 5] */
 int psm_solve_cases_poisson(psm_handle* h, const double* cells, double* p_out);       /* [sum n_i, 5] -> [sum n_i] */
 int psm_solve_cases_poisson_device(psm_handle* h, const double* d_cells, double* d_p, float* d_fields, double* d_scalars, void* stream);
+
+/* ---- the gradient-model step at the solver boundary: cells [n,5] -> p [n] through U -> grad p -> p, no state -------------------
+ * The U_to_gradP model behind the contract of psm_solve, on a PSM_VARIANT_GRADP handle with c_in == 3, c_out == 2, sdf_channel == 2
+ * (psm_solve* itself keeps refusing c_out == 2).  cells = (Ux, Uy, Cx, Cy, p(t-1)) float64 in, p float64 out.  One step:
+ *   head   psm_solve's two launches as they are: U = max sqrt(Ux^2 + Uy^2), then mesh -> grid.  `maxs` of the geometry call is read
+ *          as (max_abs_Ux, max_abs_Uy, max_abs_dist, unused); the model's convention is normalise_sdf = 1, fill_input = 1
+ *          (Eval_dual_Dense_onlycil.py:447-451, :466), passed by the caller to psm_set_geometry* as for the delta step.
+ *   solve  the route psm_set_geometry* bound for the mesh, without a row scale: the gradient stays in the network's normalised units.
+ *   filter with apply_filter, the sigma_field filter of psm_bind_poststeps on both components, as in psm_gradp_frames_device.
+ *   integration  the two launches of psm_integrate_gradp_device on tables of the binding's own, built from the raw sdfunct given to
+ *          psm_set_geometry* (the handle keeps a float64 host copy) and the caller's cut, with the spacings
+ *          sx = dx * max_abs_dPdx / extent_x and sy = dy * max_abs_dPdy / extent_y (:537-538, the inverse of :441-442 and :467-468).
+ *          The integration is linear in (SdPx dx, SdPy dy), so the float32 plane q [ny][nx] it leaves is p / U^2.
+ *   tail   reference PSM_GRADP_REF_OUTLET: s = mean_y(3 q[y][nx-1] - q[y][nx-2]) / 3 (the outlet rule of python_module.py:472 /
+ *          SM_call.py:350 on the integrated plane; p = 0 at the outlet), in float64 over all ny rows, recomputed by every workgroup in
+ *          one fixed tree: no atomics, a step is bit-reproducible.  PSM_GRADP_REF_NONE: s = 0.0 exactly.  Per mesh cell n, every
+ *          operation rounded on its own: acc = sum_j ((double)q[cell_of_point[vtx[n][j]]] - s) * wts[n][j] for j = 0, 1, 2 in order,
+ *          p = acc * (U * U); p_out[n] = p, or cells[n][4] bit for bit where psm_solve falls back (near-wall cell, negative weight,
+ *          NaN acc: PM:494-496).  A NaN in q's last two columns makes s NaN: every cell then keeps its previous p.
+ * The whole step is one graph replay: two head launches, the solve, optionally two filter launches, two integration launches, one
+ * tail launch.  There is no state, no priming step and no skip rule: U enters as it does in psm_solve.
+ * psm_bind_gradp_solve: needs the gradP handle (PSM_ERR_UNSUPPORTED otherwise), the single mesh of psm_set_geometry (PSM_ERR_STATE; on
+ * a case set the message names psm_bind_gradp_solve_cases) with its grid -> mesh tables (PSM_ERR_ARG without them) and, with
+ * apply_filter, psm_bind_poststeps (PSM_ERR_STATE naming it); dx, dy, extent_x, extent_y and max_abs_grad = (max_abs_dPdx, max_abs_dPdy)
+ * finite and non-zero and a known `reference` (PSM_ERR_ARG); a cut the reference itself cannot process is PSM_ERR_UNSUPPORTED with the
+ * message of psm_bind_integration (a cut outside the grid: PSM_ERR_ARG).  All-or-nothing: it allocates the integration tables, the
+ * image, the gradient, the q plane and the scalar slots; after it a step allocates nothing.  Whatever drops the mesh, the plan, the
+ * model or, with apply_filter, the post-steps drops it.
+ * psm_solve_gradp: host buffers, synchronous: one H2D copy of cells and one D2H copy of p through the handle's pinned staging, or
+ * straight from / into ranges registered with psm_host_register.  One step in flight per handle across all step kinds.
+ * psm_solve_gradp_device: device pointers, asynchronous on `stream` (NULL: the handle's), copies nothing.  Optional outputs, any of
+ * them NULL: d_image [ny][nx][3] float32, the image that was solved; d_gradp [ny][nx][2] float32, the gradient behind the filter;
+ * d_pgrid [ny][nx] float32, q before the shift; d_scalars [8] float64 = U, U^2, s, sx, sy, 0, 0, 0 (NULL: the binding's slots).
+ * Alignment (8 bytes for cells, p, d_gradp and d_scalars, 4 for d_image and d_pgrid) is checked before anything is enqueued.
+ * Not provided: _begin / _end halves and the psm_pin_buffers direct routes.
+ * The `_cases` entries are the same step for the case set of psm_set_geometry_cases, which accepts the gradP model for them alone
+ * (psm_solve_cases* and the delta entries on such a set stay PSM_ERR_UNSUPPORTED): K meshes advanced by ONE graph replay, the case is
+ * launch dimension y of the mesh ends.  center_y / center_x [K] are the cuts in case order (an unprocessable one is named "case k: ");
+ * cells [sum n_i, 5], p [sum n_i], d_image [K][ny][nx][3], d_gradp [K][ny][nx][2], d_pgrid [K][ny][nx], d_scalars [K][8].  For case k
+ * every bit of p, q and s is what psm_solve_gradp gives on a handle holding that case's tables alone.  Each form's step entries
+ * refuse the other's binding by name (PSM_ERR_STATE); psm_unbind_gradp_solve serves whichever of the two is held. */
+#define PSM_GRADP_REF_NONE   0
+#define PSM_GRADP_REF_OUTLET 1
+int psm_bind_gradp_solve(psm_handle* h, int32_t center_y, int32_t center_x, double dx, double dy, double extent_x, double extent_y,
+                         const double* max_abs_grad /* [2]: dPdx, dPdy */, int32_t apply_filter, int32_t reference);
+int psm_bind_gradp_solve_cases(psm_handle* h, const int32_t* center_y, const int32_t* center_x, double dx, double dy, double extent_x,
+                               double extent_y, const double* max_abs_grad, int32_t apply_filter, int32_t reference);
+int psm_unbind_gradp_solve(psm_handle* h);
+int psm_solve_gradp(psm_handle* h, const double* cells, int64_t n, int32_t rank, double* p_out);
+int psm_solve_gradp_device(psm_handle* h, const double* d_cells, double* d_p, float* d_image, float* d_gradp, float* d_pgrid,
+                           double* d_scalars, void* stream);
+int psm_solve_cases_gradp(psm_handle* h, const double* cells, double* p_out);         /* [sum n_i, 5] -> [sum n_i] */
+int psm_solve_cases_gradp_device(psm_handle* h, const double* d_cells, double* d_p, float* d_image, float* d_gradp, float* d_pgrid,
+                                 double* d_scalars, void* stream);
 
 /* Dispatch-level time of EVERY kernel of the solve path: `steps` solves of d_grid through the launch sequence of
  * psm_solve_grid_device on the handle's stream, each dispatch stamped with its own begin / end by

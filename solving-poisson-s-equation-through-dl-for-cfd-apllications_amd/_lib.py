@@ -199,6 +199,13 @@ SIGNATURES = {
     "psm_poisson_solve_push_cases": (C.c_int, [_hp, _f64p]),
     "psm_solve_cases_poisson": (C.c_int, [_hp, _f64p, _f64p]),
     "psm_solve_cases_poisson_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_bind_gradp_solve": (C.c_int, [_hp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, _f64p, C.c_int32, C.c_int32]),
+    "psm_bind_gradp_solve_cases": (C.c_int, [_hp, _i32p, _i32p, C.c_double, C.c_double, C.c_double, C.c_double, _f64p, C.c_int32, C.c_int32]),
+    "psm_unbind_gradp_solve": (C.c_int, [_hp]),
+    "psm_solve_gradp": (C.c_int, [_hp, _f64p, C.c_int64, C.c_int32, _f64p]),
+    "psm_solve_gradp_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_solve_cases_gradp": (C.c_int, [_hp, _f64p, _f64p]),
+    "psm_solve_cases_gradp_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
     "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),

@@ -134,6 +134,7 @@ int psm_bind_poststeps(psm_handle* h, const double* sigma_field, const double* s
   HIPCHK(h, hipStreamSynchronize(h->stream));           // post-steps in flight read the tables that are replaced,
   drop_post_graphs(h);                                  // and the captured solve + post-step graphs hold their addresses
   poisson_solve_free(h);                                // psm_bind_poisson_solve stands on this binding
+  if (h->gsolve.apply_filter) gradp_solve_free(h);      // and so does psm_bind_gradp_solve* with apply_filter
   psm_gauss_init();
   PostSet& s = h->post;
   post_free(s);
@@ -162,7 +163,7 @@ int psm_bind_poststeps(psm_handle* h, const double* sigma_field, const double* s
 
 
 int psm_unbind_poststeps(psm_handle* h) {
-  return unbind(h, [h] { drop_post_graphs(h); poisson_solve_free(h); post_free(h->post); });
+  return unbind(h, [h] { drop_post_graphs(h); poisson_solve_free(h); if (h->gsolve.apply_filter) gradp_solve_free(h); post_free(h->post); });
 }
 
 

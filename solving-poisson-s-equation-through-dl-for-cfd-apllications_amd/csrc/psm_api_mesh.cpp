@@ -56,6 +56,7 @@ int mesh_buffers_alloc(psm_handle* h, MeshBuffers& b, size_t total_cells, size_t
 void mesh_buffers_free(MeshBuffers& b) {
   mesh_tables_free(b.t);
   dev_free(b.d_cells); dev_free(b.d_p); dev_free(b.d_umax); dev_free(b.d_umax_part);
+  b.h_sdf.clear();
   if (b.h_cells) { (void)hipHostFree(b.h_cells); b.h_cells = nullptr; }
   if (b.h_p) { (void)hipHostFree(b.h_p); b.h_p = nullptr; }
 }
@@ -81,7 +82,7 @@ int cases_check(psm_handle* h) {
     return fail(h, PSM_ERR_STATE, "the handle holds the single mesh of psm_set_geometry: psm_solve_cases* needs a case set (psm_set_geometry_cases)");
   if (!h->mcs.ready || !h->planned)
     return fail(h, PSM_ERR_STATE, "psm_set_geometry_cases has not been called (or its case set was dropped by a later psm_set_* / psm_plan_grid)");
-  // a case set under the four-channel model serves psm_solve_cases_poisson* alone
+  // a case set under the four-channel model serves psm_solve_cases_poisson* alone, one under the gradP model psm_solve_cases_gradp*
   if (h->cfg.c_in != 3 || h->cfg.c_out != 1) return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292)");
   return PSM_OK;
 }
@@ -156,6 +157,7 @@ int psm_set_geometry(psm_handle* h, int64_t n_cells, int32_t ny, int32_t nx, con
   // all-or-nothing from here on: a failure leaves no geometry
   if ((rc = mesh_tables_upload(h, m.t, t)) || (rc = mesh_buffers_alloc(h, m, (size_t)n_cells, 1, 256, PSM_ERR_HIP, "mesh staging"))) { free_geometry(h); return rc; }
   h->n_cells = n_cells;
+  m.h_sdf = t.sdf;                                         // the raw sdfunct, for psm_bind_gradp_solve
   for (int k = 0; k < 4; ++k) h->maxs[k] = maxs[k];
   h->normalise_sdf = normalise_sdf; h->fill_input = fill_input;
   h->have_g2m = t.have_g2m;
@@ -361,10 +363,12 @@ int psm_set_geometry_cases(psm_handle* h, int32_t n_cases, const int64_t* n_cell
   if (!n_cells || !vtx_m2g || !wts_m2g || !indices || !sdfunct || !vtx_g2m || !wts_g2m || !maxs) return fail(h, PSM_ERR_ARG, "null geometry table");
   if (n_cases < 1 || n_cases > h->cfg.max_cases) return fail(h, PSM_ERR_ARG, "n_cases outside [1, max_cases]");
   // the three-channel models of psm_solve_cases*, or the four-channel Poisson model, whose set serves psm_solve_cases_poisson* alone
-  // (maxs: max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp, as the single mesh reads them for that model)
+  // (maxs: max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp, as the single mesh reads them for that model), or the gradP model
+  // (c_in == 3, c_out == 2; maxs: max_abs_Ux, max_abs_Uy, max_abs_dist, unused), whose set serves psm_solve_cases_gradp* alone
   const bool poisson_model = h->cfg.c_in == 4 && h->cfg.c_out == 1 && h->cfg.sdf_channel == 3;
-  if (!poisson_model && (h->cfg.c_in != 3 || h->cfg.c_out != 1))
-    return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292), or the Poisson model's c_in == 4, c_out == 1, sdf_channel == 3");
+  const bool gradp_model = h->cfg.c_in == 3 && h->cfg.c_out == 2;
+  if (!poisson_model && !gradp_model && (h->cfg.c_in != 3 || h->cfg.c_out != 1))
+    return fail(h, PSM_ERR_UNSUPPORTED, "the mesh entry needs c_in == 3 and c_out == 1 (python_module.py:288-292), the Poisson model's c_in == 4, c_out == 1, sdf_channel == 3, or the gradP model's c_in == 3, c_out == 2");
   if (ny < 1 || nx < 1) return fail(h, PSM_ERR_ARG, "bad grid shape");
   // everything that needs no device first: a bad table leaves the handle as it was
   std::vector<PsmMeshCaseInput> in(n_cases);
@@ -391,6 +395,7 @@ int psm_set_geometry_cases(psm_handle* h, int32_t n_cases, const int64_t* n_cell
   a.vtx_g2m = m.t.vtx_g2m; a.wts_g2m = m.t.wts_g2m; a.cell_of_point = m.t.cell_of_point; a.field = h->d_fields_stage;
   a.near_wall = m.t.near_wall; a.max_cells = t.max_cells; a.max_abs_p = maxs[3]; a.c_out = h->cfg.c_out;
   m.off = t.cell_off; m.n_cases = n_cases;
+  m.h_sdf = t.sdf;                                          // the K raw sdfuncts, for psm_bind_gradp_solve_cases
   // The entry builds its K images from THESE sdfuncts at every step: bind the K geometries for psm_solve_cases* only (scope 1,
   // like psm_set_geometry binds its one; a single case takes the single-case binding and with it the route of psm_solve).
   if (h->cfg.sdf_channel == 2 && getenv("PSM_NO_BIND") == nullptr) {

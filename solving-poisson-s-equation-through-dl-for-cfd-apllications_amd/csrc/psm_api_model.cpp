@@ -125,6 +125,7 @@ void free_plan(psm_handle* h) {
   post_free(h->post);                   // and so is psm_bind_poststeps
   feat_free(h->feat);                   // and psm_bind_features
   frames_free(h);                       // psm_bind_frames belongs to the mesh that went with the plan
+  gradp_solve_free(h);                  // and so does psm_bind_gradp_solve*, sized by this plan's grid
 }
 
 
@@ -180,6 +181,7 @@ void unpin_buffers(psm_handle* h) {
 void mesh_cases_free(psm_handle* h) {
   MeshCaseSet& m = h->mcs;
   if (h->psolve.cases) poisson_solve_free(h);   // psm_bind_poisson_solve_cases stands on this set's tables and cell ranges
+  if (h->gsolve.cases) gradp_solve_free(h);     // and so does psm_bind_gradp_solve_cases
   mesh_buffers_free(m);
   m.ready = false; m.inflight = false; m.n_cases = 0; m.off.clear();
   delta_drop(h);                        // U(t-1) of the delta step belongs to the cells that go here
@@ -190,6 +192,7 @@ void free_geometry(psm_handle* h) {
   unpin_buffers(h);
   mesh_cases_free(h);
   frames_free(h);                       // the frame batch reads this mesh's tables
+  gradp_solve_free(h);                  // psm_bind_gradp_solve* reads them and the mesh's sdfunct
   mesh_buffers_free(h->mesh);
   integ_free(h->integ_host); integ_free(h->integ_dev);
   h->have_geometry = false;
@@ -367,6 +370,7 @@ int psm_set_pca(psm_handle* h, const double* comp_in, const double* mean_in, con
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
+  h->gsolve.ready = false;               // and psm_bind_gradp_solve*
   std::vector<float> mi(h->K_in), mo(h->K_out);
   for (int k = 0; k < h->K_in; ++k) mi[k] = (float)mean_in[k];
   for (int k = 0; k < h->K_out; ++k) mo[k] = (float)mean_out[k];
@@ -437,6 +441,7 @@ int psm_set_dense(psm_handle* h, int32_t layer, int32_t n_in, int32_t n_out, con
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
+  h->gsolve.ready = false;               // and psm_bind_gradp_solve*
   DenseLayer& d = h->dense[layer];
   d.linear = false;                                     // psm_set_attention sets it again after this call
   if (d.ln && (d.n_out != n_out || (d.ln_residual && n_in != n_out))) {      // a LayerNormalization of another width, or its residual x + input on a
@@ -529,6 +534,7 @@ int psm_set_layernorm(psm_handle* h, int32_t layer, int32_t n, const float* gamm
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
+  h->gsolve.ready = false;               // and psm_bind_gradp_solve*
   // zero-padded to whole 16-byte pieces past the consumer's leading dimension: a Dense launch that applies this normalisation to
   // its input (launch_all) reads gamma / beta with the clamped column index of its operand loads
   std::vector<float> g(round_up(n, 32) + 32, 0.f), b(round_up(n, 32) + 32, 0.f);
@@ -562,6 +568,7 @@ int psm_set_conv1d(psm_handle* h, int32_t layer, int32_t n_layers, int32_t kerne
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
+  h->gsolve.ready = false;               // and psm_bind_gradp_solve*
   if (!same_stack) {
     for (auto& c : h->conv1d) { dev_free(c.W); dev_free(c.b); }
     h->conv1d.assign(n_layers, Conv1dLayer{});
@@ -593,6 +600,7 @@ int psm_set_scaler(psm_handle* h, const double* in_a, const double* in_b, const 
   h->mcs.ready = false;                  // and the case set of psm_set_geometry_cases (its binding is gone)
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
+  h->gsolve.ready = false;               // and psm_bind_gradp_solve*
   std::vector<float> ia(h->ld_in, 0.f), ib(h->ld_in, 0.f), sa(h->ld_out, 0.f), sb(h->ld_out, 0.f);
   // x_in = coeff*ia + ib ; res' = res*sa + sb  (affine forms of SMD:505-539, evaluated in f64 here)
   for (int p = 0; p < h->cfg.p_in; ++p) {

@@ -68,18 +68,20 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
   if (!st) st = h->stream;
   const float* d_scale = nullptr;
   if ((rc = ensure_encode_aux(h, n_cases))) return rc;
-  const bool rows = step.rows.rows, psolve = step.psolve.cells;
+  const bool rows = step.rows.rows, psolve = step.psolve.cells, gsolve = step.gsolve.cells;
   if (step.rows.scaled() || psolve) d_scale = h->ws0.d_row_scale;   // the finish launch of the rows stage / the mesh -> grid launch of the Poisson solver step writes it, inside the sequence
   else if ((rc = prepare_scale(h, h->ws0, out_scale, n_cases, st, &d_scale))) return rc;
   const bool frames = step.frames.cols, feat = step.feat.vel, deltas = step.deltas.planes, gradp = step.gradp.planes, chapter4 = step.chapter4.planes, post = step.post.apply_filter >= 0;
   h->last_cases = gradp || chapter4 ? 1 : n_cases;  // gradp, chapter4: ws0 holds the last frame's single-case solve
   // psolve: the two head launches of the Poisson solver step in front of the features and its tail launch behind the post-steps;
+  // gsolve: psm_solve's two head launches in front of the solve; behind the filter (if any) the two integration launches and the tail launch;
   // the two rows launches (rows), the mesh -> grid launch (frames), the two feature launches (feat) or the image pack (deltas, gradp, chapter4), the solve, then the two integration launches (p) or the
   // post-steps' (at most four); gradp: the filter among the post-steps and BEHIND it the integration with the gradp binding's tables: one linear chain
   auto sequence = [&](hipStream_t on, hipEvent_t* ev) {
     int rs = rows ? rows_device(h, step.rows, n_cases, on) : PSM_OK;
     if (!rs && frames) rs = frames_device(h, step.frames, n_cases, on);
     if (!rs && psolve) rs = poisson_solve_head(h, step.psolve, on);
+    if (!rs && gsolve) rs = gradp_solve_head(h, step.gsolve, on);
     if (!rs && feat) rs = features_device(h, step.feat.vel, n_cases, step.feat.grid, on);
     if (!rs && deltas) rs = deltas_pack_device(h, step.deltas, n_cases, on);
     if (!rs && gradp) rs = gradp_pack_device(h, step.gradp, n_cases, on);
@@ -105,6 +107,7 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
     if (!rs && post) rs = poststeps_device(h, d_fields, n_cases, step.post, on);
     if (!rs && gradp) rs = integrate_device(h, h->gradp.integ, post ? step.post.result : d_fields, n_cases, step.gradp.p, on);
     if (!rs && psolve) rs = poisson_solve_tail(h, step.psolve, step.post, on);
+    if (!rs && gsolve) rs = gradp_solve_tail(h, step.gsolve, on);
     return rs;
   };
   if (prof || h->timed_kernel >= 0 || !h->use_graph) return sequence(st, prof);

@@ -1,5 +1,5 @@
 // psm_handle.h -- INTERNAL to libpsm_hip.so: the handle behind include/psm.h and the helpers its translation units share.
-// The C-ABI is implemented in nineteen files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
+// The C-ABI is implemented in twenty files along the seams of the path (nothing here is exported: namespace psm_impl is hidden):
 //   psm_api_model.cpp       psm_create / psm_destroy, model artefacts (PCA bases, scaler, Dense / Conv1D / attention / LayerNorm), packing
 //   psm_api_plan.cpp        psm_plan_grid (block layout, workspaces), psm_bind_geometry* (bound-geometry tables, closed-form chain)
 //   psm_api_solve.cpp       one solve: its route (choose_route), launch sequence (launch_all, a function per stage), argument builders, psm_solve_grid*
@@ -18,6 +18,7 @@
 //   psm_api_chapter4_frames.cpp  the Chapter-4 evaluators' frame batch on the device: psm_bind_chapter4_frames, the image / label pack psm_chapter4_image_device and the step psm_chapter4_frames* (columns -> p -> errors)
 //   psm_api_rows.cpp        a frame's dataset rows -> scalars + columns on the device: psm_bind_rows, the stage alone psm_rows_prepare_device and the evaluators' steps behind it, psm_deltas_rows* / psm_poisson_rows* / psm_gradp_rows*
 //   psm_api_poisson_solve.cpp  the Poisson-model step at the solver boundary (cells -> p, two-frame state on the device): psm_bind_poisson_solve, psm_poisson_solve_push / _reset / _state, psm_solve_poisson*; for a case set psm_bind_poisson_solve_cases, psm_poisson_solve_push_cases, psm_solve_cases_poisson*
+//   psm_api_gradp_solve.cpp  the gradient-model step at the solver boundary (cells -> p through solve, integration and the outlet level, no state): psm_bind_gradp_solve, psm_solve_gradp*; for a case set psm_bind_gradp_solve_cases, psm_solve_cases_gradp*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
@@ -215,6 +216,22 @@ struct PoissonSolveCall {
   auto tie() const { return std::tie(cells, p, scalars, weighting, prime, frames, cases); }
 };
 
+// The mesh ends of the gradient-model step at the solver boundary (psm_solve_gradp*): psm_solve's two head launches in front of the
+// solve and, behind the optional filter, the two integration launches on the binding's own tables and the tail launch (grid -> mesh
+// of q = p / U^2 with the outlet level).  Every member is held by the captured launches; the tables, the scalar slots and the planes
+// are the binding's (GradpSolveSet) and the mesh's, which drop these graphs when they go.
+struct GradpSolveCall {
+  const double* cells = nullptr;        // [N,5]; nullptr: no such stage
+  double* p = nullptr;                  // [N]
+  float* image = nullptr;               // [K][npix][3] the image the head writes and the solve reads
+  float* gradp = nullptr;               // [K][npix][2] the gradient behind the filter: what the integration reads
+  float* q = nullptr;                   // [K][npix] the integrated plane
+  double* scalars = nullptr;            // [K][8]
+  int apply_filter = 0;
+  int cases = 0;                        // 0: the single mesh; K: the case set's form (psm_solve_cases_gradp*)
+  auto tie() const { return std::tie(cells, p, image, gradp, q, scalars, apply_filter, cases); }
+};
+
 // What surrounds ONE solve (solve_device, psm_api_step.cpp), in launch order; every stage keeps its own "absent" value.  A new stage
 // is one member here and one entry in key(): the graph cache compares nothing else, so a stage in the sequence is in the cache key.
 struct StepCall {
@@ -227,12 +244,17 @@ struct StepCall {
   float* p = nullptr;                   // psm_solve_pressure*: where the bound integration (psm_bind_integration) behind the solve writes p
   PostCall post{};                      // psm_solve_poststeps*: the bound post-steps behind the solve (apply_filter == -1: none)
   PoissonSolveCall psolve{};            // psm_solve_poisson*: the head in front of the features, the tail behind the post-steps (cells == nullptr: none)
-  auto key() const { return std::make_tuple(rows.tie(), frames.key(), feat.tie(), deltas.tie(), gradp.tie(), chapter4.tie(), p, post.tie(), psolve.tie()); }
+  GradpSolveCall gsolve{};              // psm_solve_gradp*: psm_solve's head in front of the solve; behind it (and the filter) the integration and the tail (cells == nullptr: none)
+  auto key() const { return std::make_tuple(rows.tie(), frames.key(), feat.tie(), deltas.tie(), gradp.tie(), chapter4.tie(), p, post.tie(), psolve.tie(), gsolve.tie()); }
   const char* fault() const {           // the combinations the sequence does not define (null: defined); no C entry builds one
     const bool fr = frames.cols, ft = feat.vel, dl = deltas.planes, gp = gradp.planes, c4 = chapter4.planes;
     if (psolve.cells && (!ft || post.apply_filter < 0)) return "the Poisson solver step is the features, the solve and the post-steps between its mesh ends: it needs all three";
     if (psolve.cells && (rows.rows || fr || dl || gp || c4 || p)) return "the Poisson solver step writes the feature planes itself: no rows, frames, pack or integration stage beside it";
     if (psolve.cells && psolve.prime) return "a priming step of the Poisson solver step is one plain launch, not a sequence";
+    if (gsolve.cells && (!gsolve.p || !gsolve.image || !gsolve.gradp || !gsolve.q || !gsolve.scalars)) return "the gradient solver step needs the gradP handle's image, gradient, plane and scalar slots";
+    if (gsolve.cells && (rows.rows || fr || ft || dl || gp || c4 || p || psolve.cells)) return "the gradient solver step writes its image and integrates itself: no rows, frames, features, pack, integration or Poisson stage beside it";
+    if (gsolve.cells && (post.apply_filter >= 0) != (gsolve.apply_filter != 0)) return "the gradient solver step has the filter among the post-steps or no post-steps at all";
+    if (gsolve.cells && post.dU) return "the gradient solver step has no weighting: filter only";
     if (rows.rows && (!fr || rows.cols != frames.cols)) return "the rows stage writes the columns the mesh -> grid stage reads: it needs frames on its columns";
     if (dl && gp) return "the deltas and the gradP pack exclude each other";
     if (c4 && dl) return "the Chapter-4 and the deltas pack exclude each other";
@@ -298,6 +320,7 @@ struct MeshBuffers {
   MeshTablesDev t;
   double *d_cells = nullptr, *d_p = nullptr, *d_umax = nullptr, *d_umax_part = nullptr;   // staged cells, p, U_max (one per case), partial maxima
   double *h_cells = nullptr, *h_p = nullptr;   // pinned staging of the host entries
+  std::vector<double> h_sdf;            // [K][npix] the raw sdfunct as given to psm_set_geometry*: psm_bind_gradp_solve* builds its integration tables from it
   bool inflight = false;                // a *_begin is enqueued, its *_end not yet called
   double* copy_out = nullptr;           // where *_end copies p to (null: it was DMA'd / stored into the caller's registered array)
 };
@@ -385,6 +408,20 @@ struct PoissonSolveSet {
   double* d_scalars = nullptr;          // [PSM_POISSON_SCALARS] ([K] of them for a case set)
   int frames = 0;                       // frames held: 0, 1 or 2
   int64_t steps = 0;                    // steps taken since the state was last empty (a priming step does not count)
+};
+
+// Binding of the gradient-model step at the solver boundary (psm_bind_gradp_solve on the single mesh, psm_bind_gradp_solve_cases on
+// a case set): integration tables of its own from the mesh's raw sdfunct and the caller's cut(s) (integ: K case slots; integ.d_gradp
+// and integ.d_p are the step's gradient and q), the image, the field in front of the filter and the scalar slots, so that a step
+// allocates nothing.  No state: a step depends on its cells alone.
+struct GradpSolveSet {
+  bool ready = false;
+  int cases = 0;                        // 0: bound on the single mesh; K: bound on a case set of K cases
+  int apply_filter = 0, reference = 0;
+  double sx = 1.0, sy = 1.0;            // dx * max_abs_dPdx / extent_x, dy * max_abs_dPdy / extent_y
+  IntegSet integ;
+  float* d_image = nullptr;             // [K][npix][3]
+  double* d_scalars = nullptr;          // [K][PSM_GRADP_SCALARS]
 };
 
 // Binding of the rows stage (psm_bind_rows, behind psm_bind_frames): staging for the bound frame count x mesh cells x width float32
@@ -498,6 +535,7 @@ struct psm_handle {
   FrameSet frames;                      // frame batch on the single mesh (psm_bind_frames)
   RowsSet rows;                         // the rows stage's staging behind it (psm_bind_rows)
   PoissonSolveSet psolve;               // the Poisson-model step at the solver boundary behind features, post-steps and frames (psm_bind_poisson_solve) or behind features and post-steps on a case set (psm_bind_poisson_solve_cases)
+  GradpSolveSet gsolve;                 // the gradient-model step at the solver boundary on the mesh or the case set (psm_bind_gradp_solve*)
   DeltasSet deltas;                     // the deltas evaluator's frame batch behind it (psm_bind_deltas_frames)
   GradpSet gradp;                       // the U_to_gradP evaluator's frame batch behind it (psm_bind_gradp_frames)
   Chapter4Set chapter4;                 // the Chapter-4 evaluators' frame batch behind it (psm_bind_chapter4_frames)
@@ -653,6 +691,10 @@ void poisson_solve_free(psm_handle* h);   // whatever drops the feature, post-st
 // the two head launches / the tail launch of a Poisson solver step on `st` (the tail's field: next with the weighting, else result)
 int poisson_solve_head(psm_handle* h, const PoissonSolveCall& ps, hipStream_t st);
 int poisson_solve_tail(psm_handle* h, const PoissonSolveCall& ps, const PostCall& pc, hipStream_t st);
+void gradp_solve_free(psm_handle* h);     // whatever drops the mesh or the case set, the plan, the model or (with apply_filter) the post-steps drops this one (psm_api_gradp_solve.cpp)
+// the two head launches / the integration and the tail launch of a gradient solver step on `st`
+int gradp_solve_head(psm_handle* h, const GradpSolveCall& gs, hipStream_t st);
+int gradp_solve_tail(psm_handle* h, const GradpSolveCall& gs, hipStream_t st);
 int rows_device(psm_handle* h, const RowsCall& rc, int n_frames, hipStream_t st);
 int frames_state(psm_handle* h);
 int frames_count_check(psm_handle* h, int n_frames);

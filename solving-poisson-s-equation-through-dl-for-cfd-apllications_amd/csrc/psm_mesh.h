@@ -162,6 +162,49 @@ hipError_t psm_launch_poisson_partial_cases(const PsmPoissonCasesArgs& a, hipStr
 hipError_t psm_launch_poisson_to_grid_cases(const PsmPoissonCasesArgs& a, hipStream_t st);
 hipError_t psm_launch_poisson_to_mesh_cases(const PsmPoissonCasesArgs& a, hipStream_t st);
 
+// ---- the tail of the gradient-model step at the solver boundary (psm_solve_gradp*, U_to_gradP): grid -> mesh of the integrated
+// plane q = p / U^2 [ny][nx] float32 behind the two launches of psm_integ.hip.  The head of that step is psm_solve's own (partial
+// maxima, psm_to_grid_kernel), whose U_max the tail reads from the device scalar.  OUTLET: every workgroup first takes the level
+// s = mean_y(3 q[y][nx-1] - q[y][nx-2]) / 3 in float64 over all ny rows (python_module.py:472 on the integrated plane) by one fixed
+// tree, so every workgroup holds the same bits; NONE: s = 0.0 and nothing is read for it.  Then per mesh cell
+// acc = sum_j ((double)q[cell_of_point[vtx[n][j]]] - s) * wts[n][j], p = acc * (U * U), and cells[n][4] where psm_to_mesh_kernel
+// falls back (near-wall cell, negative weight, NaN).  Every operation rounds on its own (`fp contract(off)`).
+constexpr int PSM_GRADP_LEVEL_NONE = 0, PSM_GRADP_LEVEL_OUTLET = 1;   // PSM_GRADP_REF_* of psm.h
+constexpr int PSM_GRADP_SCALARS = 8;       // U, U^2, s, sx, sy, 0, 0, 0
+struct PsmGradpMeshArgs {
+  const double* cells;          // [N,5]
+  const double* umax;           // device scalar: U_max as the head's mesh -> grid launch left it
+  const int32_t* vtx;           // [N,3] grid->mesh simplices
+  const double* wts;            // [N,3]
+  const int32_t* cell_of_point; // [n_grid]
+  const float* q;               // [ny][nx] the integrated plane
+  const uint8_t* near_wall;     // [N]
+  double* p_out;                // [N]
+  int64_t n_cells;
+  int ny, nx, reference;
+  double* scalars;              // [PSM_GRADP_SCALARS], stored by workgroup 0
+  double sx, sy;                // the integration's spacings, recorded in the scalars only
+};
+hipError_t psm_launch_gradp_to_mesh(const PsmGradpMeshArgs& a, hipStream_t st);
+// The same launch for a case set: the case is launch dimension y; cell-side arrays concatenated, grid-side [K][n_grid], scalars [K][8].
+struct PsmGradpCasesArgs {
+  const double* cells;          // [sum n_i, 5]
+  const int64_t* cell_off;      // [K + 1]
+  const double* umax;           // [K]
+  int n_cases;
+  int64_t max_cells;            // largest n_i: sizes launch dimension x
+  const int32_t* vtx_g2m;       // [sum n_i, 3]
+  const double* wts_g2m;        // [sum n_i, 3]
+  const int32_t* cell_of_point; // [K][n_grid]
+  const float* q;               // [K][ny][nx]
+  const uint8_t* near_wall;     // [sum n_i]
+  double* p_out;                // [sum n_i]
+  int ny, nx, reference;
+  double* scalars;              // [K][PSM_GRADP_SCALARS]
+  double sx, sy;
+};
+hipError_t psm_launch_gradp_to_mesh_cases(const PsmGradpCasesArgs& a, hipStream_t st);
+
 // ---- the mesh ends for a case batch (psm_set_geometry_cases): K meshes on one planned grid, the case is launch dimension y.
 // Cell-side arrays are the cases' concatenated ([sum n_i, ...], case i at rows cell_off[i] .. cell_off[i + 1]), grid-side tables
 // are [K][n_grid, ...]; vertex indices are case-local as the caller gave them (the kernels add the case's offset).

@@ -10,6 +10,8 @@
 //   both ends also in DELTA form (psm_solve_delta*): U - U(t-1) in, p(t-1) + dp out, U(t-1) := U   [SMD:389-391]
 //   and as the ends of the Poisson-model step (psm_solve_poisson*, at the end of this file): six columns from cells + a two-frame
 //   state in, p(t-1) + dp out, the state turned over; for a case set too (psm_solve_cases_poisson*)  [SMP:549-556, 842-847]
+//   and the tail of the gradient-model step (psm_solve_gradp*, at the end of this file): the outlet level of the integrated plane,
+//   grid -> mesh, p = acc U^2; for a case set too (psm_solve_cases_gradp*)                          [PM:472, 481-496; UGP:537-538]
 //
 // All of them are HBM-bound gathers; interpolation is done in float64 like the reference.
 #include "psm_mesh.h"
@@ -691,5 +693,90 @@ hipError_t psm_launch_poisson_to_grid_cases(const PsmPoissonCasesArgs& a, hipStr
 hipError_t psm_launch_poisson_to_mesh_cases(const PsmPoissonCasesArgs& a, hipStream_t st) {
   if (!poisson_cases_ok(a) || a.max_cells < 1 || !a.p_out || (!a.prime && !a.field)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(static_cast<PsmPoissonCasesKernel>(psm_to_mesh_kernel), dim3((unsigned)((a.max_cells + 255) / 256), (unsigned)a.n_cases), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The tail of the gradient-model step at the solver boundary (psm_solve_gradp*, PsmGradpMeshArgs in psm_mesh.h): grid -> mesh of the
+// integrated plane q = p / U^2, an overload of the kernels of the same purpose above.  Float64, rounded operation by operation
+// (`fp contract(off)`), so that NumPy restates a cell's p bit for bit.
+
+// s = mean_y(3 q[y][nx-1] - q[y][nx-2]) / 3 over all ny rows (PM:472 on the integrated plane), by every thread of a 256-thread
+// workgroup: rows tid, tid + 256, ... in order, wave fold, LDS fold in one fixed tree -- the chain idiom of psm_integ_cols_kernel.
+// The 2 ny floats come out of L2; no atomics, so every workgroup of every run holds the same bits.
+__device__ __forceinline__ double gradp_outlet_level(const float* q, int ny, int nx) {
+#pragma clang fp contract(off)
+  __shared__ double lvl_s[4];
+  double t = 0.0;
+  for (int y = threadIdx.x; y < ny; y += 256) {
+    const float* r = q + (int64_t)y * nx + (nx - 2);
+    const double last = (double)r[1], before = (double)r[0];
+    const double three = 3.0 * last;
+    t = t + (three - before);
+  }
+  for (int o = 32; o > 0; o >>= 1) t = t + __shfl_down(t, o, 64);
+  if ((threadIdx.x & 63) == 0) lvl_s[threadIdx.x >> 6] = t;
+  __syncthreads();
+  const double sum = (lvl_s[0] + lvl_s[1]) + (lvl_s[2] + lvl_s[3]);
+  return (sum / (double)ny) / 3.0;
+}
+
+// One body, called by the single-mesh kernel and by the case-set kernel alike.  A workgroup beyond the mesh's end (a shorter case of
+// a set) returns as a whole, in front of the barrier of the level; workgroup 0 stores the scalars.
+__device__ __forceinline__ void gradp_to_mesh(PsmGradpMeshArgs a) {
+#pragma clang fp contract(off)
+  if ((int64_t)blockIdx.x * 256 >= a.n_cells) return;                // uniform per workgroup
+  const double s = a.reference == PSM_GRADP_LEVEL_OUTLET ? gradp_outlet_level(a.q, a.ny, a.nx) : 0.0;
+  const double U = *a.umax;
+  const double U2 = U * U;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    double* o = a.scalars;
+    o[0] = U; o[1] = U2; o[2] = s; o[3] = a.sx; o[4] = a.sy; o[5] = 0.0; o[6] = 0.0; o[7] = 0.0;
+  }
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n >= a.n_cells) return;
+  const int32_t* v = a.vtx + n * 3;
+  const double* w = a.wts + n * 3;
+  double acc = 0.0;
+  bool neg = false;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double d = (double)a.q[a.cell_of_point[v[j]]] - s;         // p_adim_unif = (q - s)[indices]  (PM:481)
+    const double t = d * w[j];
+    acc = acc + t;
+    neg = neg || (w[j] < 0.0);
+  }
+  double p = acc * U2;                                               // PM:490 with max_abs_p = 1
+  const double prev = a.cells[n * 5 + 4];
+  if (a.near_wall[n] || neg || acc != acc) p = prev;                 // PM:494, 496 (interpolate_fill -> NaN)
+  a.p_out[n] = p;
+}
+__device__ __forceinline__ PsmGradpMeshArgs case_gradp_mesh(const PsmGradpCasesArgs& a, int cs) {
+  const int64_t c0 = a.cell_off[cs], g0 = (int64_t)cs * a.ny * a.nx;
+  PsmGradpMeshArgs m{};
+  m.cells = a.cells + c0 * 5; m.umax = a.umax + cs; m.vtx = a.vtx_g2m + c0 * 3; m.wts = a.wts_g2m + c0 * 3; m.cell_of_point = a.cell_of_point + g0;
+  m.q = a.q + g0; m.near_wall = a.near_wall + c0; m.p_out = a.p_out + c0; m.n_cells = a.cell_off[cs + 1] - c0;
+  m.ny = a.ny; m.nx = a.nx; m.reference = a.reference;
+  m.scalars = a.scalars + (int64_t)cs * PSM_GRADP_SCALARS; m.sx = a.sx; m.sy = a.sy;
+  return m;
+}
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmGradpMeshArgs a) { gradp_to_mesh(a); }
+// the case is launch dimension y, x covers the largest case (as to_mesh_case)
+__global__ __launch_bounds__(256) void psm_to_mesh_kernel(PsmGradpCasesArgs a) { gradp_to_mesh(case_gradp_mesh(a, blockIdx.y)); }
+
+static bool gradp_level_ok(int reference, int ny, int nx) {
+  return (reference == PSM_GRADP_LEVEL_NONE || reference == PSM_GRADP_LEVEL_OUTLET) && ny >= 1 && nx >= 2;
+}
+hipError_t psm_launch_gradp_to_mesh(const PsmGradpMeshArgs& a, hipStream_t st) {
+  if (a.n_cells < 1 || !a.cells || !a.umax || !a.vtx || !a.wts || !a.cell_of_point || !a.q || !a.near_wall || !a.p_out || !a.scalars ||
+      !gradp_level_ok(a.reference, a.ny, a.nx)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmGradpMeshArgs)>(psm_to_mesh_kernel), dim3((unsigned)((a.n_cells + 255) / 256)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+hipError_t psm_launch_gradp_to_mesh_cases(const PsmGradpCasesArgs& a, hipStream_t st) {
+  if (a.n_cases < 1 || a.max_cells < 1 || !a.cells || !a.cell_off || !a.umax || !a.vtx_g2m || !a.wts_g2m || !a.cell_of_point || !a.q || !a.near_wall ||
+      !a.p_out || !a.scalars || !gradp_level_ok(a.reference, a.ny, a.nx)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(static_cast<void (*)(PsmGradpCasesArgs)>(psm_to_mesh_kernel), dim3((unsigned)((a.max_cells + 255) / 256), (unsigned)a.n_cases), dim3(256), 0,
+                     st, a);
   return hipGetLastError();
 }

@@ -12,12 +12,12 @@ from .surrogate import GridSurrogate, _f64, _p
 from .synthetic import SurrogateModel
 
 STEPS = ("absolute", "delta")
-MODULE_STEPS = STEPS + ("poisson",)      # the Poisson-model step: psm_solve_poisson (SolverModule), psm_solve_cases_poisson (SolverEnsemble)
+MODULE_STEPS = STEPS + ("poisson", "gradp")   # the Poisson-model step: psm_solve_poisson (SolverModule), psm_solve_cases_poisson (SolverEnsemble); the gradient-model step: psm_solve_gradp / psm_solve_cases_gradp
 
 
 def _check_step(step, allowed=STEPS):
     if step not in allowed:
-        raise ValueError("step must be 'absolute' or 'delta'" + (" or 'poisson'" if "poisson" in allowed else ""))
+        raise ValueError("step must be 'absolute' or 'delta'" + (" or 'poisson' or 'gradp'" if "poisson" in allowed else ""))
     return step
 
 
@@ -41,6 +41,46 @@ def _check_poisson(maxs, phi, k):
         raise ValueError("step='poisson' needs phi and k")
 
 
+def _check_gradp(maxs, reference):
+    """The argument checks of step='gradp', of SolverModule and SolverEnsemble alike, before any library call."""
+    if len(maxs) != 5:
+        raise ValueError("step='gradp' takes five maxs: (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_dPdx, max_abs_dPdy)")
+    if reference not in GridSurrogate.GRADP_REFERENCES:
+        raise ValueError("reference must be 'none' or 'outlet'")
+
+
+def _no_gradp_state(what):
+    raise RuntimeError(f"step='gradp' has no {what}: a step depends on its cells alone, use py_func")
+
+
+def gradp_grid_metrics(array, ny, nx, round_digits=2):
+    """(dx, dy, (extent_x, extent_y), x_min) of the grid ``build_geometry`` makes for ``array``: the bounds rounded as it rounds them,
+    ``np.diff(np.linspace(min, max, n))[0]`` as Eval_dual_Dense_onlycil.py:594-595 takes the spacings."""
+    a = np.asarray(array, np.float64)
+    x_min, x_max = round(np.min(a[:, 2]), round_digits), round(np.max(a[:, 2]), round_digits)
+    y_min, y_max = round(np.min(a[:, 3]), round_digits), round(np.max(a[:, 3]), round_digits)
+    xl, yl = np.linspace(x_min, x_max, nx), np.linspace(y_min, y_max, ny)
+    return float(np.diff(xl)[0]), float(np.diff(yl)[0]), (float(x_max - x_min), float(y_max - y_min)), float(x_min)
+
+
+def gradp_default_cut(sdfunct, array, delta, round_digits=2):
+    """The cut of step='gradp' with ``cut=None``: center_y is the middle row of the obstacle's solid rows -- the rows of ``sdfunct``
+    [ny,nx] that hold a zero off the grid's rim --, rounded up; center_x is the rule of Eval_dual_Dense_onlycil.py:599 on that row,
+    ``int(((xl[solid].max() + xl[solid].min()) / 2 - X0.min()) / delta)`` with ``xl = np.linspace(min_x, max_x, nx)``.  (The
+    reference's literal row 200 fits only its own grid.)"""
+    sd = np.asarray(sdfunct, np.float64)
+    ny, nx = sd.shape
+    rows = 1 + np.flatnonzero((sd[1:-1, 1:-1] == 0).any(axis=1))      # not the grid's rim, where cells outside the mesh's hull are zero too
+    if rows.size == 0:
+        raise ValueError("sdfunct holds no solid cell: pass the cut")
+    cy = int((rows.min() + rows.max() + 1) // 2)
+    _, _, (ex, _), x_min = gradp_grid_metrics(array, ny, nx, round_digits)
+    xl = np.linspace(x_min, x_min + ex, nx)
+    solid = sd[cy] == 0
+    cx = int(((xl[solid].max() + xl[solid].min()) / 2 - (x_min + delta / 2)) / delta)
+    return cy, cx
+
+
 def _poisson_state(sur):
     frames, steps = C.c_int32(), C.c_int64()
     sur._chk(sur.lib.psm_poisson_solve_state(sur.h, C.byref(frames), C.byref(steps)))
@@ -62,7 +102,7 @@ class SolverModule:
 
     def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), device: int = 0, delta: float = 5e-3,
                  geometry: str = "scipy", step: str = "absolute", phi: float = None, k: float = None, weighting: bool = True,
-                 apply_filter: bool = True, sigma_field=(10, 10), sigma_weight=(50, 50)):
+                 apply_filter: bool = None, sigma_field=(10, 10), sigma_weight=(50, 50), cut=None, reference: str = "outlet"):
         """``step``: 'absolute' (U -> p, the Chapter-5 module) or 'delta' (the deltas model behind the same two calls:
         [U(t) - U(t-1)], SDF -> p(t) - p(t-1), psm_solve_delta* of include/psm.h).  With 'delta', ``maxs`` are
         (max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp), ``init_func`` installs the tables with the deltas model's
@@ -74,6 +114,13 @@ class SolverModule:
         reference's ``timeStep``.  ``init_func`` installs the tables, binds features, post-steps, frames and the step, and pushes
         its own ``array`` as the first frame; the state is U, dU and p of the previous call, on the device: with the weighting the
         first ``py_func`` is a priming step too (it returns ``array[:,4]``), then every call returns ``array[:,4] + dp``.
+        ``step='gradp'``: the U_to_gradP model behind the same two calls (psm_solve_gradp of include/psm.h): ``maxs`` = (max_abs_Ux,
+        max_abs_Uy, max_abs_dist, max_abs_dPdx, max_abs_dPdy), the ``maxs`` file of the reference (Eval_dual_Dense_onlycil.py:54);
+        ``init_func`` installs the tables with normalise_sdf = fill_input = 1, takes the extents and spacings from the grid bounds it
+        built (``max_x - min_x``, ``np.diff(xl)[0]``, :594-595) and binds the step (with ``apply_filter``, default off for this step,
+        the post-steps with ``sigma_field`` first).  ``cut`` = (center_y, center_x) of the integration; None:
+        :func:`gradp_default_cut` (the reference's literal row 200 fits only its own grid).  ``reference``: 'outlet' (p = 0 at the
+        outlet) or 'none'.  There is no state: ``prime``, ``reset_state``, ``state`` and the begin / end halves raise.
         ``geometry``: who builds init_func's tables -- 'scipy' (default in this Python mirror: the routines the reference
         itself calls, qhull Delaunay in both directions, so that the tables -- including qhull's arbitrary choice of diagonal
         in every cocircular lattice square of the grid -> mesh step -- are the reference's) or 'native' (the library's C++
@@ -88,7 +135,11 @@ class SolverModule:
         self.geometry = geometry
         if self.step == "poisson":
             _check_poisson(self.maxs, phi, k)
-            self.phi, self.k, self.weighting, self.apply_filter = float(phi), float(k), bool(weighting), bool(apply_filter)
+            self.phi, self.k, self.weighting, self.apply_filter = float(phi), float(k), bool(weighting), apply_filter is None or bool(apply_filter)
+            self.sigma_field, self.sigma_weight = tuple(sigma_field), tuple(sigma_weight)
+        if self.step == "gradp":
+            _check_gradp(self.maxs, reference)
+            self.cut, self.reference, self.apply_filter = cut, reference, bool(apply_filter)
             self.sigma_field, self.sigma_weight = tuple(sigma_field), tuple(sigma_weight)
         self._sur = None
         self.tables = None
@@ -114,7 +165,7 @@ class SolverModule:
         self._sur = GridSurrogate(self.model, t.ny, t.nx, 1, self.device)
         v1, w1 = np.ascontiguousarray(t.vtx_m2g, np.int32), _f64(t.wts_m2g)
         v2, w2 = np.ascontiguousarray(t.vtx_g2m, np.int32), _f64(t.wts_g2m)
-        idx, sdf, mx = np.ascontiguousarray(t.indices, np.int32), _f64(t.sdfunct), _f64(self.maxs[-4:])
+        idx, sdf, mx = np.ascontiguousarray(t.indices, np.int32), _f64(t.sdfunct), self._maxs4()
         smd = int(self.step != "absolute")       # the deltas model's convention: normalise_sdf = fill_input = 1 (SM_call.py:441-443)
         self._sur._chk(self._sur.lib.psm_set_geometry(
             self._sur.h, int(np.asarray(array).shape[0]), t.ny, t.nx, _p(v1, C.c_int32), _p(w1, C.c_double),
@@ -123,9 +174,24 @@ class SolverModule:
         self.tables = t
         if self.step == "poisson":
             self._bind_poisson(sdf.reshape(t.ny, t.nx))
-        if smd:
+        if self.step == "gradp":
+            self._bind_gradp(sdf.reshape(t.ny, t.nx), array)
+        elif smd:
             self.prime(array)
         return 0
+
+    def _maxs4(self):
+        """The four maxs of psm_set_geometry: the last four; step='gradp': (max_abs_Ux, max_abs_Uy, max_abs_dist, unused)."""
+        return _f64(self.maxs[:3] + (1.0,)) if self.step == "gradp" else _f64(self.maxs[-4:])
+
+    def _bind_gradp(self, sdfunct, array):
+        """Everything a gradient-model step stands on; after it a step allocates nothing."""
+        sur = self._sur
+        dx, dy, extents, _ = gradp_grid_metrics(array, sur.ny, sur.nx)
+        self.cut_used = tuple(int(v) for v in self.cut) if self.cut is not None else gradp_default_cut(sdfunct, array, self.delta)
+        if self.apply_filter:
+            sur.bind_poststeps(self.sigma_field, self.sigma_weight)
+        sur.bind_gradp_solve(self.cut_used, dx, dy, extents, self.maxs[3:5], self.apply_filter, self.reference)
 
     def _bind_poisson(self, sdfunct):
         """Everything a Poisson-model step stands on, in the order the library asks for it; after it a step allocates nothing."""
@@ -146,7 +212,7 @@ class SolverModule:
         if self._sur is not None:
             self._sur.close()
         self._sur = GridSurrogate(self.model, ny.value, nx.value, 1, self.device)
-        mx = _f64(self.maxs[-4:])
+        mx = self._maxs4()
         if self.step != "absolute":
             n, ng = a.shape[0], ny.value * nx.value
             v1, w1, idx, sdf = np.empty((ng, 3), np.int32), np.empty((ng, 3)), np.empty((ng, 2), np.int32), np.empty(ng)
@@ -161,7 +227,10 @@ class SolverModule:
             self.tables = "native"
             if self.step == "poisson":
                 self._bind_poisson(sdf.reshape(ny.value, nx.value))
-            self.prime(a)
+            if self.step == "gradp":
+                self._bind_gradp(sdf.reshape(ny.value, nx.value), a)
+            else:
+                self.prime(a)
             return 0
         self._sur._chk(lib.psm_set_case(self._sur.h, _p(mx, C.c_double), self.delta, 10, 0.05))
         self._sur._chk(lib.psm_init_geometry(self._sur.h, _p(a, C.c_double), a.shape[0], _p(t, C.c_double), t.shape[0],
@@ -170,9 +239,11 @@ class SolverModule:
         return 0
 
     # -- the state of step='delta' (psm_delta_prime / _reset / _state) and of step='poisson' (psm_poisson_solve_push / _reset / _state)
-    def _need_delta(self):
+    def _need_delta(self, what="state"):
         if self.step == "absolute":
             raise RuntimeError("this module was built with step='absolute': the state belongs to step='delta'")
+        if self.step == "gradp":
+            _no_gradp_state(what)
         if self.tables is None:
             raise RuntimeError("init_func has not been called")
 
@@ -222,6 +293,8 @@ class SolverModule:
             raise RuntimeError("init_func has not been called")
         if self.step == "poisson":
             raise RuntimeError("step='poisson' has no begin / end halves: use py_func")
+        if self.step == "gradp":
+            _no_gradp_state("begin / end halves")
         if self.step == "delta":
             a, out = _check_cells(array_in, out)
             self._sur._chk(self._sur.lib.psm_solve_delta_begin(self._sur.h, _p(a, C.c_double), a.shape[0], 0, _p(out, C.c_double)))
@@ -236,6 +309,8 @@ class SolverModule:
         self._inflight = (a, out)                       # keeps both arrays alive until the end call (set only once the step is in flight)
 
     def py_func_end(self) -> np.ndarray:
+        if self.step == "gradp":
+            _no_gradp_state("begin / end halves")
         end = self._sur.lib.psm_solve_delta_end if self.step == "delta" else self._sur.lib.psm_solve_end
         self._sur._chk(end(self._sur.h))
         a, out = self._inflight
@@ -250,6 +325,10 @@ class SolverModule:
         if self.step == "poisson":
             a, out = _check_cells(array_in, out)
             self._sur._chk(self._sur.lib.psm_solve_poisson(self._sur.h, _p(a, C.c_double), a.shape[0], int(placeholder), _p(out, C.c_double)))
+            return out
+        if self.step == "gradp":
+            a, out = _check_cells(array_in, out)
+            self._sur._chk(self._sur.lib.psm_solve_gradp(self._sur.h, _p(a, C.c_double), a.shape[0], int(placeholder), _p(out, C.c_double)))
             return out
         if self.step == "delta":
             a, out = _check_cells(array_in, out)
@@ -275,11 +354,12 @@ class SolverEnsemble:
     'poisson' with the further arguments of :class:`SolverModule` (five ``maxs``, ``phi``, ``k``, the weighting, the filter and its
     widths), on ``psm_solve_cases_poisson``: ``init_func`` installs the K table sets, binds the features with the K SDF planes, the
     post-steps and the step, and pushes its own ``arrays`` as the first frame; one two-frame state, one frame counter and one step
-    counter for the set; no begin / end halves."""
+    counter for the set; no begin / end halves.  Or 'gradp' with ``cut`` (None, or one (center_y, center_x) per case), ``reference``
+    and ``apply_filter`` (default off) of :class:`SolverModule`, on ``psm_solve_cases_gradp``: no state, no begin / end halves."""
 
     def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), max_cases: int = 8, geometry: str = "native",
                  device: int = 0, delta: float = 5e-3, step: str = "absolute", phi: float = None, k: float = None, weighting: bool = True,
-                 apply_filter: bool = True, sigma_field=(10, 10), sigma_weight=(50, 50)):
+                 apply_filter: bool = None, sigma_field=(10, 10), sigma_weight=(50, 50), cut=None, reference: str = "outlet"):
         if geometry not in ("scipy", "native"):
             raise ValueError("geometry must be 'scipy' or 'native'")
         self.step = _check_step(step, MODULE_STEPS)
@@ -287,7 +367,11 @@ class SolverEnsemble:
         self.geometry, self.device, self.delta = geometry, device, delta
         if self.step == "poisson":
             _check_poisson(self.maxs, phi, k)
-            self.phi, self.k, self.weighting, self.apply_filter = float(phi), float(k), bool(weighting), bool(apply_filter)
+            self.phi, self.k, self.weighting, self.apply_filter = float(phi), float(k), bool(weighting), apply_filter is None or bool(apply_filter)
+            self.sigma_field, self.sigma_weight = tuple(sigma_field), tuple(sigma_weight)
+        if self.step == "gradp":
+            _check_gradp(self.maxs, reference)
+            self.cut, self.reference, self.apply_filter = cut, reference, bool(apply_filter)
             self.sigma_field, self.sigma_weight = tuple(sigma_field), tuple(sigma_weight)
         self._sur = None
         self.tables = None
@@ -305,7 +389,7 @@ class SolverEnsemble:
         lib = _lib.load()
         K = len(arrays)
         a, t, o = [_f64(x) for x in arrays], [_f64(x) for x in tops], [_f64(x) for x in obsts]
-        mx = _f64(self.maxs[-4:])
+        mx = _f64(self.maxs[:3] + (1.0,)) if self.step == "gradp" else _f64(self.maxs[-4:])
         if self.geometry == "native":
             ny, nx = C.c_int32(), C.c_int32()
             if lib.psm_geometry_shape(_p(a[0], C.c_double), a[0].shape[0], self.delta, C.byref(ny), C.byref(nx), None):
@@ -351,15 +435,25 @@ class SolverEnsemble:
             sur.bind_features(np.stack([np.asarray(sd, np.float64).reshape(ny, nx) for sd in keep[3]]), self.k, self.maxs[:4])
             sur.bind_poststeps(self.sigma_field, self.sigma_weight)
             sur.bind_poisson_solve_cases(self.phi, self.maxs[4], self.weighting, self.apply_filter)
-        if smd:
+        if self.step == "gradp":                 # the grid is case 0's (all cases share its shape and bounds); keep[3]: the K sdfuncts
+            dx, dy, extents, _ = gradp_grid_metrics(a[0], ny, nx)
+            sdfs = [np.asarray(sd, np.float64).reshape(ny, nx) for sd in keep[3]]
+            self.cuts_used = ([tuple(int(v) for v in c) for c in self.cut] if self.cut is not None
+                              else [gradp_default_cut(sdfs[k], a[k], self.delta) for k in range(K)])
+            if self.apply_filter:
+                sur.bind_poststeps(self.sigma_field, self.sigma_weight)
+            sur.bind_gradp_solve_cases(self.cuts_used, dx, dy, extents, self.maxs[3:5], self.apply_filter, self.reference)
+        elif smd:
             self.prime(a)
         return 0
 
     # -- the state of step='delta' (psm_delta_prime_cases / psm_delta_reset / psm_delta_state) and of step='poisson'
     # (psm_poisson_solve_push_cases / psm_poisson_solve_reset / psm_poisson_solve_state)
-    def _need_delta(self):
+    def _need_delta(self, what="state"):
         if self.step == "absolute":
             raise RuntimeError("this ensemble was built with step='absolute': the state belongs to step='delta'")
+        if self.step == "gradp":
+            _no_gradp_state(what)
 
     def prime(self, arrays):
         """U(t-1) := arrays[k][:,0:2] for every case.  ``init_func`` does this with the start fields.  step='poisson': one frame
@@ -412,11 +506,15 @@ class SolverEnsemble:
         """First half of :meth:`py_func` (psm_solve_cases_begin): enqueue the step of all cases and return."""
         if self.step == "poisson":
             raise RuntimeError("step='poisson' has no begin / end halves: use py_func")
+        if self.step == "gradp":
+            _no_gradp_state("begin / end halves")
         cells, p = self._pack(arrays)
         self._sur._chk(self._entry("psm_solve_cases_begin")(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
         self._inflight = (cells, p)                     # keeps both arrays alive until the end call
 
     def py_func_end(self):
+        if self.step == "gradp":
+            _no_gradp_state("begin / end halves")
         self._sur._chk(self._entry("psm_solve_cases_end")(self._sur.h))
         cells, p = self._inflight
         self._inflight = None
@@ -427,6 +525,9 @@ class SolverEnsemble:
         cells, p = self._pack(arrays)
         if self.step == "poisson":
             self._sur._chk(self._sur.lib.psm_solve_cases_poisson(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
+            return self._split(p)
+        if self.step == "gradp":
+            self._sur._chk(self._sur.lib.psm_solve_cases_gradp(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
             return self._split(p)
         self._sur._chk(self._entry("psm_solve_cases")(self._sur.h, _p(cells, C.c_double), _p(p, C.c_double)))
         return self._split(p)

@@ -822,8 +822,77 @@ class GridSurrogate:
         self._chk(self.lib.psm_solve_cases_poisson_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_fields or None),
                                                           C.c_void_p(d_scalars or None), C.c_void_p(stream)))
 
+    # -- the gradient-model step at the solver boundary (psm_solve_gradp*): cells [N,5] -> p [N] through U -> grad p -> p, no state
+    GRADP_SOLVE_SCALARS = ("U", "U2", "s", "sx", "sy", "_5", "_6", "_7")
+    GRADP_REFERENCES = {"none": 0, "outlet": 1}
+
+    def _gradp_solve_args(self, dx, dy, extents, max_abs_grad, apply_filter, reference):
+        """What the two bind entries take alike behind their cut(s)."""
+        if reference not in self.GRADP_REFERENCES:
+            raise ValueError("reference must be 'none' or 'outlet'")
+        ex, mg = _f64(extents).reshape(-1), _f64(max_abs_grad).reshape(-1)
+        if ex.size != 2 or mg.size != 2:
+            raise ValueError("extents = (extent_x, extent_y) and max_abs_grad = (max_abs_dPdx, max_abs_dPdy)")
+        return float(dx), float(dy), float(ex[0]), float(ex[1]), _p(mg, C.c_double), int(bool(apply_filter)), self.GRADP_REFERENCES[reference]
+
+    def bind_gradp_solve(self, cut, dx: float, dy: float, extents, max_abs_grad, apply_filter: bool = False, reference: str = "outlet"):
+        """The integration tables (from the mesh's own sdfunct and ``cut`` = (center_y, center_x)), the planes and the scalar slots
+        of the gradient solver step on a gradP handle with a single mesh (both table sets; with ``apply_filter`` behind
+        ``bind_poststeps``): after it a step allocates nothing.  The integration's spacings are ``dx * max_abs_dPdx / extent_x`` and
+        ``dy * max_abs_dPdy / extent_y``; ``reference``: 'outlet' (p = 0 at the outlet) or 'none'."""
+        cy, cx = (int(v) for v in cut)
+        self._chk(self.lib.psm_bind_gradp_solve(self.h, cy, cx, *self._gradp_solve_args(dx, dy, extents, max_abs_grad, apply_filter, reference)))
+
+    def bind_gradp_solve_cases(self, cuts, dx: float, dy: float, extents, max_abs_grad, apply_filter: bool = False, reference: str = "outlet"):
+        """``bind_gradp_solve`` on a case set of K meshes under the gradP model; ``cuts`` [K,2] = (center_y, center_x) in case order."""
+        c = np.ascontiguousarray(cuts, np.int32).reshape(-1, 2)
+        cy, cx = np.ascontiguousarray(c[:, 0]), np.ascontiguousarray(c[:, 1])
+        total = C.c_int32()
+        if self.lib.psm_mesh_cases(self.h, C.byref(total), None) == 0 and total.value != c.shape[0]:
+            raise ValueError(f"cuts must hold one (center_y, center_x) for each of the {total.value} cases")
+        self._chk(self.lib.psm_bind_gradp_solve_cases(self.h, _p(cy, C.c_int32), _p(cx, C.c_int32),
+                                                      *self._gradp_solve_args(dx, dy, extents, max_abs_grad, apply_filter, reference)))
+
+    def unbind_gradp_solve(self):
+        self._chk(self.lib.psm_unbind_gradp_solve(self.h))
+
+    def solve_gradp(self, cells: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Host buffers, synchronous: cells [N,5] float64 = (Ux, Uy, Cx, Cy, p(t-1)) -> p [N] float64; p(t-1) on the fallback cells."""
+        a = self._solver_cells(cells)
+        if out is None:
+            out = np.empty(a.shape[0], np.float64)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
+            raise ValueError("out must be a contiguous float64 array [N]")
+        self._chk(self.lib.psm_solve_gradp(self.h, _p(a, C.c_double), a.shape[0], 0, _p(out, C.c_double)))
+        return out
+
+    def solve_gradp_device(self, d_cells: int, d_p: int, d_image: int = 0, d_gradp: int = 0, d_pgrid: int = 0, d_scalars: int = 0, stream: int = 0):
+        """The same step on raw device pointers, asynchronous on ``stream``: ``d_cells`` [N,5] and ``d_p`` [N] float64; optional
+        ``d_image`` [Ny,Nx,3], ``d_gradp`` [Ny,Nx,2] and ``d_pgrid`` [Ny,Nx] float32 receive the solved image, the gradient behind
+        the filter and q = p / U^2 before the shift, ``d_scalars`` [8] float64 ``GRADP_SOLVE_SCALARS`` (0: the handle's own buffers)."""
+        self._chk(self.lib.psm_solve_gradp_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_image or None), C.c_void_p(d_gradp or None),
+                                                  C.c_void_p(d_pgrid or None), C.c_void_p(d_scalars or None), C.c_void_p(stream)))
+
+    def solve_cases_gradp(self, cells: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Host buffers, synchronous: the cases' cells concatenated in case order [sum N_i,5] float64 -> p [sum N_i] float64, per case
+        what ``solve_gradp`` returns for a single mesh."""
+        a = self._solver_cells(cells)
+        if out is None:
+            out = np.empty(a.shape[0], np.float64)
+        elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
+            raise ValueError("out must be a contiguous float64 array [sum N_i]")
+        self._cases_count(a)
+        self._chk(self.lib.psm_solve_cases_gradp(self.h, _p(a, C.c_double), _p(out, C.c_double)))
+        return out
+
+    def solve_cases_gradp_device(self, d_cells: int, d_p: int, d_image: int = 0, d_gradp: int = 0, d_pgrid: int = 0, d_scalars: int = 0, stream: int = 0):
+        """The same step on raw device pointers: ``d_cells`` [sum N_i,5], ``d_p`` [sum N_i]; the optional outputs per case:
+        ``d_image`` [K,Ny,Nx,3], ``d_gradp`` [K,Ny,Nx,2], ``d_pgrid`` [K,Ny,Nx], ``d_scalars`` [K,8]."""
+        self._chk(self.lib.psm_solve_cases_gradp_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_image or None), C.c_void_p(d_gradp or None),
+                                                        C.c_void_p(d_pgrid or None), C.c_void_p(d_scalars or None), C.c_void_p(stream)))
+
     # -- the per-frame error blocks of assembled fields on the device: eight float64 sums per (frame, pair) instead of the fields
-    RAW_SUMS = ("n", "s1", "s2", "tmin", "tmax", "pmin", "pmax", "tnan")
+    RAW_SUMS =("n", "s1", "s2", "tmin", "tmax", "pmin", "pmax", "tnan")
     METRICS = ("normVal", "biasNorm", "stdeNorm", "rmseNorm", "mean_err", "mean_sq_err")
 
     @staticmethod
