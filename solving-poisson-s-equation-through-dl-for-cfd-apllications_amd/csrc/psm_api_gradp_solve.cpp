@@ -65,17 +65,15 @@ int gradp_solve_tail(psm_handle* h, const GradpSolveCall& gs, hipStream_t st) {
 }
 
 // the binding and the form the entry serves (cases: 0 the single mesh, 1 a case set); one step in flight per handle, across all step kinds
-static int gradp_solve_state(psm_handle* h, int cases) {
-  const GradpSolveSet& S = h->gsolve;
-  if (S.ready && cases == 0 && S.cases)
-    return fail(h, PSM_ERR_STATE, "the step is bound on a case set (psm_bind_gradp_solve_cases): use psm_solve_cases_gradp*");
-  if (S.ready && cases == 1 && !S.cases)
-    return fail(h, PSM_ERR_STATE, "the step is bound on the single mesh (psm_bind_gradp_solve): use psm_solve_gradp*");
-  if (!S.ready || !h->planned || (cases ? !h->mcs.ready : !h->have_geometry))
-    return fail(h, PSM_ERR_STATE, cases ? "psm_bind_gradp_solve_cases has not been called (a new case set, plan or model and, with apply_filter, psm_bind_poststeps drop the binding)"
-                                        : "psm_bind_gradp_solve has not been called (a new mesh, plan or model and, with apply_filter, psm_bind_poststeps drop the binding)");
-  if (h->mesh.inflight || h->mcs.inflight) return fail(h, PSM_ERR_STATE, "a step is in flight on this handle: call psm_solve_end first");
-  return PSM_OK;
+static const BoundStepTexts kGradpTexts = {
+    "the step is bound on a case set (psm_bind_gradp_solve_cases): use psm_solve_cases_gradp*",
+    "the step is bound on the single mesh (psm_bind_gradp_solve): use psm_solve_gradp*",
+    "psm_bind_gradp_solve_cases has not been called (a new case set, plan or model and, with apply_filter, psm_bind_poststeps drop the binding)",
+    "psm_bind_gradp_solve has not been called (a new mesh, plan or model and, with apply_filter, psm_bind_poststeps drop the binding)"};
+
+static int gradp_solve_state(psm_handle* h, int cases) {   // this kind also asks for the plan and the mesh of the form
+  const bool usable = h->gsolve.ready && h->planned && (cases ? h->mcs.ready : h->have_geometry);
+  return bound_step_state(h, kGradpTexts, h->gsolve.ready, h->gsolve.cases, usable, cases);
 }
 
 // One call on device buffers: the step's one graph replay.  Every check is made before anything is enqueued.  A case set: d_cells
@@ -86,8 +84,7 @@ static int gradp_solve_device(psm_handle* h, int cases, const double* d_cells, d
   if (rc) return rc;
   GradpSolveSet& S = h->gsolve;
   if (!d_cells || !d_p) return fail(h, PSM_ERR_ARG, "null buffer");
-  if (((reinterpret_cast<uintptr_t>(d_cells) | reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_scalars) | reinterpret_cast<uintptr_t>(d_gradp)) & 7) ||
-      ((reinterpret_cast<uintptr_t>(d_image) | reinterpret_cast<uintptr_t>(d_pgrid)) & 3))
+  if (!aligned_to(8, {d_cells, d_p, d_scalars, d_gradp}) || !aligned_to(4, {d_image, d_pgrid}))
     return fail(h, PSM_ERR_ARG, "a pointer is misaligned (8 bytes for the cells, p, the gradient and the scalars, 4 for the image and the plane)");
   if (S.apply_filter && !h->post.ready) return fail(h, PSM_ERR_STATE, "psm_bind_poststeps has not been called: apply_filter needs it as well as psm_bind_gradp_solve");
   HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -114,20 +111,18 @@ static int gradp_solve_host(psm_handle* h, int cases, const double* cells, int64
   HIPCHK(h, hipSetDevice(h->cfg.device));
   MeshBuffers& m = cases ? static_cast<MeshBuffers&>(h->mcs) : static_cast<MeshBuffers&>(h->mesh);
   hipStream_t st = h->stream;
-  const size_t in_bytes = (size_t)n * 5 * sizeof(double), out_bytes = (size_t)n * sizeof(double);
-  const bool reg_in = host_registered(h, cells, in_bytes), reg_out = host_registered(h, p_out, out_bytes);
+  const HostStaging s(h, m, cells, p_out, (size_t)n);
   HIPCHK(h, wait_stream(st));                                // the staging buffers are a step's too
-  if (!reg_in) memcpy(m.h_cells, cells, in_bytes);
-  HIPCHK(h, hipMemcpyAsync(m.d_cells, reg_in ? cells : m.h_cells, in_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(h, s.copy_in(st));
   // no state turns over: a tripped guard (a geometry bound with psm_bind_geometry that is not the mesh's) runs the step again on the general path
   rc = guarded_host_step(h, st, cases ? "psm_solve_cases_gradp" : "psm_solve_gradp", [&](int) {
     const int rs = gradp_solve_device(h, cases, m.d_cells, m.d_p, nullptr, nullptr, nullptr, nullptr, st);
     if (rs) return rs;
-    HIPCHK(h, hipMemcpyAsync(reg_out ? p_out : m.h_p, m.d_p, out_bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, s.copy_out(st));
     return PSM_OK;
   });
   if (rc) { (void)wait_stream(st); return rc; }
-  if (!reg_out) memcpy(p_out, m.h_p, out_bytes);
+  s.deliver();
   return PSM_OK;
 }
 
@@ -159,9 +154,7 @@ static int gradp_solve_bind(psm_handle* h, const char* name, int cases, const st
   if (!rc) rc = dev_alloc(h, &s.d_image, (size_t)K * npix * 3);
   if (!rc) rc = dev_alloc(h, &s.d_scalars, (size_t)K * PSM_GRADP_SCALARS);
   if (rc) { gradp_solve_free(h); return rc; }
-  hipError_t e = hipMemsetAsync(s.d_scalars, 0, (size_t)K * PSM_GRADP_SCALARS * sizeof(double), h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { gradp_solve_free(h); return fail(h, PSM_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e)); }
+  if ((rc = bind_zero_sync(h, name, {{s.d_scalars, (size_t)K * PSM_GRADP_SCALARS * sizeof(double)}}, gradp_solve_free))) return rc;
   s.sx = sx; s.sy = sy; s.apply_filter = apply_filter ? 1 : 0; s.reference = reference; s.cases = cases;
   s.ready = true;
   return PSM_OK;

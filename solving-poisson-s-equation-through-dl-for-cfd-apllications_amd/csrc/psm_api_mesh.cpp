@@ -464,7 +464,7 @@ int psm_impl::cases_step_device(psm_handle* h, const double* d_cells, double* d_
   if (rc) return rc;
   if (h->mcs.inflight) return fail(h, PSM_ERR_STATE, "a psm_solve_cases_begin is in flight on this handle: call psm_solve_cases_end first");
   if (!d_cells || !d_p) return fail(h, PSM_ERR_ARG, "null buffer");
-  if ((reinterpret_cast<uintptr_t>(d_cells) | reinterpret_cast<uintptr_t>(d_p)) & 7) return fail(h, PSM_ERR_ARG, "device buffers must be 8-byte aligned");
+  if (!aligned_to(8, {d_cells, d_p})) return fail(h, PSM_ERR_ARG, "device buffers must be 8-byte aligned");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   return cases_sequence(h, d_cells, d_p, stream ? (hipStream_t)stream : h->stream, delta);
 }
@@ -478,16 +478,44 @@ int psm_impl::cases_step_begin(psm_handle* h, const double* cells, double* p_out
   HIPCHK(h, hipSetDevice(h->cfg.device));
   MeshCaseSet& m = h->mcs;
   hipStream_t st = h->stream;
-  const size_t total = (size_t)m.off[m.n_cases], in_bytes = total * 5 * sizeof(double), out_bytes = total * sizeof(double);
-  // one H2D of the concatenated cells, one D2H of p: straight from / into arrays registered with psm_host_register, else through the pinned staging
-  const bool reg_in = host_registered(h, cells, in_bytes), reg_out = host_registered(h, p_out, out_bytes);
-  if (!reg_in) memcpy(m.h_cells, cells, in_bytes);
-  HIPCHK(h, hipMemcpyAsync(m.d_cells, reg_in ? cells : m.h_cells, in_bytes, hipMemcpyHostToDevice, st));
+  const HostStaging s(h, m, cells, p_out, (size_t)m.off[m.n_cases]);   // the in-flight flag (above) keeps the staging this step's
+  HIPCHK(h, s.copy_in(st));
   if ((rc = cases_sequence(h, m.d_cells, m.d_p, st, delta))) return rc;
-  HIPCHK(h, hipMemcpyAsync(reg_out ? p_out : m.h_p, m.d_p, out_bytes, hipMemcpyDeviceToHost, st));
-  m.copy_out = reg_out ? nullptr : p_out;
+  HIPCHK(h, s.copy_out(st));
+  m.copy_out = s.pending();
   m.inflight = true;
   return PSM_OK;
+}
+
+psm_impl::HostStaging::HostStaging(const psm_handle* h, MeshBuffers& m, const double* cells, double* p_out, size_t n)
+    : m(m), cells(cells), p_out(p_out), in_bytes(n * 5 * sizeof(double)), out_bytes(n * sizeof(double)),
+      reg_in(host_registered(h, cells, in_bytes)), reg_out(p_out && host_registered(h, p_out, out_bytes)) {}
+
+hipError_t psm_impl::HostStaging::copy_in(hipStream_t st) const {
+  if (!reg_in) memcpy(m.h_cells, cells, in_bytes);
+  return hipMemcpyAsync(m.d_cells, reg_in ? cells : m.h_cells, in_bytes, hipMemcpyHostToDevice, st);
+}
+
+hipError_t psm_impl::HostStaging::copy_out(hipStream_t st) const {
+  return p_out ? hipMemcpyAsync(reg_out ? p_out : m.h_p, m.d_p, out_bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+int psm_impl::bound_step_state(psm_handle* h, const BoundStepTexts& t, bool ready, int bound_cases, bool usable, int cases) {
+  if (ready && cases == 0 && bound_cases) return fail(h, PSM_ERR_STATE, t.on_cases);
+  if (ready && cases == 1 && !bound_cases) return fail(h, PSM_ERR_STATE, t.on_single);
+  if (!usable) return fail(h, PSM_ERR_STATE, cases == 1 ? t.unbound_cases : t.unbound_single);
+  if (h->mesh.inflight || h->mcs.inflight) return fail(h, PSM_ERR_STATE, "a step is in flight on this handle: call psm_solve_end first");
+  return PSM_OK;
+}
+
+int psm_impl::bind_zero_sync(psm_handle* h, const char* name, std::initializer_list<std::pair<void*, size_t>> zero, void (*free_fn)(psm_handle*)) {
+  hipError_t e = hipSuccess;
+  for (const auto& z : zero)
+    if (e == hipSuccess) e = hipMemsetAsync(z.first, 0, z.second, h->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  if (e == hipSuccess) return PSM_OK;
+  free_fn(h);
+  return fail(h, PSM_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e));
 }
 
 extern "C" {

@@ -90,17 +90,14 @@ int poisson_solve_tail(psm_handle* h, const PoissonSolveCall& ps, const PostCall
 }
 
 // the mesh or the case set, the bindings under this one and this one; `cases`: the form the entry serves (-1: either)
+static const BoundStepTexts kPoissonTexts = {
+    "the step is bound on a case set (psm_bind_poisson_solve_cases): use psm_poisson_solve_push_cases / psm_solve_cases_poisson*",
+    "the step is bound on the single mesh (psm_bind_poisson_solve): use psm_poisson_solve_push / psm_solve_poisson*",
+    "psm_bind_poisson_solve_cases has not been called (a new case set, plan or model, psm_bind_features and psm_bind_poststeps drop the binding)",
+    "psm_bind_poisson_solve has not been called (a new mesh, plan or model, psm_bind_features, psm_bind_poststeps and psm_bind_frames drop the binding)"};
+
 static int poisson_solve_state(psm_handle* h, int cases) {
-  const PoissonSolveSet& S = h->psolve;
-  if (S.ready && cases == 0 && S.cases)
-    return fail(h, PSM_ERR_STATE, "the step is bound on a case set (psm_bind_poisson_solve_cases): use psm_poisson_solve_push_cases / psm_solve_cases_poisson*");
-  if (S.ready && cases == 1 && !S.cases)
-    return fail(h, PSM_ERR_STATE, "the step is bound on the single mesh (psm_bind_poisson_solve): use psm_poisson_solve_push / psm_solve_poisson*");
-  if (!S.ready)
-    return fail(h, PSM_ERR_STATE, cases == 1 ? "psm_bind_poisson_solve_cases has not been called (a new case set, plan or model, psm_bind_features and psm_bind_poststeps drop the binding)"
-                                             : "psm_bind_poisson_solve has not been called (a new mesh, plan or model, psm_bind_features, psm_bind_poststeps and psm_bind_frames drop the binding)");
-  if (h->mesh.inflight || h->mcs.inflight) return fail(h, PSM_ERR_STATE, "a step is in flight on this handle: call psm_solve_end first");
-  return PSM_OK;
+  return bound_step_state(h, kPoissonTexts, h->psolve.ready, h->psolve.cases, h->psolve.ready, cases);
 }
 
 // the whole frame is on the device: the counters move
@@ -113,7 +110,7 @@ static int poisson_solve_device(psm_handle* h, int cases, const double* d_cells,
   if (rc) return rc;
   PoissonSolveSet& S = h->psolve;
   if (!d_cells || !d_p) return fail(h, PSM_ERR_ARG, "null buffer");
-  if (((reinterpret_cast<uintptr_t>(d_cells) | reinterpret_cast<uintptr_t>(d_p) | reinterpret_cast<uintptr_t>(d_scalars)) & 7) || (reinterpret_cast<uintptr_t>(d_fields) & 3))
+  if (!aligned_to(8, {d_cells, d_p, d_scalars}) || !aligned_to(4, {d_fields}))
     return fail(h, PSM_ERR_ARG, "a pointer is misaligned (8 bytes for the cells, p and the scalars, 4 for the fields)");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   const int K = S.cases ? S.cases : 1;
@@ -148,20 +145,18 @@ static int poisson_solve_host(psm_handle* h, int cases, const double* cells, int
   HIPCHK(h, hipSetDevice(h->cfg.device));
   MeshBuffers& m = cases ? static_cast<MeshBuffers&>(h->mcs) : static_cast<MeshBuffers&>(h->mesh);
   hipStream_t st = h->stream;
-  const size_t in_bytes = (size_t)n * 5 * sizeof(double), out_bytes = (size_t)n * sizeof(double);
-  const bool reg_in = host_registered(h, cells, in_bytes), reg_out = !push_only && host_registered(h, p_out, out_bytes);
+  const HostStaging s(h, m, cells, push_only ? nullptr : p_out, (size_t)n);
   HIPCHK(h, wait_stream(st));                                // the staging buffers are a step's too
-  if (!reg_in) memcpy(m.h_cells, cells, in_bytes);
-  HIPCHK(h, hipMemcpyAsync(m.d_cells, reg_in ? cells : m.h_cells, in_bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(h, s.copy_in(st));
   if ((rc = poisson_solve_device(h, cases, m.d_cells, m.d_p, nullptr, nullptr, st, push_only))) { (void)wait_stream(st); return rc; }
-  if (!push_only) HIPCHK(h, hipMemcpyAsync(reg_out ? p_out : m.h_p, m.d_p, out_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(h, s.copy_out(st));
   HIPCHK(h, wait_stream(st));
   if (guard_take(h, h->ws0)) {
     // The state has turned over with the step: it cannot run again on the general path as a grid-native solve does.
     if ((rc = guard_drop(h, cases ? "psm_solve_cases_poisson" : "psm_solve_poisson"))) return rc;
     return fail(h, PSM_ERR_STATE, h->err + "; the step's p is not valid and its frame was pushed: psm_poisson_solve_reset and prime again");
   }
-  if (!push_only && !reg_out) memcpy(p_out, m.h_p, out_bytes);
+  s.deliver();
   return PSM_OK;
 }
 
@@ -180,11 +175,8 @@ static int poisson_solve_bind(psm_handle* h, const char* name, int cases, size_t
   if ((rc = dev_alloc(h, &s.d_state, 5 * n)) || (rc = dev_alloc(h, &s.d_part, rows * 2 * PSM_POISSON_PARTS)) ||
       (rc = dev_alloc(h, &s.d_scalars, rows * PSM_POISSON_SCALARS))) { poisson_solve_free(h); return rc; }
   // the state is defined before the first push reads u_prev (and discards what it makes of it)
-  hipError_t e = hipMemsetAsync(s.d_state, 0, 5 * n * sizeof(double), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s.d_part, 0, rows * 2 * PSM_POISSON_PARTS * sizeof(double), h->stream);
-  if (e == hipSuccess) e = hipMemsetAsync(s.d_scalars, 0, rows * PSM_POISSON_SCALARS * sizeof(double), h->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) { poisson_solve_free(h); return fail(h, PSM_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e)); }
+  if ((rc = bind_zero_sync(h, name, {{s.d_state, 5 * n * sizeof(double)}, {s.d_part, rows * 2 * PSM_POISSON_PARTS * sizeof(double)},
+                                     {s.d_scalars, rows * PSM_POISSON_SCALARS * sizeof(double)}}, poisson_solve_free))) return rc;
   s.phi = phi; s.max_abs_dp = max_abs_delta_p; s.weighting = weighting ? 1 : 0; s.apply_filter = apply_filter ? 1 : 0;
   s.cases = cases;
   s.ready = true;

@@ -36,6 +36,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <tuple>
@@ -736,6 +737,36 @@ int step_end(psm_handle* h, MeshBuffers& b, int64_t total_cells, const char* beg
 int cases_check(psm_handle* h);
 int cases_step_device(psm_handle* h, const double* d_cells, double* d_p, void* stream, bool delta);
 int cases_step_begin(psm_handle* h, const double* cells, double* p_out, bool delta);
+// The host staging of one cells [n,5] -> p [n] step on a mesh's buffers (psm_api_mesh.cpp): one H2D of the cells and one D2H of p,
+// straight from / into ranges registered with psm_host_register, else through the pinned staging.  p_out null: no output (a push).
+// The caller keeps its own order around the calls: nothing before copy_in may still use the staging (the stream waited for, or the
+// in-flight flag), and p is delivered -- memcpy h_p -> pending() -- once the stream has been waited for.
+struct HostStaging {
+  MeshBuffers& m;
+  const double* cells;
+  double* p_out;
+  size_t in_bytes, out_bytes;
+  bool reg_in, reg_out;
+  HostStaging(const psm_handle* h, MeshBuffers& m, const double* cells, double* p_out, size_t n);
+  hipError_t copy_in(hipStream_t st) const;
+  hipError_t copy_out(hipStream_t st) const;
+  double* pending() const { return reg_out ? nullptr : p_out; }   // where p is still to be copied to (null: it was DMA'd, or there is none)
+  void deliver() const { if (pending()) memcpy(p_out, m.h_p, out_bytes); }
+};
+// What the entries of a bound step kind at the solver boundary (Poisson model, gradient model) ask before anything else: bound on the
+// form the entry serves (cases: 0 the single mesh, 1 a case set, -1 either), bound at all -- `usable`: the binding is ready and what
+// else the kind stands on is there --, no step in flight.  The texts are the kind's.
+struct BoundStepTexts { const char *on_cases, *on_single, *unbound_cases, *unbound_single; };
+int bound_step_state(psm_handle* h, const BoundStepTexts& t, bool ready, int bound_cases, bool usable, int cases);
+// The tail of a psm_bind_*_solve* entry: `zero` (pointer, bytes) cleared on the handle's stream and the stream drained; on a failure
+// free_fn and the error under the bind entry's name.
+int bind_zero_sync(psm_handle* h, const char* name, std::initializer_list<std::pair<void*, size_t>> zero, void (*free_fn)(psm_handle*));
+// every pointer of `ps` (null included) is a multiple of `bytes` (a power of two)
+inline bool aligned_to(uintptr_t bytes, std::initializer_list<const void*> ps) {
+  uintptr_t u = 0;
+  for (const void* p : ps) u |= reinterpret_cast<uintptr_t>(p);
+  return (u & (bytes - 1)) == 0;
+}
 void delta_drop(psm_handle* h);       // the geometry or case set goes: so does U(t-1)
 // the stages of `step` and the solve between them on one stream / in one graph replay; the combinations of stages: step_check there
 int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* out_scale, float* d_fields,

@@ -758,23 +758,35 @@ class GridSurrogate:
             raise ValueError("cells must be [N,5] = (Ux, Uy, Cx, Cy, p)")
         return a
 
-    def solve_poisson(self, cells: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
-        """Host buffers, synchronous: cells [N,5] float64 = (Ux, Uy, Cx, Cy, p(t-1)) -> p [N] float64 = p(t-1) + dp; p(t-1) itself
-        on a priming or skipped step and on the fallback cells."""
+    def _solver_step(self, entry, cells, out, cases: bool):
+        """What the four host steps at the solver boundary share: the checks of cells and ``out``, of a case set's cell count, then
+        ``entry`` on the single mesh (cells, N, rank 0, p) or on the case set (cells, p)."""
         a = self._solver_cells(cells)
         if out is None:
             out = np.empty(a.shape[0], np.float64)
         elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
-            raise ValueError("out must be a contiguous float64 array [N]")
-        self._chk(self.lib.psm_solve_poisson(self.h, _p(a, C.c_double), a.shape[0], 0, _p(out, C.c_double)))
+            raise ValueError(f"out must be a contiguous float64 array [{'sum N_i' if cases else 'N'}]")
+        if cases:
+            self._cases_count(a)
+            self._chk(entry(self.h, _p(a, C.c_double), _p(out, C.c_double)))
+        else:
+            self._chk(entry(self.h, _p(a, C.c_double), a.shape[0], 0, _p(out, C.c_double)))
         return out
+
+    def _solver_step_device(self, entry, d_cells, d_p, optional, stream):
+        """The device form: cells and p, the entry's optional outputs (0: a null pointer), the stream."""
+        self._chk(entry(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), *[C.c_void_p(d or None) for d in optional], C.c_void_p(stream)))
+
+    def solve_poisson(self, cells: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Host buffers, synchronous: cells [N,5] float64 = (Ux, Uy, Cx, Cy, p(t-1)) -> p [N] float64 = p(t-1) + dp; p(t-1) itself
+        on a priming or skipped step and on the fallback cells."""
+        return self._solver_step(self.lib.psm_solve_poisson, cells, out, False)
 
     def solve_poisson_device(self, d_cells: int, d_p: int, d_fields: int = 0, d_scalars: int = 0, stream: int = 0):
         """The same step on raw device pointers, asynchronous on ``stream``: ``d_cells`` [N,5] and ``d_p`` [N] float64;
         ``d_fields`` [3,Ny*Nx] float32 receives (result, change, next) and ``d_scalars`` [8] float64 ``POISSON_SOLVE_SCALARS``
         (0: the handle's own buffers)."""
-        self._chk(self.lib.psm_solve_poisson_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_fields or None),
-                                                    C.c_void_p(d_scalars or None), C.c_void_p(stream)))
+        self._solver_step_device(self.lib.psm_solve_poisson_device, d_cells, d_p, (d_fields, d_scalars), stream)
 
     # -- the same step for the case set of psm_set_geometry_cases (psm_solve_cases_poisson*): cells [sum N_i,5] -> p [sum N_i]
     def bind_poisson_solve_cases(self, phi: float, max_abs_delta_p: float, weighting: bool = True, apply_filter: bool = True):
@@ -791,14 +803,7 @@ class GridSurrogate:
     def solve_cases_poisson(self, cells: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
         """Host buffers, synchronous: the cases' cells concatenated in case order [sum N_i,5] float64 -> p [sum N_i] float64, per case
         what ``solve_poisson`` returns for a single mesh."""
-        a = self._solver_cells(cells)
-        if out is None:
-            out = np.empty(a.shape[0], np.float64)
-        elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
-            raise ValueError("out must be a contiguous float64 array [sum N_i]")
-        self._cases_count(a)
-        self._chk(self.lib.psm_solve_cases_poisson(self.h, _p(a, C.c_double), _p(out, C.c_double)))
-        return out
+        return self._solver_step(self.lib.psm_solve_cases_poisson, cells, out, True)
 
     def _cases_count(self, a):
         """The entries of a case set take no cell count, so the mirror checks it; without a case set the entry itself refuses."""
@@ -819,8 +824,7 @@ class GridSurrogate:
         """The same step on raw device pointers, asynchronous on ``stream``: ``d_cells`` [sum N_i,5] and ``d_p`` [sum N_i] float64;
         ``d_fields`` [3,K,Ny*Nx] float32 receives (result, change, next) and ``d_scalars`` [K,8] float64 ``POISSON_SOLVE_SCALARS`` per
         case (0: the handle's own buffers)."""
-        self._chk(self.lib.psm_solve_cases_poisson_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_fields or None),
-                                                          C.c_void_p(d_scalars or None), C.c_void_p(stream)))
+        self._solver_step_device(self.lib.psm_solve_cases_poisson_device, d_cells, d_p, (d_fields, d_scalars), stream)
 
     # -- the gradient-model step at the solver boundary (psm_solve_gradp*): cells [N,5] -> p [N] through U -> grad p -> p, no state
     GRADP_SOLVE_SCALARS = ("U", "U2", "s", "sx", "sy", "_5", "_6", "_7")
@@ -858,38 +862,23 @@ class GridSurrogate:
 
     def solve_gradp(self, cells: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
         """Host buffers, synchronous: cells [N,5] float64 = (Ux, Uy, Cx, Cy, p(t-1)) -> p [N] float64; p(t-1) on the fallback cells."""
-        a = self._solver_cells(cells)
-        if out is None:
-            out = np.empty(a.shape[0], np.float64)
-        elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
-            raise ValueError("out must be a contiguous float64 array [N]")
-        self._chk(self.lib.psm_solve_gradp(self.h, _p(a, C.c_double), a.shape[0], 0, _p(out, C.c_double)))
-        return out
+        return self._solver_step(self.lib.psm_solve_gradp, cells, out, False)
 
     def solve_gradp_device(self, d_cells: int, d_p: int, d_image: int = 0, d_gradp: int = 0, d_pgrid: int = 0, d_scalars: int = 0, stream: int = 0):
         """The same step on raw device pointers, asynchronous on ``stream``: ``d_cells`` [N,5] and ``d_p`` [N] float64; optional
         ``d_image`` [Ny,Nx,3], ``d_gradp`` [Ny,Nx,2] and ``d_pgrid`` [Ny,Nx] float32 receive the solved image, the gradient behind
         the filter and q = p / U^2 before the shift, ``d_scalars`` [8] float64 ``GRADP_SOLVE_SCALARS`` (0: the handle's own buffers)."""
-        self._chk(self.lib.psm_solve_gradp_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_image or None), C.c_void_p(d_gradp or None),
-                                                  C.c_void_p(d_pgrid or None), C.c_void_p(d_scalars or None), C.c_void_p(stream)))
+        self._solver_step_device(self.lib.psm_solve_gradp_device, d_cells, d_p, (d_image, d_gradp, d_pgrid, d_scalars), stream)
 
     def solve_cases_gradp(self, cells: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
         """Host buffers, synchronous: the cases' cells concatenated in case order [sum N_i,5] float64 -> p [sum N_i] float64, per case
         what ``solve_gradp`` returns for a single mesh."""
-        a = self._solver_cells(cells)
-        if out is None:
-            out = np.empty(a.shape[0], np.float64)
-        elif not isinstance(out, np.ndarray) or out.dtype != np.float64 or not out.flags.c_contiguous or out.shape != (a.shape[0],):
-            raise ValueError("out must be a contiguous float64 array [sum N_i]")
-        self._cases_count(a)
-        self._chk(self.lib.psm_solve_cases_gradp(self.h, _p(a, C.c_double), _p(out, C.c_double)))
-        return out
+        return self._solver_step(self.lib.psm_solve_cases_gradp, cells, out, True)
 
     def solve_cases_gradp_device(self, d_cells: int, d_p: int, d_image: int = 0, d_gradp: int = 0, d_pgrid: int = 0, d_scalars: int = 0, stream: int = 0):
         """The same step on raw device pointers: ``d_cells`` [sum N_i,5], ``d_p`` [sum N_i]; the optional outputs per case:
         ``d_image`` [K,Ny,Nx,3], ``d_gradp`` [K,Ny,Nx,2], ``d_pgrid`` [K,Ny,Nx], ``d_scalars`` [K,8]."""
-        self._chk(self.lib.psm_solve_cases_gradp_device(self.h, C.c_void_p(d_cells), C.c_void_p(d_p), C.c_void_p(d_image or None), C.c_void_p(d_gradp or None),
-                                                        C.c_void_p(d_pgrid or None), C.c_void_p(d_scalars or None), C.c_void_p(stream)))
+        self._solver_step_device(self.lib.psm_solve_cases_gradp_device, d_cells, d_p, (d_image, d_gradp, d_pgrid, d_scalars), stream)
 
     # -- the per-frame error blocks of assembled fields on the device: eight float64 sums per (frame, pair) instead of the fields
     RAW_SUMS =("n", "s1", "s2", "tmin", "tmax", "pmin", "pmax", "tnan")

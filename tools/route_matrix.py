@@ -75,6 +75,10 @@ BOUNDARY = {
     "delta_host_umax": {},                                   # psm_solve_delta from an unprimed state: the priming step, then two delta steps
     "delta_partials": {},                                    # the same three steps on the 32769 + 37 cells of solve_partials
     "cases_delta_k3": {},                                    # psm_solve_cases_delta on the three meshes of cases_k3, three steps from unprimed
+    "poisson_solve": {}, "poisson_solve_noweight": {},       # psm_solve_poisson behind SolverModule(step='poisson'): the priming step(s), then three steps
+    "poisson_cases_k3": {},                                  # psm_solve_cases_poisson on the three meshes of cases_k3
+    "gradp_solve": {}, "gradp_solve_noref": {},              # psm_solve_gradp behind SolverModule(step='gradp'), reference 'outlet' / 'none', filter on
+    "gradp_cases_k3": {},                                    # psm_solve_cases_gradp on the three meshes of cases_k3
     "mesh_to_grid": {},                                      # psm_mesh_to_grid k = 1 and 3, fill 0 / 1, on hand-made tables (130 x 131)
     "frames_to_grid": {},                                    # psm_frames_to_grid_device: 2 frames, a float64 plane, a float32 plane, a skipped column
     "block_error": {},                                       # psm_block_error behind a solve: label blocks + the per-block sums
@@ -335,6 +339,41 @@ def boundary_config(name):
             for k, p in enumerate(se.py_func(arrays)):
                 line(f"p step{step + 1} case{k}", p)
         se._sur.close()
+    elif name.startswith(("poisson_", "gradp_")):            # the two bound step kinds, through the classes that bind them
+        OBSTACLES = (dict(), dict(cx=0.55, cy=0.05, R=0.06), dict(cx=0.9, cy=-0.08, R=0.1, step=2))
+        if name.startswith("poisson_"):
+            model = synthetic.make_model("deltas", p_in=48, p_out=40, c_in=4, seed_pca=777, seed_w=5)
+            model.sdf_ch = 3
+            kw = dict(maxs=(2.7, 0.004, 0.004, 0.35, 0.005), step="poisson", phi=0.16, k=0.5, weighting="noweight" not in name, apply_filter=True)
+        else:
+            model = synthetic.make_model("gradp", p_in=8, p_out=8)
+            kw = dict(maxs=(2.5, 0.6, 0.35, 40.0, 25.0), step="gradp", apply_filter=True, sigma_field=(2.0, 3.0), sigma_weight=(2.0, 2.0),
+                      reference="none" if "noref" in name else "outlet")
+            OBSTACLES = (dict(), dict(step=2), dict(step=5))   # one obstacle (a cut the integration takes), three time levels of the fields
+        if name.endswith("_k3"):
+            mesh = [synthetic.channel_mesh(**o) for o in OBSTACLES]
+            se = SolverEnsemble(model, max_cases=4, geometry="native", **kw)
+            se.init_func(*zip(*mesh))                        # step='poisson': pushes the first frame
+            for step in range(1, 5):                         # the fields move from step to step, p is the one just returned
+                arrays = [synthetic.channel_mesh(**dict(o, step=o.get("step", 0) + step))[0] for o in OBSTACLES]
+                if step > 1:
+                    for a, p in zip(arrays, ps):
+                        a[:, 4] = p
+                ps = se.py_func(arrays)
+                for k, p in enumerate(ps):
+                    line(f"p step{step} case{k}", p)
+            se._sur.close()
+        else:
+            sm = SolverModule(model, geometry="native", **kw)
+            sm.init_func(*synthetic.channel_mesh())
+            p = None
+            for step in range(1, 5):                         # with the weighting the first call is a priming step too
+                a = synthetic.channel_mesh(step=step)[0]
+                if p is not None:
+                    a[:, 4] = p
+                p = sm.py_func(a)
+                line(f"p step{step}", p)
+            sm._sur.close()
     elif name == "mesh_to_grid":
         rng = np.random.default_rng(5)
         with GridSurrogate(synthetic.make_model("deltas", p_in=32, p_out=32), HY, HX, 1) as sur:
