@@ -1,5 +1,6 @@
 // psm_alloc.cpp -- see psm_alloc.h
 #include "psm_alloc.h"
+#include "psm_switches.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -12,10 +13,7 @@ struct Guarded { void* va; size_t reserved, mapped; hipMemGenericAllocationHandl
 std::mutex g_mu;
 std::unordered_map<void*, Guarded> g_live;
 
-int guard_kind() {                                                 // 0 off, 1 unmapped granule BEHIND the buffer, 2 in FRONT of it
-  static const int k = [] { const char* e = getenv("PSM_GUARD_PAGES"); return (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0; }();
-  return k;
-}
+int guard_kind() { return psm_switches_process().guard_pages; }   // 0 off, 1 unmapped granule BEHIND the buffer, 2 in FRONT of it
 bool guard_mode() { return guard_kind() != 0; }
 }  // namespace
 
@@ -51,14 +49,14 @@ hipError_t psm_dev_malloc(void** p, size_t bytes) {
   }
   // PSM_GUARD_FILL=<byte>: fill the whole mapping (memory from hipMemCreate is not cleared) -- 0 mimics the fresh pages hipMalloc
   // usually hands out, 255 poisons: floats read as NaN, indices as -1, so a kernel that depends on what it never wrote shows
-  if (const char* f = getenv("PSM_GUARD_FILL")) {
-    if ((e = hipMemset(g.va, atoi(f) & 255, g.mapped)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
+  if (const int fill = psm_switches_process().guard_fill; fill >= 0) {
+    if ((e = hipMemset(g.va, fill, g.mapped)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) {
       (void)hipMemUnmap(g.va, g.mapped); (void)hipMemRelease(g.handle); (void)hipMemAddressFree(base, g.reserved); return e;
     }
   }
   const size_t used = (bytes + 15) / 16 * 16;
   *p = guard_kind() == 2 ? g.va : (char*)g.va + (g.mapped - used);   // kind 1: the buffer ends where the mapping ends; kind 2: it starts where it starts
-  if (getenv("PSM_GUARD_LOG")) fprintf(stderr, "psm_alloc: + %p %zu B (va %p, mapped %zu)\n", *p, bytes, g.va, g.mapped);
+  if (psm_switches_process().guard_log) fprintf(stderr, "psm_alloc: + %p %zu B (va %p, mapped %zu)\n", *p, bytes, g.va, g.mapped);
   std::lock_guard<std::mutex> lk(g_mu);
   g_live[*p] = g;
   return hipSuccess;
@@ -78,7 +76,7 @@ hipError_t psm_dev_free(void* p) {
     g = it->second;
     g_live.erase(it);
   }
-  if (getenv("PSM_GUARD_LOG")) fprintf(stderr, "psm_alloc: - %p (va %p, mapped %zu)\n", p, g.va, g.mapped);
+  if (psm_switches_process().guard_log) fprintf(stderr, "psm_alloc: - %p (va %p, mapped %zu)\n", p, g.va, g.mapped);
   hipError_t e = hipDeviceSynchronize();                          // hipFree's implicit synchronisation
   (void)hipMemUnmap(g.va, g.mapped);
   (void)hipMemRelease(g.handle);

@@ -68,7 +68,7 @@ static int mesh_sequence(psm_handle* h, int64_t n, hipStream_t st) {
   HIPCHK(h, psm_launch_stage_cells(m.pinned_cells_dev, m.d_cells, n, m.d_umax_part, &n_partials, st));
   HIPCHK(h, psm_launch_to_grid(to_grid_args(h, nullptr, 0.0, n_partials), st));
   h->in_mesh_solve = true;
-  int rc = launch_all(h, h->ws0, h->d_grid_stage, 1, h->d_fields_stage, h->d_ones, st, nullptr);
+  int rc = launch_all(h, h->ws0, h->d_grid_stage, 1, h->d_fields_stage, h->d_ones, st, nullptr, psm_switches_per_solve());
   h->in_mesh_solve = false;
   if (rc) return rc;
   HIPCHK(h, psm_launch_to_mesh(to_mesh_args(h, m.d_umax, 0.0, m.pinned_p_dev), st));
@@ -164,7 +164,7 @@ int psm_set_geometry(psm_handle* h, int64_t n_cells, int32_t ny, int32_t nx, con
   h->have_geometry = true;
   // The mesh entry builds its grid from THIS sdfunct at every step, so the geometry of psm_solve is fixed from here
   // on: bind it (scope: psm_solve only -- grid-native solves on the same handle stay general until psm_bind_geometry).
-  if (h->cfg.c_in == 3 && h->cfg.sdf_channel == 2 && t.have_g2m && getenv("PSM_NO_BIND") == nullptr) {
+  if (h->cfg.c_in == 3 && h->cfg.sdf_channel == 2 && t.have_g2m && !psm_switches_at_bind().no_bind) {
     hipError_t ec = psm_copy_h2d(h->d_grid_stage, t.sdf_image.data(), t.sdf_image.size() * sizeof(float));   // the SDF channel exactly as psm_to_grid_kernel writes it
     if (ec != hipSuccess) { free_geometry(h); return fail(h, PSM_ERR_HIP, std::string("psm_copy_h2d(sdf image): ") + hipGetErrorString(ec)); }
     h->bound_scope = 1;                                      // before the bind: this scope builds no SDF-fold tables
@@ -239,17 +239,10 @@ int step_end(psm_handle* h, MeshBuffers& b, int64_t total_cells, const char* beg
 }
 
 // ---- the route of a step on the single mesh, chosen once (like choose_route of a solve, psm_api_solve.cpp) --------------------------
-// Its environment switches, read here and nowhere else.  Once per process, at the first step: PSM_MESH_GRAPH (registered + mapped
-// buffers: 0 = the staged route, 1 = one graph replay, 2 = the same sequence as plain launches, the measured default, DESIGN.md
-// section 5), PSM_MESH_STAGE_MAX (largest mesh psm_stage_cells_kernel reads over PCIe), PSM_DEVICE_UMAX (set: small meshes reduce
-// U_max by psm_umax_kernel, not on the host).  At every psm_pin_buffers: PSM_NO_DIRECT_IN / _OUT (set: no mapped address, DMA only).
-struct MeshEnv { int graph_mode; int64_t stage_max; bool device_umax; };
-static const MeshEnv& mesh_env() {
-  static const MeshEnv env{getenv("PSM_MESH_GRAPH") ? atoi(getenv("PSM_MESH_GRAPH")) : 2,
-                           getenv("PSM_MESH_STAGE_MAX") ? atoll(getenv("PSM_MESH_STAGE_MAX")) : PSM_MESH_STAGE_MAX_DEFAULT, getenv("PSM_DEVICE_UMAX") != nullptr};
-  return env;
-}
-static bool mesh_env_direct(bool out) { return getenv(out ? "PSM_NO_DIRECT_OUT" : "PSM_NO_DIRECT_IN") == nullptr; }
+// Its switches, from the handle's table (psm_create): PSM_MESH_GRAPH (registered + mapped buffers: 0 = the staged route, 1 = one
+// graph replay, 2 = the same sequence as plain launches, the measured default), PSM_MESH_STAGE_MAX (largest
+// mesh psm_stage_cells_kernel reads over PCIe), PSM_DEVICE_UMAX (set: small meshes reduce U_max by psm_umax_kernel, not on the
+// host).  At every psm_pin_buffers: PSM_NO_DIRECT_IN / _OUT (set: no mapped address, DMA only).
 
 // mapped_*: both arrays registered (psm_pin_buffers) and mapped -- psm_stage_cells_kernel reads the cells over PCIe and takes the
 // partial maxima of U_max on the way (no DMA-engine copy, no host pass, U_max never leaves the device: to_grid reduces the partials
@@ -262,10 +255,10 @@ enum class MeshRouteKind { mapped_graph, mapped_plain, staged };
 enum class UmaxFrom { none, host, device_scalar, partials };
 struct MeshRoute { MeshRouteKind kind; UmaxFrom umax; bool direct_p; };   // direct_p: to_mesh stores p over PCIe into the registered output, no D2H copy
 static MeshRoute choose_mesh_route(const psm_handle* h, const double* cells, int64_t n, const double* p_out, bool delta) {
-  const MeshEnv& env = mesh_env();
+  const PsmSwitches::AtCreate& env = h->sw.at_create;
   const MeshSingle& m = h->mesh;
-  if (!delta && env.graph_mode != 0 && h->timed_kernel < 0 && n <= env.stage_max && cells == m.pinned_cells && m.pinned_cells_dev && p_out == m.pinned_p && m.pinned_p_dev)
-    return MeshRoute{env.graph_mode == 2 ? MeshRouteKind::mapped_plain : MeshRouteKind::mapped_graph, UmaxFrom::partials, true};
+  if (!delta && env.mesh_graph != 0 && h->timed_kernel < 0 && n <= env.mesh_stage_max && cells == m.pinned_cells && m.pinned_cells_dev && p_out == m.pinned_p && m.pinned_p_dev)
+    return MeshRoute{env.mesh_graph == 2 ? MeshRouteKind::mapped_plain : MeshRouteKind::mapped_graph, UmaxFrom::partials, true};
   const UmaxFrom umax = delta && !h->delta.primed ? UmaxFrom::none : n > 32768 ? UmaxFrom::partials : env.device_umax ? UmaxFrom::device_scalar : UmaxFrom::host;
   return MeshRoute{MeshRouteKind::staged, umax, p_out == m.pinned_p && m.pinned_p_dev != nullptr};
 }
@@ -398,7 +391,7 @@ int psm_set_geometry_cases(psm_handle* h, int32_t n_cases, const int64_t* n_cell
   m.h_sdf = t.sdf;                                          // the K raw sdfuncts, for psm_bind_gradp_solve_cases
   // The entry builds its K images from THESE sdfuncts at every step: bind the K geometries for psm_solve_cases* only (scope 1,
   // like psm_set_geometry binds its one; a single case takes the single-case binding and with it the route of psm_solve).
-  if (h->cfg.sdf_channel == 2 && getenv("PSM_NO_BIND") == nullptr) {
+  if (h->cfg.sdf_channel == 2 && !psm_switches_at_bind().no_bind) {
     HIPCHK(h, psm_copy_h2d(h->d_grid_stage, t.sdf_image.data(), t.sdf_image.size() * sizeof(float)));
     h->bound_scope = 1;
     rc = bind_geometry_device(h, h->d_grid_stage, n_cases);
@@ -540,12 +533,13 @@ int psm_pin_buffers(psm_handle* h, const double* cells, double* p_out) {
   HIPCHK(h, hipSetDevice(h->cfg.device));
   HIPCHK(h, hipStreamSynchronize(h->stream));
   unpin_buffers(h);
+  const PsmSwitches::AtBind sw = psm_switches_at_bind();
   if (cells) {
     hipError_t e = hipHostRegister((void*)cells, (size_t)h->n_cells * 5 * sizeof(double), hipHostRegisterDefault);
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(h, PSM_ERR_HIP, std::string("hipHostRegister(cells): ") + hipGetErrorString(e)); }
     h->mesh.pinned_cells = cells;
     void* dc = nullptr;                                   // mapped address: lets psm_stage_cells_kernel read the cells from the host array
-    if (hipHostGetDevicePointer(&dc, (void*)cells, 0) == hipSuccess && mesh_env_direct(false)) h->mesh.pinned_cells_dev = (const double*)dc;
+    if (hipHostGetDevicePointer(&dc, (void*)cells, 0) == hipSuccess && !sw.no_direct_in) h->mesh.pinned_cells_dev = (const double*)dc;
     else (void)hipGetLastError();
   }
   if (p_out) {
@@ -553,7 +547,7 @@ int psm_pin_buffers(psm_handle* h, const double* cells, double* p_out) {
     if (e != hipSuccess) { (void)hipGetLastError(); unpin_buffers(h); return fail(h, PSM_ERR_HIP, std::string("hipHostRegister(p_out): ") + hipGetErrorString(e)); }
     h->mesh.pinned_p = p_out;
     void* dp = nullptr;                                   // mapped address: lets psm_to_mesh_kernel store p into the host array
-    if (hipHostGetDevicePointer(&dp, (void*)p_out, 0) == hipSuccess && mesh_env_direct(true)) h->mesh.pinned_p_dev = (double*)dp;
+    if (hipHostGetDevicePointer(&dp, (void*)p_out, 0) == hipSuccess && !sw.no_direct_out) h->mesh.pinned_p_dev = (double*)dp;
     else (void)hipGetLastError();
   }
   return PSM_OK;

@@ -11,23 +11,15 @@ namespace psm_impl {
 // 300 us), after which the thread blocks, and never when this process shares its cores with more MPI / torchrun
 // ranks than it has cores (a spinning rank would then steal the time of another rank's solver thread).
 // PSM_SYNC_BLOCK=1 forces blocking waits, PSM_SYNC_BLOCK=0 forces the bounded spin.
-static int local_ranks_from_env() {
-  for (const char* k : {"OMPI_COMM_WORLD_LOCAL_SIZE", "MPI_LOCALNRANKS", "PMI_LOCAL_SIZE", "SLURM_NTASKS_PER_NODE", "LOCAL_WORLD_SIZE"}) {
-    const char* v = getenv(k);
-    if (v && atoi(v) > 0) return atoi(v);
-  }
-  return 1;
-}
-
 bool sync_blocks() {
   static const bool b = [] {
-    const char* e = getenv("PSM_SYNC_BLOCK");
-    if (e) return e[0] != '0';
+    const int forced = psm_switches_process().sync_block;
+    if (forced >= 0) return forced != 0;
     cpu_set_t set;
     int cores = 0;
     if (sched_getaffinity(0, sizeof(set), &set) == 0) cores = CPU_COUNT(&set);
     if (cores <= 0) cores = (int)std::thread::hardware_concurrency();
-    return local_ranks_from_env() > cores;       // oversubscribed: sleep instead of spinning
+    return psm_switches_process().local_ranks > cores;       // oversubscribed: sleep instead of spinning
   }();
   return b;
 }
@@ -298,8 +290,8 @@ int psm_create(const psm_config* cfg, psm_handle** out) {
   // replay per solve costs ~5 us more per solve than the same kernels launched eagerly (a gap
   // of ~8 us between consecutive replays against back-to-back kernels), and the host enqueues
   // the ~9 launches faster than the GPU retires them.  PSM_GRAPH=1 selects graph replay.
-  const char* ug = getenv("PSM_GRAPH");
-  h->use_graph = (ug && ug[0] == '1');
+  h->sw.at_create = psm_switches_at_create();
+  h->use_graph = h->sw.at_create.graph;
   if (hipSetDevice(cfg->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
     delete h;
     return fail(nullptr, PSM_ERR_HIP, "cannot create a stream on the device");
@@ -308,10 +300,11 @@ int psm_create(const psm_config* cfg, psm_handle** out) {
   // guard of the bound-geometry contract: one word per workspace in mapped pinned memory (host-side detection; without a
   // mapped view the device-side NaN poisoning still works) and the zero the unguarded solves read as their flag
   {
-    const char* ng = getenv("PSM_NO_GUARD");
-    h->guard_on = !(ng && ng[0] == '1');
-    h->x6_mode = getenv("PSM_X6") ? atoi(getenv("PSM_X6")) : -1;
-    h->keep_hidden = getenv("PSM_KEEP_HIDDEN") && atoi(getenv("PSM_KEEP_HIDDEN")) != 0;
+    h->guard_on = h->sw.at_create.guard;
+    h->x6_mode = h->sw.at_create.x6;
+    h->keep_hidden = h->sw.at_create.keep_hidden;
+    h->ring_slots = h->sw.at_create.ring_use;
+    h->ring_graph = h->sw.at_create.ring_graph ? 1 : 0;
     if (hipHostMalloc((void**)&h->h_guard, 64 * sizeof(int), hipHostMallocMapped) == hipSuccess) {
       memset(h->h_guard, 0, 64 * sizeof(int));
       if (hipHostGetDevicePointer((void**)&h->m_guard, h->h_guard, 0) != hipSuccess) { (void)hipGetLastError(); h->m_guard = nullptr; }

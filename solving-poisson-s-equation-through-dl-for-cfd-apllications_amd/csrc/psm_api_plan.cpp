@@ -185,7 +185,7 @@ int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases) {
   // the chain runs row-parallel in one wave (lane = block column); more than 64 blocks take the two-launch form of the
   // case batches (chain launch + chunked decode + paste), f32 only
   const bool small = h->B <= 64;
-  if (h->plan.cp.n_x >= 64 || h->B > 4096 || h->ld_out > 128 || nl < 2 || !h->d_comp_nat || getenv("PSM_NO_FUSED_ASSEMBLE") != nullptr)
+  if (h->plan.cp.n_x >= 64 || h->B > 4096 || h->ld_out > 128 || nl < 2 || !h->d_comp_nat || h->sw.at_plan.no_fused_assemble)
     return fail(h, PSM_ERR_UNSUPPORTED, "geometry binding needs < 64 block columns, <= 128 output components and a hidden layer");
   // bf16: the decode rounds `res`, so the head layer cannot be folded into the tables: rows over the ld_out components
   const int Kh = bf16 ? h->ld_out : h->dense[nl - 1].Kpad, C = h->cfg.c_out;
@@ -251,7 +251,7 @@ int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases) {
   // strips; a single U_to_gradP case: 3.7 MB); a batch of U_to_gradP cases (1800 rows per case against 728) keeps the
   // chain launch.
   const double cf_bytes = (double)n_cases * C * h->B * h->B * Kh * 4.0, strip_bytes = (double)all * Kh * 4.0;
-  if (h->B <= 64 && getenv("PSM_NO_CLOSED_FORM") == nullptr && cf_bytes <= std::max(8.0e6, 1.5 * strip_bytes)) {
+  if (h->B <= 64 && !h->sw.at_plan.no_closed_form && cf_bytes <= std::max(8.0e6, 1.5 * strip_bytes)) {
     if ((rc = build_closed_form(h, n_cases, rows, Kh))) return rc;
     if (h->bound_cf && (rc = dev_alloc(h, &h->ws0.d_dots2, h->cf_rows_all))) return rc;
   }
@@ -367,18 +367,10 @@ int psm_plan_grid(psm_handle* h, int32_t ny, int32_t nx) {
     h->h_shiftW = w;
   }
   HIPCHK(h, hipDeviceSynchronize());
-  {
-    const char* ds = getenv("PSM_DEBUG_SKIP");
-    h->debug_skip = ds ? atoi(ds) : 0;
-  }
-  {
-    const char* nr = getenv("PSM_NO_FUSED_REDUCE");
-    h->fuse_reduce_dense1 = !(nr && nr[0] == '1');
-  }
-  {
-    const char* nf = getenv("PSM_NO_FUSED_ASSEMBLE");
-    h->fused_assemble = (h->B <= 64 && h->plan.cp.n_x < 64) && !(nf && nf[0] == '1');
-  }
+  h->sw.at_plan = psm_switches_at_plan();
+  h->debug_skip = h->sw.at_plan.debug_skip;
+  h->fuse_reduce_dense1 = !h->sw.at_plan.no_fused_reduce;
+  h->fused_assemble = (h->B <= 64 && h->plan.cp.n_x < 64) && !h->sw.at_plan.no_fused_assemble;
   h->planned = true;
   return PSM_OK;
 }

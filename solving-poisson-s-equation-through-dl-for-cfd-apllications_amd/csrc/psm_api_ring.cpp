@@ -26,12 +26,7 @@ static int ring_init(psm_handle* h) {
   if (h->ring_ready) return PSM_OK;
   const size_t npix = (size_t)h->Ny * h->Nx;
   const size_t gin = (size_t)h->cfg.max_cases * npix * h->cfg.c_in, gout = (size_t)h->cfg.max_cases * npix * h->cfg.c_out;
-  const char* rg = getenv("PSM_RING_GRAPH");
-  h->ring_graph = (rg && rg[0] == '0') ? 0 : 1;
-  const char* ru = getenv("PSM_RING_USE");
-  h->ring_slots = (ru && atoi(ru) >= 1 && atoi(ru) <= psm_handle::SLOTS) ? atoi(ru) : psm_handle::SLOTS;
-  const char* rp = getenv("PSM_RING_PULL");
-  h->ring_dma = (rp && rp[0] == '1') ? 0 : 1;
+  h->ring_dma = h->sw.at_create.ring_pull ? 0 : 1;
   for (auto& s : h->slot) {
     HIPCHK(h, hipHostMalloc((void**)&s.h_in, gin * sizeof(float), hipHostMallocMapped));
     HIPCHK(h, hipHostMalloc((void**)&s.h_out, gout * sizeof(float), hipHostMallocMapped));
@@ -62,19 +57,19 @@ static int ring_init(psm_handle* h) {
 //    dst_dev -- kernels only;
 //  DMA form (src_dev == nullptr): hipMemcpyAsync H2D from src, kernels, hipMemcpyAsync D2H into dst (copies optional:
 //    with_copies = false enqueues the kernels alone).
-static int ring_sequence(psm_handle* h, psm_handle::Slot& s, int n_cases, bool scale, const float* src_dev, float* dst_dev,
+static int ring_sequence(psm_handle* h, psm_handle::Slot& s, int n_cases, bool scale, const PsmSwitches::PerSolve& ps, const float* src_dev, float* dst_dev,
                          const float* src, float* dst, bool with_copies) {
   const size_t npix = (size_t)h->Ny * h->Nx;
   const size_t nin = (size_t)n_cases * npix * h->cfg.c_in, nout = (size_t)n_cases * npix * h->cfg.c_out;
   const int M = n_cases * h->B;
   if (src_dev) {
-    static const int dbg = getenv("PSM_RING_DEBUG") ? atoi(getenv("PSM_RING_DEBUG")) : 0;   // timing experiments only: 1 no stage-in, 2 field stays on the device
+    const int dbg = h->sw.at_create.ring_debug;   // timing experiments only: 1 no stage-in, 2 field stays on the device
     if (!(dbg & 1)) HIPCHK(h, psm_launch_stage_in(src_dev, s.d_in, nin, scale ? s.m_rs : nullptr, s.ws.d_row_scale, M, h->B, s.st));
-    return launch_all(h, s.ws, s.d_in, n_cases, (dbg & 2) ? s.d_out : dst_dev, scale ? s.ws.d_row_scale : h->d_ones, s.st, nullptr);
+    return launch_all(h, s.ws, s.d_in, n_cases, (dbg & 2) ? s.d_out : dst_dev, scale ? s.ws.d_row_scale : h->d_ones, s.st, nullptr, ps);
   }
   if (with_copies) HIPCHK(h, hipMemcpyAsync(s.d_in, src, nin * sizeof(float), hipMemcpyHostToDevice, s.st));
   if (scale) HIPCHK(h, hipMemcpyAsync(s.ws.d_row_scale, s.h_rs, (size_t)M * sizeof(float), hipMemcpyHostToDevice, s.st));
-  int rc = launch_all(h, s.ws, s.d_in, n_cases, s.d_out, scale ? s.ws.d_row_scale : h->d_ones, s.st, nullptr);
+  int rc = launch_all(h, s.ws, s.d_in, n_cases, s.d_out, scale ? s.ws.d_row_scale : h->d_ones, s.st, nullptr, ps);
   if (rc) return rc;
   if (with_copies) HIPCHK(h, hipMemcpyAsync(dst, s.d_out, nout * sizeof(float), hipMemcpyDeviceToHost, s.st));
   return PSM_OK;
@@ -106,10 +101,11 @@ static int ring_launch(psm_handle* h, psm_handle::Slot& s, int n_cases, const fl
       for (int c = 0; c < n_cases; ++c)
         for (int b = 0; b < h->B; ++b) s.h_rs[c * h->B + b] = out_scale[c];
   }
-  const int key = sequence_key(h, n_cases, scale, true);
+  const PsmSwitches::PerSolve ps = psm_switches_per_solve();     // this ticket's one read: the key and the route see the same values
+  const int key = sequence_key(h, n_cases, scale, ps, true);
   const bool graphs = h->ring_graph && h->timed_kernel < 0;
   auto capture = [&](const float* from_dev, float* to_dev, bool with_copies, hipGraphExec_t* out) {   // on the slot's own buffers
-    return capture_graph(h, s.st, "ring", [&] { return ring_sequence(h, s, n_cases, scale, from_dev, to_dev, s.h_in, s.h_out, with_copies); }, out);
+    return capture_graph(h, s.st, "ring", [&] { return ring_sequence(h, s, n_cases, scale, ps, from_dev, to_dev, s.h_in, s.h_out, with_copies); }, out);
   };
   int rc;
   if (src_dev && graphs && own) {                        // pull form on the slot's own buffers: the whole ticket is one replay
@@ -120,11 +116,11 @@ static int ring_launch(psm_handle* h, psm_handle::Slot& s, int n_cases, const fl
     }
     HIPCHK(h, hipGraphLaunch(s.g_full, s.st));
   } else if (src_dev || !graphs) {                       // pull form on caller memory (pointers differ per ticket) / plain launches
-    if ((rc = ring_sequence(h, s, n_cases, scale, src_dev, dst_dev, src, dst, true))) return rc;
+    if ((rc = ring_sequence(h, s, n_cases, scale, ps, src_dev, dst_dev, src, dst, true))) return rc;
   } else {
     // Default: the two copies are hipMemcpyAsync calls on the slot's stream (DMA engines; inside a graph they would
     // become blit kernels, which read host memory at ~20 GB/s), the kernels in between are one graph replay.
-    static const int dbg = getenv("PSM_RING_DEBUG") ? atoi(getenv("PSM_RING_DEBUG")) : 0;   // timing experiments only: 1 no H2D, 2 no D2H
+    const int dbg = h->sw.at_create.ring_debug;   // timing experiments only: 1 no H2D, 2 no D2H
     if (!(dbg & 1)) HIPCHK(h, hipMemcpyAsync(s.d_in, src, gin, hipMemcpyHostToDevice, s.st));
     if (!s.g_kern || s.g_kern_key != key) {
       if (s.g_kern) { (void)hipGraphExecDestroy(s.g_kern); s.g_kern = nullptr; }

@@ -22,21 +22,19 @@ namespace psm_impl {
 // Below 96 rows (4 cases: 37.6 against 38.0 us) the launch is bound by the basis stream and the one-slab-per-slice form stays.
 // PSM_ENCODE_KGROUPS=n forces the group count (1: the old form), PSM_ENCODE_MT_MIN_ROWS the first row count.
 static int encode_groups(const psm_handle* h, int Mpad) {
-  static const int min_rows = getenv("PSM_ENCODE_MT_MIN_ROWS") ? atoi(getenv("PSM_ENCODE_MT_MIN_ROWS")) : 96;
-  if (h->cfg.precision == PSM_PRECISION_BF16 || h->NT > 4 || Mpad % 32 != 0 || Mpad < min_rows || ((PSM_PIX_PER_SLICE * h->cfg.c_in) % 32) != 0) return 1;
+  if (h->cfg.precision == PSM_PRECISION_BF16 || h->NT > 4 || Mpad % 32 != 0 || Mpad < h->sw.at_create.encode_mt_min_rows || ((PSM_PIX_PER_SLICE * h->cfg.c_in) % 32) != 0) return 1;
   if (h->x6_mode >= 0 && !(h->x6_mode & 1)) return 1;
   // psm_encode_x6_mt_kernel addresses the grids of the whole case batch with unsigned 32-bit BYTE offsets from a scalar base
   if ((int64_t)h->cfg.max_cases * h->Ny * h->Nx * h->cfg.c_in >= ((int64_t)1 << 30)) return 1;
-  static const int kg_env = getenv("PSM_ENCODE_KGROUPS") ? atoi(getenv("PSM_ENCODE_KGROUPS")) : 0;
   const int row_groups = (Mpad + PSM_ENC_MT_ROWS - 1) / PSM_ENC_MT_ROWS;
   static const int by_rg[9] = {0, 256, 256, 256, 128, 256, 128, 64, 64};
   int groups = row_groups <= 8 ? by_rg[row_groups] : std::max(1, 512 / row_groups);
   groups = std::max((h->n_slices + 7) / 8, std::min(h->n_slices, groups));
-  if (kg_env > 0) groups = kg_env;
+  if (h->sw.at_create.encode_kgroups > 0) groups = h->sw.at_create.encode_kgroups;
   return (groups > 1 && groups <= h->n_slices && (h->n_slices + groups - 1) / groups <= 8) ? groups : 1;
 }
 // Slabs the float32 / x6 encode launch (psm_launch_encode, psm_encode.hip) writes for these arguments = what the reduce behind it must sum.
-// ONE place mirrors the launcher's three branches (the count used to be rebuilt step by step inside launch_all).
+// The launcher's three branches, in its order; psm_encode_pairs is a predicate of the arguments alone, so this is the one place the rule lives.
 static int encode_slabs(const PsmEncodeArgs& a) {
   const int n_slices = a.S * a.S / PSM_PIX_PER_SLICE;
   if (a.x6 && a.kgroup > 1) return a.kgroup;              // M-tiled x6 form: one slab per K group
@@ -65,11 +63,10 @@ bool bound_applies(const psm_handle* h, int n_cases) {
 // The SDF fold applies to a solve of this many cases (psm_handle.h): a float32 single case of one row tile on a geometry bound with
 // psm_bind_geometry (whose guard riders then check the SDF channel's values; not psm_solve's own binding, whose grids nobody checks),
 // float32 MFMA arithmetic.  PSM_SDF_FOLD=0 switches it off; read per solve, and part of sequence_key.
-bool fold_applies(const psm_handle* h, int n_cases) {
+bool fold_applies(const psm_handle* h, int n_cases, const PsmSwitches::PerSolve& ps) {
   if (!(bound_applies(h, n_cases) && n_cases == 1 && h->bound_scope == 2 && h->fold_bound && h->d_bpack_fold && h->d_ib_fold && h->d_sdf_bound)) return false;
   if (h->cfg.precision != PSM_PRECISION_F32 || h->NT > 4 || round_up(h->B, 32) != 32 || (h->x6_mode >= 0 && (h->x6_mode & 1))) return false;
-  const char* e = getenv("PSM_SDF_FOLD");
-  return !(e && atoi(e) == 0);
+  return ps.sdf_fold;
 }
 
 static PsmEncodeArgs encode_args(const psm_handle* h, const Workspace& w, const SolveRoute& r, const float* d_grid) {
@@ -80,12 +77,12 @@ static PsmEncodeArgs encode_args(const psm_handle* h, const Workspace& w, const 
   ea.M = r.M; ea.Mpad = r.Mpad; ea.NT = h->NT; ea.ldp = h->ld_in; ea.S = h->S; ea.c_in = h->cfg.c_in;
   ea.aligned = r.aligned; ea.whole = r.whole; ea.x6 = r.x6; ea.kgroup = r.kgroup;
   if (r.kgroup > 1) ea.bpack_x6 = h->d_bpack_x6;
-  ea.pairs_ok = r.bf16 ? 0 : 1;   // a single case of four component tiles: two K slices per workgroup, half the slabs (psm_encode_pair_kernel)
+  ea.pairs_ok = (!r.bf16 && h->sw.at_create.encode_pairs) ? 1 : 0;   // PSM_ENCODE_PAIRS=0 keeps one slab per slice.  A single case of four component tiles: two K slices per workgroup, half the slabs (psm_encode_pair_kernel)
   return ea;
 }
 
 // Makes no HIP call and writes nothing to the handle.  Runs when launches are enqueued or captured, never on a graph replay.
-SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_grid, int n_cases, bool profiled) {
+SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_grid, int n_cases, bool profiled, const PsmSwitches::PerSolve& ps) {
   SolveRoute r;
   const int nl = (int)h->dense.size();
   r.n_cases = n_cases; r.M = n_cases * h->B; r.Mpad = round_up(r.M, 32);
@@ -101,13 +98,17 @@ SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_
 
   r.stamp_encode = h->timed_kernel == PSM_K_ENCODE && !profiled;   // dominant kernel: dispatch-level begin / end stamps (no marker packets around the launch)
   r.aligned = (h->plan_aligned && (reinterpret_cast<uintptr_t>(d_grid) & 15) == 0) ? 1 : 0;
-  { static const bool chunked = getenv("PSM_ENCODE_CHUNKED") != nullptr; r.whole = chunked ? 0 : 1; }
+  r.whole = h->sw.at_create.encode_chunked ? 0 : 1;
   // arithmetic of the encode contraction: exact-float32 MFMA for a single row tile (one case: the launch is bound by the basis
   // stream, the matrix phase is short), the x6 form (six bf16 MFMA terms of exactly split operands, float32 accuracy,
   // psm_encode_x6_kernel) from two row tiles up, where the matrix phase is the longest serial phase of the launch
   // (8 cases: 17.6 -> 15.5 us, 64 cases: 75 -> 60 us).  PSM_X6=0 / 1 forces float32 / x6 everywhere.
   r.x6 = h->x6_mode < 0 ? (r.Mpad > 32 ? 1 : 0) : ((h->x6_mode & 1) ? 1 : 0);
-  r.fold = r.bound && !r.bf16 && !r.x6 && r.Mpad == 32 && fold_applies(h, n_cases);
+  // Negative result, kept as a knob: two workgroups per slice of the x6 form (64 rows each, half the LDS, two per CU so that one's
+  // matrix phase covers the other's load latency) -- 17.7 against 15.0 us at 8 cases, 21.8 against 17.6 us at 12: the launch is bound
+  // by its streams, and the split reads the basis slice twice.  PSM_ENCODE_ROWSPLIT=1 selects it.
+  r.row_wgs = (r.x6 && h->sw.at_create.encode_rowsplit && r.Mpad > 64 && r.Mpad <= 32 * PSM_MT_CHUNK) ? 2 : 1;
+  r.fold = r.bound && !r.bf16 && !r.x6 && r.Mpad == 32 && fold_applies(h, n_cases, ps);
   // Large case batches (>= 32 cases of 9 blocks): the M-tiled, wave-specialised x6 form (encode_groups / ensure_encode_aux)
   const int groups = (r.x6 && !r.bf16) ? encode_groups(h, r.Mpad) : 1;
   r.kgroup = (groups > 1 && h->d_bpack_x6) ? groups : 1;
@@ -120,8 +121,7 @@ SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_
   // (PsmDenseArgs::in_packed / out_packed): the consumer's row loads are then contiguous KiBs -- 64 cases: 10.0 -> 8.4 us per hidden
   // layer, 32 cases: 6.7 -> 5.2 (profiles/r06_case_batch.txt).  Not with a LayerNormalization behind the producer (its kernel and the
   // fused form read rows), not for bf16 handles, not in front of the Conv1D head.  PSM_DENSE_PACKED=0 keeps rows everywhere.
-  static const bool packed_env = !(getenv("PSM_DENSE_PACKED") && atoi(getenv("PSM_DENSE_PACKED")) == 0);
-  bool pack = packed_env && r.Mpad > 128 && !r.bf16;
+  bool pack = h->sw.at_create.dense_packed && r.Mpad > 128 && !r.bf16;
   for (const DenseLayer& q : h->dense) if (q.ln) pack = false;       // densePCA_attention: its normalisations (and their residuals) read rows
   r.packed.assign(nl, 0);
   for (int l = 0; pack && l < nl - 1; ++l) r.packed[l] = h->dense[l].ldw % 16 == 0 && h->dense[l + 1].Kp <= h->dense[l].ldw;
@@ -130,23 +130,28 @@ SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_
   // rows in the prologue, the residual of NNs.py:64 in its epilogue) -- no launch; the last one, whose consumers are the head,
   // the strip-dot riders and the introspection entries, finishes its activation with psm_layernorm_kernel.  PSM_LN_FUSE=0
   // launches every normalisation on its own.
-  const char* ln_env = getenv("PSM_LN_FUSE");            // read per solve (diagnostic; the tests switch it in-process)
-  r.ln_fuse = !(ln_env && atoi(ln_env) == 0);
+  r.ln_fuse = ps.ln_fuse;                                // read per solve (diagnostic; the tests switch it in-process), part of sequence_key
   // Large case batches: the guard workgroups (one per 4096 pixels: 1024 for 64 cases, 50 MB of grid to look at again) are dealt
   // evenly over the hidden-layer launches and the head launch instead of all riding behind the head (64 cases: 14.9 us for a
   // 4.3 us layer).  PSM_GUARD_SPREAD=0 keeps them behind the head.
-  static const bool spread_env = !(getenv("PSM_GUARD_SPREAD") && atoi(getenv("PSM_GUARD_SPREAD")) == 0);
   r.rider_carriers = nl - 1 - (r.fuse1 ? 1 : 0);       // hidden layers launched through psm_launch_dense
-  r.spread = r.guard && spread_env && r.guard_wgs > 256 && r.rider_carriers > 0;
+  r.spread = r.guard && h->sw.at_create.guard_spread && r.guard_wgs > 256 && r.rider_carriers > 0;
   r.rider_share = r.spread ? r.guard_wgs / (r.rider_carriers + 1) : 0;
 
   // decode + paste on a bound geometry: x6 arithmetic by default (single case 8.44 -> 8.16 us, 8 cases 10.2 -> 8.8 us; same
   // accuracy as the float32 MFMA, tools/x6_check.py); PSM_X6 bit 1 = 0 keeps v_mfma_f32_32x32x2_f32
   r.decode_x6 = (r.bound && (h->x6_mode < 0 || (h->x6_mode & 2))) ? 1 : 0;
   r.one_launch_tail = r.bound && n_cases == 1 && h->B <= 64;
-  static const bool bufst = !(getenv("PSM_PASTE_BUFFER_STORES") && atoi(getenv("PSM_PASTE_BUFFER_STORES")) == 0);
+  // Case batches (psm_launch_decode_paste_batch): one 32-row tile per chunk, the row tiles spread over up to `decode_wgs / column
+  // workgroups` row groups (grid.y): measured against two and three tiles per chunk (fewer passes over the basis slice, but 2-3x the
+  // LDS and registers per workgroup) at 8 ... 64 cases and both field counts -- 16 cases: 12.5 against 20.0 us, 64 cases: 30.2
+  // against 48.8 us, U_to_gradP 8 cases: 24.1 against 36.8 us, 8 deltas cases: equal (tools/attic/decode_mtc_sweep.py).  With fewer
+  // than 256 column workgroups (a single-field basis: 128) that spreads the rows -- 8 cases x 9 blocks of a one-field model ran as
+  // 128 workgroups of 3 tiles (14.7 us), as 384 workgroups of one tile they take 10.6 us.  PSM_DECODE_MTC (1..3; the 4-tile form
+  // spills: acc + tile + row operands) / PSM_DECODE_WGS: diagnostic.
+  r.decode_mtc = h->sw.at_create.decode_mtc; r.decode_wgs = h->sw.at_create.decode_wgs;
   const int64_t fb = (int64_t)n_cases * h->Ny * h->Nx * h->cfg.c_out * (int64_t)sizeof(float);
-  r.field_bytes = (r.bound && bufst && fb < ((int64_t)1 << 32)) ? (uint32_t)fb : 0u;
+  r.field_bytes = (r.bound && h->sw.at_create.paste_buffer_stores && fb < ((int64_t)1 << 32)) ? (uint32_t)fb : 0u;
   // few blocks, few cases: every paste workgroup re-runs the chain (one launch less); for case batches one chain workgroup
   // per case + a streaming paste
   r.fused_assemble = !r.bound && h->fused_assemble && n_cases < 4;
@@ -219,7 +224,7 @@ static PsmGuardArgs guard_args(const Solve& s, int carrier) {
 static int stage_encode(Solve& s) {
   psm_handle* h = s.h;
   const PsmEncodeArgs ea = encode_args(h, s.w, s.r, s.grid);
-  auto launch = [&](hipEvent_t e0, hipEvent_t e1) { return s.r.bf16 ? psm_launch_encode_bf16(ea, s.st, e0, e1) : psm_launch_encode(ea, s.st, e0, e1); };
+  auto launch = [&](hipEvent_t e0, hipEvent_t e1) { return s.r.bf16 ? psm_launch_encode_bf16(ea, s.st, e0, e1) : psm_launch_encode(ea, s.st, e0, e1, s.r.row_wgs); };
   if (s.r.stamp_encode) {
     hipEvent_t e0, e1;
     HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
@@ -356,7 +361,7 @@ static int stage_bound_tail(Solve& s) {
   if (!r.cf) HIPCHK(h, psm_launch_chain_dots(bb, h->cfg.c_out, s.st));     // closed form: no chain launch
   s.tm.after(PSM_K_CHAIN);
   s.tm.before(PSM_K_PASTE);
-  HIPCHK(h, psm_launch_decode_paste_batch(de, bb, h->cfg.c_out, s.st, r.bf16 ? 1 : 0));
+  HIPCHK(h, psm_launch_decode_paste_batch(de, bb, h->cfg.c_out, s.st, r.decode_mtc, r.decode_wgs, r.bf16 ? 1 : 0));
   s.tm.after(PSM_K_PASTE);
   return PSM_OK;
 }
@@ -385,8 +390,8 @@ static int stage_general_tail(Solve& s) {
 }
 
 int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, float* d_fields, const float* d_row_scale,
-               hipStream_t st, hipEvent_t* prof) {
-  const SolveRoute r = choose_route(h, w, d_grid, n_cases, prof != nullptr);
+               hipStream_t st, hipEvent_t* prof, const PsmSwitches::PerSolve& ps) {
+  const SolveRoute r = choose_route(h, w, d_grid, n_cases, prof != nullptr, ps);
   // the record of what this solve leaves (a ring slot's solve leaves nothing readable: the rest of the record is stale then)
   if (&w == &h->ws0) h->last = Ws0Solve{true, r.pred_stored, r.cf, h->dense.size() > 1 && r.packed[h->dense.size() - 2], d_row_scale};
   else h->last.on_ws0 = false;

@@ -25,11 +25,10 @@ static int prepare_scale(psm_handle* h, Workspace& w, const float* out_scale, in
 // else the route depends on is fixed while cached graphs live, because what changes it drops them: psm_plan_grid (free_plan), the
 // model setters, psm_bind_geometry* / psm_unbind_geometry and a guard trip (destroy_graphs, which calls ring_drop_graphs), the
 // integration, post-step and feature bind / unbind entries (the graphs that hold their tables); timed and profiled solves are never captured.
-// PSM_SDF_FOLD, which the route also reads per solve, IS part of the key (fold_applies): a sequence captured with the folded encode is
-// never replayed under PSM_SDF_FOLD=0, nor the other way round.
-// NOT covered: PSM_LN_FUSE, which the route reads per solve -- a graph captured under one value is replayed under the other.
-int sequence_key(const psm_handle* h, int n_cases, bool scale, bool ring) {
-  const int k = ((n_cases * 2 + (scale ? 1 : 0)) * 2 + (bound_applies(h, n_cases) ? 1 : 0)) * 2 + (fold_applies(h, n_cases) ? 1 : 0);
+// Both per-solve switches, PSM_SDF_FOLD (fold_applies) and PSM_LN_FUSE, ARE part of the key, from the same read (`ps`) the route gets: a
+// sequence captured under one value of either is never replayed under the other.
+int sequence_key(const psm_handle* h, int n_cases, bool scale, const PsmSwitches::PerSolve& ps, bool ring) {
+  const int k = (((n_cases * 2 + (scale ? 1 : 0)) * 2 + (bound_applies(h, n_cases) ? 1 : 0)) * 2 + (fold_applies(h, n_cases, ps) ? 1 : 0)) * 2 + (ps.ln_fuse ? 1 : 0);
   return ring ? k * 2 + (h->ring_dma ? 1 : 0) : k;
 }
 
@@ -66,6 +65,7 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
   if (n_cases < 1 || n_cases > h->cfg.max_cases) return fail(h, PSM_ERR_ARG, "n_cases outside [1, max_cases]");
   HIPCHK(h, hipSetDevice(h->cfg.device));
   if (!st) st = h->stream;
+  const PsmSwitches::PerSolve ps = psm_switches_per_solve();      // this solve's one read: the key and the route see the same values
   const float* d_scale = nullptr;
   if ((rc = ensure_encode_aux(h, n_cases))) return rc;
   const bool rows = step.rows.rows, psolve = step.psolve.cells, gsolve = step.gsolve.cells;
@@ -93,7 +93,7 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
       // decodes them again.
       const size_t npix = (size_t)h->Ny * h->Nx, rows = (size_t)h->B * h->ld_out;
       for (int f = 0; f < n_cases && !rs; ++f) {
-        rs = launch_all(h, h->ws0, d_grid + f * npix * h->cfg.c_in, 1, d_fields + f * npix * h->cfg.c_out, d_scale + (d_scale == h->d_ones ? 0 : f * h->B), on, ev);
+        rs = launch_all(h, h->ws0, d_grid + f * npix * h->cfg.c_in, 1, d_fields + f * npix * h->cfg.c_out, d_scale + (d_scale == h->d_ones ? 0 : f * h->B), on, ev, ps);
         if (!rs && deltas && hipMemcpyAsync(step.deltas.res + f * rows, h->ws0.d_res, rows * sizeof(float), hipMemcpyDeviceToDevice, on) != hipSuccess)
           rs = fail(h, PSM_ERR_HIP, "psm_deltas_frames: copy of the network output");
       }
@@ -102,7 +102,7 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
         h->last.row_scale = d_scale;
         h->last.res = step.deltas.res;
       }
-    } else if (!rs) rs = launch_all(h, h->ws0, d_grid, n_cases, d_fields, d_scale, on, ev);
+    } else if (!rs) rs = launch_all(h, h->ws0, d_grid, n_cases, d_fields, d_scale, on, ev, ps);
     if (!rs && step.p) rs = integrate_device(h, d_fields, n_cases, step.p, on);
     if (!rs && post) rs = poststeps_device(h, d_fields, n_cases, step.post, on);
     if (!rs && gradp) rs = integrate_device(h, h->gradp.integ, post ? step.post.result : d_fields, n_cases, step.gradp.p, on);
@@ -111,7 +111,7 @@ int solve_device(psm_handle* h, const float* d_grid, int n_cases, const float* o
     return rs;
   };
   if (prof || h->timed_kernel >= 0 || !h->use_graph) return sequence(st, prof);
-  const GraphKey key{sequence_key(h, n_cases, d_scale != h->d_ones), d_grid, d_fields, step};
+  const GraphKey key{sequence_key(h, n_cases, d_scale != h->d_ones, ps), d_grid, d_fields, step};
   auto it = h->graphs.find(key);
   if (it == h->graphs.end()) {
     if (h->graphs.size() > 64) destroy_graphs(h);

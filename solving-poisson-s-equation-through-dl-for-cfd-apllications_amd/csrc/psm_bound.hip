@@ -627,23 +627,13 @@ __global__ __launch_bounds__(256) void psm_decode_paste_batch_kernel(PsmDecodeAr
   }
 }
 
-hipError_t psm_launch_decode_paste_batch(const PsmDecodeArgs& a, const PsmBoundBatchArgs& p, int c_out, hipStream_t st, int bf16) {
+hipError_t psm_launch_decode_paste_batch(const PsmDecodeArgs& a, const PsmBoundBatchArgs& p, int c_out, hipStream_t st, int mtc, int wg_target, int bf16) {
   if (a.ld_res > 128 || a.ld_res % 32 != 0 || a.Mpad % 32 != 0 || p.B > 4096 || p.B < 1 || a.M != p.B * p.n_cases) return hipErrorInvalidValue;
   if (c_out != 1 && c_out != 2) return hipErrorInvalidValue;
+  if (mtc < 1 || mtc > 3) return hipErrorInvalidValue;     // row tiles per chunk: the 4-tile form of this kernel spills (acc + tile + row operands)
   const int nwg = (a.n_coltiles + 3) / 4;
-  // at most 3 tiles of 32 rows per chunk: the 4-tile form of this kernel spills (acc + tile + row operands)
-  // Row tiles per chunk (mtc <= 3: the 4-tile form spills) and row groups (grid.y).  With 256 or more column workgroups:
-  // the most rows per pass over the weights.  With fewer (a single-field basis: 128) the rows are spread over up to
-  // 512 / nwg groups, one chunk each where possible -- 8 cases x 9 blocks of a one-field model ran as 128 workgroups of 3
-  // tiles (14.7 us), as 384 workgroups of one tile they take 10.6 us.  PSM_DECODE_MTC forces mtc (diagnostic).
+  // mtc row tiles per chunk, the chunks spread over up to `wg_target / nwg` row groups (grid.y): the route's choice, measured there
   const int tiles = a.Mpad / 32, wpb = (128 / c_out) / 32;
-  // One 32-row tile per chunk, the row tiles spread over up to `target / nwg` row groups (grid.y): measured against two and
-  // three tiles per chunk (fewer passes over the basis slice, but 2-3x the LDS and registers per workgroup) at 8 ... 64
-  // cases and both field counts -- 16 cases: 12.5 against 20.0 us, 64 cases: 30.2 against 48.8 us, U_to_gradP 8 cases: 24.1
-  // against 36.8 us, 8 deltas cases: equal (tools/attic/decode_mtc_sweep.py).  PSM_DECODE_MTC / PSM_DECODE_WGS: diagnostic.
-  static const int mtc_force = getenv("PSM_DECODE_MTC") ? atoi(getenv("PSM_DECODE_MTC")) : 0;
-  static const int wg_target = getenv("PSM_DECODE_WGS") ? atoi(getenv("PSM_DECODE_WGS")) : 512;
-  const int mtc = mtc_force ? std::min(std::max(mtc_force, 1), 3) : 1;
   const int groups = std::min((tiles + mtc - 1) / mtc, std::max(1, wg_target / nwg));
   const int R = mtc * 32;
   const bool x6 = a.x6 && !bf16;

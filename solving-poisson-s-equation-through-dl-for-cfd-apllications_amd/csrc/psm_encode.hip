@@ -831,30 +831,25 @@ __global__ __launch_bounds__(256, 2) void psm_encode_x6_mt_kernel(PsmEncodeArgs 
 }
 
 // x6 covers <= 128 components (NT <= 4) and an LDS footprint of three bf16 planes
-static bool psm_encode_x6_fits(const PsmEncodeArgs& a, size_t* lds, int* row_wgs) {
-  // Negative result, kept as a knob: two workgroups per slice (64 rows each, half the LDS, two per CU so that one's matrix
-  // phase covers the other's load latency) -- 17.7 against 15.0 us at 8 cases, 21.8 against 17.6 us at 12: the launch is bound
-  // by its streams, and the split reads the basis slice twice.  PSM_ENCODE_ROWSPLIT=1 selects it.
-  static const bool row_split = getenv("PSM_ENCODE_ROWSPLIT") != nullptr;
-  *row_wgs = (a.Mpad > 64 && a.Mpad <= 32 * PSM_MT_CHUNK && row_split) ? 2 : 1;
-  const int rows = a.Mpad <= 32 ? 32 : (*row_wgs == 2 ? 64 : 32 * PSM_MT_CHUNK);
+static bool psm_encode_x6_fits(const PsmEncodeArgs& a, int row_wgs, size_t* lds) {
+  const int rows = a.Mpad <= 32 ? 32 : (row_wgs == 2 ? 64 : 32 * PSM_MT_CHUNK);
   *lds = (size_t)3 * rows * (PSM_PIX_PER_SLICE * a.c_in + 4) * 2;
   return a.NT <= 4 && *lds <= 156 * 1024 && a.Mpad % 32 == 0;
 }
 
 // the two-slices-per-workgroup form (psm_encode_pair_kernel): one row tile, exactly four component tiles, float32 MFMA, an even
-// number of slices.  PSM_ENCODE_PAIRS=0 keeps one slab per slice.  The slab count the reduce launches must use: n_slices / 2 when psm_encode_pairs(args) (launch_all, psm_api_solve.cpp).
+// number of slices; a predicate of the arguments alone (pairs_ok carries the route's say).  The slab count the reduce launches must use: n_slices / 2 when psm_encode_pairs(args) (launch_all, psm_api_solve.cpp).
 bool psm_encode_pairs(const PsmEncodeArgs& a) {
-  static const bool on = !(getenv("PSM_ENCODE_PAIRS") && atoi(getenv("PSM_ENCODE_PAIRS")) == 0);
   const int n_slices = a.S * a.S / PSM_PIX_PER_SLICE;
-  return on && a.pairs_ok && !a.x6 && a.kgroup <= 1 && a.Mpad == 32 && a.NT == 4 && n_slices % 2 == 0;
+  return a.pairs_ok && !a.x6 && a.kgroup <= 1 && a.Mpad == 32 && a.NT == 4 && n_slices % 2 == 0;
 }
-hipError_t psm_launch_encode(const PsmEncodeArgs& a, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop) {
+hipError_t psm_launch_encode(const PsmEncodeArgs& a, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, int row_wgs) {
   const int n_slices = a.S * a.S / PSM_PIX_PER_SLICE;
   const int rows = a.Mpad <= 32 ? 32 : 32 * PSM_MT_CHUNK;        // one tile, or 2 x 64-row buffers / a 128-row chunk
   size_t lds = (size_t)rows * (PSM_PIX_PER_SLICE * a.c_in + 4) * sizeof(float);
   size_t lds_x6 = 0;
-  int row_wgs = 1;
+  // two workgroups per slice (the route's choice): only where the kernel has the 64-row form, more than two and at most four row tiles
+  if (row_wgs != 1 && !(row_wgs == 2 && a.Mpad > 64 && a.Mpad <= 32 * PSM_MT_CHUNK)) return hipErrorInvalidValue;
   // SDF fold: only the float32 forms of one row tile have the arm (choose_route, psm_api_solve.cpp, asks for nothing else)
   if (a.fold && (a.x6 || a.kgroup > 1 || a.Mpad != 32 || a.NT > 4 || a.c_in < 2)) return hipErrorInvalidValue;
   if (a.x6 && a.kgroup > 1) {
@@ -865,7 +860,7 @@ hipError_t psm_launch_encode(const PsmEncodeArgs& a, hipStream_t st, hipEvent_t 
     PSM_LAUNCH_ENCODE_FAMILY(psm_encode_x6_mt_kernel, grid, 0, st, ev_start, ev_stop, a);
     return hipGetLastError();
   }
-  if (a.x6 && psm_encode_x6_fits(a, &lds_x6, &row_wgs)) {
+  if (a.x6 && psm_encode_x6_fits(a, row_wgs, &lds_x6)) {
     lds = lds_x6;
     PSM_LAUNCH_ENCODE_FAMILY(psm_encode_x6_kernel, dim3(n_slices, row_wgs), lds, st, ev_start, ev_stop, a);
     return hipGetLastError();

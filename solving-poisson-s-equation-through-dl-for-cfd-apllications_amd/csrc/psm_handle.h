@@ -20,6 +20,8 @@
 //   psm_api_poisson_solve.cpp  the Poisson-model step at the solver boundary (cells -> p, two-frame state on the device): psm_bind_poisson_solve, psm_poisson_solve_push / _reset / _state, psm_solve_poisson*; for a case set psm_bind_poisson_solve_cases, psm_poisson_solve_push_cases, psm_solve_cases_poisson*
 //   psm_api_gradp_solve.cpp  the gradient-model step at the solver boundary (cells -> p through solve, integration and the outlet level, no state): psm_bind_gradp_solve, psm_solve_gradp*; for a case set psm_bind_gradp_solve_cases, psm_solve_cases_gradp*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
+// The PSM_* environment switches of all of them are read in psm_switches.cpp (host only): psm_create and psm_plan_grid fill h->sw, the
+// bind entries and a solve read theirs at the entry, the rest is one process-wide table.  No file above reads the environment itself.
 // Compiled with hipcc for gfx950 only.  There is no CPU fallback: without a usable device psm_create fails with PSM_ERR_NO_DEVICE.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,6 +56,7 @@
 #include "psm_plan.h"
 #include "psm_fold.h"
 #include "psm_errors.h"
+#include "psm_switches.h"
 
 struct PsmMeshCaseTables;   // psm_mesh_tables.h
 
@@ -113,10 +116,12 @@ struct SolveRoute {
   int rider_share = 0, rider_carriers = 0;   // (bf16 handles: their dots launch) carries the rest.  Not spread: all of them ride there
   bool stamp_encode = false;            // encode timed by dispatch stamps (no event pair around the launch)
   int aligned = 0, whole = 1, x6 = 0, kgroup = 1, n_slabs = 0;   // encode: PsmEncodeArgs fields of the same name; slabs the reduce sums
+  int row_wgs = 1;                      // encode, x6 form of two to four row tiles: workgroups per slice (2: PSM_ENCODE_ROWSPLIT)
   bool fuse1 = false;                   // slab reduce + Dense 0 in one launch
   std::vector<char> packed;             // [layers] the output of Dense layer l is written in MFMA operand order
   bool ln_fuse = true;                  // LayerNormalization deferred into the next hidden launch where there is one
   int decode_x6 = 0;                    // bound: x6 arithmetic of decode + paste
+  int decode_mtc = 1, decode_wgs = 512; // bound case batch: row tiles per chunk (1..3) and workgroup target of decode + paste
   bool one_launch_tail = false;         // bound: decode + chain + paste in one launch (single case of <= 64 blocks), else chain launch + batch paste
   uint32_t field_bytes = 0;             // bound: the paste stores through a buffer descriptor of this size (PsmBoundArgs::field_bytes)
   bool fused_assemble = false;          // general: chain + paste in one launch
@@ -584,6 +589,7 @@ struct psm_handle {
   hipStream_t stream = nullptr;
   struct SolveGraph { hipGraphExec_t exec; Ws0Solve left; };   // left: what the captured solve leaves on ws0
   std::map<GraphKey, SolveGraph> graphs;
+  PsmSwitches sw;                       // at_create: psm_create, at_plan: psm_plan_grid (psm_switches.h); the fields below named after a switch are filled from it
   bool use_graph = true;
   bool fused_assemble = false;
   // scratch of the helper entries (gaussian filter, mesh -> grid, Poisson features, gradp integration): one device and one
@@ -710,12 +716,13 @@ std::vector<uint16_t> pack_comp_in_bf16(const double* comp, int P, int K, int c_
 std::vector<uint16_t> pack_comp_out_bf16(const double* comp, int P, int K_out, int G);
 bool model_complete(const psm_handle* h);
 int ensure_encode_aux(psm_handle* h, int n_cases);
-SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_grid, int n_cases, bool profiled);
+// ps: the per-solve switches, read once by the entry that starts the solve (solve_device, ring_launch, mesh_sequence) and handed down
+SolveRoute choose_route(const psm_handle* h, const Workspace& w, const float* d_grid, int n_cases, bool profiled, const PsmSwitches::PerSolve& ps);
 int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, float* d_fields, const float* d_row_scale,
-               hipStream_t st, hipEvent_t* prof);
+               hipStream_t st, hipEvent_t* prof, const PsmSwitches::PerSolve& ps);
 bool bound_applies(const psm_handle* h, int n_cases);
-bool fold_applies(const psm_handle* h, int n_cases);
-int sequence_key(const psm_handle* h, int n_cases, bool scale, bool ring = false);
+bool fold_applies(const psm_handle* h, int n_cases, const PsmSwitches::PerSolve& ps);
+int sequence_key(const psm_handle* h, int n_cases, bool scale, const PsmSwitches::PerSolve& ps, bool ring = false);
 int capture_graph(psm_handle* h, hipStream_t st, const char* label, const std::function<int()>& enqueue, hipGraphExec_t* exec);
 // one builder per kernel-argument block (psm_api_solve.cpp): the stages of launch_all, psm_read_stage, psm_block_error and psm_reassemble
 PsmDecodeArgs decode_args(const psm_handle* h, const Workspace& w, int n_cases, const float* row_scale, float* pred, int x6 = 0);
@@ -811,8 +818,6 @@ inline hipStream_t stream_of(const psm_handle* h, void* stream) { return stream 
 int bind_geometry_device(psm_handle* h, const float* d_grid, int n_cases = 1);
 bool host_registered(const psm_handle* h, const void* p, size_t bytes);
 
-inline double spin_budget_us() { static const double v = [] { const char* e = getenv("PSM_SPIN_US"); return e ? atof(e) : 300.0; }(); return v; }
-
 template <typename Query, typename Block>
 hipError_t bounded_wait(Query query, Block block) {
   if (sync_blocks()) return block();
@@ -820,7 +825,7 @@ hipError_t bounded_wait(Query query, Block block) {
   hipError_t e;
   int n = 0;
   while ((e = query()) == hipErrorNotReady) {
-    if ((++n & 63) == 0 && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > spin_budget_us())
+    if ((++n & 63) == 0 && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() > psm_switches_process().spin_us)
       return block();
   }
   return e;
@@ -968,14 +973,5 @@ struct Timer {                      // optional event pair around one kernel gro
   void skip(int kernel) { before(kernel); after(kernel); }   // a group this route does not launch: its (empty) event pair, in order
 };
 
-
-#ifndef PSM_MESH_STAGE_MAX_DEFAULT
-
-// cells up to which psm_solve reads registered input with the stage kernel; above, the DMA engine's higher large-copy rate (49 against
-// 40 GB/s over this PCIe link) wins: measured crossover between 44 k (stage 107 / DMA 110 us) and 69 k cells (147 / 142 us),
-// profiles/archive/r04_psm_solve.txt
-#define PSM_MESH_STAGE_MAX_DEFAULT 50000
-
-#endif
 
 }  // namespace psm_impl

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/psm.h"
+#include "psm_switches.h"
 
 extern "C" int psm_bench_host(psm_handle* h, const float* grids, int32_t n_inputs, int32_t n_cases, int32_t mode, int32_t depth,
                               int32_t steps, int32_t warmup, double* seconds, float* last_fields) {
@@ -29,7 +30,7 @@ extern "C" int psm_bench_host(psm_handle* h, const float* grids, int32_t n_input
   std::vector<float*> slot_out(PSM_RING_SLOTS, nullptr);
   const float* last = nullptr;
   // PSM_BENCH_VERBOSE=1: where the calling thread spends its time (submission calls / waits), to stderr
-  const bool verbose = std::getenv("PSM_BENCH_VERBOSE") != nullptr;
+  const bool verbose = psm_switches_process().bench_verbose;
   double t_submit = 0.0, t_wait = 0.0;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };

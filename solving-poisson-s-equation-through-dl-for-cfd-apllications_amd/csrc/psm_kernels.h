@@ -32,7 +32,7 @@ struct PsmEncodeArgs {
   int kgroup;              // > 1: the M-tiled, wave-specialised form for large case batches (psm_encode_x6_mt_kernel) with `kgroup` K GROUPS: a
                            // workgroup owns one group of consecutive K slices x PSM_ENC_MT_ROWS (64) block rows and writes ONE slab -- part [kgroup][Mpad][ldp];
                            // 0 / 1: one slab per slice (psm_encode_x6_kernel / psm_encode_kernel)
-  int pairs_ok;            // the two-slices-per-workgroup form may run (psm_encode_pair_kernel): when psm_encode_pairs(args) is true the launch writes n_slices / 2 slabs and the caller's reduce must sum that many (launch_all, psm_api_solve.cpp)
+  int pairs_ok;            // the two-slices-per-workgroup form may run (psm_encode_pair_kernel): PSM_ENCODE_PAIRS is ANDed in by the route; when psm_encode_pairs(args) is true the launch writes n_slices / 2 slabs and the caller's reduce must sum that many (launch_all, psm_api_solve.cpp)
 };
 bool psm_encode_pairs(const PsmEncodeArgs& a);   // true: this launch writes n_slices / 2 slabs
 constexpr int PSM_ENC_MT_ROWS = 64;    // block rows of a workgroup of the M-tiled encode (two 32-row MFMA tiles)
@@ -234,7 +234,7 @@ hipError_t psm_launch_pair_fold(const PsmPairFoldArgs& a, hipStream_t s);
 hipError_t psm_launch_act_dots(const PsmDotsArgs& d, const float* act, int ld_act, int round_bf16, hipStream_t s, int packed = 0);
 hipError_t psm_launch_bind(const PsmBindArgs& a, hipStream_t s);
 hipError_t psm_launch_chain_dots(const PsmBoundBatchArgs& p, int c_out, hipStream_t s);
-hipError_t psm_launch_decode_paste_batch(const PsmDecodeArgs& a, const PsmBoundBatchArgs& p, int c_out, hipStream_t s, int bf16 = 0);
+hipError_t psm_launch_decode_paste_batch(const PsmDecodeArgs& a, const PsmBoundBatchArgs& p, int c_out, hipStream_t s, int mtc, int wg_target, int bf16 = 0);   // mtc: 32-row tiles per chunk, 1..3; wg_target: workgroups the row groups fill (SolveRoute)
 // head layer + strip dots in one launch (f32, 16-row tiles)
 hipError_t psm_launch_dense_dots(const PsmDenseArgs& a, const PsmDotsArgs& d, hipStream_t s);
 // decode + offset chain + paste in one launch: ld_res <= 128, Mpad <= 64 (one case, B <= 64, n_x < 64)
@@ -245,7 +245,7 @@ hipError_t psm_launch_res_dots(const PsmDotsArgs& d, const float* res, int ld_re
 
 hipError_t psm_read_stamps(unsigned long long* out);   // [64]; zeros unless built with -DPSM_STAMPS
 // ev_start / ev_stop (optional): stamped with the dispatch's own begin / end (hipExtLaunchKernel)
-hipError_t psm_launch_encode(const PsmEncodeArgs& a, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+hipError_t psm_launch_encode(const PsmEncodeArgs& a, hipStream_t s, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, int row_wgs = 1);   // row_wgs: workgroups per slice of the x6 form, 1 or 2 (SolveRoute)
 // basis [slices][NT][KS/8][64] float4 (pack_comp_in) -> three bf16 planes in MFMA fragment order [slices][NT][KS/16][plane 3][64] uint4
 hipError_t psm_launch_split_basis(const float4* bpack, uint4* out, int n_slices, int NT, int KS, hipStream_t s);
 // bf16 operand path (psm_bf16.hip): bpack / weights point to bf16 data in the same tilings

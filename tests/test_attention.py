@@ -165,6 +165,40 @@ def test_gpu_attention_fused_and_standalone_layernorm_agree(monkeypatch, n_cases
 
 
 @pytest.mark.gpu
+def test_gpu_attention_ln_fuse_is_part_of_the_graph_key(monkeypatch):
+    """PSM_LN_FUSE is read per solve and is a bit of the sequence key, like PSM_SDF_FOLD (test_sdf_fold.py): a graph captured with
+    the deferred normalisations is not replayed under PSM_LN_FUSE=0, nor the other way round.  The references are plain-launch
+    handles under either value; they differ by the float32 rounding of the moments, so which sequence ran shows in the bits."""
+    from hipmem import DeviceArray
+    grid, model = cases.build(NAME)
+    g32 = grid.astype(np.float32)[None]
+    d_in, d_out = DeviceArray(g32), DeviceArray(shape=(1, 256, 256, model.c_out))
+
+    def solve(sur):
+        sur.solve_device(d_in.ptr, 1, d_out.ptr, 0)
+        sur.synchronize()
+        return d_out.numpy()[0].copy()
+
+    ref = {}
+    monkeypatch.setenv("PSM_GRAPH", "0")
+    for mode in ("1", "0"):
+        monkeypatch.setenv("PSM_LN_FUSE", mode)
+        with GridSurrogate(model, 256, 256) as sur:
+            ref[mode] = solve(sur)
+    assert not np.array_equal(ref["1"], ref["0"])               # else the sequence below could not tell the two apart
+    monkeypatch.setenv("PSM_GRAPH", "1")
+    monkeypatch.setenv("PSM_LN_FUSE", "1")
+    with GridSurrogate(model, 256, 256) as sur:
+        for _ in range(3):                                      # capture, then two replays
+            np.testing.assert_array_equal(solve(sur), ref["1"])
+        monkeypatch.setenv("PSM_LN_FUSE", "0")
+        np.testing.assert_array_equal(solve(sur), ref["0"])
+        monkeypatch.setenv("PSM_LN_FUSE", "1")
+        np.testing.assert_array_equal(solve(sur), ref["1"])
+    d_in.free(); d_out.free()
+
+
+@pytest.mark.gpu
 def test_gpu_attention_32_row_tiles_and_wide_layers():
     """More than 128 block rows (the 32-row tile of the Dense kernel: two row sets per lane in the moment prologue) and a hidden
     width above 512 (two passes over the contraction: moments from L2 instead of the operand registers)."""

@@ -1,6 +1,7 @@
 """The round-6 fast paths have a switch each; the forms they replace stay in the library -- for fields of
 4 GiB or more (branch-predicated paste stores) and for models whose Dense chain cannot be packed -- and must give the same fields.
-The switches are read once per process, so each form runs in a process of its own; the arithmetic is identical, the fields must be too."""
+The switches are read once per handle, at psm_create (csrc/psm_switches.cpp); each form still runs in a process of its own, as a
+host program sets them; the arithmetic is identical, the fields must be too."""
 import os
 import subprocess
 import sys

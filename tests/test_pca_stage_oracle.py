@@ -18,10 +18,10 @@ of each product, below the six-term accumulation depth the bound allows), or a d
 Not covered (the issue's remaining parts): the reassembly (offsets, paste, shift) and the fused bound-path decode + paste /
 chain_dots / closed form stay with check_against_oracle in test_gpu_parity.py (normwise), so the injected faults "offset taken
 from a neighbour", "overlap column from the wrong block", "shift applied twice" and "NaN mask off by one row" are not
-modelled; LayerNormalization and the Conv1D head; the child-process sweeps of the per-process switches.  SWEPT below lists
+modelled; LayerNormalization and the Conv1D head.  SWEPT below lists
 what this module launches; not_swept_reason says why each other table entry is not.
 
-Measured on an MI355X (test_zz_report prints it; GPU part of the module 11.4 s, 71 of the 220 table entries launched), worst
+Measured on an MI355X (test_zz_report prints it; GPU part of the module 12.8 s with the four PSM_DECODE_MTC rows, 74 of the 220 table entries launched; the ratios are unchanged by those rows), worst
 |dev - r| / E: encode 1.1e-3 (f32 form, c_in = 1, odd Nx; pair 7.3e-4, x6 2.9e-4, x6_mt 3.9e-5), dense0 0.060, dense1-2 0.0025,
 head 0.031, decode 0.153 (32 components)."""
 import ctypes as C
@@ -261,6 +261,15 @@ _CONFIGS = {
     "deltas_bound_one": ("deltas", 3, (256, 256), 32, 32, 1, "f32", {}, True),
     "gradp_bound_n4": ("gradp", 3, (256, 256), 64, 96, 4, "f32", {}, True),
     "deltas_bound_bf16": ("deltas", 3, (256, 256), 64, 128, 1, "bf16", {}, True),
+    # decode + paste of a bound case batch with two / three 32-row tiles per chunk (the gradp grid has 30 blocks).  8 cases = 240 block
+    # rows, eight tiles: four full chunks of two, two full chunks of three and a ragged one; 3 cases = 90 rows, three tiles: a full
+    # and a ragged chunk of two, exactly one chunk of three.  The stage oracle reads no stage behind `res` on a bound geometry, so
+    # what these launches paste is held to the fields of the same solve with one tile per chunk, bit for bit (the tiles per chunk
+    # change which rows share a pass over the basis, not the order of any row's sum), and through them to the float64 oracle.
+    "gradp_bound_n8_mtc2": ("gradp", 3, (256, 256), 64, 96, 8, "f32", {"PSM_DECODE_MTC": "2"}, True),
+    "gradp_bound_n8_mtc3": ("gradp", 3, (256, 256), 64, 96, 8, "f32", {"PSM_DECODE_MTC": "3"}, True),
+    "gradp_bound_n3_mtc2": ("gradp", 3, (256, 256), 64, 96, 3, "f32", {"PSM_DECODE_MTC": "2"}, True),
+    "gradp_bound_n3_mtc3": ("gradp", 3, (256, 256), 64, 96, 3, "f32", {"PSM_DECODE_MTC": "3"}, True),
 }
 
 
@@ -273,7 +282,21 @@ def test_gpu_stages_within_bound(name, monkeypatch):
         monkeypatch.setenv(k, v)
     model = _model(variant, c_in, p_in, p_out, widths=(512, 512, 512), seed=11)
     grids = _grids(n, ny, nx, c_in, seed=7)
-    _check(name, model, grids, precision, bind)
+    names, fields = _check(name, model, grids, precision, bind)
+    if "PSM_DECODE_MTC" in env:
+        mtc = env["PSM_DECODE_MTC"]
+        assert any(k.startswith(f"psm_decode_paste_batch_kernel<{mtc},") for k in names), names
+        monkeypatch.delenv("PSM_DECODE_MTC")
+        names1, _, fields1 = _solve(model, grids, precision, bind)
+        assert any(k.startswith("psm_decode_paste_batch_kernel<1,") for k in names1), names1
+        np.testing.assert_array_equal(fields, fields1)
+        for c in (0, n - 1):             # and against the float64 oracle, the bound test_gpu_parity.py holds bound-path fields to
+            ref = orc.solve_grid(grids[c].astype(np.float64), _omodel(model)).fields
+            ok = ~np.isnan(ref)
+            np.testing.assert_array_equal(np.isnan(fields[c]), ~ok)
+            err = np.abs(fields[c][ok] - ref[ok]).max() / np.abs(ref[ok]).max()
+            print(f"\n{name} case {c}: max |field - oracle| / max |oracle| = {err:.3g}")
+            assert err <= 2e-4, (name, c, err)
     _DONE.add(name)
 
 
@@ -410,11 +433,12 @@ SWEPT = {
     "psm_assemble_kernel<1>", "psm_assemble_kernel<2>", "psm_chain_dots_kernel<2>", "psm_chain_kernel",
     "psm_decode128_kernel<1>", "psm_decode128_kernel<4>", "psm_decode_bf16_kernel<1>", "psm_decode_bf16_kernel<4>",
     "psm_decode_kernel<1,4>", "psm_decode_kernel<2,4>", "psm_decode_kernel<4,4>", "psm_decode_paste_batch_kernel<1,2,96,2>",
+    "psm_decode_paste_batch_kernel<2,2,96,2>", "psm_decode_paste_batch_kernel<3,2,96,2>",
     "psm_decode_paste_kernel<1,1,128,1>", "psm_decode_paste_kernel<1,1,32,2>", "psm_dense_kernel<1,false,16,false,false>",
     "psm_dense_kernel<1,false,32,false,false>", "psm_dense_kernel<1,true,16,false,false>",
     "psm_dense_kernel<1,true,32,false,false>", "psm_dense_kernel<2,false,32,false,false>",
     "psm_dense_kernel<4,false,16,false,false>", "psm_dense_kernel<4,false,16,true,false>",
-    "psm_dense_kernel<4,false,32,false,false>", "psm_dense_kernel<4,true,16,false,false>",
+    "psm_dense_kernel<4,false,32,false,false>", "psm_dense_kernel<4,false,32,true,false>", "psm_dense_kernel<4,true,16,false,false>",
     "psm_dense_kernel<4,true,32,false,false>", "psm_encode_bf16_kernel<1,false>", "psm_encode_bf16_kernel<1,true>",
     "psm_encode_bf16_kernel<2,false>", "psm_encode_bf16_kernel<2,true>", "psm_encode_bf16_kernel<3,false>",
     "psm_encode_bf16_kernel<3,true>", "psm_encode_bf16_kernel<4,false>", "psm_encode_bf16_kernel<4,true>",
@@ -438,7 +462,7 @@ def not_swept_reason(k):
     if k.startswith(("psm_layernorm_kernel", "psm_conv1d_kernel")) or (k.startswith("psm_dense_kernel") and k.endswith(",true>")):
         return "LayerNormalization / Conv1D head: not read back, not swept here (test_attention.py, test_conv1d_head.py, normwise)"
     if k.startswith("psm_decode_paste_batch_kernel<2") or k.startswith("psm_decode_paste_batch_kernel<3"):
-        return "reachable only with PSM_DECODE_MTC (read once per process): no child-process sweep yet"
+        return "reachable with PSM_DECODE_MTC=2 / 3 (read per handle): launched at two fields, 96 components, x6 only, their fields held bit for bit to the one-tile form; the other C / LDR / arithmetic combinations are not launched by this module yet"
     if k == "psm_act_dots_kernel":
         return "runs only inside psm_read_stage(OFFSETS / SHIFT) after a closed-form solve"
     return "reachable, not launched by this module yet"

@@ -9,8 +9,8 @@ the same order (--dispatches prints a trace as one line per dispatch, to be comp
     python tools/route_matrix.py --table LIST_A LIST_B      two such lists as one numbered table of the distinct lines + each list as numbers
 
 The `boundary` configurations (--only boundary, or one of BOUNDARY by name) hash the mesh ends of the library at the smallest shapes
-that can go wrong: every one runs in a child process of its own with its switches in the environment (they are read once per
-process) and prints one SHA-256 line per output.
+that can go wrong: every one runs in a child process of its own with its switches in the environment (as a host program sets
+them) and prints one SHA-256 line per output.
 
 The `steps` configurations (--only steps, or one of STEPS by name) hash the entries that put stages around a solve (solve_device,
 csrc/psm_api_step.cpp), each in a child process of its own: per variant (with / without out_scale, apply_filter 0 / 1) one call on a
@@ -27,8 +27,9 @@ The `refusals` configuration (--only refusals) is a fixed list of calls that the
 entries refuse from their argument checks, before anything is enqueued: one line per call with the return code and the text of
 psm_last_error, to be compared with diff between two builds.
 
---lib: the library to load (default: the tree's libpsm_hip.so), e.g. the parent commit's build.  PSM_MESH_GRAPH is read once per
-process: the `mesh` configuration runs in the mode --mesh-graph sets (default 2), so the three modes take three runs.
+--lib: the library to load (default: the tree's libpsm_hip.so), e.g. the parent commit's build.  The `mesh` configuration runs in the one
+mode --mesh-graph sets (default 2), so the three modes take three runs: a parent build given with --lib may still read PSM_MESH_GRAPH
+once per process (this tree reads it at psm_create).
 """
 import argparse
 import ctypes as C
