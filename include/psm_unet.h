@@ -115,6 +115,62 @@ int psm_unet_debug_run_layer(psm_unet* u, int32_t idx, float* stamps_us);
 /* Algorithmic work of one forward pass of one case at the planned size. */
 int64_t psm_unet_flops(const psm_unet* u);
 
+/* ---- the convolutional path at the solver boundary: K meshes, cells -> p through the U-Net -----------------------------------
+ * The per-timestep call of psm_solve_cases* (psm.h) with a planned psm_unet in the place of the PCA model: one call advances
+ * K >= 1 meshes on one grid shape, cells [sum n_i, 5] = (Ux, Uy, Cx, Cy, p) float64 -> p [sum n_i] float64, the cases' rows
+ * concatenated in case order; K = 1 is the single mesh's py_func.  A step is, on one stream and without a host synchronisation or
+ * a copy of an image: the partial maxima of the squared speed per case, mesh -> canvas (U_max per case, barycentric gather of
+ * U / U_max in float64, interpolate_fill, / max_abs_*, NaN -> 0, the SDF channel: the statements of psm_solve's mesh -> grid end),
+ * psm_unet_forward_device on the K canvases, canvas -> mesh (p = acc * max_abs_p * U_max^2, and cells[:,4] bit for bit where
+ * psm_solve keeps the previous p: near-wall cell, negative weight, NaN).  A case's result does not depend on its slot or on the
+ * other cases' cells.
+ * CANVAS.  The geometry's grid shape (ny, nx) may be any shape; the network runs on the canvas (ny_c, nx_c) = ny and nx rounded up to
+ * multiples of 2^(n_levels - 1) (psm_unet_canvas_shape), which is what the caller plans the network for: psm_unet_plan(u, ny_c, nx_c,
+ * max_cases).  The image occupies canvas rows [0, ny) and columns [0, nx); every other canvas pixel is +0.0 in all three channels --
+ * SDF = 0, the no-flow value -- zeroed when the geometry is set and never written again.  Field values outside the image are not
+ * read.  THIS PADDING RULE IS BUILD-DEFINED: the conv path has no reference network (see the top of this file), so nothing in the
+ * reference says how a 138 x 300 or 400 x 3000 grid meets a network that halves its image n_levels - 1 times.
+ * psm_unet_mesh wraps a psm_unet, it does not extend or own it: the network must outlive the binding, stay planned for
+ * (ny_c, nx_c, >= max_cases) and not run a forward pass of its own while a psm_unet_solve_device step is in flight.
+ * psm_unet_mesh_create: `u` planned (PSM_ERR_STATE), for a canvas of that size (PSM_ERR_ARG: ny_c, nx_c multiples of 2^(n_levels - 1)
+ * whose work psm_unet_flops confirms); stem c_in == 3 and head c_out == 1, read through psm_unet_conv_shape (PSM_ERR_UNSUPPORTED);
+ * `device` the network's; max_cases >= 1; step PSM_UNET_STEP_ABSOLUTE or PSM_UNET_STEP_DELTA.  Allocates the canvases and fields.
+ * psm_unet_mesh_set_geometry: the tables of psm_set_geometry_cases (psm.h) with its validation, all-or-nothing -- a refused call
+ * leaves the binding as it was; 1 <= n_cases <= max_cases and the canvas of (ny, nx) equal to (ny_c, nx_c), else PSM_ERR_ARG.  maxs =
+ * (max_abs_Ux, max_abs_Uy, max_abs_dist, max_abs_p), for the delta step (max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp).  Uploads
+ * the tables and reserves every per-step buffer: a step allocates nothing.  Drops the delta state.
+ * psm_unet_solve: host buffers, synchronous (pinned staging, one H2D and one D2H copy, the wait polls like psm_unet_forward's).
+ * psm_unet_solve_device: device pointers (8-byte aligned), asynchronous on `stream` (NULL: the binding's).
+ * DELTA step (psm_solve_cases_delta* of psm.h on this path): the image holds (U(t) - U(t-1)) / U_max with U_max of the CURRENT
+ * cells, the field is dp, p = cells[:,4] + dp by one rounded add; U(t-1) [sum n_i][2] stays on the device and the step's last
+ * launch turns it over.  psm_unet_mesh_prime sets U(t-1) := cells[:,0:2]; psm_unet_mesh_reset forgets it and zeroes `steps`;
+ * psm_unet_mesh_state reports *primed and *steps (either may be NULL).  A step on a state that is not primed is the PRIMING step:
+ * p = cells[:,4] bit for bit, U(t-1) := cells[:,0:2], one launch, the network does not run, `steps` not incremented.  On an
+ * absolute binding prime and reset are PSM_ERR_STATE and the state reads (0, 0).
+ * psm_unet_mesh_read (introspection for the tests; waits for the binding's stream): of the last solve, PSM_UNET_READ_CANVAS
+ * [K][ny_c][nx_c][3] float32, PSM_UNET_READ_FIELD [K][ny_c][nx_c] float32, PSM_UNET_READ_UMAX [K] float64; cap = capacity of dst in
+ * bytes.  PSM_ERR_STATE before the first step that ran the network. */
+typedef struct psm_unet_mesh psm_unet_mesh;
+#define PSM_UNET_STEP_ABSOLUTE 0
+#define PSM_UNET_STEP_DELTA    1
+#define PSM_UNET_READ_CANVAS 0
+#define PSM_UNET_READ_FIELD  1
+#define PSM_UNET_READ_UMAX   2
+int psm_unet_canvas_shape(int32_t n_levels, int32_t ny, int32_t nx, int32_t* ny_c, int32_t* nx_c);
+int psm_unet_mesh_create(psm_unet* u, int32_t device, int32_t ny_c, int32_t nx_c, int32_t max_cases, int32_t step, psm_unet_mesh** out);
+void psm_unet_mesh_destroy(psm_unet_mesh* m);
+const char* psm_unet_mesh_last_error(const psm_unet_mesh* m);
+int psm_unet_mesh_set_geometry(psm_unet_mesh* m, int32_t n_cases, const int64_t* n_cells, int32_t ny, int32_t nx,
+                               const int32_t* const* vtx_m2g, const double* const* wts_m2g, const int32_t* const* indices,
+                               const double* const* sdfunct, const int32_t* const* vtx_g2m, const double* const* wts_g2m,
+                               const double* maxs, int32_t normalise_sdf, int32_t fill_input, double wall_threshold);
+int psm_unet_solve(psm_unet_mesh* m, const double* cells, double* p_out);                         /* [sum n_i, 5] -> [sum n_i] */
+int psm_unet_solve_device(psm_unet_mesh* m, const double* d_cells, double* d_p, void* stream);
+int psm_unet_mesh_prime(psm_unet_mesh* m, const double* cells);
+int psm_unet_mesh_reset(psm_unet_mesh* m);
+int psm_unet_mesh_state(const psm_unet_mesh* m, int32_t* primed, int64_t* steps);
+int psm_unet_mesh_read(psm_unet_mesh* m, int32_t what, void* dst, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

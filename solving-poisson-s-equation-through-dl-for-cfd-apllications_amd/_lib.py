@@ -265,7 +265,22 @@ SIGNATURES_UNET = {
                                           C.POINTER(C.c_double), _i32ptr, C.c_char_p]),
     "psm_unet_debug_run_layer": (C.c_int, [_up, C.c_int32, _f32p]),
     "psm_unet_flops": (C.c_int64, [_up]),
+    # the mesh binding on a planned network (psm_unet_mesh): K meshes, cells -> p through the U-Net
+    "psm_unet_canvas_shape": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _i32ptr, _i32ptr]),
+    "psm_unet_mesh_create": (C.c_int, [_up, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_up)]),
+    "psm_unet_mesh_destroy": (None, [_up]),
+    "psm_unet_mesh_last_error": (C.c_char_p, [_up]),
+    "psm_unet_mesh_set_geometry": (C.c_int, [_up, C.c_int32, C.POINTER(C.c_int64), C.c_int32, C.c_int32] + [C.c_void_p] * 6 +
+                                   [C.POINTER(C.c_double), C.c_int32, C.c_int32, C.c_double]),
+    "psm_unet_solve": (C.c_int, [_up, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "psm_unet_solve_device": (C.c_int, [_up, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_unet_mesh_prime": (C.c_int, [_up, C.POINTER(C.c_double)]),
+    "psm_unet_mesh_reset": (C.c_int, [_up]),
+    "psm_unet_mesh_state": (C.c_int, [_up, _i32ptr, C.POINTER(C.c_int64)]),
+    "psm_unet_mesh_read": (C.c_int, [_up, C.c_int32, C.c_void_p, C.c_int64]),
 }
+UNET_STEPS = {"absolute": 0, "delta": 1}                     # PSM_UNET_STEP_*
+UNET_READ = {"canvas": 0, "field": 1, "umax": 2}             # PSM_UNET_READ_*
 
 _lib = None
 

@@ -15,6 +15,7 @@
 //
 // All of them are HBM-bound gathers; interpolation is done in float64 like the reference.
 #include "psm_mesh.h"
+#include "psm_mesh_dev.h"   // sqrt_rn, nanmax2, umax_of_partials, add_np, psm_uv2: shared with psm_unet_mesh.hip
 
 #include <algorithm>
 
@@ -29,21 +30,6 @@ __device__ __forceinline__ double speed2_np(double ux, double uy) {
   const double xx = ux * ux, yy = uy * uy;
   return xx + yy;
 }
-__device__ __forceinline__ double sqrt_rn(double x) {
-  double r = sqrt(x);
-  const unsigned long long eb = __double_as_longlong(r) & 0x7ff0000000000000ull;
-  if (eb > (53ull << 52) && eb < 0x7ff0000000000000ull) {                       // normal, finite, not NaN
-    const double u = __longlong_as_double(eb - (52ull << 52));                  // ulp(r)
-    const double e = fma(-r, r, x);                                             // x - r^2, exact
-    const double lim = r * u;                                                   // |sqrt(x) - r| <= u / 2  <=>  |e| <= r u (to 2nd order)
-    if (e > lim) r += u; else if (e < -lim) r -= u;
-  }
-  return r;
-}
-
-// np.max semantics on doubles: NaN propagates
-__device__ __forceinline__ double nanmax2(double a, double b) { return (b > a || b != b) ? b : a; }
-
 __global__ __launch_bounds__(1024) void psm_umax_kernel(const double* cells, int64_t n, double* umax) {
   __shared__ double red[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -85,23 +71,6 @@ __device__ __forceinline__ void umax2_partial(const double* cells, int64_t n, do
     *out = r;
   }
 }
-
-// U_max from a row of <= 256 partial maxima of the SQUARED speed, folded by every thread of a 256-thread workgroup: sqrt_rn last
-__device__ __forceinline__ double umax_of_partials(const double* partials, int n_partials) {
-  __shared__ double um_s[4];
-  double m = partials[min((int)threadIdx.x, n_partials - 1)];
-  for (int o = 32; o > 0; o >>= 1) m = nanmax2(m, __shfl_down(m, o, 64));
-  if ((threadIdx.x & 63) == 0) um_s[threadIdx.x >> 6] = m;
-  __syncthreads();
-  return sqrt_rn(nanmax2(nanmax2(um_s[0], um_s[1]), nanmax2(um_s[2], um_s[3])));
-}
-
-// p(t-1) + dp as NumPy adds them: one rounding, never folded into the multiplications in front of it
-__device__ __forceinline__ double add_np(double a, double b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-typedef double psm_uv2 __attribute__((ext_vector_type(2)));   // one row of u_prev [N][2]: 16 bytes, 16-byte aligned
 
 // image cell `cell` of the mesh whose tables `a` points at.  DELTA (psm_solve_delta*, the deltas model at the solver boundary):
 // the gathered value is U(t) - U(t-1), formed in float64 per vertex in front of the chain (SM_call.py:389-391), with U(t-1) from
