@@ -963,6 +963,37 @@ int psm_solve_cases_gradp(psm_handle* h, const double* cells, double* p_out);   
 int psm_solve_cases_gradp_device(psm_handle* h, const double* d_cells, double* d_p, float* d_image, float* d_gradp, float* d_pgrid,
                                  double* d_scalars, void* stream);
 
+/* ---- input trust: can the model represent the image the last solve ran on? ----
+ * The network sees nothing but the p_in PCA coefficients of every input block; a block far outside the span of the retained
+ * components gives coefficients, and a p, that mean nothing, and no other entry says so.  For block row m = case * B + b of the
+ * LAST solve on the handle's own workspace, with x the block's S*S*c_in float32 image values in the column order of comp_in
+ * ([r][c][ch]), mu = (float)mean_in, C = (float)comp_in[:p_in], G = C C^T in float64 and z the coefficients the encode of that solve
+ * produced -- PSM_STAGE_X_INPUT with the model's input scaler undone in float64, z_p = (xin[m][p] - ib[p]) / ia[p]:
+ *     n   = sum_k (x_k - mu_k)^2
+ *     spe = n - 2 sum_p z_p^2 + z^T G z        ( = |x - mu - C^T z|^2 at z = C (x - mu), for any C, orthonormal or not: the SPE / Q
+ *                                                statistic; the encode's float32 rounding of z moves spe / n by 1e-10 .. 5e-7 )
+ * two float64 per block row, out[(case * B + b) * 2 + {0, 1}].  Nothing is clamped (a spe slightly below zero is rounding); n == 0
+ * gives spe = 0.  1 - spe / n is the explained share, comparable with the var_in the model's input PCA was cut at; the caller forms
+ * it, and decides what a low value means for its step.  Float64 sums, no atomics, one fixed tree: the same solve gives the same bits.
+ * psm_bind_trust: once per model + plan, behind psm_plan_grid.  comp_in [p_in][K_in] is the array psm_set_pca was given; the Gram
+ * matrix is built on the device from a float32 copy that is released before the call returns; after it the entries below allocate
+ * nothing.  PSM_ERR_UNSUPPORTED on a bf16 handle (its encode rounds the inputs), PSM_ERR_ARG when a factor of the input scaler is
+ * zero or not finite in float32.  psm_plan_grid and the model setters drop the binding.
+ * psm_trust_last_device: two launches on `stream` (NULL: the handle's), asynchronous, d_out [n_cases][B][2] float64 in device
+ * memory.  The scored solve is whatever chain ran last: psm_solve_grid*, every step at the solver boundary (psm_solve*,
+ * psm_solve_cases*, the delta, Poisson and gradient steps; of a priming or skipped step, the chain before it) with n_cases the
+ * solve's; an evaluator's frame step solves its frames one by one, so it leaves its last frame, n_cases = 1.  The image must still be
+ * there unchanged: the library's own images are (a released one is PSM_ERR_STATE), the d_grid of psm_solve_grid_device and of the
+ * *_device step entries is the caller's to keep.  The launches are ordered on `stream` only: give the solve's stream.
+ * psm_trust_last: the same through the binding's staging, synchronous; *n_cases (may be NULL) receives the scored solve's case
+ * count, out_doubles is the capacity of `out` (>= n_cases * B * 2, else PSM_ERR_ARG).
+ * PSM_ERR_STATE, nothing enqueued: not bound, not planned, no solve since the plan, or the last solve ran on a ring slot's workspace
+ * (the rule of psm_block_error).  No entry here is part of any solve's launch sequence, and none changes a bit of a field. */
+int psm_bind_trust(psm_handle* h, const double* comp_in);
+int psm_unbind_trust(psm_handle* h);
+int psm_trust_last_device(psm_handle* h, double* d_out, void* stream);
+int psm_trust_last(psm_handle* h, int32_t* n_cases, double* out, size_t out_doubles);
+
 /* Dispatch-level time of EVERY kernel of the solve path: `steps` solves of d_grid through the launch sequence of
  * psm_solve_grid_device on the handle's stream, each dispatch stamped with its own begin / end by
  * hipExtLaunchKernelGGL (the timestamps rocprofv3 --kernel-trace reads).  names [cap][64] receives the kernel

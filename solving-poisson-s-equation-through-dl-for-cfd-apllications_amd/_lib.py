@@ -206,6 +206,10 @@ SIGNATURES = {
     "psm_solve_gradp_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "psm_solve_cases_gradp": (C.c_int, [_hp, _f64p, _f64p]),
     "psm_solve_cases_gradp_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "psm_bind_trust": (C.c_int, [_hp, _f64p]),
+    "psm_unbind_trust": (C.c_int, [_hp]),
+    "psm_trust_last_device": (C.c_int, [_hp, C.c_void_p, C.c_void_p]),
+    "psm_trust_last": (C.c_int, [_hp, _i32p, _f64p, C.c_size_t]),
     "psm_set_integration": (C.c_int, [_hp, C.c_int32, C.c_int32, _f64p, C.c_int32, C.c_int32, C.c_double, C.c_double]),
     "psm_integrate_gradp": (C.c_int, [_hp, _f32p, _f32p]),
     "psm_bind_integration": (C.c_int, [_hp, _f64p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_double, C.c_double]),

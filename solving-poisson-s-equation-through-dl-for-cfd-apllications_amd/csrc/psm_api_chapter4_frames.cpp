@@ -26,6 +26,7 @@ void chapter4_free(psm_handle* h) {
   dev_free(s.d_result);
   pin_free(s.h_result);
   eval_free(s);
+  image_gone(h);
 }
 
 // The pack launch on `st`: the binding's SDF plane and scales, the call's planes and destinations.

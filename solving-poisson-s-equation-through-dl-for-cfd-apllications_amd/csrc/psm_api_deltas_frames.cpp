@@ -26,6 +26,7 @@ void deltas_free(psm_handle* h) {
   for (auto& e : s.u2_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
   s.u2_pos = 0;
   eval_free(s);
+  image_gone(h);
 }
 
 // The pack launch on `st`: the binding's SDF plane, scales and U^2 array, the call's planes and destinations.

@@ -144,6 +144,7 @@ int psm_bind_features(psm_handle* h, const double* sdfunct, int32_t n_cases, dou
   poisson_solve_free(h);                                // psm_bind_poisson_solve stands on this binding
   FeatureSet& s = h->feat;
   feat_free(s);
+  image_gone(h);
   const size_t npix = (size_t)h->Ny * h->Nx, nwg = (npix + 255) / 256, n = (size_t)n_cases;
   int rc;
   if ((rc = dev_alloc(h, &s.d_sdf, n * npix)) || (rc = dev_alloc(h, &s.d_term, n * npix)) || (rc = dev_alloc(h, &s.d_partial, n * 2 * nwg)) ||
@@ -169,7 +170,7 @@ int psm_bind_features(psm_handle* h, const double* sdfunct, int32_t n_cases, dou
 
 
 int psm_unbind_features(psm_handle* h) {
-  return unbind(h, [h] { drop_feature_graphs(h); poisson_solve_free(h); feat_free(h->feat); });
+  return unbind(h, [h] { drop_feature_graphs(h); poisson_solve_free(h); feat_free(h->feat); image_gone(h); });
 }
 
 

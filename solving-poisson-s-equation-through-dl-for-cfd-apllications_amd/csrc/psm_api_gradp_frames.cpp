@@ -28,6 +28,7 @@ void gradp_free(psm_handle* h) {
   integ_free(s.integ);
   pin_free(s.h_gradp); pin_free(s.h_p);
   eval_free(s);
+  image_gone(h);
 }
 
 // The pack launch on `st`: the binding's SDF plane and scales, the call's planes and destinations.

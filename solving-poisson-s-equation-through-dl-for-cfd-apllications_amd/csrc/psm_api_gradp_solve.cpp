@@ -20,6 +20,7 @@ void gradp_solve_free(psm_handle* h) {
   drop_gradp_solve_graphs(h);
   integ_free(s.integ);
   dev_free(s.d_image); dev_free(s.d_scalars);
+  image_gone(h);
   s.ready = false; s.cases = 0; s.apply_filter = 0;
 }
 

@@ -118,6 +118,8 @@ void free_plan(psm_handle* h) {
   feat_free(h->feat);                   // and psm_bind_features
   frames_free(h);                       // psm_bind_frames belongs to the mesh that went with the plan
   gradp_solve_free(h);                  // and so does psm_bind_gradp_solve*, sized by this plan's grid
+  trust_free(h);                        // and psm_bind_trust (its partials are sized by this plan's blocks)
+  image_gone(h);                        // the staging image went above: no solve to score until the next one
 }
 
 
@@ -364,6 +366,7 @@ int psm_set_pca(psm_handle* h, const double* comp_in, const double* mean_in, con
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
   h->gsolve.ready = false;               // and psm_bind_gradp_solve*
+  h->trust.ready = false;                // and psm_bind_trust (its Gram matrix and scaler check are this model's)
   std::vector<float> mi(h->K_in), mo(h->K_out);
   for (int k = 0; k < h->K_in; ++k) mi[k] = (float)mean_in[k];
   for (int k = 0; k < h->K_out; ++k) mo[k] = (float)mean_out[k];
@@ -435,6 +438,7 @@ int psm_set_dense(psm_handle* h, int32_t layer, int32_t n_in, int32_t n_out, con
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
   h->gsolve.ready = false;               // and psm_bind_gradp_solve*
+  h->trust.ready = false;                // and psm_bind_trust (its Gram matrix and scaler check are this model's)
   DenseLayer& d = h->dense[layer];
   d.linear = false;                                     // psm_set_attention sets it again after this call
   if (d.ln && (d.n_out != n_out || (d.ln_residual && n_in != n_out))) {      // a LayerNormalization of another width, or its residual x + input on a
@@ -528,6 +532,7 @@ int psm_set_layernorm(psm_handle* h, int32_t layer, int32_t n, const float* gamm
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
   h->gsolve.ready = false;               // and psm_bind_gradp_solve*
+  h->trust.ready = false;                // and psm_bind_trust (its Gram matrix and scaler check are this model's)
   // zero-padded to whole 16-byte pieces past the consumer's leading dimension: a Dense launch that applies this normalisation to
   // its input (launch_all) reads gamma / beta with the clamped column index of its operand loads
   std::vector<float> g(round_up(n, 32) + 32, 0.f), b(round_up(n, 32) + 32, 0.f);
@@ -562,6 +567,7 @@ int psm_set_conv1d(psm_handle* h, int32_t layer, int32_t n_layers, int32_t kerne
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
   h->gsolve.ready = false;               // and psm_bind_gradp_solve*
+  h->trust.ready = false;                // and psm_bind_trust (its Gram matrix and scaler check are this model's)
   if (!same_stack) {
     for (auto& c : h->conv1d) { dev_free(c.W); dev_free(c.b); }
     h->conv1d.assign(n_layers, Conv1dLayer{});
@@ -594,6 +600,7 @@ int psm_set_scaler(psm_handle* h, const double* in_a, const double* in_b, const 
   h->feat.ready = false;                 // and psm_bind_features
   h->frames.ready = false;               // and psm_bind_frames
   h->gsolve.ready = false;               // and psm_bind_gradp_solve*
+  h->trust.ready = false;                // and psm_bind_trust (its Gram matrix and scaler check are this model's)
   std::vector<float> ia(h->ld_in, 0.f), ib(h->ld_in, 0.f), sa(h->ld_out, 0.f), sb(h->ld_out, 0.f);
   // x_in = coeff*ia + ib ; res' = res*sa + sb  (affine forms of SMD:505-539, evaluated in f64 here)
   for (int p = 0; p < h->cfg.p_in; ++p) {

@@ -393,7 +393,7 @@ int launch_all(psm_handle* h, Workspace& w, const float* d_grid, int n_cases, fl
                hipStream_t st, hipEvent_t* prof, const PsmSwitches::PerSolve& ps) {
   const SolveRoute r = choose_route(h, w, d_grid, n_cases, prof != nullptr, ps);
   // the record of what this solve leaves (a ring slot's solve leaves nothing readable: the rest of the record is stale then)
-  if (&w == &h->ws0) h->last = Ws0Solve{true, r.pred_stored, r.cf, h->dense.size() > 1 && r.packed[h->dense.size() - 2], d_row_scale};
+  if (&w == &h->ws0) h->last = Ws0Solve{true, r.pred_stored, r.cf, h->dense.size() > 1 && r.packed[h->dense.size() - 2], d_row_scale, nullptr, d_grid, n_cases};
   else h->last.on_ws0 = false;
   Solve s{h, w, r, d_grid, d_fields, d_row_scale, st, Timer{h, st, 0, prof}};
   int rc;

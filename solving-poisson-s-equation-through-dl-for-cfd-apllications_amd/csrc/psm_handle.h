@@ -19,6 +19,7 @@
 //   psm_api_rows.cpp        a frame's dataset rows -> scalars + columns on the device: psm_bind_rows, the stage alone psm_rows_prepare_device and the evaluators' steps behind it, psm_deltas_rows* / psm_poisson_rows* / psm_gradp_rows*
 //   psm_api_poisson_solve.cpp  the Poisson-model step at the solver boundary (cells -> p, two-frame state on the device): psm_bind_poisson_solve, psm_poisson_solve_push / _reset / _state, psm_solve_poisson*; for a case set psm_bind_poisson_solve_cases, psm_poisson_solve_push_cases, psm_solve_cases_poisson*
 //   psm_api_gradp_solve.cpp  the gradient-model step at the solver boundary (cells -> p through solve, integration and the outlet level, no state): psm_bind_gradp_solve, psm_solve_gradp*; for a case set psm_bind_gradp_solve_cases, psm_solve_cases_gradp*
+//   psm_api_trust.cpp       the input-trust score of the last solve (per-block PCA reconstruction residual): psm_bind_trust, psm_trust_last*
 //   psm_api_introspect.cpp  psm_read_stage, profiling and kernel timing, host-side reference reassembly
 // The PSM_* environment switches of all of them are read in psm_switches.cpp (host only): psm_create and psm_plan_grid fill h->sw, the
 // bind entries and a solve read theirs at the entry, the rest is one process-wide table.  No file above reads the environment itself.
@@ -53,6 +54,7 @@
 #include "psm_filter.h"
 #include "psm_integ.h"
 #include "psm_features.h"
+#include "psm_trust.h"
 #include "psm_plan.h"
 #include "psm_fold.h"
 #include "psm_errors.h"
@@ -99,6 +101,10 @@ struct Ws0Solve {
   bool pred_stored = false, used_cf = false, act_packed = false;
   const float* row_scale = nullptr;     // its row scale
   const float* res = nullptr;           // where its network output rows [cases * B][ld_out] are when not in ws0.d_res (psm_deltas_frames*: one solve per frame)
+  // the image its encode read and its case count (psm_trust_last* scores exactly that chain: an evaluator's step leaves its last
+  // frame's single-case solve).  Null once the buffer that held an image of the library's own is released (image_gone).
+  const float* grid = nullptr;
+  int n_cases = 0;
 };
 
 // Every decision of one solve's launch sequence, made once by choose_route (psm_api_solve.cpp) from the handle, the workspace, the grid
@@ -501,6 +507,18 @@ struct Chapter4Set : EvalSet {
 }  // namespace psm_impl
 using namespace psm_impl;
 
+namespace psm_impl __attribute__((visibility("hidden"))) {
+// Binding of the input-trust score (psm_bind_trust): the Gram matrix of the input basis and every buffer a call touches, so that
+// psm_trust_last* allocates nothing.  The mean is the handle's own d_mean_in, which is in natural order.
+struct TrustSet {
+  bool ready = false;
+  int bands = 0;
+  double* d_gram = nullptr;             // [p_in][p_in] C C^T of the float32 basis, float64
+  double* d_part = nullptr;             // [max_cases][B][bands]
+  double *d_out = nullptr, *h_out = nullptr;   // [max_cases][B][2], device and pinned: the host entry's staging
+};
+}  // namespace psm_impl
+
 struct psm_handle {
   psm_config cfg{};
   std::string err;
@@ -542,6 +560,7 @@ struct psm_handle {
   RowsSet rows;                         // the rows stage's staging behind it (psm_bind_rows)
   PoissonSolveSet psolve;               // the Poisson-model step at the solver boundary behind features, post-steps and frames (psm_bind_poisson_solve) or behind features and post-steps on a case set (psm_bind_poisson_solve_cases)
   GradpSolveSet gsolve;                 // the gradient-model step at the solver boundary on the mesh or the case set (psm_bind_gradp_solve*)
+  TrustSet trust;                       // the input-trust score of the last solve (psm_bind_trust)
   DeltasSet deltas;                     // the deltas evaluator's frame batch behind it (psm_bind_deltas_frames)
   GradpSet gradp;                       // the U_to_gradP evaluator's frame batch behind it (psm_bind_gradp_frames)
   Chapter4Set chapter4;                 // the Chapter-4 evaluators' frame batch behind it (psm_bind_chapter4_frames)
@@ -694,6 +713,9 @@ void deltas_free(psm_handle* h);
 void gradp_free(psm_handle* h);
 void chapter4_free(psm_handle* h);
 void rows_free(psm_handle* h);
+void trust_free(psm_handle* h);           // psm_plan_grid drops the trust binding; the model setters clear its flag (psm_api_trust.cpp)
+// a buffer of the library's own that held a solve's image is released: psm_trust_last* has no image to score until the next solve
+inline void image_gone(psm_handle* h) { h->last.grid = nullptr; }
 void poisson_solve_free(psm_handle* h);   // whatever drops the feature, post-step or frame binding, the mesh or the case set drops this one (psm_api_poisson_solve.cpp)
 // the two head launches / the tail launch of a Poisson solver step on `st` (the tail's field: next with the weighting, else result)
 int poisson_solve_head(psm_handle* h, const PoissonSolveCall& ps, hipStream_t st);

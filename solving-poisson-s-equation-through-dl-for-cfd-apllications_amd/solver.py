@@ -168,7 +168,7 @@ class _SolverBase:
     CASES = 0
     NOUN = "module"
 
-    def __init__(self, model, maxs, max_cases, geometry, device, delta, step, **step_args):
+    def __init__(self, model, maxs, max_cases, geometry, device, delta, step, trust=False, **step_args):
         if geometry not in ("scipy", "native"):
             raise ValueError("geometry must be 'scipy' or 'native'")
         self.step = _check_step(step, MODULE_STEPS)
@@ -183,6 +183,7 @@ class _SolverBase:
         self._sur = None
         self.tables = None
         self._inflight = None
+        self._trust = bool(trust)
 
     def _call(self, entry, *args):
         sur = self._sur
@@ -222,6 +223,8 @@ class _SolverBase:
         self.tables = tables if tables == "native" else self._one(tables)
         if kind.bind:
             kind.bind(self, sur, [np.asarray(sd, np.float64).reshape(ny, nx) for sd in keep[3]], a)
+        if self._trust:
+            sur.bind_trust()
         if kind.primes:
             self.prime(self._one(a))
         return 0
@@ -235,6 +238,22 @@ class _SolverBase:
                                       o[k].shape[0], self.delta, 10, *[_p(col[k], ct) for col, (_, _, _, _, ct) in zip(keep, _TABLES)]):
                 raise ValueError((f"case {k}: " if self.CASES else "") + lib.psm_geometry_last_error().decode())
         return keep
+
+    # -- trust=True: the input-trust score of the last step (psm_bind_trust / psm_trust_last of include/psm.h)
+    def trust(self):
+        """Per case of the last ``py_func``, how much of the network's input the model's retained input components represent: a
+        dict of ``n`` = |x - mean|^2 and ``spe`` (the PCA reconstruction residual) per block [B], ``explained`` = 1 - spe / n [B],
+        ``explained_min`` and ``explained_total`` = 1 - sum(spe) / sum(n).  Compare with the var_in the model was trained to; what a
+        low value means for the step (keep the solver's own p as the initial guess) is the caller's decision.  The scored image is
+        the one the last launch chain ran on: a priming step runs none and leaves the chain before it."""
+        if not self._trust:
+            raise RuntimeError(f"this {self.NOUN} was built without trust=True")
+        self._need_init()
+        t = self._sur.trust_last()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self._one([{"n": n, "spe": spe, "explained": ex, "explained_min": float(np.min(ex)),
+                               "explained_total": float(1.0 - spe.sum() / n.sum())}
+                              for n, spe, ex in zip(t["n"], t["spe"], t["explained"])])
 
     # -- the state of step='delta' (psm_delta_prime* / _reset / _state) and of step='poisson' (psm_poisson_solve_push* / _reset / _state)
     def _need_state(self):
@@ -285,7 +304,8 @@ class SolverModule(_SolverBase):
 
     def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), device: int = 0, delta: float = 5e-3,
                  geometry: str = "scipy", step: str = "absolute", phi: float = None, k: float = None, weighting: bool = True,
-                 apply_filter: bool = None, sigma_field=(10, 10), sigma_weight=(50, 50), cut=None, reference: str = "outlet"):
+                 apply_filter: bool = None, sigma_field=(10, 10), sigma_weight=(50, 50), cut=None, reference: str = "outlet",
+                 trust: bool = False):
         """``step``: 'absolute' (U -> p, the Chapter-5 module) or 'delta' (the deltas model behind the same two calls:
         [U(t) - U(t-1)], SDF -> p(t) - p(t-1), psm_solve_delta* of include/psm.h).  With 'delta', ``maxs`` are
         (max_abs_dUx, max_abs_dUy, max_abs_dist, max_abs_dp), ``init_func`` installs the tables with the deltas model's
@@ -310,8 +330,10 @@ class SolverModule(_SolverBase):
         builder behind ``psm_init_geometry``, csrc/psm_geometry.cpp: what a C++ solver gets; no SciPy).  The two differ only
         where the reference's own result is an accident of qhull (include/psm.h): fixed lattice diagonals -- a second-order
         difference on smooth fields, O(1) per cell on the white-noise fields of randomly initialised test networks
-        (tests/measure/mesh_native_vs_scipy.py) -- and the simplex used for lattice points outside the hull."""
-        super().__init__(model, maxs, 1, geometry, device, delta, step, phi=phi, k=k, weighting=weighting, apply_filter=apply_filter,
+        (tests/measure/mesh_native_vs_scipy.py) -- and the simplex used for lattice points outside the hull.
+        ``trust=True``: ``init_func`` also binds the input-trust score behind the step's own bindings and :meth:`trust` reports it for
+        the last step; off, the module makes exactly the library calls it makes without the option."""
+        super().__init__(model, maxs, 1, geometry, device, delta, step, trust=trust, phi=phi, k=k, weighting=weighting, apply_filter=apply_filter,
                          sigma_field=sigma_field, sigma_weight=sigma_weight, cut=cut, reference=reference)
 
     # -- grid-native body (python_module.py:299-473)
@@ -397,14 +419,16 @@ class SolverEnsemble(_SolverBase):
     widths), on ``psm_solve_cases_poisson``: ``init_func`` installs the K table sets, binds the features with the K SDF planes, the
     post-steps and the step, and pushes its own ``arrays`` as the first frame; one two-frame state, one frame counter and one step
     counter for the set; no begin / end halves.  Or 'gradp' with ``cut`` (None, or one (center_y, center_x) per case), ``reference``
-    and ``apply_filter`` (default off) of :class:`SolverModule`, on ``psm_solve_cases_gradp``: no state, no begin / end halves."""
+    and ``apply_filter`` (default off) of :class:`SolverModule`, on ``psm_solve_cases_gradp``: no state, no begin / end halves.
+    ``trust=True``: as for :class:`SolverModule`; :meth:`trust` returns one dict per case."""
     CASES = 1
     NOUN = "ensemble"
 
     def __init__(self, model: SurrogateModel, maxs=(1.0, 1.0, 1.0, 1.0), max_cases: int = 8, geometry: str = "native",
                  device: int = 0, delta: float = 5e-3, step: str = "absolute", phi: float = None, k: float = None, weighting: bool = True,
-                 apply_filter: bool = None, sigma_field=(10, 10), sigma_weight=(50, 50), cut=None, reference: str = "outlet"):
-        super().__init__(model, maxs, max_cases, geometry, device, delta, step, phi=phi, k=k, weighting=weighting, apply_filter=apply_filter,
+                 apply_filter: bool = None, sigma_field=(10, 10), sigma_weight=(50, 50), cut=None, reference: str = "outlet",
+                 trust: bool = False):
+        super().__init__(model, maxs, max_cases, geometry, device, delta, step, trust=trust, phi=phi, k=k, weighting=weighting, apply_filter=apply_filter,
                          sigma_field=sigma_field, sigma_weight=sigma_weight, cut=cut, reference=reference)
         self.cell_off = None
 

@@ -1331,6 +1331,33 @@ class GridSurrogate:
         _lib.check(_lib.load().psm_error_metrics_from_sums(_p(r, C.c_double), _p(out, C.c_double)))
         return {key: float(v) for key, v in zip(cls.METRICS, out)}
 
+    # -- input trust: the per-block PCA reconstruction residual of the last solve (include/psm.h, psm_bind_trust)
+    def bind_trust(self):
+        """psm_bind_trust with the model's input basis: once per surrogate; after it :meth:`trust_last` allocates nothing."""
+        ci = _f64(self.model.comp_in)
+        self._chk(self.lib.psm_bind_trust(self.h, _p(ci, C.c_double)))
+
+    def unbind_trust(self):
+        self._chk(self.lib.psm_unbind_trust(self.h))
+
+    def trust_last(self) -> dict:
+        """The score of the image the last solve ran on: ``n`` = |x - mean|^2 and ``spe`` = |x - mean - C^T z|^2 per block, float64
+        ``[n_cases, B]``, and ``explained`` = 1 - spe / n, the share the retained components represent (comparable with the var_in
+        the model was trained to; NaN where n == 0).  An evaluator's frame step leaves its last frame: n_cases = 1."""
+        out = np.empty((self.max_cases, self.B, 2), np.float64)
+        n = C.c_int32()
+        self._chk(self.lib.psm_trust_last(self.h, C.byref(n), _p(out, C.c_double), out.size))
+        out = out[:n.value]
+        nn, spe = out[..., 0].copy(), out[..., 1].copy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            explained = 1.0 - spe / nn
+        return {"n": nn, "spe": spe, "explained": explained}
+
+    def trust_last_device(self, d_out: int, stream: int = 0):
+        """psm_trust_last_device: two asynchronous launches on ``stream`` (0: the handle's); ``d_out`` [n_cases, B, 2] float64 in
+        device memory, (n, spe) per block row."""
+        self._chk(self.lib.psm_trust_last_device(self.h, C.c_void_p(self._dev_ptr(d_out, 8, "d_out")), C.c_void_p(stream)))
+
     # -- introspection
     def stage(self, name: str, n_cases: int = 1, layer: int = 0) -> np.ndarray:
         """An intermediate of the last solve; ``name='hidden'``: the output of hidden Dense layer ``layer`` (the handle must have
